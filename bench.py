@@ -15,12 +15,16 @@ N GPUs: `python bench.py --gpus N` starts N ranks ITSELF (a child `python -m tor
 before this process imports torch or touches HIP) unless it already runs under a launcher (WORLD_SIZE set); every rank asserts
 WORLD_SIZE == --gpus.  One process per GPU; ranks shard with no data-path collective -- torch.distributed/RCCL is used only for
 the barrier and the max-over-ranks reduction of the timing.  At N > 1 `value` is WEAK scaling -- proofs are independent units, every
-rank verifies its own 2^20 (per-GPU work fixed as N grows), `value` = all ranks' proofs / the slowest rank's time -- and the line also
-carries `strong`: ONE 2^20 batch over the whole node, contiguous shards of 2^20 / N proofs per rank (`--scaling strong` makes that
-one `value`; both are always measured and printed).  Each rank's host hashing takes usable CPUs / N workers.  `node_multi` = the product's own
+rank verifies its own 2^20 (per-GPU work fixed as N grows), `value` = all ranks' proofs / the slowest rank's time -- and with --full the
+line also carries `strong`: ONE 2^20 batch over the whole node, contiguous shards of 2^20 / N proofs per rank (`--scaling strong` makes that
+one `value`; --full measures and prints both).  Each rank's host hashing takes usable CPUs / N workers.  `node_multi` = the product's own
 multi-GPU path: ONE process, one act_node handle over all N devices, one 2^20 batch from host memory (rank 0, the other ranks idle).
 
-The one JSON line carries
+A plain run does only what `value` needs: it makes the batch, warms up, times exactly --steps steps, writes the statuses of
+the last timed step if --dump-outputs DIR is given (DIR/statuses.npy, float32, one per proof; rank k > 0 of an N-GPU run writes
+DIR/statuses_rank<k>.npy) and prints the line: metric, value, unit, higher_is_better, dtype, ms_per_step (one timed step),
+config, kernel_ms_per_step and the per-rank report.  At N > 1 it times only the region that becomes `value`.
+Everything below is measured only with --full (at N > 1 also the other scaling region and its other transcript mode):
   roofline             the binding roofline of the dominant kernel, k_spend_bits: 64-bit integer multiply-accumulates per second
                        against a v_mad_u64_u32 micro-kernel timed in this run on this GPU; the multiply-accumulates per verify
                        are counted, not estimated (the kernels' own lane bodies executed on the host with counting field
@@ -37,6 +41,7 @@ and at N = 1
   extra.verify_L64                 BASELINE config 2: 2^16 verifies at L = 64
 
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full --dump-outputs bench_outputs
     python bench.py --gpus 8                      # starts 8 ranks itself
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
@@ -325,9 +330,13 @@ def parse_args(argv=None):
                          "this benchmark owns its GPU; 16 = what act_ctx_create leaves (the library never widens on its own)")
     ap.add_argument("--extra-log2", type=int, default=18, help="proofs per extra measurement (refund, host-memory variants)")
     ap.add_argument("--pipeline-depth", type=int, default=2, help="chunks in flight; 1 for profiling runs (rocprofv3 per-kernel durations then do not overlap)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
-    ap.add_argument("--no-node-multi", action="store_true", help="skip the one-process act_node measurement over all N devices")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside `value`: rooflines, CPU baseline, host-memory / node paths, extras, both N > 1 scaling regions")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the statuses of the last timed step to DIR/statuses.npy (float32; rank k > 0: statuses_rank<k>.npy)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the N = 1 extras")
+    ap.add_argument("--no-node-multi", action="store_true", help="with --full: skip the one-process act_node measurement over all N devices")
     # test hooks: exercise the N>1 control path on a box with one GPU (RCCL refuses two ranks on one device)
     ap.add_argument("--dist-backend", default="nccl")
     ap.add_argument("--force-device", type=int, default=-1)
@@ -378,8 +387,8 @@ def main():
     local_world = int(os.environ.get("LOCAL_WORLD_SIZE", str(world)))
     if world != args.gpus:
         raise SystemExit("bench.py: --gpus %d but WORLD_SIZE = %d: every rank must be one of the N GPUs the line reports" % (args.gpus, world))
-    want_cpu = world == 1 and not args.no_cpu_baseline
-    paths = prebuild_cpu_side(want_cpu) if rank == 0 else {}
+    want_cpu = args.full and world == 1 and not args.no_cpu_baseline
+    paths = prebuild_cpu_side(want_cpu) if rank == 0 and args.full else {}
 
     import datetime
     import numpy as np
@@ -480,14 +489,23 @@ def main():
 
     # N = 1: one region.  N > 1: weak scaling = every rank its own 2^batch_log2 proofs (`value` by default: the path shards into
     # independent proofs, per-GPU work fixed as N grows) and strong scaling = ONE batch of 2^batch_log2 cut over the whole node;
-    # --scaling picks which is `value`, both are printed.
+    # --scaling picks which is `value`; a plain run times only that one, --full times and prints both.
     scaling = "weak" if (world == 1 or args.scaling == "auto") else args.scaling
-    weak_elapsed, weak_prof, weak_loc = timed_region(n, args.steps, args.warmup)
+    n_s = n // world
+    outputs = None                # the statuses of the last timed step of the region that becomes `value` (--dump-outputs)
+    if scaling == "weak" or args.full:
+        weak_elapsed, weak_prof, weak_loc = timed_region(n, args.steps, args.warmup)
+        if scaling == "weak" and args.dump_outputs:
+            outputs = status[:n].clone()
     strong = None
-    if world > 1:
-        n_s = n // world
+    if world > 1 and (scaling == "strong" or args.full):
         status.zero_()
         s_elapsed, s_prof, s_loc = timed_region(n_s, args.steps, args.warmup)
+        if scaling == "strong" and args.dump_outputs:
+            outputs = status[:n_s].clone()
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, rank, outputs, np)
+    if world > 1 and args.full:
         strong = {"value": world * n_s * args.steps / s_elapsed, "unit": "verifies/s", "ms_per_step": 1e3 * s_elapsed / args.steps, "batch_total": world * n_s,
                   "batch_per_gpu": n_s, "launch_chunks_per_gpu": -(-n_s // args.max_batch), "scaling": "strong",
                   "what": "BASELINE.json's metric as worded: ONE 2^%d batch over the whole node, contiguous shards of 2^%d / %d proofs per rank, no collective"
@@ -508,7 +526,7 @@ def main():
         elapsed, prof, n_rank, loc = weak_elapsed, weak_prof, n, weak_loc
     # what every rank saw in the region that became `value` (N > 1: gathered on rank 0): the first thing to look at when the 1 -> 8
     # curve bends -- a slow GPU (clock, k_spend_bits busy), a starved host side (hash_busy_fraction near 1), or the link
-    mine = rank_report(capi, eng, local, prof, loc, args.steps, n_rank, L)
+    mine = rank_report(capi, eng, local, prof, loc, args.steps, n_rank, L, probe=args.full)
     per_rank = [mine]
     if use_dist:
         gathered = [None] * world
@@ -563,6 +581,9 @@ def main():
             out["strong"] = strong
             out["weak"] = {"value": world * n * args.steps / weak_elapsed, "unit": "verifies/s", "ms_per_step": 1e3 * weak_elapsed / args.steps, "batch_per_gpu": n,
                            "scaling": "weak", "what": "every rank its own 2^%d proofs" % args.batch_log2}
+        out["kernel_ms_per_step"] = kernel_ms
+        out["config"]["full"] = args.full
+    if rank == 0 and args.full:
         sha = kernel_source_sha16()
         # ---- the binding roofline: measured peak of the multiply-accumulate instruction, counted work per verify --------
         proofs_host = dev[:4].cpu().numpy().tobytes()
@@ -616,7 +637,6 @@ def main():
                                 "cycles_per_valu_instruction_per_simd_2waves": j["cycles_per_valu_instruction_per_simd_2waves"],
                                 "effective_clock_ghz": j["effective_clock_ghz"], "launch_ms_solo_under_pmc": j["launch_ms_under_pmc"].get("SQ_INSTS_VALU")}
         out["roofline"] = roof
-        out["kernel_ms_per_step"] = kernel_ms
         out["kernel_source_sha16"] = sha
         try:
             out["roofline_prover"] = prover_roofline(paths["hostcheck"], prover_prof, peak_mad, h, L, eng, distinct, t_prove, args.max_batch)
@@ -625,7 +645,7 @@ def main():
 
     # ---- the product's own multi-GPU path: ONE process, one node handle over all N devices, one batch from host memory ----------
     # (rank 0; the other ranks wait on the CPU-side control group with their GPUs idle)
-    if rank == 0 and not args.no_node_multi:
+    if rank == 0 and args.full and not args.no_node_multi:
         devices = tuple(range(world)) if args.force_device < 0 else (args.force_device,) * world
         try:
             res = node_host_path(args, capi, torch, np, sk, dev, expect, h, devices, L, PB)
@@ -636,7 +656,7 @@ def main():
         dist.barrier(group=ctl)
 
     if rank == 0:
-        if world == 1 and not args.no_extras:
+        if world == 1 and args.full and not args.no_extras:
             out["extra"] = extras(args, eng, capi, torch, np, sk, dev, expect, h, local, L, PB, distinct)
         if want_cpu:
             # the oracle's sample = the first lanes of the batch; plus every tampered lane of the first launch chunk
@@ -656,17 +676,27 @@ def main():
 EXTRA_SAMPLES = 3
 
 
-def rank_report(capi, eng, device, prof, loc, steps, n_rank, L):
-    """One rank's view of its timed region: its own wall time, the clock its GPU gives a sustained integer load (the roofline probe),
-    how long k_spend_bits was executing, how busy the host side of the host-transcript mode was, and the PCIe traffic of that mode."""
-    peak, _ = capi.ubench_mad(device)
+def rank_report(capi, eng, device, prof, loc, steps, n_rank, L, probe=True):
+    """One rank's view of its timed region: its own wall time, the clock its GPU gives a sustained integer load (the roofline probe,
+    --full only), how long k_spend_bits was executing, how busy the host side of the host-transcript mode was, and the PCIe traffic of
+    that mode."""
     bits = prof.get("k_spend_bits", {"busy_ms": 0.0, "launches": 0})
     elapsed_s = loc["elapsed"]
     rep = {"rank": int(os.environ.get("RANK", "0")), "device": device, "ms_per_step": round(1e3 * elapsed_s / steps, 2), "proofs_per_step": n_rank,
-           "verifies_per_s": round(n_rank * steps / elapsed_s), "probe_clock_ghz": round(peak / 16384 / 1e9, 3),
+           "verifies_per_s": round(n_rank * steps / elapsed_s),
            "k_spend_bits_busy_ms_per_step": round(bits["busy_ms"] / steps, 2), "k_spend_bits_busy_fraction": round(bits["busy_ms"] / 1e3 / elapsed_s, 4)}
+    if probe:
+        peak, _ = capi.ubench_mad(device)
+        rep["probe_clock_ghz"] = round(peak / 16384 / 1e9, 3)
     rep.update({k: v for k, v in loc.items() if k != "elapsed"})
     return rep
+
+
+def dump_outputs(out_dir, rank, status, np):
+    """--dump-outputs: what the timed path hands its caller, one verification status per proof of this rank's region, as float32."""
+    os.makedirs(out_dir, exist_ok=True)
+    name = "statuses.npy" if rank == 0 else "statuses_rank%d.npy" % rank
+    np.save(os.path.join(out_dir, name), status.cpu().numpy().astype(np.float32))
 
 
 def timed(fn, sync, reps=EXTRA_SAMPLES):

@@ -119,7 +119,7 @@ def test_bench_two_ranks_on_one_device():
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
     args = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--batch-log2", "12", "--max-batch", "1024", "--distinct", "256",
             "--dist-backend", "gloo", "--force-device", "0"]
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + ["--full"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]                       # ONE line, relayed from rank 0
@@ -139,7 +139,7 @@ def test_bench_two_ranks_on_one_device():
     assert nm["devices"] == [0, 0] and nm["proofs"] == 4096 and nm["value"] > 0 and nm["host_pool"]["threads_created"] <= nm["host_pool"]["pool_size"]
     # under a launcher (the other way the driver may start it), --scaling strong swaps which of the two is `value`
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29671",
-           os.path.join(ROOT, "bench.py")] + args + ["--scaling", "strong", "--no-node-multi"]
+           os.path.join(ROOT, "bench.py")] + args + ["--scaling", "strong", "--no-node-multi", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
@@ -206,20 +206,28 @@ def test_eight_contexts_on_one_pool_do_not_oversubscribe(engine_factory, bench_p
     assert rates[8, H] / rates[8, D] > 0.90 * rates[2, H] / rates[2, D], rates
 
 
-def test_bench_rccl_path_with_one_rank():
+def test_bench_rccl_path_with_one_rank(tmp_path):
     """bench.py's RCCL calls (init_process_group("nccl", device_id=...), barrier, all_reduce MAX of the timing, destroy) on the one GPU a
     test box has: one rank under torch.distributed.run with --force-dist.  The two-rank test above uses gloo because RCCL refuses two
     ranks on one device; this one makes sure the nccl branch itself runs."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", "29673",
            os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch-log2", "12", "--max-batch", "1024",
-           "--force-dist", "--no-extras", "--no-cpu-baseline"]
+           "--force-dist", "--no-extras", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
     d = json.loads(lines[0])
     assert d["n_gpus"] == 1 and d["config"]["distinct_proofs_per_gpu"] == 4096 and d["value"] > 0
+    # a plain run times exactly --steps steps and measures nothing beside `value`
+    assert d["steps"] == 2 and abs(d["value"] - 4096 * 2 / (d["ms_per_step"] * 2 / 1e3)) < 1e-6 * d["value"]
+    assert "roofline" not in d and "host_memory_path" not in d and "extra" not in d and d["cpu_baseline"] is None
+    # --dump-outputs: the statuses of the last timed step, the bench's tamper pattern (1 lane in 1024 from lane 513: 7, 6, ...)
+    import numpy as np
+    st = np.load(os.path.join(str(tmp_path), "statuses.npy"))
+    want = np.zeros(4096, np.float32); want[513::2048] = 7; want[1537::2048] = 6
+    assert st.dtype == np.float32 and st.shape == (4096,) and np.array_equal(st, want)
 
 
 def test_single_item_refunds_from_many_threads_on_a_node_handle(engine_factory, bench_params):

@@ -5,7 +5,7 @@ knob=$1; rounds=${2:-2}; steps=${3:-8}; va=${4:-0}; vb=${5:-1}
 out=gpurun_out/ab_${knob}.txt; mkdir -p gpurun_out; : > $out
 for r in $(seq 1 $rounds); do
   for v in $va $vb; do
-    line=$(env $knob=$v timeout 300 python3 bench.py --steps $steps --warmup 2 --no-extras --no-cpu-baseline --no-node-multi 2>/dev/null | tail -1)
+    line=$(env $knob=$v timeout 300 python3 bench.py --full --steps $steps --warmup 2 --no-extras --no-cpu-baseline --no-node-multi 2>/dev/null | tail -1)
     echo "$knob=$v round $r: $(python3 -c "import json,sys; d=json.loads(sys.argv[1]); print(round(d['value']), 'verifies/s, avg launch', round(d['roofline']['avg_launch_ms'],2), 'ms, frac', round(d['roofline']['frac'],4))" "$line")" | tee -a $out
   done
 done
