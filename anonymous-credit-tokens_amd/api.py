@@ -376,5 +376,21 @@ class NullifierDb:
         """the same for a list, with the meaning of the loop in list order (a repeat inside the list is a double spend)"""
         return [b == 0 for b in self.set.check_and_insert(b"".join(bytes(k) for k in nullifiers))] if nullifiers else []
 
+    def reserve(self, capacity: int):
+        """grow so that `capacity` nullifiers fit; the recorded ones are kept (rehashed on the GPU)"""
+        self.set.reserve(capacity)
+
+    def save(self, path: str) -> int:
+        """snapshot of every recorded nullifier (nullifier_snapshot.py); returns how many were saved.  A point-in-time copy:
+        what is recorded after it is lost in a crash unless the caller logs it ("restart and growth")."""
+        return self.set.save(path)
+
+    @classmethod
+    def restore(cls, path: str, capacity: int = 1 << 20, device: int = 0) -> "NullifierDb":
+        """a database holding the snapshot's nullifiers (the file is validated as a whole before anything is recorded)"""
+        db = cls.__new__(cls)
+        db.set = capi.NullifierSet.restore(path, capacity=capacity, device=device)
+        return db
+
     def __len__(self):
         return len(self.set)

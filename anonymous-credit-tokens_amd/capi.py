@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import subprocess
 
@@ -25,14 +26,14 @@ EXPORTS = [
     "act_cbor_size", "act_cbor_record_bytes", "act_cbor_encode_batch", "act_cbor_decode_batch", "act_verify_spend_cbor_batch",
     "act_node_verify_spend_cbor_batch", "act_redeem_batch", "act_node_redeem_batch",
     "act_nullifier_set_create", "act_nullifier_set_destroy", "act_nullifier_set_len", "act_nullifier_set_last_error",
-    "act_nullifier_check_and_insert_batch",
+    "act_nullifier_check_and_insert_batch", "act_nullifier_set_reserve", "act_nullifier_set_export", "act_nullifier_contains_batch",
     "act_issue_check_batch", "act_issue_sign_batch", "act_refund_sign_batch",
     "act_node_create", "act_node_destroy", "act_node_device_count", "act_node_ctx", "act_node_last_error", "act_node_set_transcript_mode",
     "act_node_set_host_threads", "act_node_request_batch", "act_node_issue_batch", "act_node_issuance_to_credit_token_batch",
     "act_node_prove_spend_batch", "act_node_verify_spend_batch", "act_node_refund_batch", "act_node_refund_to_credit_token_batch",
     "act_node_issue_check_batch", "act_node_issue_sign_batch", "act_node_refund_sign_batch",
     "act_node_nullifier_set_create", "act_node_nullifier_set_destroy", "act_node_nullifier_set_len", "act_node_nullifier_set_last_error",
-    "act_node_nullifier_check_and_insert_batch",
+    "act_node_nullifier_check_and_insert_batch", "act_node_nullifier_set_reserve", "act_node_nullifier_set_export", "act_node_nullifier_contains_batch",
     "act_verify_spend_cbor_keys_batch", "act_node_verify_spend_cbor_keys_batch", "act_refund_sign_cbor_batch", "act_refund_cbor_batch", "act_refund_cbor_keys_batch",
     "act_node_refund_sign_cbor_batch", "act_node_refund_cbor_batch", "act_redeem_cbor_batch", "act_node_redeem_cbor_batch",
     "act_ctx_host_hash_stats", "act_ctx_set_tiny_calls", "act_node_set_balance", "act_node_device_stats", "act_node_balance_state", "act_debug_set_slowdown", "act_debug_fail_next_signs",
@@ -130,6 +131,9 @@ def load() -> C.CDLL:
     lib.act_nullifier_set_last_error.argtypes = [vp]
     lib.act_nullifier_set_last_error.restype = C.c_char_p
     lib.act_nullifier_check_and_insert_batch.argtypes = [vp, sz, i32, u8p, sz, u8p, u8p]
+    lib.act_nullifier_set_reserve.argtypes = [vp, sz]
+    lib.act_nullifier_set_export.argtypes = [vp, C.POINTER(C.c_uint64), sz, i32, u8p, C.POINTER(C.c_size_t)]
+    lib.act_nullifier_contains_batch.argtypes = [vp, sz, i32, u8p, sz, u8p]
     lib.act_prof_enable.argtypes = [vp, i32]
     lib.act_prof_reset.argtypes = [vp]
     lib.act_prof_kernel_count.argtypes = [vp]
@@ -171,6 +175,9 @@ def load() -> C.CDLL:
     lib.act_node_nullifier_set_last_error.argtypes = [vp]
     lib.act_node_nullifier_set_last_error.restype = C.c_char_p
     lib.act_node_nullifier_check_and_insert_batch.argtypes = [vp, sz, u8p, sz, u8p, u8p]
+    lib.act_node_nullifier_set_reserve.argtypes = [vp, sz]
+    lib.act_node_nullifier_set_export.argtypes = [vp, C.POINTER(C.c_uint64), sz, u8p, C.POINTER(C.c_size_t)]
+    lib.act_node_nullifier_contains_batch.argtypes = [vp, sz, u8p, sz, u8p]
     lib.act_verify_spend_cbor_keys_batch.argtypes = [vp, sz, i32, u8p, u8p, vp, u8p, u8p, u8p]
     lib.act_node_verify_spend_cbor_keys_batch.argtypes = [vp, sz, u8p, u8p, vp, u8p, u8p, u8p]
     lib.act_refund_sign_cbor_batch.argtypes = [vp, sz, i32, u8p, u8p, u8p, u8p, i32, u8p, u8p]
@@ -888,6 +895,50 @@ class NullifierSet:
     def check_and_insert_dev(self, n: int, d_nullifiers: int, stride: int, d_skip_mask: int, d_out_spent: int):
         self._ck(self.lib.act_nullifier_check_and_insert_batch(self.h, n, MEM_DEVICE, d_nullifiers, stride, d_skip_mask or None, d_out_spent))
 
+    # ---- growth, export, read-only look-up, snapshots (include/act_mi355x.h; nullifier_snapshot.py) ----
+    def reserve(self, capacity: int):
+        """grow so that `capacity` nullifiers fit (keys rehashed on the device; never shrinks)"""
+        self._ck(self.lib.act_nullifier_set_reserve(self.h, capacity))
+
+    def contains(self, nullifiers: bytes, stride: int = 32) -> bytes:
+        """read-only: 1 per recorded nullifier, else 0.  Audit and status queries only -- a spend decision is check_and_insert."""
+        n = (len(nullifiers) + stride - 32) // stride if nullifiers else 0
+        out = np.zeros(n, np.uint8); p0, k0 = _in(nullifiers)
+        self._ck(self.lib.act_nullifier_contains_batch(self.h, n, MEM_HOST, p0, stride, out.ctypes.data))
+        return out.tobytes()
+
+    def contains_dev(self, n: int, d_nullifiers: int, stride: int, d_out_found: int):
+        self._ck(self.lib.act_nullifier_contains_batch(self.h, n, MEM_DEVICE, d_nullifiers, stride, d_out_found))
+
+    def export_step(self, cursor: int, max_keys: int, out: np.ndarray = None):
+        """one export call into host memory (`out`: a reusable uint8 buffer of at least 32*max_keys bytes): -> (next cursor, keys bytes)"""
+        out = _export_buffer(out, max_keys); cur = C.c_uint64(cursor); got = C.c_size_t(0)
+        self._ck(self.lib.act_nullifier_set_export(self.h, C.byref(cur), max_keys, MEM_HOST, out.ctypes.data, C.byref(got)))
+        return cur.value, out[:32 * got.value].tobytes()
+
+    def export_dev(self, cursor: int, max_keys: int, d_out_keys: int):
+        """one export call into device memory (room for max_keys keys at d_out_keys): -> (next cursor, keys written)"""
+        cur = C.c_uint64(cursor); got = C.c_size_t(0)
+        self._ck(self.lib.act_nullifier_set_export(self.h, C.byref(cur), max_keys, MEM_DEVICE, d_out_keys, C.byref(got)))
+        return cur.value, got.value
+
+    def export(self, max_keys: int = 1 << 20) -> bytes:
+        """every recorded nullifier (reduced, 32 bytes each, unspecified order)"""
+        return _export_loop(self.export_step, max_keys)
+
+    def save(self, path: str) -> int:
+        from . import nullifier_snapshot
+        return nullifier_snapshot.write(path, self.export())
+
+    @classmethod
+    def restore(cls, path: str, capacity: int = None, device: int = 0, salt: bytes = None) -> "NullifierSet":
+        """a new set holding the snapshot's keys (validated as a whole before anything is inserted)"""
+        from . import nullifier_snapshot
+        keys = nullifier_snapshot.read(path)
+        s = cls(max(capacity or 0, len(keys) // 32, 1), device=device, salt=salt)
+        nullifier_snapshot.restore_into(s, keys)
+        return s
+
 
 class NodeNullifierSet:
     """The double-spend set over the GPUs of a node (act_node_nullifier_*): host-side routing by owner, one set per device."""
@@ -904,6 +955,8 @@ class NodeNullifierSet:
                 self.lib.act_node_nullifier_set_destroy(h)
             raise ActError(f"act_node_nullifier_set_create failed: {_ERRS.get(rc, rc)} {msg}")
         self.h = h
+        self.n_devices = len(devices)
+        self.capacity_per_device = capacity_per_device    # what every device was created or reserved for (reserve only grows it)
 
     def close(self):
         if getattr(self, "h", None):
@@ -927,3 +980,83 @@ class NodeNullifierSet:
         if rc:
             raise ActError(f"{_ERRS.get(rc, rc)}: {self.lib.act_node_nullifier_set_last_error(self.h).decode()}")
         return out.tobytes()
+
+    def _ck(self, rc):
+        if rc:
+            raise ActError(f"{_ERRS.get(rc, rc)}: {self.lib.act_node_nullifier_set_last_error(self.h).decode()}")
+
+    def reserve(self, capacity_per_device: int):
+        self._ck(self.lib.act_node_nullifier_set_reserve(self.h, capacity_per_device))
+        self.capacity_per_device = max(self.capacity_per_device, capacity_per_device)
+
+    def restore_capacity(self, n: int) -> int:
+        """per-device capacity for what the set holds plus n more keys.  Owners are a keyed hash, so a device receives about
+        1/devices of them; the margin (1/8 + 4 standard deviations + 1024) makes a device that still runs full rare, and
+        check_and_insert_growing grows it when it happens."""
+        per = -(-(len(self) + n) // self.n_devices)
+        return per + per // 8 + 4 * math.isqrt(per) + 1024
+
+    def check_and_insert_growing(self, nullifiers: bytes) -> bytes:
+        """check_and_insert of 32-byte keys that, when a device refuses its bucket for capacity (its lanes come back
+        ACT_NULLIFIER_UNDETERMINED, nothing of them recorded; the other devices' answers are final), doubles the per-device
+        capacity and resubmits exactly those lanes.  Restore's path: no device count or key spread can make it fail."""
+        n = len(nullifiers) // 32
+        keys = np.frombuffer(nullifiers, np.uint8).reshape(n, 32)
+        answer, lanes = np.zeros(n, np.uint8), np.arange(n)
+        while True:
+            sub = np.ascontiguousarray(keys[lanes]); out = np.zeros(len(lanes), np.uint8)
+            rc = self.lib.act_node_nullifier_check_and_insert_batch(self.h, len(lanes), sub.ctypes.data, 32, None, out.ctypes.data)
+            answer[lanes] = out
+            undetermined = out == 2                         # ACT_NULLIFIER_UNDETERMINED
+            if rc == 0:
+                return answer.tobytes()
+            if rc != 1 or not undetermined.any() or self.capacity_per_device >= 1 << 30:
+                self._ck(rc)
+            self.reserve(min(1 << 30, 2 * self.capacity_per_device))
+            lanes = lanes[undetermined]
+
+    def contains(self, nullifiers: bytes, stride: int = 32) -> bytes:
+        n = (len(nullifiers) + stride - 32) // stride if nullifiers else 0
+        out = np.zeros(n, np.uint8); p0, k0 = _in(nullifiers)
+        self._ck(self.lib.act_node_nullifier_contains_batch(self.h, n, p0, stride, out.ctypes.data))
+        return out.tobytes()
+
+    def export_step(self, cursor: int, max_keys: int, out: np.ndarray = None):
+        out = _export_buffer(out, max_keys); cur = C.c_uint64(cursor); got = C.c_size_t(0)
+        self._ck(self.lib.act_node_nullifier_set_export(self.h, C.byref(cur), max_keys, out.ctypes.data, C.byref(got)))
+        return cur.value, out[:32 * got.value].tobytes()
+
+    def export(self, max_keys: int = 1 << 20) -> bytes:
+        return _export_loop(self.export_step, max_keys)
+
+    def save(self, path: str) -> int:
+        from . import nullifier_snapshot
+        return nullifier_snapshot.write(path, self.export())
+
+    @classmethod
+    def restore(cls, path: str, capacity_per_device: int = None, devices=(0,), salt: bytes = None) -> "NodeNullifierSet":
+        """a new node set holding the snapshot's keys; every device is reserved for its expected share (restore_capacity)"""
+        from . import nullifier_snapshot
+        keys = nullifier_snapshot.read(path)
+        s = cls(max(capacity_per_device or 0, 1), devices=devices, salt=salt)
+        nullifier_snapshot.restore_into(s, keys)
+        return s
+
+
+EXPORT_DONE = 2**64 - 1      # ACT_NULLIFIER_EXPORT_DONE
+
+
+def _export_buffer(out, max_keys: int) -> np.ndarray:
+    if out is None:
+        return np.empty(32 * max_keys, np.uint8)
+    if out.dtype != np.uint8 or not out.flags.c_contiguous or out.size < 32 * max_keys:
+        raise ValueError(f"export buffer: need a contiguous uint8 array of at least {32 * max_keys} bytes")
+    return out
+
+
+def _export_loop(step, max_keys: int) -> bytes:
+    cur, parts, buf = 0, [], np.empty(32 * max_keys, np.uint8)      # one staging buffer for the whole loop
+    while cur != EXPORT_DONE:
+        cur, b = step(cur, max_keys, buf)
+        parts.append(b)
+    return b"".join(parts)

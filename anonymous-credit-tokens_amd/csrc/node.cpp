@@ -17,6 +17,7 @@
 #include <vector>
 #include "../../include/act_mi355x.h"
 #include "rng_source.h"
+#include "node_nullifier.h"
 
 struct act_node {
   std::vector<act_ctx*> ctx;
@@ -449,19 +450,7 @@ int act_node_refund_to_credit_token_batch(act_node* nd, size_t n, const uint8_t*
 // of the reference's sequential loop (`if is_spent(k) reject else insert(k)`, /root/reference/src/tests.rs:29-50) in lane
 // order: the host buckets the keys by owner preserving lane order, every GPU checks-and-inserts its bucket on its own
 // thread, the answers are scattered back.  33 bytes per spend cross PCIe; no peer traffic, no collective.
-struct act_node_nullifier_set {
-  std::vector<act_nullifier_set*> sets;
-  std::vector<int> devices;
-  uint64_t route_key[2] = {0, 0};
-  std::string err;
-  std::mutex mu;
-  // routing scratch, kept between calls (under mu) and only ever grown: a fresh 32 MB of key buckets per million-key call would
-  // be page-faulted in by one thread every time
-  struct Bucket { std::vector<uint32_t> lanes; std::vector<uint8_t> keys, spent; size_t count = 0; };
-  std::vector<Bucket> buckets;
-  std::vector<uint16_t> owner;
-  std::vector<size_t> place;
-};
+// (struct act_node_nullifier_set: node_nullifier.h, shared with node_nullifier.cpp)
 
 namespace {
 // 256-bit little-endian value mod l, l = 2^252 + 27742317777372353535851937790883648493 (the set itself reduces again on
@@ -536,10 +525,12 @@ const char* act_node_nullifier_set_last_error(const act_node_nullifier_set* ns) 
   return mine.c_str();
 }
 
-int act_node_nullifier_check_and_insert_batch(act_node_nullifier_set* ns, size_t n, const uint8_t* nullifiers, size_t stride, const uint8_t* skip_mask,
-                                              uint8_t* out_spent) {
-  if (!ns || (n && (!nullifiers || !out_spent)) || stride < 32) return ACT_ERR_ARG;
-  std::lock_guard<std::mutex> lock(ns->mu);
+}  // extern "C"
+
+namespace act_node_null {
+// The keys of a call, bucketed by owner on the host workers (host_pool.cpp), lane order kept inside every bucket; out[i] = 0 for
+// every lane.  Caller holds ns->mu.
+void bucket_by_owner(act_node_nullifier_set* ns, size_t n, const uint8_t* nullifiers, size_t stride, const uint8_t* skip_mask, uint8_t* out_spent) {
   const size_t parts = ns->sets.size();
   // Bucket the keys by owner, lane order kept inside every bucket, on the host workers (host_pool.cpp): the batch is cut into
   // segments; pass 1 computes every lane's owner and the segment's count per owner, a prefix sum over (segment, owner) gives each
@@ -582,15 +573,21 @@ int act_node_nullifier_check_and_insert_batch(act_node_nullifier_set* ns, size_t
         memcpy(b.keys.data() + 32 * at, r.nullifiers + i * r.stride, 32);
       }
   }, &r);
-  std::vector<int> rc(parts, ACT_OK);
-  std::vector<std::thread> th;
-  auto work = [&](size_t p) {
-    auto& b = ns->buckets[p];
-    if (b.count) rc[p] = act_nullifier_check_and_insert_batch(ns->sets[p], b.count, ACT_MEM_HOST, b.keys.data(), 32, nullptr, b.spent.data());
-  };
-  for (size_t p = 1; p < parts; p++) th.emplace_back(work, p);
-  work(0);
-  for (auto& t : th) t.join();
+}
+}  // namespace act_node_null
+using act_node_null::bucket_by_owner;
+using act_node_null::per_device;
+
+extern "C" {
+int act_node_nullifier_check_and_insert_batch(act_node_nullifier_set* ns, size_t n, const uint8_t* nullifiers, size_t stride, const uint8_t* skip_mask,
+                                              uint8_t* out_spent) {
+  if (!ns || (n && (!nullifiers || !out_spent)) || stride < 32) return ACT_ERR_ARG;
+  std::lock_guard<std::mutex> lock(ns->mu);
+  const size_t parts = ns->sets.size();
+  bucket_by_owner(ns, n, nullifiers, stride, skip_mask, out_spent);
+  std::vector<int> rc = per_device(ns, [&](size_t p, act_node_nullifier_set::Bucket& b) {
+    return act_nullifier_check_and_insert_batch(ns->sets[p], b.count, ACT_MEM_HOST, b.keys.data(), 32, nullptr, b.spent.data());
+  });
   // Every device answers for its own keys.  If one of them failed, the others have still inserted theirs: their lanes get
   // their (final) answers, the failed device's lanes get ACT_NULLIFIER_UNDETERMINED, and the call reports the error --
   // a caller that retries must resubmit only the undetermined lanes, or the lanes already inserted would come back "spent".
@@ -607,6 +604,7 @@ int act_node_nullifier_check_and_insert_batch(act_node_nullifier_set* ns, size_t
   }
   return first_rc;
 }
+
 }  // extern "C"
 
 // The issuer's whole redemption step over the GPUs of a node (act_redeem_batch's meaning, include/act_mi355x.h): verification of

@@ -112,6 +112,75 @@ __global__ void __launch_bounds__(256) k_null_mark_undetermined(uint8_t* spent, 
   if (i < n) spent[i] = (mask && mask[i]) ? 0 : ACT_NULLIFIER_UNDETERMINED;
 }
 
+// ---- export, rehash, read-only look-up (not on the redemption path: simple, bandwidth-shaped) ------------------------------
+// Committed slots of [begin, begin + count) -> out[*], dense, order unspecified.  One thread per slot: the state words are read
+// coalesced, every wave compacts its committed lanes with a ballot and takes its output range with ONE atomicAdd on counter[0];
+// a key moves as two 16-byte loads and two 16-byte stores (slots are 32-byte aligned, `out` is 16-byte aligned).
+__global__ void __launch_bounds__(256) k_null_export(const uint32_t* tab_keys, const uint32_t* tab_state, uint32_t begin, uint32_t count,
+                                                     uint4* out, uint32_t* counter) {
+  const uint32_t j = blockIdx.x * 256 + threadIdx.x;
+  const bool live = j < count && tab_state[begin + j] == 2u;
+  const unsigned long long m = __ballot(live);
+  if (m == 0) return;
+  const uint32_t lane = __lane_id(), first = (uint32_t)__ffsll((long long)m) - 1;
+  uint32_t base = 0;
+  if (lane == first) base = atomicAdd(counter, (uint32_t)__popcll(m));
+  base = __shfl(base, (int)first);
+  if (!live) return;
+  const uint32_t at = base + (uint32_t)__popcll(m & ((1ull << lane) - 1));   // committed lanes below this one in the wave
+  const uint4* src = reinterpret_cast<const uint4*>(tab_keys + (size_t)(begin + j) * 8);
+  const uint4 lo = src[0], hi = src[1];
+  out[(size_t)at * 2] = lo; out[(size_t)at * 2 + 1] = hi;
+}
+struct NullSalt { uint32_t w[4]; };
+// Every committed slot of the old table into the new one (same salt, same slot function, masked to the new capacity).  The keys are
+// known distinct, so a slot is claimed by a compare-and-swap 0 -> 2 on its state word and no key is compared; nothing reads the new
+// table before the kernel has finished.  counter[0] += keys placed (one atomic per wave), counter[1] = 1 if a key found no slot.
+__global__ void __launch_bounds__(256) k_null_rehash(const uint32_t* old_keys, const uint32_t* old_state, uint32_t old_cap, uint32_t* new_keys,
+                                                     uint32_t* new_state, uint32_t new_cap, NullSalt salt, uint32_t* counter) {
+  const uint32_t j = blockIdx.x * 256 + threadIdx.x;
+  bool placed = false;
+  if (j < old_cap && old_state[j] == 2u) {
+    const uint4* src = reinterpret_cast<const uint4*>(old_keys + (size_t)j * 8);
+    const uint4 lo = src[0], hi = src[1];
+    const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    uint32_t t = (uint32_t)(null_hash(w, salt.w) >> 32) & (new_cap - 1);
+    for (uint32_t probes = 0; probes < new_cap; probes++) {
+      if (atomicCAS(new_state + t, 0u, 2u) == 0u) {
+        uint4* dst = reinterpret_cast<uint4*>(new_keys + (size_t)t * 8);
+        dst[0] = lo; dst[1] = hi;
+        placed = true;
+        break;
+      }
+      t = (t + 1) & (new_cap - 1);
+    }
+    if (!placed) atomicExch(counter + 1, 1u);
+  }
+  const unsigned long long m = __ballot(placed);
+  if (m && __lane_id() == (uint32_t)__ffsll((long long)m) - 1) atomicAdd(counter, (uint32_t)__popcll(m));
+}
+// Read-only look-up: found[i] = 1 iff the reduced key i is committed.  Probes from the persistent table's start slot until the key
+// (found) or an empty slot (absent); no batch table, no write to the set.  The caller holds the set's lock, so no slot is being written.
+__global__ void __launch_bounds__(256) k_null_contains(const uint8_t* keys, uint32_t n, uint32_t stride, const uint32_t* tab_keys,
+                                                       const uint32_t* tab_state, uint32_t tab_cap, NullSalt salt, uint8_t* found) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  uint32_t w[8], o[8]; null_load_key(w, keys + (size_t)i * stride);
+  uint32_t t = (uint32_t)(null_hash(w, salt.w) >> 32) & (tab_cap - 1);
+  uint8_t f = 0;
+  for (uint32_t probes = 0; probes < tab_cap; probes++) {
+    const uint32_t st = tab_state[t];
+    if (st == 0u) break;
+    if (st == 2u) {
+      const uint32_t* src = tab_keys + (size_t)t * 8;
+      for (int k = 0; k < 8; k++) o[k] = src[k];
+      if (null_eq(w, o)) { f = 1; break; }
+    }
+    t = (t + 1) & (tab_cap - 1);
+  }
+  found[i] = f;
+}
+
 }  // namespace
 
 struct act_nullifier_set {
@@ -119,6 +188,7 @@ struct act_nullifier_set {
   uint32_t *tab_keys = nullptr, *tab_state = nullptr, *batch_tab = nullptr, *counters = nullptr;
   uint32_t tab_cap = 0, batch_cap = 0; uint32_t salt[4]{};
   uint8_t *d_keys = nullptr, *d_mask = nullptr, *d_spent = nullptr; size_t stage_cap = 0;
+  uint8_t* d_xout = nullptr; size_t xout_cap = 0; uint32_t* aux = nullptr;   // export staging (host output), export / rehash counters
   size_t len = 0; std::string err;
   std::mutex mu;                  // check_and_insert holds it: a set shared between host threads serves them one at a time
 };
@@ -148,7 +218,7 @@ int act_nullifier_set_create(int device, size_t capacity, const uint8_t salt[16]
 void act_nullifier_set_destroy(act_nullifier_set* s) {
   if (!s) return;
   (void)hipSetDevice(s->device);
-  void* ptrs[] = {s->tab_keys, s->tab_state, s->batch_tab, s->counters, s->d_keys, s->d_mask, s->d_spent};
+  void* ptrs[] = {s->tab_keys, s->tab_state, s->batch_tab, s->counters, s->d_keys, s->d_mask, s->d_spent, s->d_xout, s->aux};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (s->stream) (void)hipStreamDestroy(s->stream);
   delete s;
@@ -168,7 +238,8 @@ int act_nullifier_check_and_insert_batch(act_nullifier_set* s, size_t n, int mem
   std::lock_guard<std::mutex> lock(s->mu);
   NSCK(s, hipSetDevice(s->device));
   if (s->len + n > s->tab_cap / 2) {
-    // refused as a whole, nothing recorded: every unmasked lane is ACT_NULLIFIER_UNDETERMINED (and may be resubmitted, e.g. to a larger set)
+    // refused as a whole, nothing recorded: every unmasked lane is ACT_NULLIFIER_UNDETERMINED (and may be resubmitted to this set
+    // after act_nullifier_set_reserve)
     s->err = "nullifier set capacity exceeded";
     if (mem == ACT_MEM_HOST) { for (size_t i = 0; i < n; i++) out_spent[i] = (skip_mask && skip_mask[i]) ? 0 : ACT_NULLIFIER_UNDETERMINED; }
     else {
@@ -204,6 +275,109 @@ int act_nullifier_check_and_insert_batch(act_nullifier_set* s, size_t n, int mem
     NSCK(s, hipMemsetAsync(s->counters + 1, 0, 4, s->stream)); NSCK(s, hipStreamSynchronize(s->stream));
     return ACT_ERR_ARG;
   }
+  return ACT_OK;
+}
+
+// Growth: a new table sized by the rule of act_nullifier_set_create, every committed key rehashed into it on the device, then the
+// old one freed.  Any failure before the swap frees the new table and leaves the set exactly as it was.
+int act_nullifier_set_reserve(act_nullifier_set* s, size_t capacity) {
+  if (!s) return ACT_ERR_ARG;
+  std::lock_guard<std::mutex> lock(s->mu);
+  if (capacity > ((size_t)1 << 30)) { s->err = "act_nullifier_set_reserve: capacity above 2^30"; return ACT_ERR_ARG; }
+  uint32_t cap = 1024; while (cap < 2 * capacity) cap <<= 1;
+  if (cap <= s->tab_cap) return ACT_OK;                                   // never shrinks; already large enough
+  NSCK(s, hipSetDevice(s->device));
+  uint32_t *nk = nullptr, *ns = nullptr;
+  auto fail = [&](const std::string& what, hipError_t e) {
+    s->err = "act_nullifier_set_reserve: " + what + (e != hipSuccess ? std::string(": ") + hipGetErrorString(e) : std::string());
+    (void)hipGetLastError();
+    if (nk) (void)hipFree(nk);
+    if (ns) (void)hipFree(ns);
+    return ACT_ERR_HIP;
+  };
+  hipError_t e;
+  if (!s->aux && (e = hipMalloc(&s->aux, 8)) != hipSuccess) { s->aux = nullptr; return fail("hipMalloc(counters)", e); }
+  if ((e = hipMalloc(&nk, (size_t)cap * 32)) != hipSuccess) { nk = nullptr; return fail("hipMalloc(new table keys)", e); }
+  if ((e = hipMalloc(&ns, (size_t)cap * 4)) != hipSuccess) { ns = nullptr; return fail("hipMalloc(new table states)", e); }
+  if ((e = hipMemsetAsync(ns, 0, (size_t)cap * 4, s->stream)) != hipSuccess) return fail("hipMemsetAsync", e);
+  if ((e = hipMemsetAsync(s->aux, 0, 8, s->stream)) != hipSuccess) return fail("hipMemsetAsync", e);
+  NullSalt salt; memcpy(salt.w, s->salt, 16);
+  hipLaunchKernelGGL(k_null_rehash, dim3((s->tab_cap + 255) / 256), dim3(256), 0, s->stream, s->tab_keys, s->tab_state, s->tab_cap, nk, ns, cap, salt, s->aux);
+  if ((e = hipGetLastError()) != hipSuccess) return fail("k_null_rehash launch", e);
+  uint32_t cnt[2] = {0, 0};
+  if ((e = hipMemcpyAsync(cnt, s->aux, 8, hipMemcpyDeviceToHost, s->stream)) != hipSuccess) return fail("hipMemcpyAsync", e);
+  if ((e = hipStreamSynchronize(s->stream)) != hipSuccess) return fail("k_null_rehash", e);
+  if (cnt[1] || cnt[0] != s->len)
+    return fail("rehash placed " + std::to_string(cnt[0]) + " of " + std::to_string(s->len) + " keys; the old table is kept", hipSuccess);
+  (void)hipFree(s->tab_keys); (void)hipFree(s->tab_state);
+  s->tab_keys = nk; s->tab_state = ns; s->tab_cap = cap;
+  return ACT_OK;
+}
+
+// Export cursor: 0 = start; ACT_NULLIFIER_EXPORT_DONE = finished; otherwise log2(table slots) << 32 | next slot.  A reserve that
+// changes anything changes the table size, so the size names the table a cursor walks (a set grows at most 21 times).
+int act_nullifier_set_export(act_nullifier_set* s, uint64_t* cursor, size_t max_keys, int mem, uint8_t* out_keys, size_t* n_out) {
+  if (!s || !cursor || !n_out || !max_keys || !out_keys || (mem != ACT_MEM_HOST && mem != ACT_MEM_DEVICE)) return ACT_ERR_ARG;
+  std::lock_guard<std::mutex> lock(s->mu);
+  *n_out = 0;
+  if (*cursor == ACT_NULLIFIER_EXPORT_DONE) return ACT_OK;
+  const uint32_t lg = (uint32_t)__builtin_ctz(s->tab_cap);
+  uint64_t slot = 0;
+  if (*cursor != 0) {
+    slot = *cursor & 0xFFFFFFFFull;
+    if ((*cursor >> 32) != lg || slot >= s->tab_cap) {
+      s->err = "act_nullifier_set_export: stale or foreign cursor (the set was reserved since it was taken): restart from 0";
+      return ACT_ERR_ARG;
+    }
+  }
+  size_t window = std::min<size_t>(max_keys, s->tab_cap - slot);          // one slot holds at most one key: never more than max_keys
+  const bool stage = mem == ACT_MEM_HOST || (reinterpret_cast<uintptr_t>(out_keys) & 15u);
+  if (stage) window = std::min<size_t>(window, (size_t)1 << 21);         // staging of at most 64 MB
+  NSCK(s, hipSetDevice(s->device));
+  if (!s->aux) NSCK(s, hipMalloc(&s->aux, 8));
+  if (stage && window > s->xout_cap) {
+    if (s->d_xout) { NSCK(s, hipFree(s->d_xout)); s->d_xout = nullptr; s->xout_cap = 0; }
+    NSCK(s, hipMalloc(&s->d_xout, window * 32)); s->xout_cap = window;
+  }
+  uint8_t* dst = stage ? s->d_xout : out_keys;
+  NSCK(s, hipMemsetAsync(s->aux, 0, 4, s->stream));
+  hipLaunchKernelGGL(k_null_export, dim3((unsigned)((window + 255) / 256)), dim3(256), 0, s->stream, s->tab_keys, s->tab_state, (uint32_t)slot,
+                     (uint32_t)window, reinterpret_cast<uint4*>(dst), s->aux);
+  NSCK(s, hipGetLastError());
+  uint32_t got = 0;
+  NSCK(s, hipMemcpyAsync(&got, s->aux, 4, hipMemcpyDeviceToHost, s->stream));
+  NSCK(s, hipStreamSynchronize(s->stream));
+  if (stage && got) {
+    NSCK(s, hipMemcpyAsync(out_keys, s->d_xout, (size_t)got * 32, mem == ACT_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, s->stream));
+    NSCK(s, hipStreamSynchronize(s->stream));
+  }
+  const uint64_t next = slot + window;
+  *cursor = next >= s->tab_cap ? ACT_NULLIFIER_EXPORT_DONE : ((uint64_t)lg << 32 | next);
+  *n_out = got;
+  return ACT_OK;
+}
+
+int act_nullifier_contains_batch(act_nullifier_set* s, size_t n, int mem, const uint8_t* nullifiers, size_t stride, uint8_t* out_found) {
+  if (!s || (n && (!nullifiers || !out_found)) || stride < 32 || n > ((size_t)1 << 30) || (mem != ACT_MEM_HOST && mem != ACT_MEM_DEVICE)) return ACT_ERR_ARG;
+  if (n == 0) return ACT_OK;
+  std::lock_guard<std::mutex> lock(s->mu);
+  NSCK(s, hipSetDevice(s->device));
+  const uint8_t* keys = nullifiers; uint8_t* found = out_found; size_t kstride = stride;
+  if (mem == ACT_MEM_HOST) {
+    if (n > s->stage_cap) {
+      for (uint8_t** p : {&s->d_keys, &s->d_mask, &s->d_spent}) if (*p) { NSCK(s, hipFree(*p)); *p = nullptr; }
+      s->stage_cap = 0;
+      NSCK(s, hipMalloc(&s->d_keys, n * 32)); NSCK(s, hipMalloc(&s->d_mask, n)); NSCK(s, hipMalloc(&s->d_spent, n)); s->stage_cap = n;
+    }
+    NSCK(s, hipMemcpy2DAsync(s->d_keys, 32, nullifiers, stride, 32, n, hipMemcpyHostToDevice, s->stream));
+    keys = s->d_keys; found = s->d_spent; kstride = 32;
+  }
+  NullSalt salt; memcpy(salt.w, s->salt, 16);
+  hipLaunchKernelGGL(k_null_contains, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, keys, (uint32_t)n, (uint32_t)kstride, s->tab_keys,
+                     s->tab_state, s->tab_cap, salt, found);
+  NSCK(s, hipGetLastError());
+  if (mem == ACT_MEM_HOST) NSCK(s, hipMemcpyAsync(out_found, s->d_spent, n, hipMemcpyDeviceToHost, s->stream));
+  NSCK(s, hipStreamSynchronize(s->stream));
   return ACT_OK;
 }
 

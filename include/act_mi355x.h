@@ -421,6 +421,29 @@ const char *act_nullifier_set_last_error(const act_nullifier_set *set);
 int act_nullifier_check_and_insert_batch(act_nullifier_set *set, size_t n, int mem, const uint8_t *nullifiers, size_t stride,
                                          const uint8_t *skip_mask, uint8_t *out_spent);
 
+/* Growth, export and read-only look-up (restart and growth: INTEGRATION.md; the snapshot file format:
+ * anonymous-credit-tokens_amd/nullifier_snapshot.py).
+ * act_nullifier_set_reserve: afterwards the set can hold `capacity` nullifiers (the sizing rule of act_nullifier_set_create).  It
+ *   never shrinks: a capacity at or below the current one returns ACT_OK and changes nothing.  capacity > 2^30 returns ACT_ERR_ARG,
+ *   set unchanged.  If the new table cannot be allocated (or the rehash does not place every key) the call returns ACT_ERR_HIP and
+ *   the set keeps its old table, fully usable.  Otherwise every recorded key is rehashed into the new table on the device under the
+ *   set's own salt; len does not change; the set's lock is held for the whole call.  Export cursors taken before a reserve that
+ *   grew the set are stale: the next export call refuses them with ACT_ERR_ARG and a last_error text.
+ * act_nullifier_set_export: *cursor = 0 on the first call, opaque in between, ACT_NULLIFIER_EXPORT_DONE once every key has been
+ *   written.  One call writes at most max_keys (>= 1) keys to out_keys and sets *n_out, which may be 0 even when the cursor moved.
+ *   Keys are the reduced scalars, 32 bytes each, in unspecified order.  cursor and n_out are host pointers; `mem` says where
+ *   out_keys is.  A loop of calls from 0 to DONE yields every key recorded before its first call exactly once, and may also yield
+ *   keys recorded during the loop (slots never move between reserves).
+ * act_nullifier_contains_batch: out_found[i] = 1 if nullifier i (compared as a scalar: k and k + l are one key) is recorded, else
+ *   0; the set is never modified.  Nullifier i is the 32 bytes at nullifiers + i*stride, as in check-and-insert.  For audit and
+ *   status queries only: NOT a substitute for check-and-insert in a spend decision -- a look-up that does not record lets the same
+ *   nullifier pass two concurrent callers. */
+#define ACT_NULLIFIER_EXPORT_DONE UINT64_MAX
+int act_nullifier_set_reserve(act_nullifier_set *set, size_t capacity);
+int act_nullifier_set_export(act_nullifier_set *set, uint64_t *cursor, size_t max_keys, int mem, uint8_t *out_keys, size_t *n_out);
+int act_nullifier_contains_batch(act_nullifier_set *set, size_t n, int mem, const uint8_t *nullifiers, size_t stride,
+                                 uint8_t *out_found);
+
 /* The same set spread over the GPUs of a node: one set per entry of devices[], a nullifier owned by exactly one of them
  * (keyed hash of the reduced scalar), so a batch keeps the sequential meaning above in lane order.  The host buckets the
  * keys by owner (stable), every GPU checks-and-inserts its bucket from its own thread, answers are scattered back:
@@ -431,7 +454,7 @@ int act_nullifier_check_and_insert_batch(act_nullifier_set *set, size_t n, int m
  * answers (final), marks the lanes owned by the failed device ACT_NULLIFIER_UNDETERMINED in out_spent, and returns the error;
  * only the undetermined lanes may be resubmitted -- a blind retry of the whole batch would report the honest spends that
  * were already inserted as double spends.  The single-GPU form answers the same way: a batch the set has no room for is refused as
- * a whole (nothing recorded, every unmasked lane ACT_NULLIFIER_UNDETERMINED). */
+ * a whole (nothing recorded, every unmasked lane ACT_NULLIFIER_UNDETERMINED; resubmit to this set after act_nullifier_set_reserve). */
 #define ACT_NULLIFIER_UNDETERMINED 2
 typedef struct act_node_nullifier_set act_node_nullifier_set;
 int act_node_nullifier_set_create(const int *devices, int n_devices, size_t capacity_per_device, const uint8_t salt[16],
@@ -441,6 +464,14 @@ size_t act_node_nullifier_set_len(const act_node_nullifier_set *set);
 const char *act_node_nullifier_set_last_error(const act_node_nullifier_set *set);
 int act_node_nullifier_check_and_insert_batch(act_node_nullifier_set *set, size_t n, const uint8_t *nullifiers, size_t stride,
                                               const uint8_t *skip_mask, uint8_t *out_spent);
+/* Node forms of reserve / export / contains (meanings above).  reserve: every device's set is reserved to capacity_per_device; if
+ * one fails, the error names it, every set stays valid and some may already have grown.  export: host memory only; the cursor
+ * walks the devices in turn (a cursor is refused when the device it stopped inside has been grown since).  contains: the keys
+ * are routed by owner exactly as in check-and-insert and the answers scattered back. */
+int act_node_nullifier_set_reserve(act_node_nullifier_set *set, size_t capacity_per_device);
+int act_node_nullifier_set_export(act_node_nullifier_set *set, uint64_t *cursor, size_t max_keys, uint8_t *out_keys, size_t *n_out);
+int act_node_nullifier_contains_batch(act_node_nullifier_set *set, size_t n, const uint8_t *nullifiers, size_t stride,
+                                      uint8_t *out_found);
 
 /* The issuer's whole redemption step -- verify, look the nullifier up, record it, sign the refund (examples/act.rs:62-73; the
  * NullifierDb loops of src/tests.rs) -- as one call with the result of the loop
