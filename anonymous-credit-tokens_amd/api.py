@@ -246,6 +246,15 @@ class PrivateKey(_Cbor):
         st, out = _draw_signed(rng, len(msgs), lambda src, mode: e.refund_cbor(self.record, list(msgs), src, mode))
         return [out[i] if st[i] == 0 else _wire_error(st[i]) for i in range(len(msgs))]
 
+    def issue_cbor_batch(self, params: Params, msgs: Sequence[bytes], cs: Sequence, rng) -> list:
+        """`[IssuanceRequest::from_cbor(m).and_then(|r| self.issue(params, &r, c, rng)).map(to_cbor) for m, c in zip(msgs, cs)]` as one
+        call: entry i is the CBOR IssuanceResponse message, a CborError (from_cbor's) or an Error (issue's); `rng` is drawn for the
+        accepted messages only, in message order, after all verdicts (src/lib.rs:638-643)."""
+        e = params.engine()
+        cc = b"".join(scalar(c) for c in cs)
+        st, out = _draw_signed(rng, len(msgs), lambda src, mode: e.issue_cbor(self.record, list(msgs), cc, src, mode))
+        return [out[i] if st[i] == 0 else _wire_error(st[i]) for i in range(len(msgs))]
+
     def redeem_cbor_batch(self, params: Params, db: "NullifierDb", msgs: Sequence[bytes], rng, nbits: int = L) -> list:
         """The server loop of examples/act.rs:62-73 on wire bytes: from_cbor, refund's checks, the nullifier store (DoubleSpendError),
         the signature, to_cbor."""

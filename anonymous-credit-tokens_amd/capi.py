@@ -36,6 +36,8 @@ EXPORTS = [
     "act_node_nullifier_check_and_insert_batch", "act_node_nullifier_set_reserve", "act_node_nullifier_set_export", "act_node_nullifier_contains_batch",
     "act_verify_spend_cbor_keys_batch", "act_node_verify_spend_cbor_keys_batch", "act_refund_sign_cbor_batch", "act_refund_cbor_batch", "act_refund_cbor_keys_batch",
     "act_node_refund_sign_cbor_batch", "act_node_refund_cbor_batch", "act_redeem_cbor_batch", "act_node_redeem_cbor_batch",
+    "act_issue_check_cbor_batch", "act_issue_sign_cbor_batch", "act_issue_cbor_batch",
+    "act_node_issue_check_cbor_batch", "act_node_issue_sign_cbor_batch", "act_node_issue_cbor_batch",
     "act_ctx_host_hash_stats", "act_ctx_set_tiny_calls", "act_node_set_balance", "act_node_device_stats", "act_node_balance_state", "act_debug_set_slowdown", "act_debug_fail_next_signs",
 ]
 CBOR_TYPES = {"IssuanceRequest": 1, "IssuanceResponse": 2, "SpendProof": 3, "Refund": 4, "PrivateKey": 5, "PublicKey": 6,
@@ -187,6 +189,12 @@ def load() -> C.CDLL:
     lib.act_node_refund_cbor_batch.argtypes = [vp, sz, u8p, u8p, vp, u8p, i32, u8p, u8p]
     lib.act_redeem_cbor_batch.argtypes = [vp, vp, sz, i32, u8p, u8p, vp, u8p, i32, u8p, u8p]
     lib.act_node_redeem_cbor_batch.argtypes = [vp, vp, sz, u8p, u8p, vp, u8p, i32, u8p, u8p]
+    lib.act_issue_check_cbor_batch.argtypes = [vp, sz, i32, u8p, vp, u8p, u8p]
+    lib.act_issue_sign_cbor_batch.argtypes = [vp, sz, i32, u8p, u8p, u8p, u8p, u8p, i32, u8p, u8p]
+    lib.act_issue_cbor_batch.argtypes = [vp, sz, i32, u8p, u8p, vp, u8p, u8p, i32, u8p, u8p]
+    lib.act_node_issue_check_cbor_batch.argtypes = [vp, sz, u8p, vp, u8p, u8p]
+    lib.act_node_issue_sign_cbor_batch.argtypes = [vp, sz, u8p, u8p, u8p, u8p, u8p, i32, u8p, u8p]
+    lib.act_node_issue_cbor_batch.argtypes = [vp, sz, u8p, u8p, vp, u8p, u8p, i32, u8p, u8p]
     lib.act_ctx_host_hash_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64), i32]
     lib.act_ctx_set_tiny_calls.argtypes = [vp, i32]
     lib.act_node_set_balance.argtypes = [vp, i32, i32]
@@ -611,6 +619,43 @@ class Engine:
         else:
             self._ck(self.lib.act_redeem_cbor_batch(self.ctx, nullifier_set.h, n, mem, ps, p_cbor, p_offsets or None, p_rng, rng_mode, p_out, p_status))
 
+    # ---- issuance on wire bytes (act_issue_*cbor_batch): IssuanceRequest messages in, IssuanceResponse messages out ----------------
+    def issue_cbor(self, sk: bytes, messages: list, c: bytes, rng, rng_mode: int = RNG_PER_LANE):
+        """CBOR IssuanceRequest messages (byte strings of any length) -> (statuses, list of CBOR IssuanceResponse messages; b"" for a lane
+        that was not signed)"""
+        n = len(messages); p0, k0, offs = _msgs(messages); ml = self.cbor_size("IssuanceResponse")
+        st = np.zeros(n, np.uint8); out = np.zeros(ml * n, np.uint8); ps, ks = _in(sk, 64); p1, k1 = _in(c, 32 * n); pr, kr = _rng_arg(rng)
+        self._ck(self.lib.act_issue_cbor_batch(self.ctx, n, MEM_HOST, ps, p0, offs.ctypes.data, p1, pr, rng_mode, out.ctypes.data, st.ctypes.data))
+        b = out.tobytes()
+        assert all(st[i] == 0 or not out[i * ml:(i + 1) * ml].any() for i in range(n)), "a failed lane's slot is not zero"
+        return st.tobytes(), [b[i * ml:(i + 1) * ml] if st[i] == 0 else b"" for i in range(n)]
+
+    def issue_check_cbor(self, messages: list):
+        """-> (statuses, requests as from_cbor returns them: n*128 bytes, zero where the status is not 0)"""
+        n = len(messages); p0, k0, offs = _msgs(messages)
+        st = np.zeros(n, np.uint8); req = np.zeros(128 * n, np.uint8)
+        self._ck(self.lib.act_issue_check_cbor_batch(self.ctx, n, MEM_HOST, p0, offs.ctypes.data, st.ctypes.data, req.ctypes.data))
+        return st.tobytes(), req.tobytes()
+
+    def issue_sign_cbor(self, sk: bytes, req: bytes, c: bytes, status_in: bytes, rng, rng_mode: int = RNG_SEQUENTIAL):
+        n = len(status_in); ml = self.cbor_size("IssuanceResponse"); st = np.zeros(n, np.uint8); out = np.zeros(ml * n, np.uint8)
+        ps, ks = _in(sk, 64); p0, k0 = _in(req, 128 * n); p1, k1 = _in(c, 32 * n); p2, k2 = _in(status_in, n); pr, kr = _rng_arg(rng)
+        self._ck(self.lib.act_issue_sign_cbor_batch(self.ctx, n, MEM_HOST, ps, p0, p1, p2, pr, rng_mode, out.ctypes.data, st.ctypes.data))
+        b = out.tobytes()
+        return st.tobytes(), [b[i * ml:(i + 1) * ml] if st[i] == 0 else b"" for i in range(n)]
+
+    def issue_cbor_ptr(self, sk: bytes, n: int, mem: int, p_cbor: int, p_offsets: int, p_c: int, p_rng: int, rng_mode: int, p_out: int, p_status: int):
+        """act_issue_cbor_batch on raw pointers of either kind (device-memory callers); p_offsets: host memory or 0"""
+        ps, ks = _in(sk, 64)
+        self._ck(self.lib.act_issue_cbor_batch(self.ctx, n, mem, ps, p_cbor, p_offsets or None, p_c, p_rng, rng_mode, p_out, p_status))
+
+    def issue_check_cbor_ptr(self, n: int, mem: int, p_cbor: int, p_offsets: int, p_status: int, p_req: int = 0):
+        self._ck(self.lib.act_issue_check_cbor_batch(self.ctx, n, mem, p_cbor, p_offsets or None, p_status, p_req or None))
+
+    def issue_sign_cbor_ptr(self, sk: bytes, n: int, mem: int, p_req: int, p_c: int, p_status_in: int, p_rng: int, rng_mode: int, p_out: int, p_status: int):
+        ps, ks = _in(sk, 64)
+        self._ck(self.lib.act_issue_sign_cbor_batch(self.ctx, n, mem, ps, p_req, p_c, p_status_in, p_rng, rng_mode, p_out, p_status))
+
     def host_hash_stats(self, reset: bool = False) -> dict:
         """host-transcript mode: seconds the calling thread waited for transcripts / hashed them, bytes hashed, since the last reset"""
         w, hs, b = C.c_double(0), C.c_double(0), C.c_uint64(0)
@@ -831,6 +876,28 @@ class Node:
         n = len(messages); p0, k0, offs, ml = self._wire(messages)
         st = np.zeros(n, np.uint8); out = np.zeros(ml * n, np.uint8); ps, ks = _in(sk, 64); pr, kr = _rng_arg(rng)
         self._ck(self.lib.act_node_redeem_cbor_batch(self.nd, nullifier_set.h, n, ps, p0, offs.ctypes.data, pr, rng_mode, out.ctypes.data, st.ctypes.data))
+        b = out.tobytes()
+        return st.tobytes(), [b[i * ml:(i + 1) * ml] if st[i] == 0 else b"" for i in range(n)]
+
+    def issue_cbor(self, sk: bytes, messages: list, c: bytes, rng, rng_mode: int = RNG_SEQUENTIAL):
+        n = len(messages); p0, k0, offs = _msgs(messages)
+        ml = self.lib.act_cbor_size(self.lib.act_node_ctx(self.nd, 0), CBOR_TYPES["IssuanceResponse"])
+        st = np.zeros(n, np.uint8); out = np.zeros(ml * n, np.uint8); ps, ks = _in(sk, 64); p1, k1 = _in(c, 32 * n); pr, kr = _rng_arg(rng)
+        self._ck(self.lib.act_node_issue_cbor_batch(self.nd, n, ps, p0, offs.ctypes.data, p1, pr, rng_mode, out.ctypes.data, st.ctypes.data))
+        b = out.tobytes()
+        return st.tobytes(), [b[i * ml:(i + 1) * ml] if st[i] == 0 else b"" for i in range(n)]
+
+    def issue_check_cbor(self, messages: list):
+        n = len(messages); p0, k0, offs = _msgs(messages)
+        st = np.zeros(n, np.uint8); req = np.zeros(128 * n, np.uint8)
+        self._ck(self.lib.act_node_issue_check_cbor_batch(self.nd, n, p0, offs.ctypes.data, st.ctypes.data, req.ctypes.data))
+        return st.tobytes(), req.tobytes()
+
+    def issue_sign_cbor(self, sk: bytes, req: bytes, c: bytes, status_in: bytes, rng, rng_mode: int = RNG_SEQUENTIAL):
+        n = len(status_in); ml = self.lib.act_cbor_size(self.lib.act_node_ctx(self.nd, 0), CBOR_TYPES["IssuanceResponse"])
+        st = np.zeros(n, np.uint8); out = np.zeros(ml * n, np.uint8)
+        ps, ks = _in(sk, 64); p0, k0 = _in(req, 128 * n); p1, k1 = _in(c, 32 * n); p2, k2 = _in(status_in, n); pr, kr = _rng_arg(rng)
+        self._ck(self.lib.act_node_issue_sign_cbor_batch(self.nd, n, ps, p0, p1, p2, pr, rng_mode, out.ctypes.data, st.ctypes.data))
         b = out.tobytes()
         return st.tobytes(), [b[i * ml:(i + 1) * ml] if st[i] == 0 else b"" for i in range(n)]
 

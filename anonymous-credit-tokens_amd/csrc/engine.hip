@@ -63,11 +63,11 @@ const uint8_t kGeneratorEnc[32] = {0xe2, 0xf2, 0xae, 0x0a, 0x6a, 0xbc, 0x4e, 0x7
 
 enum ProfId { PK_SPEND_PREP, PK_SPEND_PREP_A, PK_SPEND_PREP_B, PK_SPEND_PREP_C, PK_SPEND_PREP_JOIN, PK_SPEND_COORDS, PK_SPEND_BITS, PK_SPEND_ENC, PK_SPEND_TAIL, PK_HASH_SPEND, PK_SPEND_FINISH, PK_SIGN_A, PK_HASH_SMALL, PK_SIGN_B,
               PK_ISSUE_A, PK_ISSUE_CHECK, PK_REQUEST_A, PK_REQUEST_B, PK_PROVE_HEAD, PK_PROVE_BITS, PK_PROVE_ENC, PK_PROVE_TAIL, PK_PROVE_RESP,
-              PK_CLIENT, PK_COPY_H2D, PK_COPY_D2H, PK_COUNT };
+              PK_CLIENT, PK_COPY_H2D, PK_COPY_D2H, PK_ISSUE_A_WIRE, PK_SIGN_B_FRAME, PK_COUNT };
 const char* const kProfNames[PK_COUNT] = {"k_spend_prep", "k_spend_prep_a", "k_spend_prep_b", "k_spend_prep_c", "k_spend_prep_join", "k_spend_coords", "k_spend_bits", "k_spend_enc", "k_spend_tail", "k_hash_xof(spend)", "k_spend_finish",
                                           "k_sign_a", "k_hash_xof(small)", "k_sign_b", "k_issue_a", "k_issue_check", "k_request_a",
                                           "k_request_b", "k_prove_head", "k_prove_bits", "k_prove_enc", "k_prove_tail", "k_prove_resp", "k_client_verify",
-                                          "copy_h2d(bulk)", "copy_d2h(transcripts)"};
+                                          "copy_h2d(bulk)", "copy_d2h(transcripts)", "k_issue_a_wire", "k_sign_b_frame"};
 
 struct PendingProf { int id; hipEvent_t e0, e1; uint64_t lanes; };
 
@@ -573,10 +573,13 @@ int prepare_rng_slots(act_ctx* c, Slot& sl, uint32_t m, size_t off, int mem, con
 uint32_t* group_counters(act_ctx* c, const Slot& sl) { return c->d_group_ctr + (size_t)(&sl - c->slots) * (GROUP_CTR_WORDS / 2); }
 // (tiny calls: see request_tiny further down)  ACT_NO_FUSED_TINY=1 keeps the multi-launch paths (A/B; the tests compare the two)
 bool tiny_enabled(const act_ctx* c) { return !tune(T_NO_FUSED_TINY) && c->tiny_on.load(); }
-int sign_phase(act_ctx* c, Slot& sl, uint32_t m, int label, const uint8_t* d_rng, const uint8_t* d_camount, uint8_t* d_out) {
+// `frame` (issue only): d_out takes IssuanceResponse messages framed by phase B (k_sign_b_frame) instead of records -- always the
+// three-launch form, whose phase B does the framing
+struct FrameOut { const uint8_t* tmpl; const uint32_t* off; uint32_t len; };
+int sign_phase(act_ctx* c, Slot& sl, uint32_t m, int label, const uint8_t* d_rng, const uint8_t* d_camount, uint8_t* d_out, const FrameOut* frame = nullptr) {
   ACT_RANGE("sign.phaseA+hash+phaseB m=%zu label=%zu", (size_t)m, (size_t)label);
   sl.d_trs_dirty = std::max(sl.d_trs_dirty, (size_t)m);
-  if (m <= TINY_MAX && tiny_enabled(c)) {
+  if (m <= TINY_MAX && tiny_enabled(c) && !frame) {
     // tiny calls: phase A, the transcript's BLAKE3 (one chunk, in the kernel: same bytes as either transcript mode) and phase B in
     // ONE launch, the five transcript points on three wavefronts (k_sign.hip k_sign_fused); nothing secret reaches global memory
     SignFusedArgs f{}; f.P = c->P; f.K = c->key; f.n = m; f.label = label; f.xa = sl.d_xa; f.rng_slot = sl.d_slot; f.c_amount = d_camount;
@@ -585,11 +588,12 @@ int sign_phase(act_ctx* c, Slot& sl, uint32_t m, int label, const uint8_t* d_rng
   }
   SignArgs s{}; s.P = c->P; s.K = c->key; s.n = m; s.label = label; s.xa = sl.d_xa; s.status = sl.d_status; s.rng_slot = sl.d_slot;
   s.rng = d_rng; s.c_amount = d_camount; s.trs = sl.d_trs; s.state = sl.d_state; s.xof = sl.d_xof; s.out = d_out; s.pbk = sl.d_buckets;
+  if (frame) { s.frame = frame->tmpl; s.frame_off = frame->off; s.frame_len = frame->len; }
   int rc;
   if ((rc = prof_launch(c, sl, PK_SIGN_A, m, [&] { launch_sign_a(s, sl.stream); }))) return rc;
   uint32_t len = c->P.prefix_len[label] + 40u * (label == LABEL_RESPOND ? 7u : 6u);
   if ((rc = hash_step(c, sl, PK_HASH_SMALL, sl.d_trs, SMALL_TR_STRIDE, len, m))) return rc;
-  return prof_launch(c, sl, PK_SIGN_B, m, [&] { launch_sign_b(s, sl.stream); });
+  return prof_launch(c, sl, frame ? PK_SIGN_B_FRAME : PK_SIGN_B, m, [&] { launch_sign_b(s, sl.stream); });
 }
 
 // ---- spend verification, pipelined over two slots ----------------------------------------------------------
@@ -1254,4 +1258,5 @@ int act_refund_batch(act_ctx* c, size_t n, int mem, const uint8_t sk[64], const 
 }  // extern "C"
 
 #include "cbor_impl.inc"
+#include "issue_wire_impl.inc"
 #include "nullifier_impl.inc"

@@ -121,16 +121,67 @@ void launch_sign_a(const SignArgs& a, hipStream_t s) {
   if (a.n <= SIGN_WIDE_MAX && !no_wide) hipLaunchKernelGGL(k_sign_a_wide, dim3((a.n + 63) / 64, 4), dim3(64), 0, s, a);
   else hipLaunchKernelGGL(k_sign_a, dim3((a.n + 63) / 64), dim3(64), 0, s, a);
 }
-void launch_sign_b(const SignArgs& a, hipStream_t s) { if (a.n) hipLaunchKernelGGL(k_sign_b, dim3((a.n + 255) / 256), dim3(256), 0, s, a); }
+
+// Framed output of phase B (act_issue_sign_cbor_batch / act_issue_cbor_batch): IssuanceResponse::to_cbor (src/cbor.rs:162-175) written by the
+// lane that signed -- the template's framing bytes, then A | e | gamma | z | c at their offsets, byte-aligned 16-byte stores.  Issuance
+// runs at ~25 M/s: framed on the host that would be ~4.4 GB/s of host writes (the refund wire path frames on host workers at 0.5 M/s).
+__global__ void __launch_bounds__(256) k_sign_b_frame(SignArgs a) {
+  uint32_t p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= a.n) return;
+  uint8_t* out = a.out + (size_t)p * a.frame_len;
+  if (a.status[p] != 0) {                                         // frame_len is a multiple of 16 (176)
+    const uint4 z4 = make_uint4(0, 0, 0, 0);
+    for (uint32_t i = 0; i < a.frame_len; i += 16) __builtin_memcpy(out + i, &z4, 16);
+    return;
+  }
+  const uint32_t* stt = a.state + (size_t)p * 24;
+  sc e, alpha; uint32_t enc_a[8], w[16];
+  for (int i = 0; i < 8; i++) { e.v[i] = stt[i]; alpha.v[i] = stt[8 + i]; enc_a[i] = stt[16 + i]; }
+  for (int i = 0; i < 16; i++) w[i] = a.xof[(size_t)p * 16 + i];
+  const sc gamma = sc_from_wide_words(w);
+  const sc z = sc_muladd(gamma, sc_add(a.K.x, e), alpha);         // :660
+  const sc c = load_sc(a.c_amount + (size_t)p * 32);
+  const uint32_t* pay[5] = {enc_a, e.v, gamma.v, z.v, c.v};
+  for (uint32_t f = 0, prev = 0; f < 5; prev = a.frame_off[f] + 32, f++) {
+    for (uint32_t i = prev; i < a.frame_off[f]; i++) out[i] = a.frame[i];
+    store32_bytes(out + a.frame_off[f], pay[f]);
+  }
+}
+void launch_sign_b(const SignArgs& a, hipStream_t s) {
+  if (!a.n) return;
+  if (a.frame) hipLaunchKernelGGL(k_sign_b_frame, dim3((a.n + 255) / 256), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(k_sign_b, dim3((a.n + 255) / 256), dim3(256), 0, s, a);
+}
 
 // ---- issue, phase A: K1 = k_bar h2 + r_bar h3 - gamma K (:629-630); X_A = g + c h1 + K (:644) --------------
-__global__ void __launch_bounds__(64, 2) k_issue_a(IssueArgs a) {
-  uint32_t p = blockIdx.x * 64 + threadIdx.x;
-  if (p >= a.n) return;
-  const uint8_t* rec = a.req + (size_t)p * 128;
-  uint32_t wk[8]; load8(wk, rec);
+// WIRE (k_issue_a_wire): the lane reads IssuanceRequest message p in place (IssuanceRequest::from_cbor, src/cbor.rs:118-148, for the
+// canonical encoding): its 13 framing bytes against the template, its four payloads with byte-aligned 16-byte loads; it writes the
+// record from_cbor returns (scalars reduced: decode_scalar) to rec_out and decodes K once, here.  A message that is not byte-for-byte
+// canonical gets wire flag 0x80, a zero record and status 255 for now: the host reader settles it (issue_wire_impl.inc).
+template <bool WIRE>
+__device__ __forceinline__ void issue_a_lane(const IssueArgs& a, uint32_t p) {
+  uint32_t wk[8];
+  sc gamma, k_bar, r_bar;
+  if (WIRE) {
+    const uint64_t beg = a.wire_off ? a.wire_off[p] : (uint64_t)p * a.msg_len, end = a.wire_off ? a.wire_off[p + 1] : beg + a.msg_len;
+    const uint8_t* src = a.wire + beg;
+    bool canon = end - beg >= a.msg_len;                          // ciborium reads one item and ignores trailing bytes: a canonical prefix is enough
+    for (uint32_t f = 0, prev = 0; canon && f < 4; prev = a.pay_off[f] + 32, f++)
+      for (uint32_t i = prev; i < a.pay_off[f]; i++) canon = canon && src[i] == a.tmpl[i];
+    uint8_t* rec = a.rec_out + (size_t)p * 128;
+    a.wire_flags[a.first + p] = canon ? 0 : 0x80;
+    if (!canon) { for (int i = 0; i < 128; i += 32) zero8(rec + i); a.flags[p] = FLAG_UNDECODABLE; return; }
+    uint32_t w[8];
+    load32_bytes(wk, src + a.pay_off[0]); store8(rec, wk);
+    load32_bytes(w, src + a.pay_off[1]); gamma = sc_from_words(w); store_sc(rec + 32, gamma);
+    load32_bytes(w, src + a.pay_off[2]); k_bar = sc_from_words(w); store_sc(rec + 64, k_bar);
+    load32_bytes(w, src + a.pay_off[3]); r_bar = sc_from_words(w); store_sc(rec + 96, r_bar);
+  } else {
+    const uint8_t* rec = a.req + (size_t)p * 128;
+    load8(wk, rec);
+    gamma = load_sc(rec + 32); k_bar = load_sc(rec + 64); r_bar = load_sc(rec + 96);
+  }
   ge K; uint32_t flags = ristretto_decode(K, wk) ? 0u : FLAG_UNDECODABLE;
-  sc gamma = load_sc(rec + 32), k_bar = load_sc(rec + 64), r_bar = load_sc(rec + 96);
   ge acc[1];
   acc[0] = fixed_base_acc(ge_identity(), a.P.tab[BASE_H2], k_bar);
   acc[0] = fixed_base_acc(acc[0], a.P.tab[BASE_H3], r_bar);
@@ -148,6 +199,16 @@ __global__ void __launch_bounds__(64, 2) k_issue_a(IssueArgs a) {
     ge_store(a.xa + (size_t)p * GE_WORDS, xa);
   }
   a.flags[p] = flags;
+}
+__global__ void __launch_bounds__(64, 2) k_issue_a(IssueArgs a) {
+  uint32_t p = blockIdx.x * 64 + threadIdx.x;
+  if (p >= a.n) return;
+  issue_a_lane<false>(a, p);
+}
+__global__ void __launch_bounds__(64, 2) k_issue_a_wire(IssueArgs a) {
+  uint32_t p = blockIdx.x * 64 + threadIdx.x;
+  if (p >= a.n) return;
+  issue_a_lane<true>(a, p);
 }
 // X_A alone, for the sign-only entry points (act_issue_sign_batch / act_refund_sign_batch: the node dispatcher's second
 // phase): issue X_A = g + c h1 + K (:644) from the request, refund X_A = g + K' (:848) from the enc(K') that
@@ -174,6 +235,7 @@ __global__ void __launch_bounds__(256) k_issue_check(IssueArgs a) {
   a.status[p] = stt;
 }
 void launch_issue_a(const IssueArgs& a, hipStream_t s) { if (a.n) hipLaunchKernelGGL(k_issue_a, dim3((a.n + 63) / 64), dim3(64), 0, s, a); }
+void launch_issue_a_wire(const IssueArgs& a, hipStream_t s) { if (a.n) hipLaunchKernelGGL(k_issue_a_wire, dim3((a.n + 63) / 64), dim3(64), 0, s, a); }
 void launch_issue_check(const IssueArgs& a, hipStream_t s) { if (a.n) hipLaunchKernelGGL(k_issue_check, dim3((a.n + 255) / 256), dim3(256), 0, s, a); }
 
 // ---- PreIssuance::request (:463-487) ---------------------------------------------------------------------

@@ -136,6 +136,9 @@ struct SignArgs {
   const uint32_t* xof;
   uint8_t* out;              // n * 128 (refund) or n * 160 (issue)
   uint32_t* pbk;             // n * 2 * BUCKET_WORDS: per-proof Pippenger buckets (msm.h chain_b)
+  // framed output (issue only; k_sign_b_frame): `out` takes n IssuanceResponse messages of frame_len bytes -- the canonical template
+  // `frame` with A | e | gamma | z | c at frame_off[0..4] -- instead of records; an unsigned lane gets an all-zero slot
+  const uint8_t* frame; const uint32_t* frame_off; uint32_t frame_len;
 };
 
 // k_sign_fused (k_sign.hip): the whole signature -- and, with `check`, the request's PoK check beside it -- in one kernel, for tiny calls
@@ -183,6 +186,15 @@ struct IssueArgs {
   const uint32_t* xof;
   uint8_t* status;
   uint32_t* pbk;             // n * 2 * BUCKET_WORDS (msm.h chain_b)
+  // wire mode (k_issue_a_wire): lane p reads IssuanceRequest message p of the chunk in place instead of record p
+  const uint8_t* wire;       // the chunk's message bytes
+  const uint64_t* wire_off;  // n + 1 offsets relative to `wire`, or null: canonical-size messages back to back
+  const uint8_t* tmpl;       // the canonical message (msg_len bytes) and the offsets of its four payloads (cbor_impl.inc cbor_layout)
+  const uint32_t* pay_off;
+  uint32_t msg_len;
+  uint8_t* rec_out;          // n * 128: the record from_cbor returns (K as on the wire, scalars reduced), what k_issue_check (req) and the sign phase read
+  uint8_t* wire_flags;       // wire_flags[first + p] = 0x80: not the canonical encoding (record zero, status 255 until the host reader settles it)
+  uint32_t first;
 };
 
 struct RequestArgs {
@@ -299,6 +311,7 @@ void launch_sign_b(const SignArgs& a, hipStream_t s);
 void launch_sign_xa(const SignXaArgs& a, hipStream_t s);
 void launch_sign_fused(const SignFusedArgs& a, bool check, hipStream_t s);
 void launch_issue_a(const IssueArgs& a, hipStream_t s);
+void launch_issue_a_wire(const IssueArgs& a, hipStream_t s);     // k_issue_a_wire: the same phase from wire bytes (IssueArgs wire mode)
 void launch_issue_check(const IssueArgs& a, hipStream_t s);
 void launch_request_a(const RequestArgs& a, hipStream_t s);
 void launch_request_b(const RequestArgs& a, hipStream_t s);
@@ -404,6 +417,25 @@ ACT_HD void zero8(uint8_t* p) {
   uint4* q = reinterpret_cast<uint4*>(p); q[0] = make_uint4(0, 0, 0, 0); q[1] = make_uint4(0, 0, 0, 0);
 #else
   memset(p, 0, 32);
+#endif
+}
+// 32 bytes at any byte offset (CBOR payloads: the framing in front of them puts them at every residue mod 4).  gfx950 takes
+// byte-aligned dwordx4 accesses to global memory (what the compiler emits for a 16-byte memcpy): two of those, not 32 byte accesses
+ACT_HD void load32_bytes(uint32_t w[8], const uint8_t* p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  uint4 a, b;
+  __builtin_memcpy(&a, p, 16); __builtin_memcpy(&b, p + 16, 16);
+  w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w; w[4] = b.x; w[5] = b.y; w[6] = b.z; w[7] = b.w;
+#else
+  memcpy(w, p, 32);
+#endif
+}
+ACT_HD void store32_bytes(uint8_t* p, const uint32_t w[8]) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const uint4 a = make_uint4(w[0], w[1], w[2], w[3]), b = make_uint4(w[4], w[5], w[6], w[7]);
+  __builtin_memcpy(p, &a, 16); __builtin_memcpy(p + 16, &b, 16);
+#else
+  memcpy(p, w, 32);
 #endif
 }
 ACT_HD sc load_sc(const uint8_t* p) { uint32_t w[8]; load8(w, p); return sc_from_words(w); }

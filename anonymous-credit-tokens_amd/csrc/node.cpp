@@ -11,6 +11,7 @@
 #include <chrono>
 #include <sys/random.h>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -430,6 +431,17 @@ int act_node_refund_cbor_batch(act_node* nd, size_t n, const uint8_t sk[64], con
   if (rc) return rc;
   return refund_sign_any(nd, n, sk, kprime.data(), verdict.data(), rng, rng_mode, true, out_refund_cbor, status);
 }
+
+// The dispatcher for node forms that live in translation units of their own (node_issue_wire.cpp): `run` over the handle, under its
+// lock, fn(context, off, m) per piece.  (The CPU test builds link this file against a mock engine that has only the single-GPU calls used here.)
+}  // extern "C"
+namespace act_node_dispatch {
+int run_pieces(act_node* nd, size_t n, const std::function<int(act_ctx*, size_t, size_t)>& fn) {
+  std::lock_guard<std::mutex> node_lock(nd->mu);
+  return run(nd, n, [&](size_t k, size_t off, size_t m) { return fn(nd->ctx[k], off, m); });
+}
+}  // namespace act_node_dispatch
+extern "C" {
 
 int act_node_refund_to_credit_token_batch(act_node* nd, size_t n, const uint8_t* prerefund, const uint8_t* proof, const uint8_t* refund,
                                           const uint8_t w[32], uint8_t* out_token, uint8_t* status) {

@@ -402,6 +402,37 @@ int act_node_refund_sign_cbor_batch(act_node *node, size_t n, const uint8_t sk[6
 int act_node_refund_cbor_batch(act_node *node, size_t n, const uint8_t sk[64], const uint8_t *cbor, const uint64_t *offsets,
                                const uint8_t *rng, int rng_mode, uint8_t *out_refund_cbor, uint8_t *status);
 
+/* The issuer's other endpoint on wire bytes: IssuanceRequest::from_cbor (src/cbor.rs:118-148), PrivateKey::issue (src/lib.rs:621-663)
+ * and IssuanceResponse::to_cbor (src/cbor.rs:162-175) without an IssuanceRequest, a RistrettoPoint or an IssuanceResponse ever existing on
+ * the host.  Messages are delimited as for act_verify_spend_cbor_batch (offsets[0..n] in host memory, or NULL for canonical-size
+ * messages back to back; bytes after the first item are ignored); c is n*32 scalars as for act_issue_batch.  Message i in, message i
+ * out: out_resp_cbor holds n slots of act_cbor_size(ctx, ACT_CBOR_ISSUANCE_RESPONSE) bytes (176), the canonical IssuanceResponse
+ * message of an accepted lane, all zero for any other lane.  status[i]: 0; ACT_STATUS_INVALID_ISSUANCE_REQUEST_PROOF; 255 = K is not a
+ * canonical Ristretto encoding (CborError::InvalidValue); ACT_STATUS_CBOR_MALFORMED; ACT_STATUS_CBOR_STRUCTURE -- from_cbor's code for
+ * a message that is wrong in several ways (as described at act_cbor_decode_batch).  Canonical messages are unframed by the issue kernel
+ * itself (the message is read once, K decoded once) and the responses framed by the signing kernel; other encodings take the host reader
+ * and one small act_issue_check_batch call.
+ *   act_issue_check_cbor_batch   from_cbor + the PoK check of issue (src/lib.rs:629-640): status, and out_req (nullable, n*128) = the
+ *                                request as from_cbor returns it (K as on the wire, scalars reduced mod l), zero where status != 0 --
+ *                                for a server that decides c after the verdicts
+ *   act_issue_sign_cbor_batch    act_issue_sign_batch for the lanes with status_in == 0, framed as IssuanceResponse messages
+ *   act_issue_cbor_batch         the whole endpoint: from_cbor -> issue -> to_cbor
+ * rng / rng_mode: ACT_RNG_PER_LANE (lane i: rng + 128 i), ACT_RNG_SEQUENTIAL (consecutive slices to the accepted lanes in lane order)
+ * or ACT_RNG_CALLBACK (one draw of 128 x accepted bytes after every verdict is known; a failing draw: ACT_ERR_RNG, nothing signed, every
+ * slot zero).  The node forms cut the batch over the GPUs like every act_node_* call. */
+int act_issue_check_cbor_batch(act_ctx *ctx, size_t n, int mem, const uint8_t *cbor, const uint64_t *offsets,
+                               uint8_t *status, uint8_t *out_req);
+int act_issue_sign_cbor_batch(act_ctx *ctx, size_t n, int mem, const uint8_t sk[64], const uint8_t *req, const uint8_t *c,
+                              const uint8_t *status_in, const uint8_t *rng, int rng_mode, uint8_t *out_resp_cbor, uint8_t *status);
+int act_issue_cbor_batch(act_ctx *ctx, size_t n, int mem, const uint8_t sk[64], const uint8_t *cbor, const uint64_t *offsets,
+                         const uint8_t *c, const uint8_t *rng, int rng_mode, uint8_t *out_resp_cbor, uint8_t *status);
+int act_node_issue_check_cbor_batch(act_node *node, size_t n, const uint8_t *cbor, const uint64_t *offsets, uint8_t *status,
+                                    uint8_t *out_req);
+int act_node_issue_sign_cbor_batch(act_node *node, size_t n, const uint8_t sk[64], const uint8_t *req, const uint8_t *c,
+                                   const uint8_t *status_in, const uint8_t *rng, int rng_mode, uint8_t *out_resp_cbor, uint8_t *status);
+int act_node_issue_cbor_batch(act_node *node, size_t n, const uint8_t sk[64], const uint8_t *cbor, const uint64_t *offsets,
+                              const uint8_t *c, const uint8_t *rng, int rng_mode, uint8_t *out_resp_cbor, uint8_t *status);
+
 /* ======== row f4: the nullifier set and the issuer's whole redemption step ====================================================== */
 /* Nullifier set: the double-spend database the crate leaves to the caller (src/lib.rs:741-745; `HashSet<Scalar>` with
  * "is_spent? reject : insert" per spend in src/tests.rs:29-50, examples/act.rs:10-30), as a hash set in one GPU's HBM.

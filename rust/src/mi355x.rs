@@ -36,6 +36,7 @@ pub struct ActRngSource {
 const ACT_RNG_SEQUENTIAL: c_int = 1;
 const ACT_RNG_CALLBACK: c_int = 2;
 const REFUND_CBOR_BYTES: usize = 141; // act_cbor_size(ctx, ACT_CBOR_REFUND): A4, then four times (key, 58 20, 32 bytes)
+const ISSUANCE_RESPONSE_CBOR_BYTES: usize = 176; // act_cbor_size(ctx, ACT_CBOR_ISSUANCE_RESPONSE): A5, then five times (key, 58 20, 32 bytes)
 const PROOF_FIELDS: usize = 14 + 4 * L;
 const PROOF_BYTES: usize = 32 * PROOF_FIELDS; // 16 832
 const PROVE_RNG_BYTES: usize = 64 * (4 * L + 12); // 33 536: draw order of src/lib.rs:978-1058
@@ -70,6 +71,13 @@ extern "C" {
                                         status: *mut u8, out_kprime: *mut u8) -> c_int;
     fn act_node_refund_cbor_batch(node: *mut ActNode, n: usize, sk: *const u8, cbor: *const u8, offsets: *const u64,
                                   rng: *const u8, rng_mode: c_int, out_refund_cbor: *mut u8, status: *mut u8) -> c_int;
+    // issuance on wire bytes (src/cbor.rs:118-148, src/lib.rs:621-663, src/cbor.rs:162-175)
+    fn act_node_issue_check_cbor_batch(node: *mut ActNode, n: usize, cbor: *const u8, offsets: *const u64, status: *mut u8,
+                                       out_req: *mut u8) -> c_int;
+    fn act_node_issue_sign_cbor_batch(node: *mut ActNode, n: usize, sk: *const u8, req: *const u8, c: *const u8, status_in: *const u8,
+                                      rng: *const u8, rng_mode: c_int, out_resp_cbor: *mut u8, status: *mut u8) -> c_int;
+    fn act_node_issue_cbor_batch(node: *mut ActNode, n: usize, sk: *const u8, cbor: *const u8, offsets: *const u64, c: *const u8,
+                                 rng: *const u8, rng_mode: c_int, out_resp_cbor: *mut u8, status: *mut u8) -> c_int;
     fn act_node_redeem_batch(node: *mut ActNode, set: *mut ActNodeNullifierSet, n: usize, sk: *const u8, proof: *const u8,
                              rng: *const u8, rng_mode: c_int, out_refund: *mut u8, status: *mut u8) -> c_int;
     fn act_node_redeem_cbor_batch(node: *mut ActNode, set: *mut ActNodeNullifierSet, n: usize, sk: *const u8, cbor: *const u8,
@@ -613,6 +621,11 @@ fn refund_messages(out: &[u8], status: &[u8]) -> Vec<Result<Vec<u8>, WireError>>
         .collect()
 }
 
+fn issuance_messages(out: &[u8], status: &[u8]) -> Vec<Result<Vec<u8>, WireError>> {
+    const M: usize = ISSUANCE_RESPONSE_CBOR_BYTES;
+    status.iter().enumerate().map(|(i, &s)| if s == 0 { Ok(out[M * i..M * (i + 1)].to_vec()) } else { Err(status_to_wire_error(s)) }).collect()
+}
+
 impl PrivateKey {
     /// `msgs.iter().map(|m| SpendProof::from_cbor(m).map(|p| self.refund(params, &p, &mut rng)).map(|r| r.to_cbor()))` as ONE call:
     /// CBOR `SpendProof` messages in, CBOR `Refund` messages out, byte for byte what that loop returns, `rng` left where it leaves
@@ -634,6 +647,34 @@ impl PrivateKey {
                                        ACT_RNG_CALLBACK, out.as_mut_ptr(), status.as_mut_ptr())
         });
         refund_messages(&out, &status[..n])
+    }
+    /// `msgs.iter().zip(amounts).map(|(m, c)| IssuanceRequest::from_cbor(m).map(|r| self.issue(params, &r, *c, &mut rng)).map(|r| r.to_cbor()))`
+    /// as ONE call: CBOR `IssuanceRequest` messages in, CBOR `IssuanceResponse` messages out, byte for byte what that loop returns,
+    /// `rng` left where it leaves it (e, alpha are drawn for accepted lanes only, in lane order, after all verdicts: src/lib.rs:638-643).
+    pub fn issue_cbor_batch(&self, params: &Params, msgs: &[&[u8]], amounts: &[Scalar], rng: impl CryptoRngCore) -> Vec<Result<Vec<u8>, WireError>> {
+        let (blob, offsets) = gather(msgs);
+        self.issue_cbor_blob(params, &blob, &offsets, amounts, rng)
+    }
+    /// The same over messages that already lie in one buffer: message i = `blob[offsets[i]..offsets[i + 1]]`.
+    pub fn issue_cbor_blob(&self, params: &Params, blob: &[u8], offsets: &[u64], amounts: &[Scalar], mut rng: impl CryptoRngCore)
+        -> Vec<Result<Vec<u8>, WireError>> {
+        assert!(!offsets.is_empty() && *offsets.last().unwrap() as usize <= blob.len());
+        let n = offsets.len() - 1;
+        assert_eq!(amounts.len(), n);
+        let mut cb = Vec::with_capacity(32 * n + 1);
+        for c in amounts {
+            put_s(&mut cb, c);
+        }
+        cb.push(0);
+        let sk = self.record();
+        let gpu = params.gpu();
+        let src = rng_source(&mut rng);
+        let (mut out, mut status) = (vec![0u8; ISSUANCE_RESPONSE_CBOR_BYTES * n + 1], vec![0u8; n + 1]);
+        gpu.check(unsafe {
+            act_node_issue_cbor_batch(gpu.0, n, sk.as_ptr(), blob.as_ptr(), offsets.as_ptr(), cb.as_ptr(), &src as *const ActRngSource as *const u8,
+                                      ACT_RNG_CALLBACK, out.as_mut_ptr(), status.as_mut_ptr())
+        });
+        issuance_messages(&out, &status[..n])
     }
     /// Verdicts only (`refund` up to the challenge check, src/lib.rs:787-844) for CBOR `SpendProof` messages.
     pub fn verify_spend_cbor_batch(&self, params: &Params, msgs: &[&[u8]]) -> Vec<Result<(), WireError>> {
@@ -990,6 +1031,20 @@ pub mod predrawn {
             act_node_refund_cbor_batch(gpu.0, 1, skr.as_ptr(), msg.as_ptr(), offsets.as_ptr(), nonces.as_ptr(), ACT_RNG_SEQUENTIAL, out.as_mut_ptr(), status.as_mut_ptr())
         });
         refund_messages(&out, &status[..1]).pop().unwrap()
+    }
+    /// One CBOR `IssuanceRequest` message in, one CBOR `IssuanceResponse` message out: unframing, the proof-of-knowledge check and the
+    /// signature beside it (src/lib.rs:629-660).  A rejected message has spent `nonces` on nothing.
+    pub fn issue_cbor(sk: &PrivateKey, params: &Params, msg: &[u8], c: Scalar, nonces: &[u8; 128]) -> Result<Vec<u8>, WireError> {
+        let offsets = [0u64, msg.len() as u64];
+        let mut cb = Vec::with_capacity(32);
+        put_s(&mut cb, &c);
+        let (skr, gpu) = (sk.record(), params.gpu());
+        let (mut out, mut status) = (vec![0u8; ISSUANCE_RESPONSE_CBOR_BYTES + 1], vec![0u8; 2]);
+        gpu.check(unsafe {
+            act_node_issue_cbor_batch(gpu.0, 1, skr.as_ptr(), msg.as_ptr(), offsets.as_ptr(), cb.as_ptr(), nonces.as_ptr(), ACT_RNG_SEQUENTIAL,
+                                      out.as_mut_ptr(), status.as_mut_ptr())
+        });
+        issuance_messages(&out, &status[..1]).pop().unwrap()
     }
     /// The whole redemption step for one message: the refund is computed first (one call), THEN the store decides whether it is handed
     /// out; a rejected message or a double spend has spent `nonces` on nothing.
