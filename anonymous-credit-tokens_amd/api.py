@@ -267,6 +267,69 @@ class PrivateKey(_Cbor):
         return params.engine(nbits).verify_spend(self.record, b"".join(p.record for p in proofs))
 
 
+class Keyring:
+    """Key rotation: an ordered ring of up to four issuer keys (the caller's order of preference -- usually newest first) that one
+    batch is verified and refunded against.  A SpendProof names no key; every method returns what the PrivateKey method of the same
+    name returns PLUS, per proof, the ring index it verified under (None where no ring key accepts it).  `sign_with=None` signs every
+    refund with the key its proof matched; `sign_with=i` signs every accepted lane with ring key i, which moves the client onto that
+    key with its next token (the client then calls to_credit_token with `ring.public(i)`).  The nullifier database is shared by all
+    keys; `Params` must be the ones every ring key issued under."""
+
+    def __init__(self, keys: Sequence[PrivateKey]):
+        if not 1 <= len(keys) <= capi.KEYRING_MAX:
+            raise ValueError("a key ring holds 1 .. %d keys" % capi.KEYRING_MAX)
+        self.keys = list(keys)
+
+    def public(self, i: int) -> PublicKey:
+        return self.keys[i].public()
+
+    def _records(self):
+        return [k.record for k in self.keys]
+
+    def _sign_key(self, sign_with):
+        if sign_with is None:
+            return capi.SIGN_MATCHED
+        if not 0 <= sign_with < len(self.keys):
+            raise ValueError("sign_with is not a ring index")
+        return sign_with
+
+    @staticmethod
+    def _indices(st, ok):
+        return [ok[i] if ok[i] != capi.KEY_NONE else None for i in range(len(st))]
+
+    def verify_spend_batch(self, params: Params, proofs: Sequence["SpendProof"]) -> Tuple[bytes, list]:
+        nbits = proofs[0].nbits if proofs else L
+        st, ok = params.engine(nbits).verify_spend_keyring(self._records(), b"".join(p.record for p in proofs))
+        return st, self._indices(st, ok)
+
+    def refund_batch(self, params: Params, proofs: Sequence["SpendProof"], rng, sign_with=None) -> Tuple[list, list]:
+        nbits = proofs[0].nbits if proofs else L
+        e = params.engine(nbits)
+        pb = b"".join(p.record for p in proofs)
+        sk = self._sign_key(sign_with)
+        matched = []
+
+        def check():
+            st, ok, kp = e.verify_spend_keyring(self._records(), pb, True)
+            matched.append(ok)
+            return st, (kp, ok if sk < 0 else bytes([sk]) * len(st))
+        st, out = _check_then_sign(rng, check, lambda s, st, rb: e.refund_sign_keyring(self._records(), s[1], s[0], st, rb, capi.RNG_SEQUENTIAL))
+        res = [Refund(out[128 * i:128 * i + 128]) if st[i] == 0 else Error(st[i]) for i in range(len(proofs))]
+        return res, self._indices(st, matched[0] if matched else b"")
+
+    def redeem_batch(self, params: Params, db: "NullifierDb", proofs: Sequence["SpendProof"], rng, sign_with=None) -> Tuple[list, list]:
+        nbits = proofs[0].nbits if proofs else L
+        e = params.engine(nbits)
+        pb = b"".join(p.record for p in proofs)
+        st, out, ok = _draw_signed(rng, len(proofs), lambda src, mode: e.redeem_keyring(db.set, self._records(), pb, src, mode, self._sign_key(sign_with)))
+        return [Refund(out[128 * i:128 * i + 128]) if st[i] == 0 else Error(st[i]) for i in range(len(proofs))], self._indices(st, ok)
+
+    def redeem_cbor_batch(self, params: Params, db: "NullifierDb", msgs: Sequence[bytes], rng, nbits: int = L, sign_with=None) -> Tuple[list, list]:
+        e = params.engine(nbits)
+        st, out, ok = _draw_signed(rng, len(msgs), lambda src, mode: e.redeem_cbor_keyring(db.set, self._records(), list(msgs), src, mode, self._sign_key(sign_with)))
+        return [out[i] if st[i] == 0 else _wire_error(st[i]) for i in range(len(msgs))], self._indices(st, ok)
+
+
 class PreIssuance(_Cbor):
     CBOR_TYPE = "PreIssuance"
 

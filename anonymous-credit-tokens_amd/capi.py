@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("ACT_LIB_PATH") or os.path.join(_HERE, "libact_mi355x.
 MEM_HOST, MEM_DEVICE = 0, 1
 RNG_PER_LANE, RNG_SEQUENTIAL, RNG_CALLBACK = 0, 1, 2
 TRANSCRIPT_HOST, TRANSCRIPT_DEVICE = 0, 1
+KEYRING_MAX, KEY_NONE, SIGN_MATCHED = 4, 255, -1      # act_*_keyring_batch: ring size, "no ring key matched", "sign with the matched key"
 _ERRS = {1: "ACT_ERR_ARG", 2: "ACT_ERR_HIP", 3: "ACT_ERR_PARAMS", 4: "ACT_ERR_NO_DEVICE", 5: "ACT_ERR_RNG"}
 
 EXPORTS = [
@@ -36,6 +37,8 @@ EXPORTS = [
     "act_node_nullifier_check_and_insert_batch", "act_node_nullifier_set_reserve", "act_node_nullifier_set_export", "act_node_nullifier_contains_batch",
     "act_verify_spend_cbor_keys_batch", "act_node_verify_spend_cbor_keys_batch", "act_refund_sign_cbor_batch", "act_refund_cbor_batch", "act_refund_cbor_keys_batch",
     "act_node_refund_sign_cbor_batch", "act_node_refund_cbor_batch", "act_redeem_cbor_batch", "act_node_redeem_cbor_batch",
+    "act_verify_spend_keyring_batch", "act_refund_sign_keyring_batch", "act_redeem_keyring_batch", "act_redeem_cbor_keyring_batch",
+    "act_node_verify_spend_keyring_batch", "act_node_refund_sign_keyring_batch", "act_node_redeem_keyring_batch", "act_node_redeem_cbor_keyring_batch",
     "act_issue_check_cbor_batch", "act_issue_sign_cbor_batch", "act_issue_cbor_batch",
     "act_node_issue_check_cbor_batch", "act_node_issue_sign_cbor_batch", "act_node_issue_cbor_batch",
     "act_ctx_host_hash_stats", "act_ctx_set_tiny_calls", "act_node_set_balance", "act_node_device_stats", "act_node_balance_state", "act_debug_set_slowdown", "act_debug_fail_next_signs",
@@ -188,6 +191,15 @@ def load() -> C.CDLL:
     lib.act_node_refund_sign_cbor_batch.argtypes = [vp, sz, u8p, u8p, u8p, u8p, i32, u8p, u8p]
     lib.act_node_refund_cbor_batch.argtypes = [vp, sz, u8p, u8p, vp, u8p, i32, u8p, u8p]
     lib.act_redeem_cbor_batch.argtypes = [vp, vp, sz, i32, u8p, u8p, vp, u8p, i32, u8p, u8p]
+    # key rotation: a ring of issuer keys (keys = nkeys x 64 bytes)
+    lib.act_verify_spend_keyring_batch.argtypes = [vp, sz, i32, u8p, i32, u8p, u8p, u8p, u8p]
+    lib.act_refund_sign_keyring_batch.argtypes = [vp, sz, i32, u8p, i32, u8p, u8p, u8p, u8p, i32, u8p, u8p]
+    lib.act_redeem_keyring_batch.argtypes = [vp, vp, sz, i32, u8p, i32, i32, u8p, u8p, i32, u8p, u8p, u8p]
+    lib.act_redeem_cbor_keyring_batch.argtypes = [vp, vp, sz, i32, u8p, i32, i32, u8p, vp, u8p, i32, u8p, u8p, u8p]
+    lib.act_node_verify_spend_keyring_batch.argtypes = [vp, sz, u8p, i32, u8p, u8p, u8p, u8p]
+    lib.act_node_refund_sign_keyring_batch.argtypes = [vp, sz, u8p, i32, u8p, u8p, u8p, u8p, i32, u8p, u8p]
+    lib.act_node_redeem_keyring_batch.argtypes = [vp, vp, sz, u8p, i32, i32, u8p, u8p, i32, u8p, u8p, u8p]
+    lib.act_node_redeem_cbor_keyring_batch.argtypes = [vp, vp, sz, u8p, i32, i32, u8p, vp, u8p, i32, u8p, u8p, u8p]
     lib.act_node_redeem_cbor_batch.argtypes = [vp, vp, sz, u8p, u8p, vp, u8p, i32, u8p, u8p]
     lib.act_issue_check_cbor_batch.argtypes = [vp, sz, i32, u8p, vp, u8p, u8p]
     lib.act_issue_sign_cbor_batch.argtypes = [vp, sz, i32, u8p, u8p, u8p, u8p, u8p, i32, u8p, u8p]
@@ -619,6 +631,55 @@ class Engine:
         else:
             self._ck(self.lib.act_redeem_cbor_batch(self.ctx, nullifier_set.h, n, mem, ps, p_cbor, p_offsets or None, p_rng, rng_mode, p_out, p_status))
 
+    # ---- key rotation: one batch against an ordered ring of issuer keys (act_*_keyring_batch; keys = list of 64-byte sk) ----------
+    def verify_spend_keyring(self, keys, proofs: bytes, want_kprime: bool = False):
+        """-> (statuses, out_key bytes: the ring index every accepted lane verified under, KEY_NONE elsewhere[, enc(K')])"""
+        n = len(proofs) // self.proof_bytes; st = np.zeros(n, np.uint8); ok = np.zeros(n, np.uint8)
+        kp = np.zeros(32 * n, np.uint8) if want_kprime else None
+        pk, kk = _in(b"".join(keys)); p0, k0 = _in(proofs, self.proof_bytes * n)
+        self._ck(self.lib.act_verify_spend_keyring_batch(self.ctx, n, MEM_HOST, pk, len(keys), p0, st.ctypes.data, ok.ctypes.data, kp.ctypes.data if want_kprime else None))
+        return (st.tobytes(), ok.tobytes(), kp.tobytes()) if want_kprime else (st.tobytes(), ok.tobytes())
+
+    def refund_sign_keyring(self, keys, key_index: bytes, kprime: bytes, status_in: bytes, rng: bytes, rng_mode: int = RNG_SEQUENTIAL):
+        n = len(status_in); out = np.zeros(128 * n, np.uint8); st = np.zeros(n, np.uint8)
+        pk, kk = _in(b"".join(keys)); pi, ki = _in(key_index, n); p0, k0 = _in(kprime, 32 * n); p1, k1 = _in(status_in, n); p2, k2 = _in(rng)
+        self._ck(self.lib.act_refund_sign_keyring_batch(self.ctx, n, MEM_HOST, pk, len(keys), pi, p0, p1, p2, rng_mode, out.ctypes.data, st.ctypes.data))
+        return st.tobytes(), out.tobytes()
+
+    def redeem_keyring(self, nullifier_set, keys, proofs: bytes, rng, rng_mode: int = RNG_PER_LANE, sign_key: int = SIGN_MATCHED, raw: bool = False):
+        """-> (statuses, refunds, out_key).  raw=True: (rc, statuses, refunds, out_key), no exception."""
+        n = len(proofs) // self.proof_bytes; out = np.full(128 * n, 7 if raw else 0, np.uint8); st = np.zeros(n, np.uint8); ok = np.zeros(n, np.uint8)
+        pk, kk = _in(b"".join(keys)); p0, k0 = _in(proofs, self.proof_bytes * n); p1, k1 = _rng_arg(rng)
+        rc = self.lib.act_redeem_keyring_batch(self.ctx, nullifier_set.h, n, MEM_HOST, pk, len(keys), sign_key, p0, p1, rng_mode, out.ctypes.data, st.ctypes.data, ok.ctypes.data)
+        if raw:
+            return rc, st.tobytes(), out.tobytes(), ok.tobytes()
+        self._ck(rc)
+        return st.tobytes(), out.tobytes(), ok.tobytes()
+
+    def redeem_cbor_keyring(self, nullifier_set, keys, messages: list, rng, rng_mode: int = RNG_SEQUENTIAL, sign_key: int = SIGN_MATCHED):
+        """wire bytes in, wire bytes out -> (statuses, list of CBOR Refund messages (b"" where not signed), out_key)"""
+        n = len(messages); p0, k0, offs = _msgs(messages); ml = self.cbor_size("Refund")
+        st = np.zeros(n, np.uint8); ok = np.zeros(n, np.uint8); out = np.zeros(ml * n, np.uint8); pk, kk = _in(b"".join(keys)); pr, kr = _rng_arg(rng)
+        self._ck(self.lib.act_redeem_cbor_keyring_batch(self.ctx, nullifier_set.h, n, MEM_HOST, pk, len(keys), sign_key, p0, offs.ctypes.data, pr, rng_mode,
+                                                        out.ctypes.data, st.ctypes.data, ok.ctypes.data))
+        b = out.tobytes()
+        assert all(st[i] == 0 or not out[i * ml:(i + 1) * ml].any() for i in range(n)), "a failed lane's slot is not zero"
+        return st.tobytes(), [b[i * ml:(i + 1) * ml] if st[i] == 0 else b"" for i in range(n)], ok.tobytes()
+
+    def keyring_ptr(self, fn: str, keys, n: int, mem: int, **p):
+        """the ring calls on raw pointers of either kind (device-memory callers): fn = verify / sign / redeem / redeem_cbor"""
+        pk, kk = _in(b"".join(keys)); nk = len(keys)
+        if fn == "verify":
+            self._ck(self.lib.act_verify_spend_keyring_batch(self.ctx, n, mem, pk, nk, p["proofs"], p["status"], p["out_key"], p.get("kprime") or None))
+        elif fn == "sign":
+            self._ck(self.lib.act_refund_sign_keyring_batch(self.ctx, n, mem, pk, nk, p["key_index"], p["kprime"], p["status_in"], p["rng"], p["rng_mode"], p["out"], p["status"]))
+        elif fn == "redeem":
+            self._ck(self.lib.act_redeem_keyring_batch(self.ctx, p["set"].h, n, mem, pk, nk, p.get("sign_key", SIGN_MATCHED), p["proofs"], p["rng"], p["rng_mode"],
+                                                       p["out"], p["status"], p["out_key"]))
+        else:
+            self._ck(self.lib.act_redeem_cbor_keyring_batch(self.ctx, p["set"].h, n, mem, pk, nk, p.get("sign_key", SIGN_MATCHED), p["cbor"], p.get("offsets") or None,
+                                                            p["rng"], p["rng_mode"], p["out"], p["status"], p["out_key"]))
+
     # ---- issuance on wire bytes (act_issue_*cbor_batch): IssuanceRequest messages in, IssuanceResponse messages out ----------------
     def issue_cbor(self, sk: bytes, messages: list, c: bytes, rng, rng_mode: int = RNG_PER_LANE):
         """CBOR IssuanceRequest messages (byte strings of any length) -> (statuses, list of CBOR IssuanceResponse messages; b"" for a lane
@@ -878,6 +939,37 @@ class Node:
         self._ck(self.lib.act_node_redeem_cbor_batch(self.nd, nullifier_set.h, n, ps, p0, offs.ctypes.data, pr, rng_mode, out.ctypes.data, st.ctypes.data))
         b = out.tobytes()
         return st.tobytes(), [b[i * ml:(i + 1) * ml] if st[i] == 0 else b"" for i in range(n)]
+
+    # ---- key rotation over the node's GPUs (act_node_*_keyring_batch) ---------------------------------------------------------
+    def verify_spend_keyring(self, keys, proofs: bytes, want_kprime: bool = False):
+        n = len(proofs) // self.proof_bytes; st = np.zeros(n, np.uint8); ok = np.zeros(n, np.uint8)
+        kp = np.zeros(32 * n, np.uint8) if want_kprime else None
+        pk, kk = _in(b"".join(keys)); p0, k0 = _in(proofs, self.proof_bytes * n)
+        self._ck(self.lib.act_node_verify_spend_keyring_batch(self.nd, n, pk, len(keys), p0, st.ctypes.data, ok.ctypes.data, kp.ctypes.data if want_kprime else None))
+        return (st.tobytes(), ok.tobytes(), kp.tobytes()) if want_kprime else (st.tobytes(), ok.tobytes())
+
+    def refund_sign_keyring(self, keys, key_index: bytes, kprime: bytes, status_in: bytes, rng: bytes, rng_mode: int = RNG_SEQUENTIAL):
+        n = len(status_in); out = np.zeros(128 * n, np.uint8); st = np.zeros(n, np.uint8)
+        pk, kk = _in(b"".join(keys)); pi, ki = _in(key_index, n); p0, k0 = _in(kprime, 32 * n); p1, k1 = _in(status_in, n); p2, k2 = _in(rng)
+        self._ck(self.lib.act_node_refund_sign_keyring_batch(self.nd, n, pk, len(keys), pi, p0, p1, p2, rng_mode, out.ctypes.data, st.ctypes.data))
+        return st.tobytes(), out.tobytes()
+
+    def redeem_keyring(self, nullifier_set, keys, proofs: bytes, rng, rng_mode: int = RNG_SEQUENTIAL, sign_key: int = SIGN_MATCHED, raw: bool = False):
+        n = len(proofs) // self.proof_bytes; out = np.full(128 * n, 7 if raw else 0, np.uint8); st = np.zeros(n, np.uint8); ok = np.zeros(n, np.uint8)
+        pk, kk = _in(b"".join(keys)); p0, k0 = _in(proofs, self.proof_bytes * n); p1, k1 = _rng_arg(rng)
+        rc = self.lib.act_node_redeem_keyring_batch(self.nd, nullifier_set.h, n, pk, len(keys), sign_key, p0, p1, rng_mode, out.ctypes.data, st.ctypes.data, ok.ctypes.data)
+        if raw:
+            return rc, st.tobytes(), out.tobytes(), ok.tobytes()
+        self._ck(rc)
+        return st.tobytes(), out.tobytes(), ok.tobytes()
+
+    def redeem_cbor_keyring(self, nullifier_set, keys, messages: list, rng, rng_mode: int = RNG_SEQUENTIAL, sign_key: int = SIGN_MATCHED):
+        n = len(messages); p0, k0, offs, ml = self._wire(messages)
+        st = np.zeros(n, np.uint8); ok = np.zeros(n, np.uint8); out = np.zeros(ml * n, np.uint8); pk, kk = _in(b"".join(keys)); pr, kr = _rng_arg(rng)
+        self._ck(self.lib.act_node_redeem_cbor_keyring_batch(self.nd, nullifier_set.h, n, pk, len(keys), sign_key, p0, offs.ctypes.data, pr, rng_mode,
+                                                             out.ctypes.data, st.ctypes.data, ok.ctypes.data))
+        b = out.tobytes()
+        return st.tobytes(), [b[i * ml:(i + 1) * ml] if st[i] == 0 else b"" for i in range(n)], ok.tobytes()
 
     def issue_cbor(self, sk: bytes, messages: list, c: bytes, rng, rng_mode: int = RNG_SEQUENTIAL):
         n = len(messages); p0, k0, offs = _msgs(messages)

@@ -606,9 +606,11 @@ namespace {
 constexpr size_t WIRE_SETTLE_WINDOW = 4096;
 }  // namespace
 
+// `ring` (keyring_impl.inc): the same pass against a ring of issuer keys instead of sk -- ring_verify_locked in place of
+// spend_batch_locked, and ring->out_key patched beside the statuses
 static int verify_spend_cbor_impl(act_ctx* c, size_t n, int mem, const uint8_t sk[64], const uint8_t* cbor, const uint64_t* offsets,
-                                  uint8_t* status, uint8_t* out_kprime, uint8_t* out_nullifier) {
-  if (!c || !sk || (n && (!cbor || !status))) return ACT_ERR_ARG;
+                                  uint8_t* status, uint8_t* out_kprime, uint8_t* out_nullifier, const RingSel* ring = nullptr) {
+  if (!c || (!sk && !ring) || (n && (!cbor || !status))) return ACT_ERR_ARG;
   if (n >= ((size_t)1 << 32)) return ACT_ERR_ARG;
   if (offsets) for (size_t i = 0; i < n; i++) if (offsets[i + 1] < offsets[i]) return ACT_ERR_ARG;     // message i = [offsets[i], offsets[i+1])
   Call call(c, n);
@@ -629,10 +631,13 @@ static int verify_spend_cbor_impl(act_ctx* c, size_t n, int mem, const uint8_t s
   HIPCK(c, hipMemsetAsync(c->d_wire_flags, 0, fcap, s0.stream));
   HIPCK(c, hipStreamSynchronize(s0.stream));                 // the other slot's stream reads the layout and the flags too
   WireSrc w{cbor, offsets, ml, out_nullifier};
-  rc = spend_batch_locked(c, n, mem, sk, nullptr, false, nullptr, ACT_RNG_PER_LANE, nullptr, status, out_kprime, &w);
+  const DevKey* d_ring = nullptr;
+  if (ring && (rc = ring_set(c, ring->keys, ring->nkeys, &d_ring))) { c->wire_layout = nullptr; return rc; }
+  rc = ring ? ring_verify_locked(c, n, mem, d_ring, ring->nkeys, nullptr, status, ring->out_key, out_kprime, &w)
+            : spend_batch_locked(c, n, mem, sk, nullptr, false, nullptr, ACT_RNG_PER_LANE, nullptr, status, out_kprime, &w);
   c->wire_layout = nullptr;
   if (rc) return rc;
-  std::vector<uint8_t> flags(n);
+  std::vector<uint8_t> flags(n), ok2, hok;
   HIPCK(c, hipMemcpy(flags.data(), c->d_wire_flags, n, hipMemcpyDeviceToHost));
   std::vector<size_t> which;
   for (size_t i = 0; i < n; i++) if (flags[i] & 0x80) which.push_back(i);
@@ -678,7 +683,9 @@ static int verify_spend_cbor_impl(act_ctx* c, size_t n, int mem, const uint8_t s
     // duplicate key or an over-long array keeps out of the record, is InvalidValue (status 255)
     if ((rc = cbor_settle_codes(c, s0.stream, codes, cands))) return rc;
     if (!good.empty()) {
-      rc = spend_batch_locked(c, good.size(), ACT_MEM_HOST, sk, recs.data(), false, nullptr, ACT_RNG_PER_LANE, nullptr, st2.data(), out_kprime ? kp2.data() : nullptr);
+      if (ring) ok2.assign(cnt, ACT_KEY_NONE);
+      rc = ring ? ring_verify_locked(c, good.size(), ACT_MEM_HOST, d_ring, ring->nkeys, recs.data(), st2.data(), ok2.data(), out_kprime ? kp2.data() : nullptr)
+                : spend_batch_locked(c, good.size(), ACT_MEM_HOST, sk, recs.data(), false, nullptr, ACT_RNG_PER_LANE, nullptr, st2.data(), out_kprime ? kp2.data() : nullptr);
       if (rc) return rc;
       for (size_t g = 0; g < good.size(); g++) verdict[good[g]] = st2[g];
     }
@@ -689,6 +696,7 @@ static int verify_spend_cbor_impl(act_ctx* c, size_t n, int mem, const uint8_t s
     const uint8_t zero32[32] = {0};
     auto kprime_of = [&](size_t k) { return (pos[k] != (size_t)-1 && verdict[k] == 0) ? kp2.data() + pos[k] * 32 : zero32; };
     auto null_of = [&](size_t k) { return pos[k] != (size_t)-1 ? recs.data() + pos[k] * pb : zero32; };          // `k` is the record's first field
+    auto key_of = [&](size_t k) { return (pos[k] != (size_t)-1 && verdict[k] == 0) ? ok2[pos[k]] : (uint8_t)ACT_KEY_NONE; };
     if (dev) {
       // the lanes [first, last] of the caller's device arrays: read once, patched on the host, written back once
       const size_t first = which[w0], lanes = which[w1 - 1] - first + 1;
@@ -696,12 +704,15 @@ static int verify_spend_cbor_impl(act_ctx* c, size_t n, int mem, const uint8_t s
       HIPCK(c, hipMemcpy(hs.data(), status + first, lanes, hipMemcpyDeviceToHost));
       if (out_kprime) { hk.resize(lanes * 32); HIPCK(c, hipMemcpy(hk.data(), out_kprime + first * 32, lanes * 32, hipMemcpyDeviceToHost)); }
       if (out_nullifier) { hn.resize(lanes * 32); HIPCK(c, hipMemcpy(hn.data(), out_nullifier + first * 32, lanes * 32, hipMemcpyDeviceToHost)); }
+      if (ring) { hok.resize(lanes); HIPCK(c, hipMemcpy(hok.data(), ring->out_key + first, lanes, hipMemcpyDeviceToHost)); }
       for (size_t k = 0; k < cnt; k++) {
         const size_t l = which[w0 + k] - first;
         hs[l] = verdict[k];
         if (out_kprime) memcpy(hk.data() + l * 32, kprime_of(k), 32);
         if (out_nullifier) memcpy(hn.data() + l * 32, null_of(k), 32);
+        if (ring) hok[l] = key_of(k);
       }
+      if (ring) HIPCK(c, hipMemcpy(ring->out_key + first, hok.data(), lanes, hipMemcpyHostToDevice));
       HIPCK(c, hipMemcpy(status + first, hs.data(), lanes, hipMemcpyHostToDevice));
       if (out_kprime) HIPCK(c, hipMemcpy(out_kprime + first * 32, hk.data(), lanes * 32, hipMemcpyHostToDevice));
       if (out_nullifier) HIPCK(c, hipMemcpy(out_nullifier + first * 32, hn.data(), lanes * 32, hipMemcpyHostToDevice));
@@ -710,6 +721,7 @@ static int verify_spend_cbor_impl(act_ctx* c, size_t n, int mem, const uint8_t s
         status[which[w0 + k]] = verdict[k];
         if (out_kprime) memcpy(out_kprime + which[w0 + k] * 32, kprime_of(k), 32);
         if (out_nullifier) memcpy(out_nullifier + which[w0 + k] * 32, null_of(k), 32);
+        if (ring) ring->out_key[which[w0 + k]] = key_of(k);
       }
     }
   }

@@ -18,6 +18,7 @@
 #include <thread>
 #include <vector>
 #include "kernels.h"
+#include "keyring.h"
 #include "rng_source.h"
 #include "../../include/act_mi355x.h"
 
@@ -63,11 +64,11 @@ const uint8_t kGeneratorEnc[32] = {0xe2, 0xf2, 0xae, 0x0a, 0x6a, 0xbc, 0x4e, 0x7
 
 enum ProfId { PK_SPEND_PREP, PK_SPEND_PREP_A, PK_SPEND_PREP_B, PK_SPEND_PREP_C, PK_SPEND_PREP_JOIN, PK_SPEND_COORDS, PK_SPEND_BITS, PK_SPEND_ENC, PK_SPEND_TAIL, PK_HASH_SPEND, PK_SPEND_FINISH, PK_SIGN_A, PK_HASH_SMALL, PK_SIGN_B,
               PK_ISSUE_A, PK_ISSUE_CHECK, PK_REQUEST_A, PK_REQUEST_B, PK_PROVE_HEAD, PK_PROVE_BITS, PK_PROVE_ENC, PK_PROVE_TAIL, PK_PROVE_RESP,
-              PK_CLIENT, PK_COPY_H2D, PK_COPY_D2H, PK_ISSUE_A_WIRE, PK_SIGN_B_FRAME, PK_COUNT };
+              PK_CLIENT, PK_COPY_H2D, PK_COPY_D2H, PK_ISSUE_A_WIRE, PK_SIGN_B_FRAME, PK_RING_CAND, PK_RING_HASH, PK_RING_FINISH, PK_COUNT };
 const char* const kProfNames[PK_COUNT] = {"k_spend_prep", "k_spend_prep_a", "k_spend_prep_b", "k_spend_prep_c", "k_spend_prep_join", "k_spend_coords", "k_spend_bits", "k_spend_enc", "k_spend_tail", "k_hash_xof(spend)", "k_spend_finish",
                                           "k_sign_a", "k_hash_xof(small)", "k_sign_b", "k_issue_a", "k_issue_check", "k_request_a",
                                           "k_request_b", "k_prove_head", "k_prove_bits", "k_prove_enc", "k_prove_tail", "k_prove_resp", "k_client_verify",
-                                          "copy_h2d(bulk)", "copy_d2h(transcripts)", "k_issue_a_wire", "k_sign_b_frame"};
+                                          "copy_h2d(bulk)", "copy_d2h(transcripts)", "k_issue_a_wire", "k_sign_b_frame", "k_ring_cand", "k_ring_hash", "k_ring_finish"};
 
 struct PendingProf { int id; hipEvent_t e0, e1; uint64_t lanes; };
 
@@ -84,8 +85,8 @@ struct Slot {
   hipStream_t stream = nullptr;
   uint8_t *d_tr = nullptr, *d_trs = nullptr, *d_status = nullptr;
   uint32_t *d_buckets = nullptr, *d_coords = nullptr, *d_d01 = nullptr, *d_xa = nullptr, *d_flags = nullptr, *d_xof = nullptr, *d_state = nullptr, *d_slot = nullptr, *d_naf = nullptr, *d_dig = nullptr;
-  static constexpr int N_STAGE = 9;
-  uint8_t* d_stage[N_STAGE] = {};   // staging for host-memory callers (grow-only); 5 = key decoding scratch, 6 = records unframed from wire bytes, 7 = their offsets, 8 = CBOR layout tables
+  static constexpr int N_STAGE = 10;
+  uint8_t* d_stage[N_STAGE] = {};   // staging for host-memory callers (grow-only); 5 = key decoding scratch, 6 = records unframed from wire bytes, 7 = their offsets, 8 = CBOR layout tables, 9 = a key ring's decoded keys (slot 0 only; keyring_impl.inc)
   size_t d_stage_cap[N_STAGE] = {};
   size_t d_stage_dirty[N_STAGE] = {};     // bytes written since the last wipe (finish_call)
   size_t d_trs_dirty = 0;                 // lanes of d_trs that a sign-beside-the-check kernel wrote (k_sign_fused<CHECK> / before_verdict): wiped by finish_call
@@ -172,7 +173,9 @@ struct act_ctx {
   uint8_t* d_tiny_tr = nullptr;        // TINY_MAX "request" transcripts of the fused issue kernel
   std::atomic<uint32_t> debug_ns_per_lane{0};    // act_debug_set_slowdown (test hook of the node dispatcher's load balance)
   std::atomic<int> debug_fail_signs{0};          // act_debug_fail_next_signs (test hook of the redeem failure contract)
+  struct RingWs* ring_ws = nullptr;              // key-ring side buffers, allocated by the context's first ring call (keyring_impl.inc)
 };
+static void ring_ws_free(act_ctx* c);            // keyring_impl.inc
 
 namespace {
 
@@ -599,12 +602,13 @@ int sign_phase(act_ctx* c, Slot& sl, uint32_t m, int label, const uint8_t* d_rng
 // ---- spend verification, pipelined over two slots ----------------------------------------------------------
 struct SpendChunk { uint32_t m = 0; size_t off = 0; const uint8_t* d_proofs = nullptr; uint8_t* d_kprime = nullptr; uint8_t* d_out = nullptr; SpendArgs a{}; bool stagger = false; };
 
-// stage 1: everything up to (and including the start of) the transcript hash
-int spend_stage1(act_ctx* c, Slot& sl, SpendChunk& ch) {
+// stage 1: everything up to (and including the start of) the transcript hash.  spend_stage1_kernels = the kernels in front of the hash,
+// under `key` (the context's cached key; a ring call's key 0, keyring_impl.inc)
+int spend_stage1_kernels(act_ctx* c, Slot& sl, SpendChunk& ch, const DevKey& key) {
   ACT_RANGE("spend.phaseA off=%zu m=%zu (prep, bits, enc, tail enqueued; transcripts on their way)", ch.off, (size_t)ch.m);
   const SpendTranscript st{c->L};
   SpendArgs& a = ch.a;
-  a = SpendArgs{}; a.P = c->P; a.K = c->key; a.proofs = ch.d_proofs; a.n = ch.m; a.tr = sl.d_tr; a.tr_stride = (uint32_t)st.stride();
+  a = SpendArgs{}; a.P = c->P; a.K = key; a.proofs = ch.d_proofs; a.n = ch.m; a.tr = sl.d_tr; a.tr_stride = (uint32_t)st.stride();
   a.coords = sl.d_coords; a.d01 = sl.d_d01; a.buckets = sl.d_buckets; a.xa = sl.d_xa; a.flags = sl.d_flags; a.xof = sl.d_xof; a.status = sl.d_status;
   a.kprime_enc = ch.d_kprime; a.naf = sl.d_naf; a.dig = sl.d_dig; a.pbk = sl.d_buckets;
   int rc;
@@ -642,7 +646,12 @@ int spend_stage1(act_ctx* c, Slot& sl, SpendChunk& ch) {
     c->last_bits_sig = sl.bits_sig; c->last_bits_release = wgs > resident ? sl.bits_wgs - resident : before + 1;
   }
   if ((rc = prof_launch(c, sl, PK_SPEND_ENC, (uint64_t)ch.m * c->L * 2, [&] { launch_spend_enc(a, sl.stream); }))) return rc;
-  if ((rc = prof_launch(c, sl, PK_SPEND_TAIL, ch.m, [&] { launch_spend_tail(a, sl.stream); }))) return rc;
+  return prof_launch(c, sl, PK_SPEND_TAIL, ch.m, [&] { launch_spend_tail(a, sl.stream); });
+}
+int spend_stage1(act_ctx* c, Slot& sl, SpendChunk& ch) {
+  const SpendTranscript st{c->L};
+  int rc;
+  if ((rc = spend_stage1_kernels(c, sl, ch, c->key))) return rc;
   if ((rc = hash_begin(c, sl, PK_HASH_SPEND, sl.d_tr, (uint32_t)st.stride(), (uint32_t)st.bytes(), ch.m))) return rc;
   sl.last_spend_lanes = ch.m;
   return ACT_OK;
@@ -778,6 +787,7 @@ void act_ctx_destroy(act_ctx* c) {
   if (c->d_tables_ct) (void)hipFree(c->d_tables_ct);
   if (c->d_tables_mf) (void)hipFree(c->d_tables_mf);
   if (c->d_wire_flags) (void)hipFree(c->d_wire_flags);
+  ring_ws_free(c);
   memset(&c->key, 0, sizeof(c->key)); memset(c->sk_cached, 0, 64);
   delete c;
 }
@@ -1136,21 +1146,9 @@ static int copy_chain_record(act_ctx* c, Slot& sl, bool out);
 
 #include "small_impl.inc"      // the small-batch schedule: small_prepare, SmallGate, spend_small_locked
 
-// verify (sign == false) or refund (sign == true), two-slot software pipeline: stage 1 of chunk i+1 is enqueued before
-// the host touches chunk i again.  The caller holds the context (Call).
-static int spend_batch_locked(act_ctx* c, size_t n, int mem, const uint8_t sk[64], const uint8_t* proof, bool sign, const uint8_t* rng,
-                              int rng_mode, uint8_t* out_refund, uint8_t* status, uint8_t* out_kprime, const WireSrc* wire = nullptr) {
-  int rc = set_key(c, sk); if (rc) return rc;
-  if (n && n <= c->small_max.load() * ((c->tr_mode == ACT_TRANSCRIPT_DEVICE && !c->small_max_set.load()) ? 2u : 1u) && n <= c->max_batch) {
-    if (!wire) return spend_small_locked(c, n, mem, proof, sign, rng, rng_mode, out_refund, status, out_kprime);
-    // wire bytes: all n messages are unframed on slot 0's stream, the small-batch schedule starts from those records
-    const uint8_t* d_records = nullptr;
-    if ((rc = wire_unframe_chunk(c, c->slots[0], *wire, mem, 0, (uint32_t)n, &d_records))) return rc;
-    return spend_small_locked(c, n, mem, nullptr, sign, rng, rng_mode, out_refund, status, out_kprime, d_records);
-  }
-  const size_t pb = ProofLayout{c->L}.bytes();
-  const uint8_t* proof_view = (mem == ACT_MEM_HOST && !wire) ? mapped_view(c, proof, n * pb) : nullptr;      // pinned: the kernels read the proofs in place
-  const bool in_host = mem == ACT_MEM_HOST && !proof_view;       // the proofs travel through the staging buffers
+// The chunk schedule of a pipelined spend-verification call over n proofs: (offset, lanes) per chunk, and whether the range kernels
+// of consecutive chunks are staggered.  `in_host`: the proofs travel through the staging buffers.
+static std::vector<std::pair<size_t, size_t>> spend_schedule(const act_ctx* c, size_t n, bool in_host, bool* stagger_out) {
   const size_t host_chunk_env = (size_t)tune(T_HOST_CHUNK);   // measurement knob (act_tuning_set)
   // host-transcript mode: a chunk's transcripts go to the host, are hashed there and come back before its status kernel, all
   // of which only overlaps with compute if there are other chunks to compute: long batches use full-size chunks (the
@@ -1191,6 +1189,27 @@ static int spend_batch_locked(act_ctx* c, size_t n, int mem, const uint8_t sk[64
     while (left) { size_t l = std::min(chunk_len, left); sched.emplace_back(off, l); off += l; left -= l; }
     for (size_t l : tail) { sched.emplace_back(off, l); off += l; }
   }
+  *stagger_out = stagger;
+  return sched;
+}
+
+// verify (sign == false) or refund (sign == true), two-slot software pipeline: stage 1 of chunk i+1 is enqueued before
+// the host touches chunk i again.  The caller holds the context (Call).
+static int spend_batch_locked(act_ctx* c, size_t n, int mem, const uint8_t sk[64], const uint8_t* proof, bool sign, const uint8_t* rng,
+                              int rng_mode, uint8_t* out_refund, uint8_t* status, uint8_t* out_kprime, const WireSrc* wire = nullptr) {
+  int rc = set_key(c, sk); if (rc) return rc;
+  if (n && n <= c->small_max.load() * ((c->tr_mode == ACT_TRANSCRIPT_DEVICE && !c->small_max_set.load()) ? 2u : 1u) && n <= c->max_batch) {
+    if (!wire) return spend_small_locked(c, n, mem, proof, sign, rng, rng_mode, out_refund, status, out_kprime);
+    // wire bytes: all n messages are unframed on slot 0's stream, the small-batch schedule starts from those records
+    const uint8_t* d_records = nullptr;
+    if ((rc = wire_unframe_chunk(c, c->slots[0], *wire, mem, 0, (uint32_t)n, &d_records))) return rc;
+    return spend_small_locked(c, n, mem, nullptr, sign, rng, rng_mode, out_refund, status, out_kprime, d_records);
+  }
+  const size_t pb = ProofLayout{c->L}.bytes();
+  const uint8_t* proof_view = (mem == ACT_MEM_HOST && !wire) ? mapped_view(c, proof, n * pb) : nullptr;      // pinned: the kernels read the proofs in place
+  const bool in_host = mem == ACT_MEM_HOST && !proof_view;       // the proofs travel through the staging buffers
+  bool stagger = false;
+  const std::vector<std::pair<size_t, size_t>> sched = spend_schedule(c, n, in_host, &stagger);
   const size_t nchunks = sched.size();
   SpendChunk chunks[2];
   size_t cursor = 0;
@@ -1252,6 +1271,8 @@ int act_refund_batch(act_ctx* c, size_t n, int mem, const uint8_t sk[64], const 
   return spend_batch(c, n, mem, sk, proof, true, rng, rng_mode, out_refund, status, nullptr);
 }
 
+#include "keyring_impl.inc"     // key rotation: verification and signing against a ring of issuer keys
+
 #include "client_impl.inc"      // prove_spend and the two to_credit_token calls
 
 #include "debug_impl.inc"       // act_debug_*, act_ubench_*, act_prof_*
@@ -1260,3 +1281,4 @@ int act_refund_batch(act_ctx* c, size_t n, int mem, const uint8_t sk[64], const 
 #include "cbor_impl.inc"
 #include "issue_wire_impl.inc"
 #include "nullifier_impl.inc"
+#include "keyring_redeem_impl.inc"

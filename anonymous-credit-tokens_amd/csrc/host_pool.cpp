@@ -27,6 +27,10 @@
 
 extern "C" void act_host_b3_xof64_x16(const uint8_t* msgs, size_t stride, uint32_t len, uint32_t* xof);   // host_hash.cpp
 
+extern "C" void act_host_b3_xof64_sib_x16(const uint8_t* msgs, size_t stride, uint32_t len, uint32_t* xof, size_t xof_stride, uint32_t* sib, size_t sib_stride);
+extern "C" void act_host_b3_xof64_patched_x16(const uint8_t* msgs, size_t stride, uint32_t len, const uint32_t* sib, size_t sib_stride, uint32_t rep_word,
+                                              const uint8_t* rep, size_t rep_stride, uint32_t* xof, size_t xof_stride);
+
 namespace {
 
 // CPUs this process may actually use: the affinity mask, capped by the cgroup CPU quota (a 16-CPU container on a
@@ -73,6 +77,32 @@ void hash_items(void* p, size_t i0, size_t i1) {
   size_t i = i0;
   for (; i + 16 <= i1; i += 16) act_host_b3_xof64_x16(a.msgs + i * a.stride, a.stride, a.len, a.xof + i * 16);
   for (; i < i1; i++) act::b3_hash_xof64(a.xof + i * 16, reinterpret_cast<const uint32_t*>(a.msgs + i * a.stride), a.len);
+}
+
+// key-ring form (act_host_hash_ring_many): the whole hash once, keeping chunk 0's path siblings, then per extra key the hash of the
+// message with the 32 bytes at rep_word replaced by that key's candidate -- chunk 0 and its ancestors only (blake3_hd.h)
+struct RingHashArgs { const uint8_t* msgs; size_t stride; uint32_t len; uint32_t nkeys, rep_word; const uint8_t* cand; uint32_t* xofs; };
+void ring_hash_items(void* p, size_t i0, size_t i1) {
+  const RingHashArgs& a = *static_cast<const RingHashArgs*>(p);
+  const uint32_t extra = a.nkeys - 1u;
+  const size_t xs = (size_t)a.nkeys * 16;
+  uint32_t sib[16 * act::B3_MAX_SIBLINGS * 8];
+  size_t i = i0;
+  for (; i + 16 <= i1; i += 16) {
+    act_host_b3_xof64_sib_x16(a.msgs + i * a.stride, a.stride, a.len, a.xofs + i * xs, xs, sib, act::B3_MAX_SIBLINGS * 8);
+    for (uint32_t k = 1; k < a.nkeys; k++)
+      act_host_b3_xof64_patched_x16(a.msgs + i * a.stride, a.stride, a.len, sib, act::B3_MAX_SIBLINGS * 8, a.rep_word,
+                                    a.cand + (i * extra + (k - 1u)) * 32, (size_t)extra * 32, a.xofs + i * xs + (size_t)k * 16, xs);
+  }
+  for (; i < i1; i++) {
+    const uint32_t* msg = reinterpret_cast<const uint32_t*>(a.msgs + i * a.stride);
+    act::b3_hash_xof64_sib(a.xofs + i * xs, msg, a.len, [&](uint32_t c, uint32_t* cv) { act::b3_chunk_cv(cv, msg, a.len, c); },
+                           [&](int l, const uint32_t* cv) { memcpy(sib + l * 8, cv, 32); });
+    for (uint32_t k = 1; k < a.nkeys; k++) {
+      uint32_t rep[8]; memcpy(rep, a.cand + (i * extra + (k - 1u)) * 32, 32);
+      act::b3_xof64_patched(a.xofs + i * xs + (size_t)k * 16, msg, a.len, sib, a.rep_word, rep);
+    }
+  }
 }
 
 class Pool {
@@ -150,6 +180,22 @@ void act_host_hash_many(const uint8_t* msgs, size_t stride, uint32_t len, size_t
   HashArgs args{msgs, stride, len, xof};
   auto job = std::make_shared<Job>();
   job->fn = hash_items; job->ctx = &args; job->n = n; job->grain = GRAIN;
+  pool.run(job, par);
+  g_hashing.fetch_sub(1, std::memory_order_acq_rel);
+}
+
+// xofs[(i*nkeys + k)*16 ..] = XOF words of message i with the 32 bytes at byte offset rep_off (a multiple of 4, inside the first
+// KiB) replaced by cand[(i*(nkeys-1) + k-1)*32 ..] for k >= 1, and of the message as it stands for k = 0.
+void act_host_hash_ring_many(const uint8_t* msgs, size_t stride, uint32_t len, size_t n, int max_threads, uint32_t nkeys, uint32_t rep_off,
+                             const uint8_t* cand, uint32_t* xofs) {
+  if (!n || !nkeys) return;
+  Pool& pool = Pool::get();
+  const int active = g_hashing.fetch_add(1, std::memory_order_acq_rel) + 1;
+  int par = std::max(1, pool.size() / active);
+  if (max_threads > 0) par = std::min(par, max_threads);
+  RingHashArgs args{msgs, stride, len, nkeys, rep_off / 4u, cand, xofs};
+  auto job = std::make_shared<Job>();
+  job->fn = ring_hash_items; job->ctx = &args; job->n = n; job->grain = GRAIN;
   pool.run(job, par);
   g_hashing.fetch_sub(1, std::memory_order_acq_rel);
 }

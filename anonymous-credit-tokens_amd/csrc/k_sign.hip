@@ -3,29 +3,33 @@
 // client's PreIssuance::request (:463-487).  Each function is "phase A -> transcript hash -> phase B"
 // (SURVEY.md fact 0.9); the hash runs on the host or in k_hash_xof depending on the context's mode.
 #include "kernels.h"
+#include "keyring.h"
 
 namespace act {
 
 // ---- sign, phase A: e, alpha <- rng;  A = (e+x)^-1 X_A;  X_g = e g + w;  Y_A = alpha A;  Y_g = alpha g --------
 // A and Y_A share X_A's doubling chain: Y_A = (alpha (e+x)^-1) X_A.
-__global__ void __launch_bounds__(64, 2) k_sign_a(SignArgs a) {
+// RING (k_sign_a_ring, key rotation): lane p signs with ring[key_index[p]] -- an entry chosen by a PUBLIC index -- instead of a.K
+template <bool RING>
+__device__ __forceinline__ void sign_a_lane(const SignArgs& a, const DevKey* ring, const uint8_t* key_index) {
   IssuerFb fb{a.P};                                               // nonces and key: no digit of them ever selects an address, in either build
   uint32_t p = blockIdx.x * 64 + threadIdx.x;
   const bool live = p < a.n && a.status[p < a.n ? p : 0] == 0;    // rng is drawn only after verification (:638-643, :842-846)
+  const DevKey& K = RING ? ring[live ? key_index[p] : 0] : a.K;
   sc e = sc_zero(), alpha = sc_zero();
   ge xa = ge_identity();
   ge acc[2] = {ge_identity(), ge_identity()};
   if (live) {
     const uint8_t* rng = a.rng + (size_t)a.rng_slot[p] * 128;
     e = load_wide(rng); alpha = load_wide(rng + 64);              // :643/:649, :846/:852
-    sc inv = sc_invert(sc_add(e, a.K.x));                         // :645 / :849
+    sc inv = sc_invert(sc_add(e, K.x));                           // :645 / :849
     xa = ge_load(a.xa + (size_t)p * GE_WORDS);
     sc s[2] = {inv, sc_mul(alpha, inv)};
     chain_ct<2>(acc, xa, s);                                                                              // acc[0] = A, acc[1] = Y_A (:650 / :853)
   }
   // the two products on g run in every lane of the wavefront, signing or not (IssuerFb: the matrix-core look-up takes its table
   // operand from all 64 lanes; a lane that does not sign multiplies by zero)
-  ge xg = ge_add(fb.mul(ge_identity(), BASE_G, e), a.K.w);        // :646 / :851
+  ge xg = ge_add(fb.mul(ge_identity(), BASE_G, e), K.w);          // :646 / :851
   ge yg = fb.mul(ge_identity(), BASE_G, alpha);                   // :651 / :854
   if (!live) return;
 
@@ -44,8 +48,11 @@ __global__ void __launch_bounds__(64, 2) k_sign_a(SignArgs a) {
   uint32_t* stt = a.state + (size_t)p * 24;
   for (int i = 0; i < 8; i++) { stt[i] = e.v[i]; stt[8 + i] = alpha.v[i]; stt[16 + i] = enc_a[i]; }
 }
+__global__ void __launch_bounds__(64, 2) k_sign_a(SignArgs a) { sign_a_lane<false>(a, nullptr, nullptr); }
+__global__ void __launch_bounds__(64, 2) k_sign_a_ring(SignRingArgs r) { sign_a_lane<true>(r.s, r.ring, r.key_index); }
 // ---- sign, phase B: z = gamma (x + e) + alpha; write Refund {A,e,gamma,z} or IssuanceResponse {A,e,gamma,z,c} ----
-__global__ void __launch_bounds__(256) k_sign_b(SignArgs a) {
+template <bool RING>
+__device__ __forceinline__ void sign_b_lane(const SignArgs& a, const DevKey* ring, const uint8_t* key_index) {
   uint32_t p = blockIdx.x * 256 + threadIdx.x;
   if (p >= a.n) return;
   const int rec = a.label == LABEL_RESPOND ? 160 : 128;
@@ -56,10 +63,16 @@ __global__ void __launch_bounds__(256) k_sign_b(SignArgs a) {
   for (int i = 0; i < 8; i++) { e.v[i] = stt[i]; alpha.v[i] = stt[8 + i]; enc_a[i] = stt[16 + i]; }
   for (int i = 0; i < 16; i++) w[i] = a.xof[(size_t)p * 16 + i];
   sc gamma = sc_from_wide_words(w);
-  sc z = sc_muladd(gamma, sc_add(a.K.x, e), alpha);               // :660 / :861
+  const sc& x = RING ? ring[key_index[p]].x : a.K.x;
+  sc z = sc_muladd(gamma, sc_add(x, e), alpha);                   // :660 / :861
   store8(out, enc_a); store_sc(out + 32, e); store_sc(out + 64, gamma); store_sc(out + 96, z);
   if (a.label == LABEL_RESPOND) store_sc(out + 128, load_sc(a.c_amount + (size_t)p * 32));
 }
+__global__ void __launch_bounds__(256) k_sign_b(SignArgs a) { sign_b_lane<false>(a, nullptr, nullptr); }
+__global__ void __launch_bounds__(256) k_sign_b_ring(SignRingArgs r) { sign_b_lane<true>(r.s, r.ring, r.key_index); }
+// the ring forms are always the one-lane-per-signature kernels (no wide / fused / framed variant)
+void launch_sign_a_ring(const SignRingArgs& a, hipStream_t s) { if (a.s.n) hipLaunchKernelGGL(k_sign_a_ring, dim3((a.s.n + 63) / 64), dim3(64), 0, s, a); }
+void launch_sign_b_ring(const SignRingArgs& a, hipStream_t s) { if (a.s.n) hipLaunchKernelGGL(k_sign_b_ring, dim3((a.s.n + 255) / 256), dim3(256), 0, s, a); }
 // The same phase for SHORT launches, four WAVEFRONTS per 64 signatures.  One lane per signature is ~6 200 dependent field operations
 // (2.2 ms) however few signatures there are -- the issuer's single-item calls (one `issue`, one `refund`) are exactly that.  The
 // five points of the transcript do not depend on each other, so they are spread over the wavefronts of a block (wavefront = role,

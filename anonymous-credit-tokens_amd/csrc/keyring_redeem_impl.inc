@@ -1,0 +1,106 @@
+// keyring_redeem_impl.inc — included by engine.hip after nullifier_impl.inc: the redemption step against a ring of issuer keys.
+// Composed as redeem_impl composes it (nullifier_impl.inc): ring verification -> check-and-insert with the verdicts as skip mask ->
+// sign what is left, each lane with the key `sign_key` names; the same failure contract (ACT_STATUS_NULLIFIER_UNDETERMINED,
+// ACT_STATUS_RECORDED_UNSIGNED, act_debug_fail_next_signs).  The nullifier set does not depend on the key.  No tiny form.
+static int redeem_keyring_impl(act_ctx* c, act_nullifier_set* set, size_t n, int mem, const uint8_t* keys, int nkeys, int sign_key, const uint8_t* proof,
+                               const uint8_t* cbor, const uint64_t* offsets, const uint8_t* rng, int rng_mode, uint8_t* out, uint8_t* status, uint8_t* out_key) {
+  const bool wire = cbor != nullptr;
+  if (!c || !set || !keys || !rng || nkeys < 1 || nkeys > ACT_KEYRING_MAX || (n && ((!proof && !cbor) || !out || !status || !out_key))) return ACT_ERR_ARG;
+  if (sign_key != ACT_SIGN_MATCHED && (sign_key < 0 || sign_key >= nkeys)) return ACT_ERR_ARG;
+  if (rng_mode != ACT_RNG_PER_LANE && rng_mode != ACT_RNG_SEQUENTIAL && rng_mode != ACT_RNG_CALLBACK) return ACT_ERR_ARG;
+  if (set->device != c->device) { c->err = "act_redeem_keyring_batch: the nullifier set lives on another device"; return ACT_ERR_ARG; }
+  if (n == 0) {      // a bad ring fails the call whatever n
+    Call call(c, 0);
+    HIPCK(c, hipSetDevice(c->device));
+    const DevKey* d_ring = nullptr;
+    int rc0 = ring_set(c, keys, nkeys, &d_ring);
+    return rc0 ? rc0 : call.finish();
+  }
+  const size_t pb = act_spend_proof_bytes(c), out_b = wire ? act_cbor_size(c, ACT_CBOR_REFUND) : 128;
+  // K', verdicts, look-up answers, key indices and (wire form) the nullifiers beside the caller's arrays
+  const size_t per_lane = 35 + (wire ? 32 : 0);
+  std::vector<uint8_t> h; DevTmp d(c);
+  uint8_t* base; int rc;
+  if (mem == ACT_MEM_DEVICE) { if ((rc = d.alloc(n * per_lane))) return rc; base = d.p; }
+  else { h.resize(n * per_lane); base = h.data(); }
+  uint8_t *kp = base, *nul = base + n * 32, *st = base + n * (per_lane - 3), *sp = st + n, *kidx = sp + n;
+  if (wire) { RingSel sel{keys, nkeys, out_key}; rc = verify_spend_cbor_impl(c, n, mem, nullptr, cbor, offsets, st, kp, nul, &sel); }
+  else rc = act_verify_spend_keyring_batch(c, n, mem, keys, nkeys, proof, st, out_key, kp);
+  if (rc) return rc;
+  const int rc_null = act_nullifier_check_and_insert_batch(set, n, mem, wire ? nul : proof, wire ? 32 : pb, st, sp);
+  std::string null_err;
+  if (rc_null) {
+    null_err = std::string("nullifier set: ") + act_nullifier_set_last_error(set);
+    if (rc_null == ACT_ERR_HIP) {
+      c->err = null_err + " (every verified lane is undetermined)";
+      if (mem == ACT_MEM_HOST) { for (size_t i = 0; i < n; i++) status[i] = st[i] ? st[i] : (uint8_t)ACT_STATUS_NULLIFIER_UNDETERMINED; memset(out, 0, n * out_b); }
+      else {
+        std::lock_guard<std::mutex> lk(c->mu);
+        (void)hipSetDevice(c->device);
+        hipLaunchKernelGGL(k_mark_undetermined_status, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, status, st, (uint32_t)n);
+        (void)hipMemsetAsync(out, 0, n * out_b, nullptr);
+        if (hipDeviceSynchronize() != hipSuccess) (void)hipGetLastError();
+      }
+      return rc_null;
+    }
+  }
+  // the verdicts with the store's answers merged in, and the key every lane is signed with (out_key keeps what the lane matched)
+  if (mem == ACT_MEM_DEVICE) {
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCK(c, hipSetDevice(c->device));
+    hipLaunchKernelGGL(k_merge_double_spend, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, st, sp, (uint32_t)n);
+    launch_ring_resolve_index(kidx, out_key, sign_key, (uint32_t)n, nullptr);
+    if (hipDeviceSynchronize() != hipSuccess) { c->err = "k_merge_double_spend failed"; (void)hipGetLastError(); return ACT_ERR_HIP; }
+  } else {
+    for (size_t i = 0; i < n; i++) { st[i] = merge_spent(st[i], sp[i]); kidx[i] = sign_key >= 0 ? (uint8_t)sign_key : out_key[i]; }
+  }
+  ResolvedRng rr(c);
+  int rc_sign = rr.resolve(c, mem, st, n, rng, rng_mode);
+  const bool fail_sign = c->debug_fail_signs.load() > 0 && c->debug_fail_signs.fetch_sub(1) > 0;
+  if (!rc_sign) {
+    if (fail_sign) { rc_sign = ACT_ERR_HIP; c->err = "act_debug_fail_next_signs: simulated failure of the signature step"; }
+    else if (!wire) rc_sign = act_refund_sign_keyring_batch(c, n, mem, keys, nkeys, kidx, kp, st, rng, rng_mode, out, status);
+    else if (mem == ACT_MEM_HOST) {      // framed as act_refund_sign_cbor_batch frames: on the host workers, where the signatures landed
+      std::vector<uint8_t> rec(n * 128);
+      rc_sign = act_refund_sign_keyring_batch(c, n, mem, keys, nkeys, kidx, kp, st, rng, rng_mode, rec.data(), status);
+      if (!rc_sign) cbor_frame_refunds_host(cbor_layout(*cbor_type(ACT_CBOR_REFUND), c->L), n, rec.data(), status, out);
+    } else {
+      DevTmp rec(c);
+      rc_sign = rec.alloc(n * 128);
+      if (!rc_sign) rc_sign = act_refund_sign_keyring_batch(c, n, mem, keys, nkeys, kidx, kp, st, rng, rng_mode, rec.p, status);
+      if (!rc_sign) rc_sign = act_cbor_encode_batch(c, ACT_CBOR_REFUND, n, mem, rec.p, out);
+      if (!rc_sign) {
+        std::lock_guard<std::mutex> lk(c->mu);
+        (void)hipSetDevice(c->device);
+        hipLaunchKernelGGL(k_cbor_zero_failed, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->slots[0].stream, out, (uint32_t)out_b, status, (uint32_t)n);
+        if (hipStreamSynchronize(c->slots[0].stream) != hipSuccess) { (void)hipGetLastError(); c->err = "k_cbor_zero_failed failed"; rc_sign = ACT_ERR_HIP; }
+      }
+    }
+  }
+  if (rc_sign) {
+    if (mem == ACT_MEM_HOST) { for (size_t i = 0; i < n; i++) status[i] = st[i] == 0 ? (uint8_t)ACT_STATUS_RECORDED_UNSIGNED : st[i]; memset(out, 0, n * out_b); }
+    else {
+      std::lock_guard<std::mutex> lk(c->mu);
+      (void)hipSetDevice(c->device);
+      hipLaunchKernelGGL(k_mark_recorded_unsigned, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, status, st, (uint32_t)n);
+      (void)hipMemsetAsync(out, 0, n * out_b, nullptr);
+      if (hipDeviceSynchronize() != hipSuccess) (void)hipGetLastError();
+    }
+    return rc_sign;
+  }
+  if (rc_null) c->err = null_err;
+  return rc_null;
+}
+
+extern "C" int act_redeem_keyring_batch(act_ctx* c, act_nullifier_set* set, size_t n, int mem, const uint8_t* keys, int nkeys, int sign_key, const uint8_t* proof,
+                                        const uint8_t* rng, int rng_mode, uint8_t* out_refund, uint8_t* status, uint8_t* out_key) {
+  if (n && !proof) return ACT_ERR_ARG;
+  return redeem_keyring_impl(c, set, n, mem, keys, nkeys, sign_key, proof, nullptr, nullptr, rng, rng_mode, out_refund, status, out_key);
+}
+extern "C" int act_redeem_cbor_keyring_batch(act_ctx* c, act_nullifier_set* set, size_t n, int mem, const uint8_t* keys, int nkeys, int sign_key,
+                                             const uint8_t* cbor, const uint64_t* offsets, const uint8_t* rng, int rng_mode, uint8_t* out_refund_cbor,
+                                             uint8_t* status, uint8_t* out_key) {
+  if (n && !cbor) return ACT_ERR_ARG;
+  static const uint8_t none = 0;
+  return redeem_keyring_impl(c, set, n, mem, keys, nkeys, sign_key, nullptr, cbor ? cbor : &none, offsets, rng, rng_mode, out_refund_cbor, status, out_key);
+}

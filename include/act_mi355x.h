@@ -541,6 +541,49 @@ int act_redeem_cbor_batch(act_ctx *ctx, act_nullifier_set *set, size_t n, int me
 int act_node_redeem_cbor_batch(act_node *node, act_node_nullifier_set *set, size_t n, const uint8_t sk[64], const uint8_t *cbor,
                                const uint64_t *offsets, const uint8_t *rng, int rng_mode, uint8_t *out_refund_cbor, uint8_t *status);
 
+/* ======== key rotation: one batch against a ring of issuer keys ========================================================================
+ * A SpendProof carries no key identifier.  While an issuer rotates its key -- the old key live until its tokens are spent or expired,
+ * the new one for everything issued since -- these calls verify every proof ONCE and say per lane WHICH key it verified under, for
+ * under 1 % of a verification per extra key, instead of one pass per key over the lanes the previous pass rejected.
+ *   keys      nkeys records of 64 bytes (x | enc(w), the `sk` layout), 1 <= nkeys <= ACT_KEYRING_MAX, in the caller's order of preference.
+ *             nkeys out of range or a null ring: ACT_ERR_ARG; a w that is not a canonical encoding: ACT_ERR_PARAMS.  Nothing of a
+ *             rejected ring is kept, and no ring call touches the key the one-key calls have cached.
+ *   out_key   per lane: the SMALLEST ring index k whose PrivateKey::refund accepts the proof (status 0); ACT_KEY_NONE on every other
+ *             lane (255 / ACT_STATUS_IDENTITY_POINT, which do not depend on the key, and ACT_STATUS_INVALID_CLIENT_SPEND_PROOF = no
+ *             ring key accepts it).  Output records of rejected lanes are all zero, as in the one-key calls.  In the redeem calls a
+ *             lane that verified and is then found ACT_STATUS_DOUBLE_SPEND / NULLIFIER_UNDETERMINED / RECORDED_UNSIGNED keeps the
+ *             index it matched.
+ *   sign_key  ACT_SIGN_MATCHED: lane p's refund is signed with ring key out_key[p] -- byte for byte PrivateKey::refund of that key over
+ *             the lane's rng slice; 0 <= sign_key < nkeys: every accepted lane is signed with that one key, which moves the client onto
+ *             it with its next token (the refund verifies under w[sign_key] only).  Anything else: ACT_ERR_ARG.
+ *   key_index (act_refund_sign_keyring_batch) the index per lane, in `mem` memory: a lane with status_in 0 whose index is not below nkeys
+ *             is not signed -- status 255, zero record, no rng slice consumed.
+ * rng conventions are those of the one-key call of the same name (ACT_RNG_CALLBACK in the redeem calls only); the generator is touched
+ * after every verdict (and nullifier answer) is known.  nkeys == 1 gives the bytes of the one-key call.  The nullifier set does not
+ * depend on the key: a nullifier spent under the old key stays spent.  Always the pipelined chunk schedule, whatever n. */
+#define ACT_KEYRING_MAX 4
+#define ACT_KEY_NONE 255
+#define ACT_SIGN_MATCHED (-1)
+int act_verify_spend_keyring_batch(act_ctx *ctx, size_t n, int mem, const uint8_t *keys, int nkeys, const uint8_t *proof, uint8_t *status,
+                                   uint8_t *out_key, uint8_t *out_kprime /* nullable */);
+int act_refund_sign_keyring_batch(act_ctx *ctx, size_t n, int mem, const uint8_t *keys, int nkeys, const uint8_t *key_index, const uint8_t *kprime,
+                                  const uint8_t *status_in, const uint8_t *rng, int rng_mode, uint8_t *out_refund, uint8_t *status);
+int act_redeem_keyring_batch(act_ctx *ctx, act_nullifier_set *set, size_t n, int mem, const uint8_t *keys, int nkeys, int sign_key,
+                             const uint8_t *proof, const uint8_t *rng, int rng_mode, uint8_t *out_refund, uint8_t *status, uint8_t *out_key);
+int act_redeem_cbor_keyring_batch(act_ctx *ctx, act_nullifier_set *set, size_t n, int mem, const uint8_t *keys, int nkeys, int sign_key,
+                                  const uint8_t *cbor, const uint64_t *offsets, const uint8_t *rng, int rng_mode, uint8_t *out_refund_cbor,
+                                  uint8_t *status, uint8_t *out_key);
+/* The same over the GPUs of a node (host memory; out_key is cut per piece like status; ACT_RNG_SEQUENTIAL stays exact across pieces). */
+int act_node_verify_spend_keyring_batch(act_node *node, size_t n, const uint8_t *keys, int nkeys, const uint8_t *proof, uint8_t *status,
+                                        uint8_t *out_key, uint8_t *out_kprime /* nullable */);
+int act_node_refund_sign_keyring_batch(act_node *node, size_t n, const uint8_t *keys, int nkeys, const uint8_t *key_index, const uint8_t *kprime,
+                                       const uint8_t *status_in, const uint8_t *rng, int rng_mode, uint8_t *out_refund, uint8_t *status);
+int act_node_redeem_keyring_batch(act_node *node, act_node_nullifier_set *set, size_t n, const uint8_t *keys, int nkeys, int sign_key,
+                                  const uint8_t *proof, const uint8_t *rng, int rng_mode, uint8_t *out_refund, uint8_t *status, uint8_t *out_key);
+int act_node_redeem_cbor_keyring_batch(act_node *node, act_node_nullifier_set *set, size_t n, const uint8_t *keys, int nkeys, int sign_key,
+                                       const uint8_t *cbor, const uint64_t *offsets, const uint8_t *rng, int rng_mode, uint8_t *out_refund_cbor,
+                                       uint8_t *status, uint8_t *out_key);
+
 /* ======== row d and test infrastructure: debug hooks, measurement knobs, kernel timing, roofline probes (nothing here is on the product's path) ==== */
 /* Debug / test hook: the exact "spend" transcript pre-images of the last act_verify_spend_batch /
  * act_refund_batch chunk (n_last * act_spend_transcript_bytes, copied to host memory). */

@@ -82,6 +82,11 @@ extern "C" {
                              rng: *const u8, rng_mode: c_int, out_refund: *mut u8, status: *mut u8) -> c_int;
     fn act_node_redeem_cbor_batch(node: *mut ActNode, set: *mut ActNodeNullifierSet, n: usize, sk: *const u8, cbor: *const u8,
                                   offsets: *const u64, rng: *const u8, rng_mode: c_int, out_refund_cbor: *mut u8, status: *mut u8) -> c_int;
+    fn act_node_redeem_keyring_batch(node: *mut ActNode, set: *mut ActNodeNullifierSet, n: usize, keys: *const u8, nkeys: c_int, sign_key: c_int,
+                                     proof: *const u8, rng: *const u8, rng_mode: c_int, out_refund: *mut u8, status: *mut u8, out_key: *mut u8) -> c_int;
+    fn act_node_redeem_cbor_keyring_batch(node: *mut ActNode, set: *mut ActNodeNullifierSet, n: usize, keys: *const u8, nkeys: c_int, sign_key: c_int,
+                                          cbor: *const u8, offsets: *const u64, rng: *const u8, rng_mode: c_int, out_refund_cbor: *mut u8,
+                                          status: *mut u8, out_key: *mut u8) -> c_int;
     fn act_node_nullifier_set_create(devices: *const c_int, n_devices: c_int, capacity_per_device: usize, salt: *const u8,
                                      out: *mut *mut ActNodeNullifierSet) -> c_int;
     fn act_node_nullifier_set_destroy(set: *mut ActNodeNullifierSet);
@@ -915,6 +920,74 @@ impl PrivateKey {
         let engine_failure = if rc != 0 { Some(unsafe { CStr::from_ptr(act_node_last_error(gpu.0)) }.to_string_lossy().into_owned()) } else { None };
         let lanes = (0..n).map(|i| if status[i] == 0 { Ok(Refund::from_record(&out[128 * i..128 * i + 128])) } else { Err(status_to_wire_error(status[i])) }).collect();
         Redeemed { lanes, engine_failure }
+    }
+}
+
+/// Key rotation: an ordered ring of up to four issuer keys (the caller's order of preference) that one batch is redeemed against.
+/// A `SpendProof` names no key: every proof is verified once, `matched[i]` says which ring key lane i verified under (`None` where
+/// no ring key accepts it; a double spend keeps the index it matched), and the refund is signed with the matched key
+/// (`sign_with = None`) or with ring key `sign_with = Some(i)` -- which moves the client onto that key with its next token (the
+/// client then calls `to_credit_token` with `ring.public(i)`).  The nullifier store is shared by all keys; `Params` must be the
+/// ones every ring key issued under.
+pub struct Keyring<'a>(pub &'a [PrivateKey]);
+pub const ACT_KEYRING_MAX: usize = 4;
+const ACT_KEY_NONE: u8 = 255;
+const ACT_SIGN_MATCHED: c_int = -1;
+/// `lanes` as `Redeemed`, plus the ring index per lane.
+pub struct RingRedeemed<T> {
+    pub redeemed: Redeemed<T>,
+    pub matched: Vec<Option<usize>>,
+}
+
+impl<'a> Keyring<'a> {
+    pub fn public(&self, i: usize) -> &PublicKey {
+        self.0[i].public()
+    }
+    fn records(&self) -> Vec<u8> {
+        assert!(!self.0.is_empty() && self.0.len() <= ACT_KEYRING_MAX, "a key ring holds 1 ..= ACT_KEYRING_MAX keys");
+        self.0.iter().flat_map(|k| k.record().to_vec()).collect()
+    }
+    fn sign_key(&self, sign_with: Option<usize>) -> c_int {
+        match sign_with {
+            None => ACT_SIGN_MATCHED,
+            Some(i) => { assert!(i < self.0.len(), "sign_with is not a ring index"); i as c_int }
+        }
+    }
+    fn matched(out_key: &[u8]) -> Vec<Option<usize>> {
+        out_key.iter().map(|&k| if k == ACT_KEY_NONE { None } else { Some(k as usize) }).collect()
+    }
+    /// `PrivateKey::redeem_cbor_batch` against the ring.
+    pub fn redeem_cbor_batch(&self, params: &Params, store: &GpuNullifierStore, msgs: &[&[u8]], sign_with: Option<usize>, mut rng: impl CryptoRngCore)
+        -> RingRedeemed<Vec<u8>> {
+        let (blob, offsets) = gather(msgs);
+        let n = msgs.len();
+        let (keys, sign_key) = (self.records(), self.sign_key(sign_with));
+        let gpu = params.gpu();
+        let src = rng_source(&mut rng);
+        let (mut out, mut status, mut out_key) = (vec![0u8; REFUND_CBOR_BYTES * n + 1], vec![0u8; n + 1], vec![ACT_KEY_NONE; n + 1]);
+        let rc = unsafe {
+            act_node_redeem_cbor_keyring_batch(gpu.0, store.0, n, keys.as_ptr(), self.0.len() as c_int, sign_key, blob.as_ptr(), offsets.as_ptr(),
+                                               &src as *const ActRngSource as *const u8, ACT_RNG_CALLBACK, out.as_mut_ptr(), status.as_mut_ptr(), out_key.as_mut_ptr())
+        };
+        let engine_failure = if rc != 0 { Some(unsafe { CStr::from_ptr(act_node_last_error(gpu.0)) }.to_string_lossy().into_owned()) } else { None };
+        RingRedeemed { redeemed: Redeemed { lanes: refund_messages(&out, &status[..n]), engine_failure }, matched: Self::matched(&out_key[..n]) }
+    }
+    /// `PrivateKey::redeem_batch` against the ring.
+    pub fn redeem_batch(&self, params: &Params, store: &GpuNullifierStore, proofs: &[SpendProof], sign_with: Option<usize>, mut rng: impl CryptoRngCore)
+        -> RingRedeemed<Refund> {
+        let n = proofs.len();
+        let rec = marshal(proofs, PROOF_BYTES, |p, out| p.write_record(out));
+        let (keys, sign_key) = (self.records(), self.sign_key(sign_with));
+        let gpu = params.gpu();
+        let src = rng_source(&mut rng);
+        let (mut out, mut status, mut out_key) = (vec![0u8; 128 * n + 1], vec![0u8; n + 1], vec![ACT_KEY_NONE; n + 1]);
+        let rc = unsafe {
+            act_node_redeem_keyring_batch(gpu.0, store.0, n, keys.as_ptr(), self.0.len() as c_int, sign_key, rec.as_ptr(), &src as *const ActRngSource as *const u8,
+                                          ACT_RNG_CALLBACK, out.as_mut_ptr(), status.as_mut_ptr(), out_key.as_mut_ptr())
+        };
+        let engine_failure = if rc != 0 { Some(unsafe { CStr::from_ptr(act_node_last_error(gpu.0)) }.to_string_lossy().into_owned()) } else { None };
+        let lanes = (0..n).map(|i| if status[i] == 0 { Ok(Refund::from_record(&out[128 * i..128 * i + 128])) } else { Err(status_to_wire_error(status[i])) }).collect();
+        RingRedeemed { redeemed: Redeemed { lanes, engine_failure }, matched: Self::matched(&out_key[..n]) }
     }
 }
 
