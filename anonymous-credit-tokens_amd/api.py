@@ -273,12 +273,17 @@ class Keyring:
     name returns PLUS, per proof, the ring index it verified under (None where no ring key accepts it).  `sign_with=None` signs every
     refund with the key its proof matched; `sign_with=i` signs every accepted lane with ring key i, which moves the client onto that
     key with its next token (the client then calls to_credit_token with `ring.public(i)`).  The nullifier database is shared by all
-    keys; `Params` must be the ones every ring key issued under."""
+    keys; `Params` must be the ones every ring key issued under.  `epochs` (one per key, 0 .. 2^24 - 1: the caller's stable name for
+    each key): redeem_batch / redeem_cbor_batch record every accepted nullifier under the epoch of the key its proof matched, so that
+    NullifierDb.retire can drop a key's nullifiers once the key has left every ring for good."""
 
-    def __init__(self, keys: Sequence[PrivateKey]):
+    def __init__(self, keys: Sequence[PrivateKey], epochs: Sequence[int] = None):
         if not 1 <= len(keys) <= capi.KEYRING_MAX:
             raise ValueError("a key ring holds 1 .. %d keys" % capi.KEYRING_MAX)
+        if epochs is not None and len(epochs) != len(keys):
+            raise ValueError("epochs: one per ring key")
         self.keys = list(keys)
+        self.epochs = list(epochs) if epochs is not None else None
 
     def public(self, i: int) -> PublicKey:
         return self.keys[i].public()
@@ -321,12 +326,12 @@ class Keyring:
         nbits = proofs[0].nbits if proofs else L
         e = params.engine(nbits)
         pb = b"".join(p.record for p in proofs)
-        st, out, ok = _draw_signed(rng, len(proofs), lambda src, mode: e.redeem_keyring(db.set, self._records(), pb, src, mode, self._sign_key(sign_with)))
+        st, out, ok = _draw_signed(rng, len(proofs), lambda src, mode: e.redeem_keyring(db.set, self._records(), pb, src, mode, self._sign_key(sign_with), key_epochs=self.epochs))
         return [Refund(out[128 * i:128 * i + 128]) if st[i] == 0 else Error(st[i]) for i in range(len(proofs))], self._indices(st, ok)
 
     def redeem_cbor_batch(self, params: Params, db: "NullifierDb", msgs: Sequence[bytes], rng, nbits: int = L, sign_with=None) -> Tuple[list, list]:
         e = params.engine(nbits)
-        st, out, ok = _draw_signed(rng, len(msgs), lambda src, mode: e.redeem_cbor_keyring(db.set, self._records(), list(msgs), src, mode, self._sign_key(sign_with)))
+        st, out, ok = _draw_signed(rng, len(msgs), lambda src, mode: e.redeem_cbor_keyring(db.set, self._records(), list(msgs), src, mode, self._sign_key(sign_with), key_epochs=self.epochs))
         return [out[i] if st[i] == 0 else _wire_error(st[i]) for i in range(len(msgs))], self._indices(st, ok)
 
 
@@ -440,13 +445,30 @@ class NullifierDb:
     def __init__(self, capacity: int = 1 << 20, device: int = 0):
         self.set = capi.NullifierSet(capacity, device)
 
-    def spend(self, nullifier: bytes) -> bool:
-        """record `nullifier`; True if it was fresh, False if it had been spent before (DoubleSpendError)"""
-        return self.set.check_and_insert(bytes(nullifier))[0] == 0
+    def spend(self, nullifier: bytes, epoch: int = 0) -> bool:
+        """record `nullifier` (under `epoch`, the name of the issuer key its token was issued under; 0 = untagged); True if it was
+        fresh, False if it had been spent before under any epoch (DoubleSpendError)"""
+        return self.set.check_and_insert(bytes(nullifier), epochs=[epoch] if epoch else None)[0] == 0
 
-    def spend_batch(self, nullifiers: Sequence[bytes]) -> List[bool]:
+    def spend_batch(self, nullifiers: Sequence[bytes], epoch: int = 0) -> List[bool]:
         """the same for a list, with the meaning of the loop in list order (a repeat inside the list is a double spend)"""
-        return [b == 0 for b in self.set.check_and_insert(b"".join(bytes(k) for k in nullifiers))] if nullifiers else []
+        if not nullifiers:
+            return []
+        return [b == 0 for b in self.set.check_and_insert(b"".join(bytes(k) for k in nullifiers), epochs=[epoch] if epoch else None)]
+
+    def epoch_len(self, epoch: int) -> int:
+        """how many nullifiers are recorded under `epoch`"""
+        return self.set.epoch_len(epoch)
+
+    def retire(self, epoch: int) -> int:
+        """Remove every nullifier recorded under `epoch` and refuse the epoch from then on (also across save / restore); returns how
+        many were removed.  ONLY once the epoch's key has been removed from every ring of every server that shares this database and
+        will never be put back: from then on no proof under that key verifies, so its nullifiers are never consulted again.
+        Retiring earlier re-enables double spends of that key's tokens."""
+        return self.set.retire_epoch(epoch)
+
+    def retired(self) -> List[int]:
+        return self.set.retired_epochs()
 
     def reserve(self, capacity: int):
         """grow so that `capacity` nullifiers fit; the recorded ones are kept (rehashed on the GPU)"""

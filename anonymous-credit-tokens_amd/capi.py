@@ -39,6 +39,11 @@ EXPORTS = [
     "act_node_refund_sign_cbor_batch", "act_node_refund_cbor_batch", "act_redeem_cbor_batch", "act_node_redeem_cbor_batch",
     "act_verify_spend_keyring_batch", "act_refund_sign_keyring_batch", "act_redeem_keyring_batch", "act_redeem_cbor_keyring_batch",
     "act_node_verify_spend_keyring_batch", "act_node_refund_sign_keyring_batch", "act_node_redeem_keyring_batch", "act_node_redeem_cbor_keyring_batch",
+    "act_nullifier_check_and_insert_epoch_batch", "act_nullifier_set_epoch_len", "act_nullifier_set_retire_epoch", "act_nullifier_set_retired_epochs",
+    "act_nullifier_set_export_epochs", "act_redeem_keyring_epochs_batch", "act_redeem_cbor_keyring_epochs_batch",
+    "act_node_nullifier_check_and_insert_epoch_batch", "act_node_nullifier_set_epoch_len", "act_node_nullifier_set_retire_epoch",
+    "act_node_nullifier_set_retired_epochs", "act_node_nullifier_set_export_epochs", "act_node_redeem_keyring_epochs_batch",
+    "act_node_redeem_cbor_keyring_epochs_batch",
     "act_issue_check_cbor_batch", "act_issue_sign_cbor_batch", "act_issue_cbor_batch",
     "act_node_issue_check_cbor_batch", "act_node_issue_sign_cbor_batch", "act_node_issue_cbor_batch",
     "act_ctx_host_hash_stats", "act_ctx_set_tiny_calls", "act_node_set_balance", "act_node_device_stats", "act_node_balance_state", "act_debug_set_slowdown", "act_debug_fail_next_signs",
@@ -200,6 +205,21 @@ def load() -> C.CDLL:
     lib.act_node_refund_sign_keyring_batch.argtypes = [vp, sz, u8p, i32, u8p, u8p, u8p, u8p, i32, u8p, u8p]
     lib.act_node_redeem_keyring_batch.argtypes = [vp, vp, sz, u8p, i32, i32, u8p, u8p, i32, u8p, u8p, u8p]
     lib.act_node_redeem_cbor_keyring_batch.argtypes = [vp, vp, sz, u8p, i32, i32, u8p, vp, u8p, i32, u8p, u8p, u8p]
+    u32p, u64p, szp = C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_size_t)
+    lib.act_nullifier_check_and_insert_epoch_batch.argtypes = [vp, sz, i32, u8p, sz, u8p, u8p, u32p, i32, u8p]
+    lib.act_nullifier_set_epoch_len.argtypes = [vp, C.c_uint32, u64p]
+    lib.act_nullifier_set_retire_epoch.argtypes = [vp, C.c_uint32, u64p]
+    lib.act_nullifier_set_retired_epochs.argtypes = [vp, u32p, sz, szp]
+    lib.act_nullifier_set_export_epochs.argtypes = [vp, u64p, sz, i32, u8p, vp, szp]
+    lib.act_redeem_keyring_epochs_batch.argtypes = [vp, vp, sz, i32, u8p, i32, u32p, i32, u8p, u8p, i32, u8p, u8p, u8p]
+    lib.act_redeem_cbor_keyring_epochs_batch.argtypes = [vp, vp, sz, i32, u8p, i32, u32p, i32, u8p, vp, u8p, i32, u8p, u8p, u8p]
+    lib.act_node_nullifier_check_and_insert_epoch_batch.argtypes = [vp, sz, u8p, sz, u8p, u8p, u32p, i32, u8p]
+    lib.act_node_nullifier_set_epoch_len.argtypes = [vp, C.c_uint32, u64p]
+    lib.act_node_nullifier_set_retire_epoch.argtypes = [vp, C.c_uint32, u64p]
+    lib.act_node_nullifier_set_retired_epochs.argtypes = [vp, u32p, sz, szp]
+    lib.act_node_nullifier_set_export_epochs.argtypes = [vp, u64p, sz, u8p, vp, szp]
+    lib.act_node_redeem_keyring_epochs_batch.argtypes = [vp, vp, sz, u8p, i32, u32p, i32, u8p, u8p, i32, u8p, u8p, u8p]
+    lib.act_node_redeem_cbor_keyring_epochs_batch.argtypes = [vp, vp, sz, u8p, i32, u32p, i32, u8p, vp, u8p, i32, u8p, u8p, u8p]
     lib.act_node_redeem_cbor_batch.argtypes = [vp, vp, sz, u8p, u8p, vp, u8p, i32, u8p, u8p]
     lib.act_issue_check_cbor_batch.argtypes = [vp, sz, i32, u8p, vp, u8p, u8p]
     lib.act_issue_sign_cbor_batch.argtypes = [vp, sz, i32, u8p, u8p, u8p, u8p, u8p, i32, u8p, u8p]
@@ -646,22 +666,34 @@ class Engine:
         self._ck(self.lib.act_refund_sign_keyring_batch(self.ctx, n, MEM_HOST, pk, len(keys), pi, p0, p1, p2, rng_mode, out.ctypes.data, st.ctypes.data))
         return st.tobytes(), out.tobytes()
 
-    def redeem_keyring(self, nullifier_set, keys, proofs: bytes, rng, rng_mode: int = RNG_PER_LANE, sign_key: int = SIGN_MATCHED, raw: bool = False):
-        """-> (statuses, refunds, out_key).  raw=True: (rc, statuses, refunds, out_key), no exception."""
+    def redeem_keyring(self, nullifier_set, keys, proofs: bytes, rng, rng_mode: int = RNG_PER_LANE, sign_key: int = SIGN_MATCHED, raw: bool = False,
+                       key_epochs=None):
+        """-> (statuses, refunds, out_key).  raw=True: (rc, statuses, refunds, out_key), no exception.  key_epochs: one epoch per ring
+        key; an accepted lane's nullifier is recorded under the epoch of the key it matched (act_redeem_keyring_epochs_batch)."""
         n = len(proofs) // self.proof_bytes; out = np.full(128 * n, 7 if raw else 0, np.uint8); st = np.zeros(n, np.uint8); ok = np.zeros(n, np.uint8)
         pk, kk = _in(b"".join(keys)); p0, k0 = _in(proofs, self.proof_bytes * n); p1, k1 = _rng_arg(rng)
-        rc = self.lib.act_redeem_keyring_batch(self.ctx, nullifier_set.h, n, MEM_HOST, pk, len(keys), sign_key, p0, p1, rng_mode, out.ctypes.data, st.ctypes.data, ok.ctypes.data)
+        if key_epochs is not None:
+            ke = _epoch_table(key_epochs, len(keys))
+            rc = self.lib.act_redeem_keyring_epochs_batch(self.ctx, nullifier_set.h, n, MEM_HOST, pk, len(keys), ke.ctypes.data, sign_key, p0, p1, rng_mode,
+                                                          out.ctypes.data, st.ctypes.data, ok.ctypes.data)
+        else:
+            rc = self.lib.act_redeem_keyring_batch(self.ctx, nullifier_set.h, n, MEM_HOST, pk, len(keys), sign_key, p0, p1, rng_mode, out.ctypes.data, st.ctypes.data, ok.ctypes.data)
         if raw:
             return rc, st.tobytes(), out.tobytes(), ok.tobytes()
         self._ck(rc)
         return st.tobytes(), out.tobytes(), ok.tobytes()
 
-    def redeem_cbor_keyring(self, nullifier_set, keys, messages: list, rng, rng_mode: int = RNG_SEQUENTIAL, sign_key: int = SIGN_MATCHED):
+    def redeem_cbor_keyring(self, nullifier_set, keys, messages: list, rng, rng_mode: int = RNG_SEQUENTIAL, sign_key: int = SIGN_MATCHED, key_epochs=None):
         """wire bytes in, wire bytes out -> (statuses, list of CBOR Refund messages (b"" where not signed), out_key)"""
         n = len(messages); p0, k0, offs = _msgs(messages); ml = self.cbor_size("Refund")
         st = np.zeros(n, np.uint8); ok = np.zeros(n, np.uint8); out = np.zeros(ml * n, np.uint8); pk, kk = _in(b"".join(keys)); pr, kr = _rng_arg(rng)
-        self._ck(self.lib.act_redeem_cbor_keyring_batch(self.ctx, nullifier_set.h, n, MEM_HOST, pk, len(keys), sign_key, p0, offs.ctypes.data, pr, rng_mode,
-                                                        out.ctypes.data, st.ctypes.data, ok.ctypes.data))
+        if key_epochs is not None:
+            ke = _epoch_table(key_epochs, len(keys))
+            self._ck(self.lib.act_redeem_cbor_keyring_epochs_batch(self.ctx, nullifier_set.h, n, MEM_HOST, pk, len(keys), ke.ctypes.data, sign_key, p0, offs.ctypes.data,
+                                                                   pr, rng_mode, out.ctypes.data, st.ctypes.data, ok.ctypes.data))
+        else:
+            self._ck(self.lib.act_redeem_cbor_keyring_batch(self.ctx, nullifier_set.h, n, MEM_HOST, pk, len(keys), sign_key, p0, offs.ctypes.data, pr, rng_mode,
+                                                            out.ctypes.data, st.ctypes.data, ok.ctypes.data))
         b = out.tobytes()
         assert all(st[i] == 0 or not out[i * ml:(i + 1) * ml].any() for i in range(n)), "a failed lane's slot is not zero"
         return st.tobytes(), [b[i * ml:(i + 1) * ml] if st[i] == 0 else b"" for i in range(n)], ok.tobytes()
@@ -673,6 +705,14 @@ class Engine:
             self._ck(self.lib.act_verify_spend_keyring_batch(self.ctx, n, mem, pk, nk, p["proofs"], p["status"], p["out_key"], p.get("kprime") or None))
         elif fn == "sign":
             self._ck(self.lib.act_refund_sign_keyring_batch(self.ctx, n, mem, pk, nk, p["key_index"], p["kprime"], p["status_in"], p["rng"], p["rng_mode"], p["out"], p["status"]))
+        elif fn in ("redeem", "redeem_cbor") and p.get("key_epochs") is not None:
+            ke = _epoch_table(p["key_epochs"], nk)
+            if fn == "redeem":
+                self._ck(self.lib.act_redeem_keyring_epochs_batch(self.ctx, p["set"].h, n, mem, pk, nk, ke.ctypes.data, p.get("sign_key", SIGN_MATCHED), p["proofs"],
+                                                                  p["rng"], p["rng_mode"], p["out"], p["status"], p["out_key"]))
+            else:
+                self._ck(self.lib.act_redeem_cbor_keyring_epochs_batch(self.ctx, p["set"].h, n, mem, pk, nk, ke.ctypes.data, p.get("sign_key", SIGN_MATCHED), p["cbor"],
+                                                                       p.get("offsets") or None, p["rng"], p["rng_mode"], p["out"], p["status"], p["out_key"]))
         elif fn == "redeem":
             self._ck(self.lib.act_redeem_keyring_batch(self.ctx, p["set"].h, n, mem, pk, nk, p.get("sign_key", SIGN_MATCHED), p["proofs"], p["rng"], p["rng_mode"],
                                                        p["out"], p["status"], p["out_key"]))
@@ -954,20 +994,31 @@ class Node:
         self._ck(self.lib.act_node_refund_sign_keyring_batch(self.nd, n, pk, len(keys), pi, p0, p1, p2, rng_mode, out.ctypes.data, st.ctypes.data))
         return st.tobytes(), out.tobytes()
 
-    def redeem_keyring(self, nullifier_set, keys, proofs: bytes, rng, rng_mode: int = RNG_SEQUENTIAL, sign_key: int = SIGN_MATCHED, raw: bool = False):
+    def redeem_keyring(self, nullifier_set, keys, proofs: bytes, rng, rng_mode: int = RNG_SEQUENTIAL, sign_key: int = SIGN_MATCHED, raw: bool = False,
+                       key_epochs=None):
         n = len(proofs) // self.proof_bytes; out = np.full(128 * n, 7 if raw else 0, np.uint8); st = np.zeros(n, np.uint8); ok = np.zeros(n, np.uint8)
         pk, kk = _in(b"".join(keys)); p0, k0 = _in(proofs, self.proof_bytes * n); p1, k1 = _rng_arg(rng)
-        rc = self.lib.act_node_redeem_keyring_batch(self.nd, nullifier_set.h, n, pk, len(keys), sign_key, p0, p1, rng_mode, out.ctypes.data, st.ctypes.data, ok.ctypes.data)
+        if key_epochs is not None:
+            ke = _epoch_table(key_epochs, len(keys))
+            rc = self.lib.act_node_redeem_keyring_epochs_batch(self.nd, nullifier_set.h, n, pk, len(keys), ke.ctypes.data, sign_key, p0, p1, rng_mode,
+                                                               out.ctypes.data, st.ctypes.data, ok.ctypes.data)
+        else:
+            rc = self.lib.act_node_redeem_keyring_batch(self.nd, nullifier_set.h, n, pk, len(keys), sign_key, p0, p1, rng_mode, out.ctypes.data, st.ctypes.data, ok.ctypes.data)
         if raw:
             return rc, st.tobytes(), out.tobytes(), ok.tobytes()
         self._ck(rc)
         return st.tobytes(), out.tobytes(), ok.tobytes()
 
-    def redeem_cbor_keyring(self, nullifier_set, keys, messages: list, rng, rng_mode: int = RNG_SEQUENTIAL, sign_key: int = SIGN_MATCHED):
+    def redeem_cbor_keyring(self, nullifier_set, keys, messages: list, rng, rng_mode: int = RNG_SEQUENTIAL, sign_key: int = SIGN_MATCHED, key_epochs=None):
         n = len(messages); p0, k0, offs, ml = self._wire(messages)
         st = np.zeros(n, np.uint8); ok = np.zeros(n, np.uint8); out = np.zeros(ml * n, np.uint8); pk, kk = _in(b"".join(keys)); pr, kr = _rng_arg(rng)
-        self._ck(self.lib.act_node_redeem_cbor_keyring_batch(self.nd, nullifier_set.h, n, pk, len(keys), sign_key, p0, offs.ctypes.data, pr, rng_mode,
-                                                             out.ctypes.data, st.ctypes.data, ok.ctypes.data))
+        if key_epochs is not None:
+            ke = _epoch_table(key_epochs, len(keys))
+            self._ck(self.lib.act_node_redeem_cbor_keyring_epochs_batch(self.nd, nullifier_set.h, n, pk, len(keys), ke.ctypes.data, sign_key, p0, offs.ctypes.data,
+                                                                        pr, rng_mode, out.ctypes.data, st.ctypes.data, ok.ctypes.data))
+        else:
+            self._ck(self.lib.act_node_redeem_cbor_keyring_batch(self.nd, nullifier_set.h, n, pk, len(keys), sign_key, p0, offs.ctypes.data, pr, rng_mode,
+                                                                 out.ctypes.data, st.ctypes.data, ok.ctypes.data))
         b = out.tobytes()
         return st.tobytes(), [b[i * ml:(i + 1) * ml] if st[i] == 0 else b"" for i in range(n)], ok.tobytes()
 
@@ -1044,15 +1095,65 @@ class NullifierSet:
         if rc:
             raise ActError(f"{_ERRS.get(rc, rc)}: {self.lib.act_nullifier_set_last_error(self.h).decode()}")
 
-    def check_and_insert(self, nullifiers: bytes, stride: int = 32, skip_mask: bytes = None) -> bytes:
+    def check_and_insert(self, nullifiers: bytes, stride: int = 32, skip_mask: bytes = None, epoch_index: bytes = None, epochs=None, raw: bool = False):
+        """epochs (a list of 1 .. 255 epochs) / epoch_index (one byte per lane, an index into it; None = every lane epochs[0]): a fresh
+        lane is recorded under epochs[epoch_index[i]] (act_nullifier_check_and_insert_epoch_batch); neither = untagged, the existing
+        call.  raw=True: (rc, answers), no exception (a lane with an index outside the table is answered 2 beside the others)."""
         n = (len(nullifiers) + stride - 32) // stride if nullifiers else 0
         out = np.zeros(n, np.uint8)
         p0, k0 = _in(nullifiers); pm, km = _in(skip_mask, n) if skip_mask is not None else (None, None)
-        self._ck(self.lib.act_nullifier_check_and_insert_batch(self.h, n, MEM_HOST, p0, stride, pm, out.ctypes.data))
+        if epochs is None and epoch_index is None:
+            rc = self.lib.act_nullifier_check_and_insert_batch(self.h, n, MEM_HOST, p0, stride, pm, out.ctypes.data)
+        else:
+            tab = _epoch_table(epochs if epochs is not None else [0]); pe, ke = _in(epoch_index, n) if epoch_index is not None else (None, None)
+            rc = self.lib.act_nullifier_check_and_insert_epoch_batch(self.h, n, MEM_HOST, p0, stride, pm, pe, tab.ctypes.data, len(tab), out.ctypes.data)
+        if raw:
+            return rc, out.tobytes()
+        self._ck(rc)
         return out.tobytes()
 
     def check_and_insert_dev(self, n: int, d_nullifiers: int, stride: int, d_skip_mask: int, d_out_spent: int):
         self._ck(self.lib.act_nullifier_check_and_insert_batch(self.h, n, MEM_DEVICE, d_nullifiers, stride, d_skip_mask or None, d_out_spent))
+
+    def check_and_insert_epoch_dev(self, n: int, d_nullifiers: int, stride: int, d_skip_mask: int, d_epoch_index: int, epochs, d_out_spent: int, raw: bool = False):
+        """device pointers; `epochs` is the (host) table"""
+        tab = _epoch_table(epochs)
+        rc = self.lib.act_nullifier_check_and_insert_epoch_batch(self.h, n, MEM_DEVICE, d_nullifiers, stride, d_skip_mask or None, d_epoch_index or None,
+                                                                 tab.ctypes.data, len(tab), d_out_spent)
+        if raw:
+            return rc
+        self._ck(rc)
+
+    # ---- epochs: count, retire, list, export with epochs (include/act_mi355x.h "Epochs") ----
+    def epoch_len(self, epoch: int) -> int:
+        c = C.c_uint64(0)
+        self._ck(self.lib.act_nullifier_set_epoch_len(self.h, epoch, C.byref(c)))
+        return c.value
+
+    def retire_epoch(self, epoch: int) -> int:
+        """remove every nullifier recorded under `epoch` and refuse the epoch from then on -> how many were removed.  Only for a key that
+        has left every ring of every server sharing the set, for good."""
+        c = C.c_uint64(0)
+        self._ck(self.lib.act_nullifier_set_retire_epoch(self.h, epoch, C.byref(c)))
+        return c.value
+
+    def retired_epochs(self) -> list:
+        return _retired_list(lambda p, m, n: self._ck(self.lib.act_nullifier_set_retired_epochs(self.h, p, m, n)))
+
+    def export_epochs_step(self, cursor: int, max_keys: int):
+        """one export call into host memory -> (next cursor, keys bytes, epochs as a uint32 array)"""
+        out = np.empty(32 * max_keys, np.uint8); ep = np.empty(max_keys, np.uint32); cur = C.c_uint64(cursor); got = C.c_size_t(0)
+        self._ck(self.lib.act_nullifier_set_export_epochs(self.h, C.byref(cur), max_keys, MEM_HOST, out.ctypes.data, ep.ctypes.data, C.byref(got)))
+        return cur.value, out[:32 * got.value].tobytes(), ep[:got.value].copy()
+
+    def export_epochs_dev(self, cursor: int, max_keys: int, d_out_keys: int, d_out_epochs: int):
+        cur = C.c_uint64(cursor); got = C.c_size_t(0)
+        self._ck(self.lib.act_nullifier_set_export_epochs(self.h, C.byref(cur), max_keys, MEM_DEVICE, d_out_keys, d_out_epochs, C.byref(got)))
+        return cur.value, got.value
+
+    def export_epochs(self, max_keys: int = 1 << 20):
+        """every recorded nullifier with its epoch -> (keys bytes, uint32 array), unspecified order"""
+        return _export_epochs_loop(self.export_epochs_step, max_keys)
 
     # ---- growth, export, read-only look-up, snapshots (include/act_mi355x.h; nullifier_snapshot.py) ----
     def reserve(self, capacity: int):
@@ -1086,16 +1187,18 @@ class NullifierSet:
         return _export_loop(self.export_step, max_keys)
 
     def save(self, path: str) -> int:
+        """format v2 when the set holds a non-zero epoch or a retired epoch, else today's v1 bytes (nullifier_snapshot.py)"""
         from . import nullifier_snapshot
-        return nullifier_snapshot.write(path, self.export())
+        keys, epochs = self.export_epochs()
+        return nullifier_snapshot.write_epochs(path, keys, epochs, self.retired_epochs())
 
     @classmethod
     def restore(cls, path: str, capacity: int = None, device: int = 0, salt: bytes = None) -> "NullifierSet":
-        """a new set holding the snapshot's keys (validated as a whole before anything is inserted)"""
+        """a new set holding the snapshot's keys, their epochs and its retired list (validated as a whole before anything is inserted)"""
         from . import nullifier_snapshot
-        keys = nullifier_snapshot.read(path)
+        keys, epochs, retired = nullifier_snapshot.read_epochs(path)
         s = cls(max(capacity or 0, len(keys) // 32, 1), device=device, salt=salt)
-        nullifier_snapshot.restore_into(s, keys)
+        nullifier_snapshot.restore_epochs_into(s, keys, epochs, retired)
         return s
 
 
@@ -1131,11 +1234,17 @@ class NodeNullifierSet:
     def __len__(self):
         return self.lib.act_node_nullifier_set_len(self.h)
 
-    def check_and_insert(self, nullifiers: bytes, stride: int = 32, skip_mask: bytes = None) -> bytes:
+    def check_and_insert(self, nullifiers: bytes, stride: int = 32, skip_mask: bytes = None, epoch_index: bytes = None, epochs=None, raw: bool = False):
         n = (len(nullifiers) + stride - 32) // stride if nullifiers else 0
         out = np.zeros(n, np.uint8)
         p0, k0 = _in(nullifiers); pm, km = _in(skip_mask, n) if skip_mask is not None else (None, None)
-        rc = self.lib.act_node_nullifier_check_and_insert_batch(self.h, n, p0, stride, pm, out.ctypes.data)
+        if epochs is None and epoch_index is None:
+            rc = self.lib.act_node_nullifier_check_and_insert_batch(self.h, n, p0, stride, pm, out.ctypes.data)
+        else:
+            tab = _epoch_table(epochs if epochs is not None else [0]); pe, ke = _in(epoch_index, n) if epoch_index is not None else (None, None)
+            rc = self.lib.act_node_nullifier_check_and_insert_epoch_batch(self.h, n, p0, stride, pm, pe, tab.ctypes.data, len(tab), out.ctypes.data)
+        if raw:
+            return rc, out.tobytes()
         if rc:
             raise ActError(f"{_ERRS.get(rc, rc)}: {self.lib.act_node_nullifier_set_last_error(self.h).decode()}")
         return out.tobytes()
@@ -1155,7 +1264,7 @@ class NodeNullifierSet:
         per = -(-(len(self) + n) // self.n_devices)
         return per + per // 8 + 4 * math.isqrt(per) + 1024
 
-    def check_and_insert_growing(self, nullifiers: bytes) -> bytes:
+    def check_and_insert_growing(self, nullifiers: bytes, epoch: int = 0) -> bytes:
         """check_and_insert of 32-byte keys that, when a device refuses its bucket for capacity (its lanes come back
         ACT_NULLIFIER_UNDETERMINED, nothing of them recorded; the other devices' answers are final), doubles the per-device
         capacity and resubmits exactly those lanes.  Restore's path: no device count or key spread can make it fail."""
@@ -1164,7 +1273,11 @@ class NodeNullifierSet:
         answer, lanes = np.zeros(n, np.uint8), np.arange(n)
         while True:
             sub = np.ascontiguousarray(keys[lanes]); out = np.zeros(len(lanes), np.uint8)
-            rc = self.lib.act_node_nullifier_check_and_insert_batch(self.h, len(lanes), sub.ctypes.data, 32, None, out.ctypes.data)
+            if epoch:
+                tab = _epoch_table([epoch])
+                rc = self.lib.act_node_nullifier_check_and_insert_epoch_batch(self.h, len(lanes), sub.ctypes.data, 32, None, None, tab.ctypes.data, 1, out.ctypes.data)
+            else:
+                rc = self.lib.act_node_nullifier_check_and_insert_batch(self.h, len(lanes), sub.ctypes.data, 32, None, out.ctypes.data)
             answer[lanes] = out
             undetermined = out == 2                         # ACT_NULLIFIER_UNDETERMINED
             if rc == 0:
@@ -1188,17 +1301,42 @@ class NodeNullifierSet:
     def export(self, max_keys: int = 1 << 20) -> bytes:
         return _export_loop(self.export_step, max_keys)
 
+    def epoch_len(self, epoch: int) -> int:
+        c = C.c_uint64(0)
+        self._ck(self.lib.act_node_nullifier_set_epoch_len(self.h, epoch, C.byref(c)))
+        return c.value
+
+    def retire_epoch(self, epoch: int) -> int:
+        """device after device; if one fails the others have retired and a repeat of the call finishes the job"""
+        c = C.c_uint64(0)
+        self._ck(self.lib.act_node_nullifier_set_retire_epoch(self.h, epoch, C.byref(c)))
+        return c.value
+
+    def retired_epochs(self) -> list:
+        """the epochs every device has retired"""
+        return _retired_list(lambda p, m, n: self._ck(self.lib.act_node_nullifier_set_retired_epochs(self.h, p, m, n)))
+
+    def export_epochs_step(self, cursor: int, max_keys: int):
+        out = np.empty(32 * max_keys, np.uint8); ep = np.empty(max_keys, np.uint32); cur = C.c_uint64(cursor); got = C.c_size_t(0)
+        self._ck(self.lib.act_node_nullifier_set_export_epochs(self.h, C.byref(cur), max_keys, out.ctypes.data, ep.ctypes.data, C.byref(got)))
+        return cur.value, out[:32 * got.value].tobytes(), ep[:got.value].copy()
+
+    def export_epochs(self, max_keys: int = 1 << 20):
+        return _export_epochs_loop(self.export_epochs_step, max_keys)
+
     def save(self, path: str) -> int:
         from . import nullifier_snapshot
-        return nullifier_snapshot.write(path, self.export())
+        keys, epochs = self.export_epochs()
+        return nullifier_snapshot.write_epochs(path, keys, epochs, self.retired_epochs())
 
     @classmethod
     def restore(cls, path: str, capacity_per_device: int = None, devices=(0,), salt: bytes = None) -> "NodeNullifierSet":
-        """a new node set holding the snapshot's keys; every device is reserved for its expected share (restore_capacity)"""
+        """a new node set holding the snapshot's keys, epochs and retired list; every device is reserved for its expected share
+        (restore_capacity)"""
         from . import nullifier_snapshot
-        keys = nullifier_snapshot.read(path)
+        keys, epochs, retired = nullifier_snapshot.read_epochs(path)
         s = cls(max(capacity_per_device or 0, 1), devices=devices, salt=salt)
-        nullifier_snapshot.restore_into(s, keys)
+        nullifier_snapshot.restore_epochs_into(s, keys, epochs, retired)
         return s
 
 
@@ -1219,3 +1357,31 @@ def _export_loop(step, max_keys: int) -> bytes:
         cur, b = step(cur, max_keys, buf)
         parts.append(b)
     return b"".join(parts)
+
+
+EPOCH_MAX = 0xFFFFFF         # ACT_NULLIFIER_EPOCH_MAX
+
+
+def _epoch_table(epochs, want_len: int = None) -> np.ndarray:
+    tab = np.ascontiguousarray(list(epochs), dtype=np.uint32)
+    if not 1 <= len(tab) <= 255 or (want_len is not None and len(tab) != want_len):
+        raise ValueError(f"epochs: {len(tab)} entries" + (f", expected {want_len}" if want_len is not None else ", expected 1 .. 255"))
+    return tab
+
+
+def _retired_list(call) -> list:
+    n = C.c_size_t(0)
+    call(None, 0, C.byref(n))
+    while True:
+        buf = np.zeros(max(1, n.value), np.uint32); room = len(buf)
+        call(buf.ctypes.data, room, C.byref(n))
+        if n.value <= room:
+            return [int(e) for e in buf[:n.value]]
+
+
+def _export_epochs_loop(step, max_keys: int):
+    cur, keys, eps = 0, [], []
+    while cur != EXPORT_DONE:
+        cur, b, e = step(cur, max_keys)
+        keys.append(b); eps.append(e)
+    return b"".join(keys), (np.concatenate(eps) if eps else np.zeros(0, np.uint32))

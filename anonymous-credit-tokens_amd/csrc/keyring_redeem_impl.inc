@@ -1,14 +1,21 @@
 // keyring_redeem_impl.inc — included by engine.hip after nullifier_impl.inc: the redemption step against a ring of issuer keys.
 // Composed as redeem_impl composes it (nullifier_impl.inc): ring verification -> check-and-insert with the verdicts as skip mask ->
 // sign what is left, each lane with the key `sign_key` names; the same failure contract (ACT_STATUS_NULLIFIER_UNDETERMINED,
-// ACT_STATUS_RECORDED_UNSIGNED, act_debug_fail_next_signs).  The nullifier set does not depend on the key.  No tiny form.
-static int redeem_keyring_impl(act_ctx* c, act_nullifier_set* set, size_t n, int mem, const uint8_t* keys, int nkeys, int sign_key, const uint8_t* proof,
+// ACT_STATUS_RECORDED_UNSIGNED, act_debug_fail_next_signs).  Membership in the nullifier set does not depend on the key.  No tiny form.
+// key_epochs (nullable, host memory, nkeys values): an accepted lane's nullifier is recorded under the epoch of the key it MATCHED --
+// out_key, as the ring verification leaves it, is the epoch index of the insert.
+static int redeem_keyring_impl(act_ctx* c, act_nullifier_set* set, size_t n, int mem, const uint8_t* keys, int nkeys, const uint32_t* key_epochs, int sign_key, const uint8_t* proof,
                                const uint8_t* cbor, const uint64_t* offsets, const uint8_t* rng, int rng_mode, uint8_t* out, uint8_t* status, uint8_t* out_key) {
   const bool wire = cbor != nullptr;
   if (!c || !set || !keys || !rng || nkeys < 1 || nkeys > ACT_KEYRING_MAX || (n && ((!proof && !cbor) || !out || !status || !out_key))) return ACT_ERR_ARG;
   if (sign_key != ACT_SIGN_MATCHED && (sign_key < 0 || sign_key >= nkeys)) return ACT_ERR_ARG;
   if (rng_mode != ACT_RNG_PER_LANE && rng_mode != ACT_RNG_SEQUENTIAL && rng_mode != ACT_RNG_CALLBACK) return ACT_ERR_ARG;
   if (set->device != c->device) { c->err = "act_redeem_keyring_batch: the nullifier set lives on another device"; return ACT_ERR_ARG; }
+  if (key_epochs) {      // refused before any verification work: nothing recorded, nothing signed, no status written
+    std::string why;
+    { std::lock_guard<std::mutex> lk(set->mu); why = null_epochs_refused(set, key_epochs, nkeys); }
+    if (!why.empty()) { c->err = "act_redeem_keyring_epochs_batch: " + why; return ACT_ERR_ARG; }
+  }
   if (n == 0) {      // a bad ring fails the call whatever n
     Call call(c, 0);
     HIPCK(c, hipSetDevice(c->device));
@@ -27,7 +34,8 @@ static int redeem_keyring_impl(act_ctx* c, act_nullifier_set* set, size_t n, int
   if (wire) { RingSel sel{keys, nkeys, out_key}; rc = verify_spend_cbor_impl(c, n, mem, nullptr, cbor, offsets, st, kp, nul, &sel); }
   else rc = act_verify_spend_keyring_batch(c, n, mem, keys, nkeys, proof, st, out_key, kp);
   if (rc) return rc;
-  const int rc_null = act_nullifier_check_and_insert_batch(set, n, mem, wire ? nul : proof, wire ? 32 : pb, st, sp);
+  const int rc_null = key_epochs ? act_nullifier_check_and_insert_epoch_batch(set, n, mem, wire ? nul : proof, wire ? 32 : pb, st, out_key, key_epochs, nkeys, sp)
+                                 : act_nullifier_check_and_insert_batch(set, n, mem, wire ? nul : proof, wire ? 32 : pb, st, sp);
   std::string null_err;
   if (rc_null) {
     null_err = std::string("nullifier set: ") + act_nullifier_set_last_error(set);
@@ -95,12 +103,24 @@ static int redeem_keyring_impl(act_ctx* c, act_nullifier_set* set, size_t n, int
 extern "C" int act_redeem_keyring_batch(act_ctx* c, act_nullifier_set* set, size_t n, int mem, const uint8_t* keys, int nkeys, int sign_key, const uint8_t* proof,
                                         const uint8_t* rng, int rng_mode, uint8_t* out_refund, uint8_t* status, uint8_t* out_key) {
   if (n && !proof) return ACT_ERR_ARG;
-  return redeem_keyring_impl(c, set, n, mem, keys, nkeys, sign_key, proof, nullptr, nullptr, rng, rng_mode, out_refund, status, out_key);
+  return redeem_keyring_impl(c, set, n, mem, keys, nkeys, nullptr, sign_key, proof, nullptr, nullptr, rng, rng_mode, out_refund, status, out_key);
 }
 extern "C" int act_redeem_cbor_keyring_batch(act_ctx* c, act_nullifier_set* set, size_t n, int mem, const uint8_t* keys, int nkeys, int sign_key,
                                              const uint8_t* cbor, const uint64_t* offsets, const uint8_t* rng, int rng_mode, uint8_t* out_refund_cbor,
                                              uint8_t* status, uint8_t* out_key) {
   if (n && !cbor) return ACT_ERR_ARG;
   static const uint8_t none = 0;
-  return redeem_keyring_impl(c, set, n, mem, keys, nkeys, sign_key, nullptr, cbor ? cbor : &none, offsets, rng, rng_mode, out_refund_cbor, status, out_key);
+  return redeem_keyring_impl(c, set, n, mem, keys, nkeys, nullptr, sign_key, nullptr, cbor ? cbor : &none, offsets, rng, rng_mode, out_refund_cbor, status, out_key);
+}
+extern "C" int act_redeem_keyring_epochs_batch(act_ctx* c, act_nullifier_set* set, size_t n, int mem, const uint8_t* keys, int nkeys, const uint32_t* key_epochs,
+                                               int sign_key, const uint8_t* proof, const uint8_t* rng, int rng_mode, uint8_t* out_refund, uint8_t* status, uint8_t* out_key) {
+  if (!key_epochs || (n && !proof)) return ACT_ERR_ARG;
+  return redeem_keyring_impl(c, set, n, mem, keys, nkeys, key_epochs, sign_key, proof, nullptr, nullptr, rng, rng_mode, out_refund, status, out_key);
+}
+extern "C" int act_redeem_cbor_keyring_epochs_batch(act_ctx* c, act_nullifier_set* set, size_t n, int mem, const uint8_t* keys, int nkeys, const uint32_t* key_epochs,
+                                                    int sign_key, const uint8_t* cbor, const uint64_t* offsets, const uint8_t* rng, int rng_mode,
+                                                    uint8_t* out_refund_cbor, uint8_t* status, uint8_t* out_key) {
+  if (!key_epochs || (n && !cbor)) return ACT_ERR_ARG;
+  static const uint8_t none = 0;
+  return redeem_keyring_impl(c, set, n, mem, keys, nkeys, key_epochs, sign_key, nullptr, cbor ? cbor : &none, offsets, rng, rng_mode, out_refund_cbor, status, out_key);
 }

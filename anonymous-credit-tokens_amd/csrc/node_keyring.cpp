@@ -15,6 +15,7 @@
 #include <string>
 #include <vector>
 #include "../../include/act_mi355x.h"
+#include "node_keyring.h"
 #include "rng_source.h"
 
 namespace act_node_dispatch {
@@ -46,9 +47,13 @@ int sign_pieces(act_node* nd, size_t n, const uint8_t* keys, int nkeys, const ui
 }
 
 constexpr size_t WIRE_BLOCK = (size_t)1 << 16;      // messages decoded into host records at a time (1.1 GB at L = 128)
+}  // namespace
 
-int node_redeem_keyring(act_node* nd, act_node_nullifier_set* set, size_t n, const uint8_t* keys, int nkeys, int sign_key, const uint8_t* proof,
-                        const uint8_t* cbor, const uint64_t* offsets, const uint8_t* rng, int rng_mode, uint8_t* out, uint8_t* status, uint8_t* out_key) {
+// null_step (nullable): the nullifier step when it is not the plain check-and-insert (node_epochs.cpp records the matched key's epoch:
+// it is handed out_key beside the verdicts).  A parameter and not a call, so that this file needs nothing of the engine's epoch calls.
+int act_node_keyring::redeem(act_node* nd, act_node_nullifier_set* set, size_t n, const uint8_t* keys, int nkeys, int sign_key, const uint8_t* proof,
+                             const uint8_t* cbor, const uint64_t* offsets, const uint8_t* rng, int rng_mode, uint8_t* out, uint8_t* status, uint8_t* out_key,
+                             const NullStep* null_step) {
   const bool wire = cbor != nullptr;
   if (!nd || !set || !rng || !ring_ok(keys, nkeys) || (n && ((!proof && !cbor) || !out || !status || !out_key))) return ACT_ERR_ARG;
   if (sign_key != ACT_SIGN_MATCHED && (sign_key < 0 || sign_key >= nkeys)) return ACT_ERR_ARG;
@@ -88,7 +93,8 @@ int node_redeem_keyring(act_node* nd, act_node_nullifier_set* set, size_t n, con
       }
     }
   }
-  const int rc_null = act_node_nullifier_check_and_insert_batch(set, n, wire ? nul.data() : proof, wire ? 32 : pb, verdict.data(), spent.data());
+  const int rc_null = null_step ? (*null_step)(set, n, wire ? nul.data() : proof, wire ? 32 : pb, verdict.data(), out_key, spent.data())
+                                : act_node_nullifier_check_and_insert_batch(set, n, wire ? nul.data() : proof, wire ? 32 : pb, verdict.data(), spent.data());
   std::vector<uint8_t> kidx(n);
   for (size_t i = 0; i < n; i++) {
     if (verdict[i] == 0 && spent[i]) verdict[i] = spent[i] == 1 ? ACT_STATUS_DOUBLE_SPEND : ACT_STATUS_NULLIFIER_UNDETERMINED;
@@ -118,7 +124,7 @@ int node_redeem_keyring(act_node* nd, act_node_nullifier_set* set, size_t n, con
   }
   return rc_null;
 }
-}  // namespace
+using act_node_keyring::redeem;
 
 extern "C" {
 
@@ -144,13 +150,13 @@ int act_node_refund_sign_keyring_batch(act_node* nd, size_t n, const uint8_t* ke
 int act_node_redeem_keyring_batch(act_node* nd, act_node_nullifier_set* set, size_t n, const uint8_t* keys, int nkeys, int sign_key, const uint8_t* proof,
                                   const uint8_t* rng, int rng_mode, uint8_t* out_refund, uint8_t* status, uint8_t* out_key) {
   if (n && !proof) return ACT_ERR_ARG;
-  return node_redeem_keyring(nd, set, n, keys, nkeys, sign_key, proof, nullptr, nullptr, rng, rng_mode, out_refund, status, out_key);
+  return redeem(nd, set, n, keys, nkeys, sign_key, proof, nullptr, nullptr, rng, rng_mode, out_refund, status, out_key, nullptr);
 }
 int act_node_redeem_cbor_keyring_batch(act_node* nd, act_node_nullifier_set* set, size_t n, const uint8_t* keys, int nkeys, int sign_key, const uint8_t* cbor,
                                        const uint64_t* offsets, const uint8_t* rng, int rng_mode, uint8_t* out_refund_cbor, uint8_t* status, uint8_t* out_key) {
   if (n && !cbor) return ACT_ERR_ARG;
   static const uint8_t none = 0;
-  return node_redeem_keyring(nd, set, n, keys, nkeys, sign_key, nullptr, cbor ? cbor : &none, offsets, rng, rng_mode, out_refund_cbor, status, out_key);
+  return redeem(nd, set, n, keys, nkeys, sign_key, nullptr, cbor ? cbor : &none, offsets, rng, rng_mode, out_refund_cbor, status, out_key, nullptr);
 }
 
 }  // extern "C"

@@ -42,20 +42,20 @@ int act_node_nullifier_set_reserve(act_node_nullifier_set* ns, size_t capacity_p
   return first_rc;
 }
 
-// Node cursor: device index << 40 | that device's set cursor (which is below 2^40 until it is ACT_NULLIFIER_EXPORT_DONE); the
-// device's own cursor check refuses one that stopped inside a set grown since.
+// Node cursor: device index << kCursorShift | that device's set cursor (node_nullifier.h); the device's own cursor check refuses one
+// that stopped inside a set that has been grown, or has had an epoch retired, since.
 int act_node_nullifier_set_export(act_node_nullifier_set* ns, uint64_t* cursor, size_t max_keys, uint8_t* out_keys, size_t* n_out) {
   if (!ns || !cursor || !n_out || !max_keys || !out_keys) return ACT_ERR_ARG;
   std::lock_guard<std::mutex> lock(ns->mu);
   *n_out = 0;
   if (*cursor == ACT_NULLIFIER_EXPORT_DONE) return ACT_OK;
-  const uint64_t part = *cursor >> 40;
+  const uint64_t part = *cursor >> act_node_null::kCursorShift;
   if (part >= ns->sets.size()) { ns->err = "act_node_nullifier_set_export: foreign cursor"; return ACT_ERR_ARG; }
-  uint64_t inner = *cursor & ((1ull << 40) - 1);
+  uint64_t inner = *cursor & ((1ull << act_node_null::kCursorShift) - 1);
   const int rc = act_nullifier_set_export(ns->sets[part], &inner, max_keys, ACT_MEM_HOST, out_keys, n_out);
   if (rc) { ns->err = "device " + std::to_string(ns->devices[part]) + ": " + act_nullifier_set_last_error(ns->sets[part]); return rc; }
-  if (inner != ACT_NULLIFIER_EXPORT_DONE) *cursor = part << 40 | inner;
-  else *cursor = part + 1 < ns->sets.size() ? (part + 1) << 40 : ACT_NULLIFIER_EXPORT_DONE;
+  if (inner != ACT_NULLIFIER_EXPORT_DONE) *cursor = part << act_node_null::kCursorShift | inner;
+  else *cursor = part + 1 < ns->sets.size() ? (part + 1) << act_node_null::kCursorShift : ACT_NULLIFIER_EXPORT_DONE;
   return ACT_OK;
 }
 }  // extern "C"

@@ -26,6 +26,9 @@ struct act_node_nullifier_set {
 
 
 namespace act_node_null {
+// Node export cursor: device index << kCursorShift | that device's set cursor (which is below 2^51 until it is
+// ACT_NULLIFIER_EXPORT_DONE; at most 4096 devices, so a node cursor never reaches ACT_NULLIFIER_EXPORT_DONE by itself).
+constexpr int kCursorShift = 51;
 // The keys of a call bucketed by owner (ns->buckets, lane order kept inside every bucket); out[i] = 0 for every lane.  Caller holds ns->mu.
 void bucket_by_owner(act_node_nullifier_set* ns, size_t n, const uint8_t* nullifiers, size_t stride, const uint8_t* skip_mask, uint8_t* out);
 // every device's bucket through `call` on its own thread, in parallel; rc per device

@@ -475,6 +475,38 @@ int act_nullifier_set_export(act_nullifier_set *set, uint64_t *cursor, size_t ma
 int act_nullifier_contains_batch(act_nullifier_set *set, size_t n, int mem, const uint8_t *nullifiers, size_t stride,
                                  uint8_t *out_found);
 
+/* Epochs: every recorded nullifier carries the epoch of the issuer key it was spent under, and a key that has left every ring for
+ * good can have its nullifiers removed (the rule for when that is safe: INTEGRATION.md section 8).  An epoch is a uint32_t the caller
+ * chooses per issuer key, 0 ... ACT_NULLIFIER_EPOCH_MAX; 0 is "untagged", what every call without epochs records, and can never be
+ * retired.  Membership ignores the epoch: a nullifier recorded under any live epoch is a double spend for every later spend; the
+ * epoch of the first recorder sticks.  The epoch lives in the high 24 bits of the slot's state word: a slot stays 36 bytes.
+ * act_nullifier_check_and_insert_epoch_batch: act_nullifier_check_and_insert_batch where a fresh lane i is recorded under
+ *   epoch_table[epoch_index[i]].  epoch_table: HOST memory, 1 <= n_epochs <= 255.  epoch_index: n bytes in `mem` memory (e.g. the out_key
+ *   array of a ring verification), or NULL = every lane uses epoch_table[0].  A table entry above ACT_NULLIFIER_EPOCH_MAX or naming a
+ *   retired epoch refuses the whole call as a batch without room is refused: ACT_ERR_ARG, nothing recorded, every unmasked lane
+ *   ACT_NULLIFIER_UNDETERMINED.  An unmasked lane whose index is not below n_epochs is neither looked up nor recorded and reports
+ *   ACT_NULLIFIER_UNDETERMINED; the other lanes are served; the call returns ACT_ERR_ARG.  Table {0} with NULL indices is the existing call.
+ * act_nullifier_set_epoch_len: *out_count = the nullifiers recorded under `epoch` (0 for an unknown or retired one); one pass over
+ *   the state words on the device.
+ * act_nullifier_set_retire_epoch: removes every nullifier of `epoch` (*out_removed, nullable, = how many), gives their slots back and
+ *   refuses the epoch from then on.  epoch 0 or above the maximum: ACT_ERR_ARG, set unchanged.  Retiring a retired epoch, or one without
+ *   keys, is ACT_OK with 0 removed (and the epoch is remembered).  Built like reserve -- a second table of the same capacity, swapped in
+ *   when every other key has been placed; on any failure (ACT_ERR_HIP) the set is exactly as it was and the epoch is NOT retired.  len
+ *   drops by *out_removed; capacity does not change; the set's lock is held for the whole call; export cursors taken before a
+ *   retirement that removed a key are stale.
+ * act_nullifier_set_retired_epochs: the retired epochs, ascending, at most max_epochs of them; *n_out = how many there are.  Host pointers.
+ * act_nullifier_set_export_epochs: act_nullifier_set_export with out_epochs[i] (in `mem` memory) the epoch of out_keys[32 i ...]; the two
+ *   calls share one cursor space. */
+#define ACT_NULLIFIER_EPOCH_MAX 0xFFFFFFu
+int act_nullifier_check_and_insert_epoch_batch(act_nullifier_set *set, size_t n, int mem, const uint8_t *nullifiers, size_t stride,
+                                               const uint8_t *skip_mask, const uint8_t *epoch_index, const uint32_t *epoch_table,
+                                               int n_epochs, uint8_t *out_spent);
+int act_nullifier_set_epoch_len(act_nullifier_set *set, uint32_t epoch, uint64_t *out_count);
+int act_nullifier_set_retire_epoch(act_nullifier_set *set, uint32_t epoch, uint64_t *out_removed);
+int act_nullifier_set_retired_epochs(act_nullifier_set *set, uint32_t *out_epochs, size_t max_epochs, size_t *n_out);
+int act_nullifier_set_export_epochs(act_nullifier_set *set, uint64_t *cursor, size_t max_keys, int mem, uint8_t *out_keys,
+                                    uint32_t *out_epochs, size_t *n_out);
+
 /* The same set spread over the GPUs of a node: one set per entry of devices[], a nullifier owned by exactly one of them
  * (keyed hash of the reduced scalar), so a batch keeps the sequential meaning above in lane order.  The host buckets the
  * keys by owner (stable), every GPU checks-and-inserts its bucket from its own thread, answers are scattered back:
@@ -503,6 +535,18 @@ int act_node_nullifier_set_reserve(act_node_nullifier_set *set, size_t capacity_
 int act_node_nullifier_set_export(act_node_nullifier_set *set, uint64_t *cursor, size_t max_keys, uint8_t *out_keys, size_t *n_out);
 int act_node_nullifier_contains_batch(act_node_nullifier_set *set, size_t n, const uint8_t *nullifiers, size_t stride,
                                       uint8_t *out_found);
+/* Node forms of the epoch calls (host memory).  check-and-insert: routed by owner as above, the lanes' epoch indices with them.
+ * epoch_len: the sum over the devices.  retire_epoch: device after device; a failure names the device, leaves every set valid and some
+ * already retired, and a repeat of the call finishes the job.  retired_epochs: the epochs EVERY device has retired (an insert naming an
+ * epoch that any device has retired is refused all the same).  export_epochs shares the cursor space of act_node_nullifier_set_export. */
+int act_node_nullifier_check_and_insert_epoch_batch(act_node_nullifier_set *set, size_t n, const uint8_t *nullifiers, size_t stride,
+                                                    const uint8_t *skip_mask, const uint8_t *epoch_index, const uint32_t *epoch_table,
+                                                    int n_epochs, uint8_t *out_spent);
+int act_node_nullifier_set_epoch_len(act_node_nullifier_set *set, uint32_t epoch, uint64_t *out_count);
+int act_node_nullifier_set_retire_epoch(act_node_nullifier_set *set, uint32_t epoch, uint64_t *out_removed);
+int act_node_nullifier_set_retired_epochs(act_node_nullifier_set *set, uint32_t *out_epochs, size_t max_epochs, size_t *n_out);
+int act_node_nullifier_set_export_epochs(act_node_nullifier_set *set, uint64_t *cursor, size_t max_keys, uint8_t *out_keys,
+                                         uint32_t *out_epochs, size_t *n_out);
 
 /* The issuer's whole redemption step -- verify, look the nullifier up, record it, sign the refund (examples/act.rs:62-73; the
  * NullifierDb loops of src/tests.rs) -- as one call with the result of the loop
@@ -560,7 +604,7 @@ int act_node_redeem_cbor_batch(act_node *node, act_node_nullifier_set *set, size
  *             is not signed -- status 255, zero record, no rng slice consumed.
  * rng conventions are those of the one-key call of the same name (ACT_RNG_CALLBACK in the redeem calls only); the generator is touched
  * after every verdict (and nullifier answer) is known.  nkeys == 1 gives the bytes of the one-key call.  The nullifier set does not
- * depend on the key: a nullifier spent under the old key stays spent.  Always the pipelined chunk schedule, whatever n. */
+ * depend on the key: a nullifier spent under the old key stays spent (until that key's epoch is retired, below).  Always the pipelined chunk schedule, whatever n. */
 #define ACT_KEYRING_MAX 4
 #define ACT_KEY_NONE 255
 #define ACT_SIGN_MATCHED (-1)
@@ -583,6 +627,23 @@ int act_node_redeem_keyring_batch(act_node *node, act_node_nullifier_set *set, s
 int act_node_redeem_cbor_keyring_batch(act_node *node, act_node_nullifier_set *set, size_t n, const uint8_t *keys, int nkeys, int sign_key,
                                        const uint8_t *cbor, const uint64_t *offsets, const uint8_t *rng, int rng_mode, uint8_t *out_refund_cbor,
                                        uint8_t *status, uint8_t *out_key);
+/* The ring redemption calls with epochs: key_epochs = nkeys values in HOST memory, key_epochs[k] the epoch of ring key k.  Everything
+ * the calls above return is byte for byte the same; an accepted lane's nullifier is recorded under the epoch of the key its proof
+ * MATCHED (key_epochs[out_key[i]]), never the key it is signed with: the nullifier belongs to the token being spent.  An epoch above
+ * ACT_NULLIFIER_EPOCH_MAX or a retired one fails the call with ACT_ERR_ARG before any verification: nothing recorded, nothing
+ * signed, status[] not written. */
+int act_redeem_keyring_epochs_batch(act_ctx *ctx, act_nullifier_set *set, size_t n, int mem, const uint8_t *keys, int nkeys,
+                                    const uint32_t *key_epochs, int sign_key, const uint8_t *proof, const uint8_t *rng, int rng_mode,
+                                    uint8_t *out_refund, uint8_t *status, uint8_t *out_key);
+int act_redeem_cbor_keyring_epochs_batch(act_ctx *ctx, act_nullifier_set *set, size_t n, int mem, const uint8_t *keys, int nkeys,
+                                         const uint32_t *key_epochs, int sign_key, const uint8_t *cbor, const uint64_t *offsets,
+                                         const uint8_t *rng, int rng_mode, uint8_t *out_refund_cbor, uint8_t *status, uint8_t *out_key);
+int act_node_redeem_keyring_epochs_batch(act_node *node, act_node_nullifier_set *set, size_t n, const uint8_t *keys, int nkeys,
+                                         const uint32_t *key_epochs, int sign_key, const uint8_t *proof, const uint8_t *rng, int rng_mode,
+                                         uint8_t *out_refund, uint8_t *status, uint8_t *out_key);
+int act_node_redeem_cbor_keyring_epochs_batch(act_node *node, act_node_nullifier_set *set, size_t n, const uint8_t *keys, int nkeys,
+                                              const uint32_t *key_epochs, int sign_key, const uint8_t *cbor, const uint64_t *offsets,
+                                              const uint8_t *rng, int rng_mode, uint8_t *out_refund_cbor, uint8_t *status, uint8_t *out_key);
 
 /* ======== row d and test infrastructure: debug hooks, measurement knobs, kernel timing, roofline probes (nothing here is on the product's path) ==== */
 /* Debug / test hook: the exact "spend" transcript pre-images of the last act_verify_spend_batch /

@@ -97,6 +97,19 @@ extern "C" {
     fn act_node_nullifier_set_reserve(set: *mut ActNodeNullifierSet, capacity_per_device: usize) -> c_int;
     fn act_node_nullifier_set_export(set: *mut ActNodeNullifierSet, cursor: *mut u64, max_keys: usize, out_keys: *mut u8, n_out: *mut usize) -> c_int;
     fn act_node_nullifier_contains_batch(set: *mut ActNodeNullifierSet, n: usize, nullifiers: *const u8, stride: usize, out_found: *mut u8) -> c_int;
+    fn act_node_nullifier_check_and_insert_epoch_batch(set: *mut ActNodeNullifierSet, n: usize, nullifiers: *const u8, stride: usize, skip_mask: *const u8,
+                                                       epoch_index: *const u8, epoch_table: *const u32, n_epochs: c_int, out_spent: *mut u8) -> c_int;
+    fn act_node_nullifier_set_epoch_len(set: *mut ActNodeNullifierSet, epoch: u32, out_count: *mut u64) -> c_int;
+    fn act_node_nullifier_set_retire_epoch(set: *mut ActNodeNullifierSet, epoch: u32, out_removed: *mut u64) -> c_int;
+    fn act_node_nullifier_set_retired_epochs(set: *mut ActNodeNullifierSet, out_epochs: *mut u32, max_epochs: usize, n_out: *mut usize) -> c_int;
+    fn act_node_nullifier_set_export_epochs(set: *mut ActNodeNullifierSet, cursor: *mut u64, max_keys: usize, out_keys: *mut u8, out_epochs: *mut u32,
+                                            n_out: *mut usize) -> c_int;
+    fn act_node_redeem_keyring_epochs_batch(node: *mut ActNode, set: *mut ActNodeNullifierSet, n: usize, keys: *const u8, nkeys: c_int, key_epochs: *const u32,
+                                            sign_key: c_int, proof: *const u8, rng: *const u8, rng_mode: c_int, out_refund: *mut u8, status: *mut u8,
+                                            out_key: *mut u8) -> c_int;
+    fn act_node_redeem_cbor_keyring_epochs_batch(node: *mut ActNode, set: *mut ActNodeNullifierSet, n: usize, keys: *const u8, nkeys: c_int,
+                                                 key_epochs: *const u32, sign_key: c_int, cbor: *const u8, offsets: *const u64, rng: *const u8, rng_mode: c_int,
+                                                 out_refund_cbor: *mut u8, status: *mut u8, out_key: *mut u8) -> c_int;
     fn act_node_device_stats(node: *mut ActNode, k: c_int, weight: *mut f64, last_lanes: *mut u64, last_seconds: *mut f64, last_calls: *mut u64) -> c_int;
 }
 
@@ -731,6 +744,21 @@ impl GpuNullifierStore {
     pub fn reserve(&self, capacity_per_device: usize) -> Result<(), String> {
         self.check(unsafe { act_node_nullifier_set_reserve(self.0, capacity_per_device) })
     }
+    /// How many nullifiers are recorded under `epoch` (the caller's name for an issuer key; `Keyring::with_epochs`).
+    pub fn epoch_len(&self, epoch: u32) -> Result<u64, String> {
+        let mut count = 0u64;
+        self.check(unsafe { act_node_nullifier_set_epoch_len(self.0, epoch, &mut count) })?;
+        Ok(count)
+    }
+    /// Remove every nullifier recorded under `epoch` and refuse the epoch from then on; returns how many were removed.  ONLY once the
+    /// epoch's key has been removed from every ring of every server that shares this store and will never be put back: from then on no
+    /// proof under that key verifies, so its nullifiers are never consulted again; retiring earlier re-enables double spends of that
+    /// key's tokens.  GPU after GPU: after an error some have retired, every set is valid, and a repeat of the call finishes the job.
+    pub fn retire_epoch(&self, epoch: u32) -> Result<u64, String> {
+        let mut removed = 0u64;
+        self.check(unsafe { act_node_nullifier_set_retire_epoch(self.0, epoch, &mut removed) })?;
+        Ok(removed)
+    }
     /// Read-only: is each nullifier recorded?  For audit and status queries -- a spend decision is `redeem_*_batch`, which records.
     pub fn contains(&self, nullifiers: &[Scalar]) -> Result<Vec<bool>, String> {
         let keys: Vec<u8> = nullifiers.iter().flat_map(|k| k.to_bytes()).collect();
@@ -928,8 +956,10 @@ impl PrivateKey {
 /// no ring key accepts it; a double spend keeps the index it matched), and the refund is signed with the matched key
 /// (`sign_with = None`) or with ring key `sign_with = Some(i)` -- which moves the client onto that key with its next token (the
 /// client then calls `to_credit_token` with `ring.public(i)`).  The nullifier store is shared by all keys; `Params` must be the
-/// ones every ring key issued under.
-pub struct Keyring<'a>(pub &'a [PrivateKey]);
+/// ones every ring key issued under.  With epochs (`with_epochs`: one `u32` up to 2^24 - 1 per key, the caller's stable name for it) an
+/// accepted nullifier is recorded under the epoch of the key its proof matched, so that `GpuNullifierStore::retire_epoch` can drop a
+/// key's nullifiers once the key has left every ring for good.
+pub struct Keyring<'a>(pub &'a [PrivateKey], pub Option<&'a [u32]>);
 pub const ACT_KEYRING_MAX: usize = 4;
 const ACT_KEY_NONE: u8 = 255;
 const ACT_SIGN_MATCHED: c_int = -1;
@@ -940,6 +970,13 @@ pub struct RingRedeemed<T> {
 }
 
 impl<'a> Keyring<'a> {
+    pub fn new(keys: &'a [PrivateKey]) -> Self {
+        Keyring(keys, None)
+    }
+    pub fn with_epochs(keys: &'a [PrivateKey], epochs: &'a [u32]) -> Self {
+        assert!(keys.len() == epochs.len(), "one epoch per ring key");
+        Keyring(keys, Some(epochs))
+    }
     pub fn public(&self, i: usize) -> &PublicKey {
         self.0[i].public()
     }
@@ -966,8 +1003,13 @@ impl<'a> Keyring<'a> {
         let src = rng_source(&mut rng);
         let (mut out, mut status, mut out_key) = (vec![0u8; REFUND_CBOR_BYTES * n + 1], vec![0u8; n + 1], vec![ACT_KEY_NONE; n + 1]);
         let rc = unsafe {
-            act_node_redeem_cbor_keyring_batch(gpu.0, store.0, n, keys.as_ptr(), self.0.len() as c_int, sign_key, blob.as_ptr(), offsets.as_ptr(),
-                                               &src as *const ActRngSource as *const u8, ACT_RNG_CALLBACK, out.as_mut_ptr(), status.as_mut_ptr(), out_key.as_mut_ptr())
+            match self.1 {
+                Some(ep) => act_node_redeem_cbor_keyring_epochs_batch(gpu.0, store.0, n, keys.as_ptr(), self.0.len() as c_int, ep.as_ptr(), sign_key, blob.as_ptr(),
+                                                                      offsets.as_ptr(), &src as *const ActRngSource as *const u8, ACT_RNG_CALLBACK, out.as_mut_ptr(),
+                                                                      status.as_mut_ptr(), out_key.as_mut_ptr()),
+                None => act_node_redeem_cbor_keyring_batch(gpu.0, store.0, n, keys.as_ptr(), self.0.len() as c_int, sign_key, blob.as_ptr(), offsets.as_ptr(),
+                                                           &src as *const ActRngSource as *const u8, ACT_RNG_CALLBACK, out.as_mut_ptr(), status.as_mut_ptr(), out_key.as_mut_ptr()),
+            }
         };
         let engine_failure = if rc != 0 { Some(unsafe { CStr::from_ptr(act_node_last_error(gpu.0)) }.to_string_lossy().into_owned()) } else { None };
         RingRedeemed { redeemed: Redeemed { lanes: refund_messages(&out, &status[..n]), engine_failure }, matched: Self::matched(&out_key[..n]) }
@@ -982,8 +1024,13 @@ impl<'a> Keyring<'a> {
         let src = rng_source(&mut rng);
         let (mut out, mut status, mut out_key) = (vec![0u8; 128 * n + 1], vec![0u8; n + 1], vec![ACT_KEY_NONE; n + 1]);
         let rc = unsafe {
-            act_node_redeem_keyring_batch(gpu.0, store.0, n, keys.as_ptr(), self.0.len() as c_int, sign_key, rec.as_ptr(), &src as *const ActRngSource as *const u8,
-                                          ACT_RNG_CALLBACK, out.as_mut_ptr(), status.as_mut_ptr(), out_key.as_mut_ptr())
+            match self.1 {
+                Some(ep) => act_node_redeem_keyring_epochs_batch(gpu.0, store.0, n, keys.as_ptr(), self.0.len() as c_int, ep.as_ptr(), sign_key, rec.as_ptr(),
+                                                                 &src as *const ActRngSource as *const u8, ACT_RNG_CALLBACK, out.as_mut_ptr(), status.as_mut_ptr(),
+                                                                 out_key.as_mut_ptr()),
+                None => act_node_redeem_keyring_batch(gpu.0, store.0, n, keys.as_ptr(), self.0.len() as c_int, sign_key, rec.as_ptr(), &src as *const ActRngSource as *const u8,
+                                                      ACT_RNG_CALLBACK, out.as_mut_ptr(), status.as_mut_ptr(), out_key.as_mut_ptr()),
+            }
         };
         let engine_failure = if rc != 0 { Some(unsafe { CStr::from_ptr(act_node_last_error(gpu.0)) }.to_string_lossy().into_owned()) } else { None };
         let lanes = (0..n).map(|i| if status[i] == 0 { Ok(Refund::from_record(&out[128 * i..128 * i + 128])) } else { Err(status_to_wire_error(status[i])) }).collect();

@@ -7,7 +7,7 @@ root=$(cd "$(dirname "$0")/.." && pwd)
 src=$root/anonymous-credit-tokens_amd/csrc
 out=$root/build/$name
 mkdir -p "$out"
-make -C "$src" host_hash.o host_pool.o node.o node_nullifier.o node_issue_wire.o node_keyring.o >/dev/null
+make -C "$src" host_hash.o host_pool.o node.o node_nullifier.o node_issue_wire.o node_keyring.o node_epochs.o >/dev/null
 pids=()
 # FILES="k_spend_verify ..." restricts the extra flags to those translation units (default: all)
 for f in engine k_misc k_spend_verify k_spend_bits k_sign k_prove k_client k_keyring; do
@@ -21,5 +21,5 @@ done
 for p in "${pids[@]}"; do wait $p; done
 extra_libs=()
 [[ " $* " == *" -DACT_ROCTX "* ]] && extra_libs=(-L/opt/rocm/lib -lrocprofiler-sdk-roctx)      # named ranges for rocprofv3 --marker-trace
-hipcc --offload-arch=gfx950 -shared -fPIC -o "$root/anonymous-credit-tokens_amd/libact_$name.so" "$out"/*.o "$src/host_hash.o" "$src/host_pool.o" "$src/node.o" "$src/node_nullifier.o" "$src/node_issue_wire.o" "$src/node_keyring.o" -lpthread "${extra_libs[@]}"
+hipcc --offload-arch=gfx950 -shared -fPIC -o "$root/anonymous-credit-tokens_amd/libact_$name.so" "$out"/*.o "$src/host_hash.o" "$src/host_pool.o" "$src/node.o" "$src/node_nullifier.o" "$src/node_issue_wire.o" "$src/node_keyring.o" "$src/node_epochs.o" -lpthread "${extra_libs[@]}"
 echo "built libact_$name.so"

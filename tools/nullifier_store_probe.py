@@ -1,5 +1,7 @@
 """Nullifier-set growth, export and read-only look-up on one GPU: keys/s for export (to host and to device memory), for contains
 with check-and-insert beside it, and seconds per reserve (a rehash into a table twice as large) at 2^24 and 2^26 recorded keys.
+Epochs: the epoch insert beside check-and-insert (same batch, a random index over a table of four epochs), and on a set whose keys
+are spread over four epochs the seconds of one epoch_len and of retire_epoch of one epoch in four (a rehash into a table of the same size).
 Host clock around calls that end in a device synchronise; every timed call is preceded by a warm-up of the same shape.
 
     python tools/nullifier_store_probe.py [--out profiles/nullifier_store_probe.json] [--sizes 24,26]
@@ -36,16 +38,25 @@ def timed(torch, fn):
     return time.perf_counter() - t, r
 
 
-def fill(capi, torch, n, seed, chunk=1 << 22):
+def fill(capi, torch, n, seed, chunk=1 << 22, keys=None, epochs=None):
+    """a set of n recorded keys; `epochs` (a table): every key under a random entry of it, the per-key indices returned as well"""
     s = capi.NullifierSet(n, device=0, salt=seed.to_bytes(16, "little"))
     out = torch.zeros(chunk, dtype=torch.uint8, device="cuda")
-    keys = keys_on_device(torch, n, seed)
+    keys = keys_on_device(torch, n, seed) if keys is None else keys
+    eidx = None
+    if epochs:
+        g = torch.Generator(device="cuda"); g.manual_seed(seed)
+        eidx = torch.randint(0, len(epochs), (n,), dtype=torch.uint8, device="cuda", generator=g)
+        torch.cuda.synchronize()
     for i in range(0, n, chunk):
         m = min(chunk, n - i)
-        s.check_and_insert_dev(m, keys[i:i + m].data_ptr(), 32, 0, out.data_ptr())
+        if epochs:
+            s.check_and_insert_epoch_dev(m, keys[i:i + m].data_ptr(), 32, 0, eidx[i:i + m].data_ptr(), epochs, out.data_ptr())
+        else:
+            s.check_and_insert_dev(m, keys[i:i + m].data_ptr(), 32, 0, out.data_ptr())
     torch.cuda.synchronize()
     assert len(s) == n, (len(s), n)
-    return s, keys
+    return (s, keys, eidx) if epochs else (s, keys)
 
 
 def export_dev_all(capi, s, buf, max_keys):
@@ -90,6 +101,15 @@ def probe(lg, capi, torch):
         t, _ = timed(torch, lambda: s2.check_and_insert_dev(m, q.data_ptr(), 32, 0, found.data_ptr()))
         s2.close()
     res["check_and_insert"] = {"keys": m, "seconds": t, "keys_per_s": m / t}
+    # the epoch insert of the same batch: a random index per lane over a table of four epochs
+    table = [0, 11, 12, 13]
+    qidx = torch.randint(0, 4, (m,), dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    for rep in range(2):
+        s2 = capi.NullifierSet(n, device=0)
+        t, _ = timed(torch, lambda: s2.check_and_insert_epoch_dev(m, q.data_ptr(), 32, 0, qidx.data_ptr(), table, found.data_ptr()))
+        s2.close()
+    res["check_and_insert_epoch"] = {"keys": m, "seconds": t, "keys_per_s": m / t}
     # reserve: a rehash of all n keys into a table twice as large (the first reserve of a process is warmed on a small set)
     w = capi.NullifierSet(1024); w.check_and_insert(bytes(32)); w.reserve(4096); w.close()
     t, _ = timed(torch, lambda: s.reserve(2 * n))
@@ -98,6 +118,21 @@ def probe(lg, capi, torch):
     res["reserve"] = {"seconds": t, "new_table_slots": 2 * slots, "approx_hbm_bytes": moved}
     s.contains_dev(m, q.data_ptr(), 32, found.data_ptr())
     assert int(found.sum().item()) == m // 2
+    s.close()
+    # epoch_len and retire_epoch on a set of n keys spread over four epochs (the first retirement of a process is warmed on a small set)
+    s, _, eidx = fill(capi, torch, n, 2000 + lg, keys=keys, epochs=table)
+    want = int((eidx == 2).sum().item())
+    s.epoch_len(12)
+    t, got = timed(torch, lambda: s.epoch_len(12))
+    assert got == want
+    res["epoch_len"] = {"seconds": t, "slots_per_s": slots / t, "state_bytes": 4 * slots}
+    w = capi.NullifierSet(1024); w.check_and_insert(bytes(32), epochs=[3]); w.retire_epoch(3); w.close()
+    t, removed = timed(torch, lambda: s.retire_epoch(12))
+    assert removed == want and len(s) == n - want
+    moved = slots * 4 * 2 + (n - want) * 32 + slots * 4 * 2 + (n - want) * 32      # states counted and read, kept keys read; new states cleared + CAS, keys written
+    res["retire_epoch"] = {"seconds": t, "removed": removed, "of": n, "table_slots": slots, "approx_hbm_bytes": moved}
+    s.contains_dev(m, q.data_ptr(), 32, found.data_ptr())
+    assert int(found.sum().item()) == int((eidx[:m // 2] != 2).sum().item())
     s.close()
     return res
 
