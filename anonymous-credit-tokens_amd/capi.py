@@ -15,6 +15,8 @@ MEM_HOST, MEM_DEVICE = 0, 1
 RNG_PER_LANE, RNG_SEQUENTIAL, RNG_CALLBACK = 0, 1, 2
 TRANSCRIPT_HOST, TRANSCRIPT_DEVICE = 0, 1
 KEYRING_MAX, KEY_NONE, SIGN_MATCHED = 4, 255, -1      # act_*_keyring_batch: ring size, "no ring key matched", "sign with the matched key"
+STATUS_WRONG_CHARGE = 250                             # act_redeem_*admit_batch: s is not the expected charge
+ADMIT_COUNTS = ("lanes", "wire_rejected", "wrong_charge", "spent_before", "verified", "rejected_by_verification", "double_spend_after", "accepted")
 _ERRS = {1: "ACT_ERR_ARG", 2: "ACT_ERR_HIP", 3: "ACT_ERR_PARAMS", 4: "ACT_ERR_NO_DEVICE", 5: "ACT_ERR_RNG"}
 
 EXPORTS = [
@@ -44,6 +46,7 @@ EXPORTS = [
     "act_node_nullifier_check_and_insert_epoch_batch", "act_node_nullifier_set_epoch_len", "act_node_nullifier_set_retire_epoch",
     "act_node_nullifier_set_retired_epochs", "act_node_nullifier_set_export_epochs", "act_node_redeem_keyring_epochs_batch",
     "act_node_redeem_cbor_keyring_epochs_batch",
+    "act_redeem_admit_batch", "act_redeem_cbor_admit_batch",
     "act_issue_check_cbor_batch", "act_issue_sign_cbor_batch", "act_issue_cbor_batch",
     "act_node_issue_check_cbor_batch", "act_node_issue_sign_cbor_batch", "act_node_issue_cbor_batch",
     "act_ctx_host_hash_stats", "act_ctx_set_tiny_calls", "act_node_set_balance", "act_node_device_stats", "act_node_balance_state", "act_debug_set_slowdown", "act_debug_fail_next_signs",
@@ -221,6 +224,9 @@ def load() -> C.CDLL:
     lib.act_node_redeem_keyring_epochs_batch.argtypes = [vp, vp, sz, u8p, i32, u32p, i32, u8p, u8p, i32, u8p, u8p, u8p]
     lib.act_node_redeem_cbor_keyring_epochs_batch.argtypes = [vp, vp, sz, u8p, i32, u32p, i32, u8p, vp, u8p, i32, u8p, u8p, u8p]
     lib.act_node_redeem_cbor_batch.argtypes = [vp, vp, sz, u8p, u8p, vp, u8p, i32, u8p, u8p]
+    # admission before verification: the expected charge and the spent nullifiers first (out_counts: ACT_ADMIT_COUNTS values, host)
+    lib.act_redeem_admit_batch.argtypes = [vp, vp, sz, i32, u8p, i32, u32p, i32, u8p, u8p, u8p, i32, u8p, u8p, u8p, u64p]
+    lib.act_redeem_cbor_admit_batch.argtypes = [vp, vp, sz, i32, u8p, i32, u32p, i32, u8p, vp, u8p, u8p, i32, u8p, u8p, u8p, u64p]
     lib.act_issue_check_cbor_batch.argtypes = [vp, sz, i32, u8p, vp, u8p, u8p]
     lib.act_issue_sign_cbor_batch.argtypes = [vp, sz, i32, u8p, u8p, u8p, u8p, u8p, i32, u8p, u8p]
     lib.act_issue_cbor_batch.argtypes = [vp, sz, i32, u8p, u8p, vp, u8p, u8p, i32, u8p, u8p]
@@ -719,6 +725,62 @@ class Engine:
         else:
             self._ck(self.lib.act_redeem_cbor_keyring_batch(self.ctx, p["set"].h, n, mem, pk, nk, p.get("sign_key", SIGN_MATCHED), p["cbor"], p.get("offsets") or None,
                                                             p["rng"], p["rng_mode"], p["out"], p["status"], p["out_key"]))
+
+    # ---- admission before verification (act_redeem_admit_batch / act_redeem_cbor_admit_batch) ---------------------------------------
+    def redeem_admit(self, nullifier_set, keys, proofs: bytes, rng, rng_mode: int = RNG_PER_LANE, sign_key: int = SIGN_MATCHED, charges: bytes = None,
+                     key_epochs=None, raw: bool = False):
+        """redeem_keyring with the admission stage in front: a lane whose charge s is not charges[i] (STATUS_WRONG_CHARGE) or whose
+        nullifier is already in the set (3) is answered without being verified.  -> (statuses, refunds, out_key, counts dict);
+        raw=True: (rc, statuses, refunds, out_key, counts), no exception."""
+        n = len(proofs) // self.proof_bytes; out = np.full(128 * n, 7 if raw else 0, np.uint8); st = np.zeros(n, np.uint8); ok = np.zeros(n, np.uint8)
+        pk, kk = _in(b"".join(keys)); p0, k0 = _in(proofs, self.proof_bytes * n); p1, k1 = _rng_arg(rng)
+        pc, kc = _in(charges, 32 * n) if charges is not None else (None, None)
+        ke = _epoch_table(key_epochs, len(keys)) if key_epochs is not None else None
+        cnt = (C.c_uint64 * len(ADMIT_COUNTS))()
+        rc = self.lib.act_redeem_admit_batch(self.ctx, nullifier_set.h, n, MEM_HOST, pk, len(keys), ke.ctypes.data if ke is not None else None, sign_key, p0, pc, p1,
+                                             rng_mode, out.ctypes.data, st.ctypes.data, ok.ctypes.data, cnt)
+        counts = dict(zip(ADMIT_COUNTS, (int(v) for v in cnt)))
+        if raw:
+            return rc, st.tobytes(), out.tobytes(), ok.tobytes(), counts
+        self._ck(rc)
+        return st.tobytes(), out.tobytes(), ok.tobytes(), counts
+
+    def redeem_cbor_admit(self, nullifier_set, keys, messages: list, rng, rng_mode: int = RNG_SEQUENTIAL, sign_key: int = SIGN_MATCHED, charges: bytes = None,
+                          key_epochs=None, raw: bool = False):
+        """wire bytes in, wire bytes out -> (statuses, list of CBOR Refund messages (b"" where not signed), out_key, counts dict)"""
+        n = len(messages); p0, k0, offs = _msgs(messages); ml = self.cbor_size("Refund")
+        st = np.zeros(n, np.uint8); ok = np.zeros(n, np.uint8); out = np.zeros(ml * n, np.uint8); pk, kk = _in(b"".join(keys)); pr, kr = _rng_arg(rng)
+        pc, kc = _in(charges, 32 * n) if charges is not None else (None, None)
+        ke = _epoch_table(key_epochs, len(keys)) if key_epochs is not None else None
+        cnt = (C.c_uint64 * len(ADMIT_COUNTS))()
+        rc = self.lib.act_redeem_cbor_admit_batch(self.ctx, nullifier_set.h, n, MEM_HOST, pk, len(keys), ke.ctypes.data if ke is not None else None, sign_key, p0,
+                                                  offs.ctypes.data, pc, pr, rng_mode, out.ctypes.data, st.ctypes.data, ok.ctypes.data, cnt)
+        counts = dict(zip(ADMIT_COUNTS, (int(v) for v in cnt)))
+        b = out.tobytes()
+        msgs = [b[i * ml:(i + 1) * ml] if st[i] == 0 else b"" for i in range(n)]
+        if raw:
+            return rc, st.tobytes(), msgs, ok.tobytes(), counts
+        self._ck(rc)
+        assert all(st[i] == 0 or not out[i * ml:(i + 1) * ml].any() for i in range(n)), "a failed lane's slot is not zero"
+        return st.tobytes(), msgs, ok.tobytes(), counts
+
+    def admit_ptr(self, fn: str, keys, n: int, mem: int, **p):
+        """the admission calls on raw pointers of either kind: fn = redeem / redeem_cbor; p: set, proofs | cbor (+ offsets), charges,
+        rng, rng_mode, out, status, out_key, key_epochs, sign_key.  -> counts dict"""
+        pk, kk = _in(b"".join(keys)); nk = len(keys)
+        ke = _epoch_table(p["key_epochs"], nk) if p.get("key_epochs") is not None else None
+        kep = ke.ctypes.data if ke is not None else None
+        cnt = (C.c_uint64 * len(ADMIT_COUNTS))()
+        if fn == "redeem":
+            rc = self.lib.act_redeem_admit_batch(self.ctx, p["set"].h, n, mem, pk, nk, kep, p.get("sign_key", SIGN_MATCHED), p["proofs"], p.get("charges") or None,
+                                                 p["rng"], p["rng_mode"], p["out"], p["status"], p["out_key"], cnt)
+        else:
+            rc = self.lib.act_redeem_cbor_admit_batch(self.ctx, p["set"].h, n, mem, pk, nk, kep, p.get("sign_key", SIGN_MATCHED), p["cbor"], p.get("offsets") or None,
+                                                      p.get("charges") or None, p["rng"], p["rng_mode"], p["out"], p["status"], p["out_key"], cnt)
+        if not p.get("raw"):
+            self._ck(rc)
+        counts = dict(zip(ADMIT_COUNTS, (int(v) for v in cnt)))
+        return (rc, counts) if p.get("raw") else counts
 
     # ---- issuance on wire bytes (act_issue_*cbor_batch): IssuanceRequest messages in, IssuanceResponse messages out ----------------
     def issue_cbor(self, sk: bytes, messages: list, c: bytes, rng, rng_mode: int = RNG_PER_LANE):

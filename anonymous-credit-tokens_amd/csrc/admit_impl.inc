@@ -1,0 +1,390 @@
+// admit_impl.inc — included by engine.hip after keyring_redeem_impl.inc: admission before verification (DESIGN 4.7; kernels in
+// k_admit.hip, lane bodies in admit_lanes.h).  act_redeem_admit_batch / act_redeem_cbor_admit_batch are the ring redeem calls with a
+// screen in front: per lane the charge is compared with the expected one and the nullifier is looked up (read only) BEFORE the proof
+// is verified, and only the lanes that pass go through verification -> check-and-insert -> sign.
+//   1. screen        k and s of every lane (records: fields 0 and 1; wire: the payloads of a canonical message, the host reader's
+//                    record of any other spelling, in windows of ADMIT_READ_WINDOW) -> pre-status, reduced k       [k_admit_screen]
+//   2. compaction    the survivors' lane numbers in lane order                                  [k_admit_count / _scan / _write]
+//   3. verification  of the survivors only, their records / messages gathered ADMIT_WINDOW_BATCHES * max_batch at a time
+//   4. once per call check-and-insert and signing over the compact 32-byte arrays (redeem_keyring_tail): one rng draw per call
+//   5. scatter       statuses, out_key and refunds back to their lanes; shed lanes get all-zero records           [k_admit_scatter]
+// Nothing is shed (m == n): the caller's pointers go straight to redeem_keyring_impl; everything is shed: no verification kernel runs.
+// The decision that RECORDS is still the check-and-insert behind verification; the look-up of step 1 only spares work.
+namespace {
+
+constexpr size_t ADMIT_READ_WINDOW = 4096;       // messages per host-reader window (as WIRE_SETTLE_WINDOW)
+constexpr size_t ADMIT_WINDOW_BATCHES = 4;       // survivors gathered and verified at a time, in units of max_batch
+constexpr size_t ADMIT_WIRE_LAUNCH = (size_t)1 << 20;      // messages per launch of the framing compare
+
+#define ADCK(c, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { (c)->err = std::string("admission: ") + #expr + ": " + hipGetErrorString(e_); (void)hipGetLastError(); return ACT_ERR_HIP; } } while (0)
+
+// the per-lane rng slices of the survivors (ACT_RNG_PER_LANE, device-memory callers): the context's own buffer, wiped on every exit
+struct AdmitRngDev {
+  act_ctx* c; size_t dirty = 0;
+  explicit AdmitRngDev(act_ctx* c_) : c(c_) {}
+  int reserve(size_t bytes) {
+    std::lock_guard<std::mutex> lk(c->mu);
+    ADCK(c, hipSetDevice(c->device));
+    if (bytes > c->d_admit_rng_cap) {
+      if (c->d_admit_rng) { ADCK(c, hipFree(c->d_admit_rng)); c->d_admit_rng = nullptr; c->d_admit_rng_cap = 0; }      // (wiped when its call ended)
+      ADCK(c, hipMalloc(&c->d_admit_rng, bytes)); c->d_admit_rng_cap = bytes;
+      ADCK(c, hipMemset(c->d_admit_rng, 0, bytes));
+      ADCK(c, hipDeviceSynchronize());      // (the memset runs on the null stream; the gather that fills the buffer does not wait for that stream)
+    }
+    dirty = bytes;
+    return ACT_OK;
+  }
+  ~AdmitRngDev() { if (dirty && c->d_admit_rng) { (void)hipSetDevice(c->device); if (hipMemset(c->d_admit_rng, 0, dirty) != hipSuccess || hipDeviceSynchronize() != hipSuccess) (void)hipGetLastError(); } }
+};
+struct AdmitHostWipe { std::vector<uint8_t>& v; ~AdmitHostWipe() { if (!v.empty()) wipe_host(v.data(), v.size()); } };
+
+// n bytes in the caller's kind of memory
+struct AdmitArr {
+  std::vector<uint8_t> h; DevTmp d; uint8_t* p = nullptr;
+  explicit AdmitArr(act_ctx* c) : d(c) {}
+  int alloc(int mem, size_t bytes) {
+    if (mem == ACT_MEM_DEVICE) { int rc = d.alloc(bytes); if (rc) return rc; p = d.p; hipError_t e = hipMemset(p, 0, bytes ? bytes : 1); if (e == hipSuccess) e = hipDeviceSynchronize(); if (e != hipSuccess) { (void)hipGetLastError(); return ACT_ERR_HIP; } }
+    else { h.assign(bytes ? bytes : 1, 0); p = h.data(); }
+    return ACT_OK;
+  }
+};
+
+struct AdmitWireJob { AdmitWireArgs a; };
+struct AdmitRowsJob { uint8_t* dst; const uint8_t* src; const uint32_t* idx; size_t row; };
+struct AdmitMsgsJob { uint8_t* dst; const uint64_t* dst_off; const uint8_t* src; const uint64_t* src_beg; };
+
+void admit_counts_of(uint64_t* out_counts, size_t n, const uint8_t* pre, size_t m, const uint8_t* cst) {
+  if (!out_counts) return;
+  uint64_t k[ACT_ADMIT_COUNTS] = {n, 0, 0, 0, m, 0, 0, 0};
+  for (size_t i = 0; i < n; i++) {
+    const uint8_t p = pre[i];
+    if (p == ACT_STATUS_WRONG_CHARGE) k[2]++; else if (p == ACT_STATUS_DOUBLE_SPEND) k[3]++; else if (p) k[1]++;
+  }
+  for (size_t j = 0; j < m; j++) {
+    const uint8_t s = cst[j];
+    if (s == 0) k[7]++; else if (s == ACT_STATUS_DOUBLE_SPEND) k[6]++;
+    else if (s != ACT_STATUS_NULLIFIER_UNDETERMINED && s != ACT_STATUS_RECORDED_UNSIGNED) k[5]++;
+  }
+  memcpy(out_counts, k, sizeof(k));
+}
+
+}  // namespace
+
+static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int mem, const uint8_t* keys, int nkeys, const uint32_t* key_epochs, int sign_key,
+                             const uint8_t* proof, const uint8_t* cbor, const uint64_t* offsets, const uint8_t* charge, const uint8_t* rng, int rng_mode,
+                             uint8_t* out, uint8_t* status, uint8_t* out_key, uint64_t* out_counts) {
+  const bool wire = cbor != nullptr, dev = mem == ACT_MEM_DEVICE;
+  if (out_counts) memset(out_counts, 0, sizeof(uint64_t) * ACT_ADMIT_COUNTS);
+  if (!c || (mem != ACT_MEM_HOST && mem != ACT_MEM_DEVICE) || n > ((size_t)1 << 30)) return ACT_ERR_ARG;
+  if (n && ((!proof && !cbor) || !out || !status || !out_key)) return ACT_ERR_ARG;
+  if (wire && offsets) for (size_t i = 0; i < n; i++) if (offsets[i + 1] < offsets[i]) return ACT_ERR_ARG;
+  // everything the redeem call refuses as a whole (null handles, ring size, sign_key, rng convention, device, epochs) is refused here in
+  // the same words and before anything is looked at -- host checks only; a ring whose w does not decode fails the verification step
+  // (or, for a batch that is shed completely, the empty ring call below) before anything is written
+  int rc = redeem_keyring_refused(c, set, 0, keys, nkeys, key_epochs, sign_key, nullptr, nullptr, rng, rng_mode, nullptr, nullptr, nullptr);
+  if (rc) return rc;
+  if (n == 0) return redeem_keyring_impl(c, set, 0, mem, keys, nkeys, key_epochs, sign_key, nullptr, nullptr, nullptr, rng, rng_mode, nullptr, nullptr, nullptr);
+  // one admission call at a time per context: the gathered rng slices live in the context's own buffer (d_admit_rng)
+  std::lock_guard<std::mutex> admission(c->admit_mu);
+  const size_t pb = act_spend_proof_bytes(c), out_b = wire ? act_cbor_size(c, ACT_CBOR_REFUND) : 128;
+  const CborType* T = cbor_type(ACT_CBOR_SPEND_PROOF);
+  CborLayout lay; if (wire) lay = cbor_layout(*T, c->L);
+  const size_t ml = lay.tmpl.size(), nf = lay.pay_off.size();
+  auto msg_beg = [&](size_t i) { return offsets ? (size_t)offsets[i] : i * ml; };
+  auto msg_end = [&](size_t i) { return offsets ? (size_t)offsets[i + 1] : (i + 1) * ml; };
+  hipStream_t stream = set->stream;
+
+  // ---- the stage's own device memory (public data: lane numbers, codes, nullifiers, charges) -------------------------------------------
+  const size_t nb = (n + ADMIT_BLOCK - 1) / ADMIT_BLOCK, fcap = (n + 3) & ~(size_t)3;
+  size_t need = 0;
+  auto take = [&](size_t bytes) { const size_t at = need; need += (bytes + 15) & ~(size_t)15; return at; };
+  const size_t o_pre = take(n), o_kred = take(n * 32), o_idx = take(n * 4), o_pos = take(n * 4), o_blk = take(nb * 4), o_total = take(4);
+  const bool own_ks = wire || !dev;
+  const size_t o_ks = own_ks ? take(n * 64) : 0, o_charge = (charge && !dev) ? take(n * 32) : 0;
+  const size_t o_code = wire ? take(n) : 0, o_flags = (wire && dev) ? take(fcap) : 0, o_off = (wire && dev && offsets) ? take((n + 1) * 8) : 0;
+  const size_t o_tmpl = (wire && dev) ? take(ml) : 0, o_pay = (wire && dev) ? take(nf * 4) : 0;
+  const size_t o_pwhich = wire ? take(ADMIT_READ_WINDOW * 4) : 0, o_patch = wire ? take(ADMIT_READ_WINDOW * 64) : 0;
+  DevTmp d(c);
+  if ((rc = d.alloc(need))) return rc;
+  ADCK(c, hipSetDevice(c->device));
+  uint8_t* const d_pre = d.p + o_pre; uint8_t* const d_kred = d.p + o_kred;
+  uint32_t* const d_idx = reinterpret_cast<uint32_t*>(d.p + o_idx); uint32_t* const d_pos = reinterpret_cast<uint32_t*>(d.p + o_pos);
+  uint32_t* const d_blk = reinterpret_cast<uint32_t*>(d.p + o_blk); uint32_t* const d_total = reinterpret_cast<uint32_t*>(d.p + o_total);
+  uint8_t* const d_ks = d.p + o_ks;
+
+  // ---- step 1: where k and s are ------------------------------------------------------------------------------------------------------
+  AdmitScreenArgs sa{};
+  sa.n = (uint32_t)n; sa.pre = d_pre; sa.kred = d_kred;
+  std::vector<uint8_t> h_code;
+  if (!wire) {
+    if (dev) { sa.ks = proof; sa.stride = (uint32_t)pb; }
+    else { ADCK(c, hipMemcpy2DAsync(d_ks, 64, proof, pb, 64, n, hipMemcpyHostToDevice, stream)); sa.ks = d_ks; sa.stride = 64; }      // the 64-byte fields only
+  } else {
+    std::vector<uint8_t> flags(fcap, 0), h_ks;
+    if (dev) {
+      uint8_t* d_flags = d.p + o_flags;
+      ADCK(c, hipMemsetAsync(d_flags, 0, fcap, stream));
+      ADCK(c, hipMemcpyAsync(d.p + o_tmpl, lay.tmpl.data(), ml, hipMemcpyHostToDevice, stream));
+      ADCK(c, hipMemcpyAsync(d.p + o_pay, lay.pay_off.data(), nf * 4, hipMemcpyHostToDevice, stream));
+      if (offsets) ADCK(c, hipMemcpyAsync(d.p + o_off, offsets, (n + 1) * 8, hipMemcpyHostToDevice, stream));
+      for (size_t off = 0; off < n; off += ADMIT_WIRE_LAUNCH) {      // (off is a multiple of 4: the flag words of two launches do not overlap)
+        AdmitWireArgs a{};
+        a.n = (uint32_t)std::min(ADMIT_WIRE_LAUNCH, n - off); a.n_fields = (uint32_t)nf; a.msg_len = (uint32_t)ml;
+        a.cbor = offsets ? cbor : cbor + off * ml; a.offsets = offsets ? reinterpret_cast<const uint64_t*>(d.p + o_off) + off : nullptr;
+        a.tmpl = d.p + o_tmpl; a.pay_off = reinterpret_cast<const uint32_t*>(d.p + o_pay); a.ks = d_ks + off * 64; a.flags = d_flags + off;
+        launch_admit_wire(a, stream);
+      }
+      ADCK(c, hipGetLastError());
+      ADCK(c, hipMemcpyAsync(flags.data(), d_flags, fcap, hipMemcpyDeviceToHost, stream));
+      ADCK(c, hipStreamSynchronize(stream));
+    } else {      // host memory: the same lane body on the host workers, 64 bytes per message cross the link
+      h_ks.assign(n * 64, 0);
+      AdmitWireJob job{};
+      job.a.n = (uint32_t)n; job.a.n_fields = (uint32_t)nf; job.a.msg_len = (uint32_t)ml; job.a.cbor = cbor; job.a.offsets = offsets;
+      job.a.tmpl = lay.tmpl.data(); job.a.pay_off = lay.pay_off.data(); job.a.ks = h_ks.data(); job.a.flags = flags.data();
+      act_host_parallel_for(n, 256, 0, [](void* p, size_t i0, size_t i1) {
+        const AdmitWireArgs& a = static_cast<AdmitWireJob*>(p)->a;
+        for (size_t m = i0; m < i1; m++) {
+          bool canon = true;
+          for (uint32_t f = 0; f < a.n_fields && canon; f++) canon = admit_wire_piece(a, (uint32_t)m, f);
+          a.flags[m] = canon ? 0 : 0x80;
+        }
+      }, &job);
+      ADCK(c, hipMemcpyAsync(d_ks, h_ks.data(), n * 64, hipMemcpyHostToDevice, stream));
+      ADCK(c, hipStreamSynchronize(stream));
+    }
+    // every other spelling: the general reader, ADMIT_READ_WINDOW messages at a time.  A message that reads yields the record, and so
+    // k and s; one that does not takes the code act_redeem_cbor_* gives it (the first error in wire order: cbor_settle_codes)
+    h_code.assign(n, 0);
+    std::vector<size_t> which;
+    for (size_t i = 0; i < n; i++) if (flags[i] & 0x80) which.push_back(i);
+    std::vector<uint8_t> rec(pb), bytes, patch; std::vector<uint32_t> pwhich; std::vector<size_t> at;
+    std::vector<int> codes; std::vector<CborCand> cands;
+    for (size_t w0 = 0; w0 < which.size(); w0 += ADMIT_READ_WINDOW) {
+      const size_t w1 = std::min(which.size(), w0 + ADMIT_READ_WINDOW), cnt = w1 - w0;
+      at.assign(cnt, 0);
+      if (dev) {      // the window's bytes: one copy of the span when its messages lie close together, one per message when not
+        size_t sum = 0;
+        for (size_t k = 0; k < cnt; k++) sum += msg_end(which[w0 + k]) - msg_beg(which[w0 + k]);
+        const size_t span_beg = msg_beg(which[w0]), span_end = msg_end(which[w1 - 1]);
+        if (span_end - span_beg <= 2 * sum + ((size_t)1 << 20)) {
+          bytes.resize(span_end - span_beg);
+          if (!bytes.empty()) ADCK(c, hipMemcpy(bytes.data(), cbor + span_beg, bytes.size(), hipMemcpyDeviceToHost));
+          for (size_t k = 0; k < cnt; k++) at[k] = msg_beg(which[w0 + k]) - span_beg;
+        } else {
+          bytes.resize(sum);
+          size_t o = 0;
+          for (size_t k = 0; k < cnt; k++) {
+            const size_t b = msg_beg(which[w0 + k]), l = msg_end(which[w0 + k]) - b;
+            if (l) ADCK(c, hipMemcpy(bytes.data() + o, cbor + b, l, hipMemcpyDeviceToHost));
+            at[k] = o; o += l;
+          }
+        }
+      }
+      codes.assign(cnt, CBOR_OK); cands.assign(cnt, CborCand{}); patch.assign(cnt * 64, 0); pwhich.clear();
+      std::vector<size_t> good;
+      for (size_t k = 0; k < cnt; k++) {
+        const size_t i = which[w0 + k], beg = msg_beg(i), end = msg_end(i);
+        std::fill(rec.begin(), rec.end(), 0);
+        codes[k] = cbor_read_message(*T, c->L, dev ? bytes.data() + at[k] : cbor + beg, end - beg, rec.data(), &cands[k]);
+        if (codes[k] == CBOR_OK) memcpy(patch.data() + k * 64, rec.data(), 64);
+      }
+      if ((rc = cbor_settle_codes(c, stream, codes, cands))) return rc;
+      size_t np = 0;
+      for (size_t k = 0; k < cnt; k++) {
+        const size_t i = which[w0 + k];
+        if (codes[k] == CBOR_OK) { if (np != k) memmove(patch.data() + np * 64, patch.data() + k * 64, 64); pwhich.push_back((uint32_t)i); np++; }
+        else h_code[i] = codes[k] == CBOR_ERR_VALUE ? (uint8_t)ACT_STATUS_UNDECODABLE : codes[k] == CBOR_ERR_PARSE ? (uint8_t)ACT_STATUS_CBOR_MALFORMED : (uint8_t)ACT_STATUS_CBOR_STRUCTURE;
+      }
+      if (np) {
+        ADCK(c, hipMemcpyAsync(d.p + o_pwhich, pwhich.data(), np * 4, hipMemcpyHostToDevice, stream));
+        ADCK(c, hipMemcpyAsync(d.p + o_patch, patch.data(), np * 64, hipMemcpyHostToDevice, stream));
+        AdmitPatchArgs pa{d_ks, reinterpret_cast<const uint32_t*>(d.p + o_pwhich), d.p + o_patch, (uint32_t)np};
+        launch_admit_patch(pa, stream);
+        ADCK(c, hipGetLastError());
+        ADCK(c, hipStreamSynchronize(stream));      // pwhich / patch are reused by the next window
+      }
+    }
+    ADCK(c, hipMemcpyAsync(d.p + o_code, h_code.data(), n, hipMemcpyHostToDevice, stream));
+    sa.ks = d_ks; sa.stride = 64; sa.wire_code = d.p + o_code;
+  }
+  if (charge) {
+    if (dev) sa.charge = charge;
+    else { ADCK(c, hipMemcpyAsync(d.p + o_charge, charge, n * 32, hipMemcpyHostToDevice, stream)); sa.charge = d.p + o_charge; }
+  }
+
+  // ---- steps 1 and 2: the screen (the set's lock is held while its table is read) and the compaction ----------------------------------
+  uint32_t m32 = 0;
+  std::vector<uint8_t> h_pre(n);
+  {
+    std::lock_guard<std::mutex> lk(set->mu);
+    sa.tab_keys = set->tab_keys; sa.tab_state = set->tab_state; sa.tab_cap = set->tab_cap; memcpy(sa.salt.w, set->salt, 16);
+    launch_admit_screen(sa, stream);
+    launch_admit_compact(d_pre, (uint32_t)n, d_blk, d_idx, d_pos, d_total, stream);
+    ADCK(c, hipGetLastError());
+    ADCK(c, hipMemcpyAsync(&m32, d_total, 4, hipMemcpyDeviceToHost, stream));
+    ADCK(c, hipMemcpyAsync(h_pre.data(), d_pre, n, hipMemcpyDeviceToHost, stream));
+    ADCK(c, hipStreamSynchronize(stream));
+  }
+  const size_t m = m32;
+  if (m > n) { c->err = "admission: the compaction counted more survivors than lanes"; return ACT_ERR_HIP; }
+
+  // ---- nothing shed: the honest batch pays the screen and nothing else ------------------------------------------------------------------
+  if (m == n) {
+    rc = redeem_keyring_impl(c, set, n, mem, keys, nkeys, key_epochs, sign_key, proof, cbor, offsets, rng, rng_mode, out, status, out_key);
+    if (out_counts && (rc == ACT_OK || rc == ACT_ERR_ARG)) {      // (ACT_ERR_ARG: the nullifier step refused lanes; status[] is complete)
+      std::vector<uint8_t> hs;
+      const uint8_t* s = status;
+      if (dev) { hs.resize(n); if (hipMemcpy(hs.data(), status, n, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return rc; } s = hs.data(); }
+      admit_counts_of(out_counts, n, h_pre.data(), n, s);
+    }
+    return rc;
+  }
+  // ---- everything shed: no verification, nothing recorded, no rng drawn -----------------------------------------------------------------
+  if (m == 0) {
+    if ((rc = redeem_keyring_impl(c, set, 0, mem, keys, nkeys, key_epochs, sign_key, nullptr, nullptr, nullptr, rng, rng_mode, nullptr, nullptr, nullptr))) return rc;      // a bad ring fails the call whatever is shed
+    if (dev) {
+      ADCK(c, hipMemcpyAsync(status, d_pre, n, hipMemcpyDeviceToDevice, stream));
+      ADCK(c, hipMemsetAsync(out_key, ACT_KEY_NONE, n, stream));
+      ADCK(c, hipMemsetAsync(out, 0, n * out_b, stream));
+      ADCK(c, hipStreamSynchronize(stream));
+    } else { memcpy(status, h_pre.data(), n); memset(out_key, ACT_KEY_NONE, n); memset(out, 0, n * out_b); }
+    admit_counts_of(out_counts, n, h_pre.data(), 0, nullptr);
+    return ACT_OK;
+  }
+
+  // ---- step 3: the survivors, a window at a time -------------------------------------------------------------------------------------------
+  std::vector<uint32_t> h_idx(m), h_pos;
+  ADCK(c, hipMemcpy(h_idx.data(), d_idx, m * 4, hipMemcpyDeviceToHost));
+  if (!dev) { h_pos.resize(n); ADCK(c, hipMemcpy(h_pos.data(), d_pos, n * 4, hipMemcpyDeviceToHost)); }
+  // compact arrays in the caller's kind of memory: K' | nullifiers | verdicts | look-up answers | key indices | matched keys | statuses
+  AdmitArr arr(c), cout(c);
+  if ((rc = arr.alloc(mem, m * 69))) { c->err = "admission: compact arrays"; return rc; }
+  if ((rc = cout.alloc(mem, m * out_b))) { c->err = "admission: compact output"; return rc; }
+  uint8_t *kp = arr.p, *knul = kp + m * 32, *st = knul + m * 32, *sp = st + m, *kidx = sp + m, *okey = kidx + m, *cst = okey + m;
+  // a survivor's status that the tail leaves unwritten (it returns early only on a device failure BEHIND check-and-insert) must never
+  // read as accepted: recorded, not signed
+  if (dev) { ADCK(c, hipMemset(cst, ACT_STATUS_RECORDED_UNSIGNED, m)); ADCK(c, hipDeviceSynchronize()); } else memset(cst, ACT_STATUS_RECORDED_UNSIGNED, m);
+  {      // the reduced nullifiers of the survivors, as the screen left them
+    DevTmp g(c); uint8_t* dst = knul;
+    if (!dev) { if ((rc = g.alloc(m * 32))) return rc; dst = g.p; }
+    AdmitRowsArgs ra{dst, d_kred, d_idx, (uint32_t)m, 32};
+    launch_admit_rows(ra, stream);
+    ADCK(c, hipGetLastError());
+    if (!dev) ADCK(c, hipMemcpyAsync(knul, g.p, m * 32, hipMemcpyDeviceToHost, stream));
+    ADCK(c, hipStreamSynchronize(stream));
+  }
+  // the per-lane rng slices follow their lanes (secret: staged in the context's own buffer or a host vector, wiped on every exit)
+  AdmitRngDev rng_dev(c); std::vector<uint8_t> rng_host; AdmitHostWipe rng_wipe{rng_host};
+  const uint8_t* c_rng = rng;
+  if (rng_mode == ACT_RNG_PER_LANE) {
+    if (dev) {
+      if ((rc = rng_dev.reserve(m * 128))) return rc;
+      AdmitRowsArgs ra{c->d_admit_rng, rng, d_idx, (uint32_t)m, 128};
+      launch_admit_rows(ra, stream);
+      ADCK(c, hipGetLastError());
+      ADCK(c, hipStreamSynchronize(stream));
+      c_rng = c->d_admit_rng;
+    } else {
+      rng_host.resize(m * 128);
+      for (size_t j = 0; j < m; j++) memcpy(rng_host.data() + j * 128, rng + (size_t)h_idx[j] * 128, 128);
+      c_rng = rng_host.data();
+    }
+  }
+  const size_t W = std::max<size_t>(1, ADMIT_WINDOW_BATCHES * c->max_batch);
+  DevTmp gd(c); std::vector<uint8_t> gh; size_t g_cap = 0;
+  auto g_reserve = [&](size_t bytes) -> int {      // the gather buffer, in the caller's kind of memory
+    if (bytes <= g_cap) return ACT_OK;
+    if (dev) { if (gd.p) { std::lock_guard<std::mutex> lk(c->mu); ADCK(c, hipFree(gd.p)); gd.p = nullptr; gd.bytes = 0; } int r = gd.alloc(bytes); if (r) return r; }
+    else gh.resize(bytes);
+    g_cap = bytes;
+    return ACT_OK;
+  };
+  DevTmp d_moff(c);      // wire, device memory: a window's source starts and destination offsets
+  if (wire && dev && offsets && (rc = d_moff.alloc((2 * std::min(W, m) + 1) * 8))) return rc;
+  std::vector<uint64_t> dst_off, src_beg;
+  for (size_t w0 = 0; w0 < m; w0 += W) {
+    const size_t w = std::min(W, m - w0);
+    const size_t row = wire ? ml : pb;
+    if (!wire || !offsets) {      // rows of one size
+      if ((rc = g_reserve(w * row))) return rc;
+      const uint8_t* src = wire ? cbor : proof;
+      if (dev) {
+        AdmitRowsArgs ra{gd.p, src, d_idx + w0, (uint32_t)w, row};
+        launch_admit_rows(ra, stream);
+        ADCK(c, hipGetLastError());
+        ADCK(c, hipStreamSynchronize(stream));
+      } else {
+        AdmitRowsJob job{gh.data(), src, h_idx.data() + w0, row};
+        act_host_parallel_for(w, 16, 0, [](void* p, size_t i0, size_t i1) {
+          const AdmitRowsJob& j = *static_cast<const AdmitRowsJob*>(p);
+          for (size_t k = i0; k < i1; k++) memcpy(j.dst + k * j.row, j.src + (size_t)j.idx[k] * j.row, j.row);
+        }, &job);
+      }
+    } else {                      // messages between monotone offsets, gathered with offsets of their own
+      dst_off.assign(w + 1, 0); src_beg.assign(w, 0);
+      size_t longest = 0;
+      for (size_t k = 0; k < w; k++) {
+        const size_t i = h_idx[w0 + k], len = msg_end(i) - msg_beg(i);
+        src_beg[k] = msg_beg(i); dst_off[k + 1] = dst_off[k] + len; longest = std::max(longest, len);
+      }
+      if ((rc = g_reserve((size_t)dst_off[w]))) return rc;
+      if (dev) {
+        uint64_t* d_src = reinterpret_cast<uint64_t*>(d_moff.p); uint64_t* d_dst = d_src + std::min(W, m);
+        ADCK(c, hipMemcpyAsync(d_src, src_beg.data(), w * 8, hipMemcpyHostToDevice, stream));
+        ADCK(c, hipMemcpyAsync(d_dst, dst_off.data(), (w + 1) * 8, hipMemcpyHostToDevice, stream));
+        AdmitMsgsArgs ma{gd.p, d_dst, cbor, d_src, (uint32_t)w, admit_pieces(longest)};
+        launch_admit_msgs(ma, stream);
+        ADCK(c, hipGetLastError());
+        ADCK(c, hipStreamSynchronize(stream));
+      } else {
+        AdmitMsgsJob job{gh.data(), dst_off.data(), cbor, src_beg.data()};
+        act_host_parallel_for(w, 16, 0, [](void* p, size_t i0, size_t i1) {
+          const AdmitMsgsJob& j = *static_cast<const AdmitMsgsJob*>(p);
+          for (size_t k = i0; k < i1; k++) memcpy(j.dst + j.dst_off[k], j.src + j.src_beg[k], (size_t)(j.dst_off[k + 1] - j.dst_off[k]));
+        }, &job);
+      }
+    }
+    const uint8_t* g = dev ? gd.p : gh.data();
+    if (wire) { RingSel sel{keys, nkeys, okey + w0}; rc = verify_spend_cbor_impl(c, w, mem, nullptr, g, offsets ? dst_off.data() : nullptr, st + w0, kp + w0 * 32, nullptr, &sel); }
+    else rc = act_verify_spend_keyring_batch(c, w, mem, keys, nkeys, g, st + w0, okey + w0, kp + w0 * 32);
+    if (rc) return rc;            // as in the redeem calls: nothing recorded, status untouched
+  }
+
+  // ---- step 4: once per call, over the compact arrays ---------------------------------------------------------------------------------------
+  const int rc_tail = redeem_keyring_tail(c, set, m, mem, keys, nkeys, key_epochs, sign_key, wire, knul, 32, kp, st, sp, kidx, c_rng, rng_mode, cout.p, cst, okey);
+
+  // ---- step 5: the answers back to their lanes (also behind a failure of step 4: status[] is complete on return) ----------------------------
+  std::vector<uint8_t> h_cst;
+  if (dev) {
+    AdmitScatterArgs sc{}; sc.n = (uint32_t)n; sc.out_bytes = out_b; sc.pos = d_pos; sc.pre = d_pre; sc.c_status = cst; sc.c_key = okey; sc.c_out = cout.p;
+    sc.status = status; sc.out_key = out_key; sc.out = out;
+    launch_admit_scatter(sc, stream);
+    ADCK(c, hipGetLastError());
+    if (out_counts) { h_cst.resize(m); ADCK(c, hipMemcpyAsync(h_cst.data(), cst, m, hipMemcpyDeviceToHost, stream)); }
+    ADCK(c, hipStreamSynchronize(stream));
+  } else {
+    for (size_t i = 0; i < n; i++) {
+      const uint32_t j = h_pos[i];
+      if (j == ADMIT_SHED) { status[i] = h_pre[i]; out_key[i] = ACT_KEY_NONE; memset(out + i * out_b, 0, out_b); }
+      else { status[i] = cst[j]; out_key[i] = okey[j]; memcpy(out + i * out_b, cout.p + (size_t)j * out_b, out_b); }
+    }
+  }
+  admit_counts_of(out_counts, n, h_pre.data(), m, dev ? h_cst.data() : cst);
+  return rc_tail;
+}
+
+extern "C" int act_redeem_admit_batch(act_ctx* c, act_nullifier_set* set, size_t n, int mem, const uint8_t* keys, int nkeys, const uint32_t* key_epochs, int sign_key,
+                                      const uint8_t* proof, const uint8_t* charge, const uint8_t* rng, int rng_mode, uint8_t* out_refund, uint8_t* status,
+                                      uint8_t* out_key, uint64_t* out_counts) {
+  if (n && !proof) return ACT_ERR_ARG;
+  return redeem_admit_impl(c, set, n, mem, keys, nkeys, key_epochs, sign_key, proof, nullptr, nullptr, charge, rng, rng_mode, out_refund, status, out_key, out_counts);
+}
+extern "C" int act_redeem_cbor_admit_batch(act_ctx* c, act_nullifier_set* set, size_t n, int mem, const uint8_t* keys, int nkeys, const uint32_t* key_epochs, int sign_key,
+                                           const uint8_t* cbor, const uint64_t* offsets, const uint8_t* charge, const uint8_t* rng, int rng_mode,
+                                           uint8_t* out_refund_cbor, uint8_t* status, uint8_t* out_key, uint64_t* out_counts) {
+  if (n && !cbor) return ACT_ERR_ARG;
+  static const uint8_t none = 0;
+  return redeem_admit_impl(c, set, n, mem, keys, nkeys, key_epochs, sign_key, nullptr, cbor ? cbor : &none, offsets, charge, rng, rng_mode, out_refund_cbor, status,
+                           out_key, out_counts);
+}

@@ -19,6 +19,7 @@
 #include <vector>
 #include "kernels.h"
 #include "keyring.h"
+#include "admit.h"
 #include "rng_source.h"
 #include "../../include/act_mi355x.h"
 
@@ -173,6 +174,8 @@ struct act_ctx {
   uint8_t* d_tiny_tr = nullptr;        // TINY_MAX "request" transcripts of the fused issue kernel
   std::atomic<uint32_t> debug_ns_per_lane{0};    // act_debug_set_slowdown (test hook of the node dispatcher's load balance)
   std::atomic<int> debug_fail_signs{0};          // act_debug_fail_next_signs (test hook of the redeem failure contract)
+  std::mutex admit_mu;                 // an admission call holds it from start to end (admit_impl.inc): d_admit_rng below belongs to ONE call at a time; taken before mu, never under it
+  uint8_t* d_admit_rng = nullptr; size_t d_admit_rng_cap = 0;      // the survivors' per-lane rng slices of an admission call (admit_impl.inc): wiped when the call ends
   struct RingWs* ring_ws = nullptr;              // key-ring side buffers, allocated by the context's first ring call (keyring_impl.inc)
 };
 static void ring_ws_free(act_ctx* c);            // keyring_impl.inc
@@ -478,6 +481,9 @@ int finish_call(act_ctx* c, size_t n) {
   // a small-batch call that returned early (a HIP error half way through its schedule) may still have kernels on the aux streams
   // writing d_small and the slot buffers: nothing is wiped under them
   if (c->aux_used) { c->aux_used = false; for (hipStream_t a : c->aux) if (a) HIPCK(c, hipStreamSynchronize(a)); }
+  // slot 0's areas 8 and 9 (the CBOR layout tables, a key ring's decoded keys) are read by BOTH slots' kernels: when the call's last
+  // chunk runs on slot 1, a wipe queued on slot 0's idle stream would land under it (a ring signature then saw x = 0 in k_sign_b_ring)
+  if (c->slots[0].d_stage_dirty[8] || c->slots[0].d_stage_dirty[9]) for (Slot& sl : c->slots) if (sl.stream) HIPCK(c, hipStreamSynchronize(sl.stream));
   for (Slot& sl : c->slots) {
     for (int i = 0; i < Slot::N_STAGE; i++)
       if (sl.d_stage_dirty[i]) { HIPCK(c, hipMemsetAsync(sl.d_stage[i], 0, sl.d_stage_dirty[i], sl.stream)); sl.d_stage_dirty[i] = 0; }
@@ -787,6 +793,7 @@ void act_ctx_destroy(act_ctx* c) {
   if (c->d_tables_ct) (void)hipFree(c->d_tables_ct);
   if (c->d_tables_mf) (void)hipFree(c->d_tables_mf);
   if (c->d_wire_flags) (void)hipFree(c->d_wire_flags);
+  if (c->d_admit_rng) { (void)hipMemset(c->d_admit_rng, 0, c->d_admit_rng_cap); (void)hipFree(c->d_admit_rng); }
   ring_ws_free(c);
   memset(&c->key, 0, sizeof(c->key)); memset(c->sk_cached, 0, 64);
   delete c;
@@ -1282,3 +1289,4 @@ int act_refund_batch(act_ctx* c, size_t n, int mem, const uint8_t sk[64], const 
 #include "issue_wire_impl.inc"
 #include "nullifier_impl.inc"
 #include "keyring_redeem_impl.inc"
+#include "admit_impl.inc"          // admission before verification: act_redeem_admit_batch, act_redeem_cbor_admit_batch

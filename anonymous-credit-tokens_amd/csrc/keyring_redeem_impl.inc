@@ -4,38 +4,16 @@
 // ACT_STATUS_RECORDED_UNSIGNED, act_debug_fail_next_signs).  Membership in the nullifier set does not depend on the key.  No tiny form.
 // key_epochs (nullable, host memory, nkeys values): an accepted lane's nullifier is recorded under the epoch of the key it MATCHED --
 // out_key, as the ring verification leaves it, is the epoch index of the insert.
-static int redeem_keyring_impl(act_ctx* c, act_nullifier_set* set, size_t n, int mem, const uint8_t* keys, int nkeys, const uint32_t* key_epochs, int sign_key, const uint8_t* proof,
-                               const uint8_t* cbor, const uint64_t* offsets, const uint8_t* rng, int rng_mode, uint8_t* out, uint8_t* status, uint8_t* out_key) {
-  const bool wire = cbor != nullptr;
-  if (!c || !set || !keys || !rng || nkeys < 1 || nkeys > ACT_KEYRING_MAX || (n && ((!proof && !cbor) || !out || !status || !out_key))) return ACT_ERR_ARG;
-  if (sign_key != ACT_SIGN_MATCHED && (sign_key < 0 || sign_key >= nkeys)) return ACT_ERR_ARG;
-  if (rng_mode != ACT_RNG_PER_LANE && rng_mode != ACT_RNG_SEQUENTIAL && rng_mode != ACT_RNG_CALLBACK) return ACT_ERR_ARG;
-  if (set->device != c->device) { c->err = "act_redeem_keyring_batch: the nullifier set lives on another device"; return ACT_ERR_ARG; }
-  if (key_epochs) {      // refused before any verification work: nothing recorded, nothing signed, no status written
-    std::string why;
-    { std::lock_guard<std::mutex> lk(set->mu); why = null_epochs_refused(set, key_epochs, nkeys); }
-    if (!why.empty()) { c->err = "act_redeem_keyring_epochs_batch: " + why; return ACT_ERR_ARG; }
-  }
-  if (n == 0) {      // a bad ring fails the call whatever n
-    Call call(c, 0);
-    HIPCK(c, hipSetDevice(c->device));
-    const DevKey* d_ring = nullptr;
-    int rc0 = ring_set(c, keys, nkeys, &d_ring);
-    return rc0 ? rc0 : call.finish();
-  }
-  const size_t pb = act_spend_proof_bytes(c), out_b = wire ? act_cbor_size(c, ACT_CBOR_REFUND) : 128;
-  // K', verdicts, look-up answers, key indices and (wire form) the nullifiers beside the caller's arrays
-  const size_t per_lane = 35 + (wire ? 32 : 0);
-  std::vector<uint8_t> h; DevTmp d(c);
-  uint8_t* base; int rc;
-  if (mem == ACT_MEM_DEVICE) { if ((rc = d.alloc(n * per_lane))) return rc; base = d.p; }
-  else { h.resize(n * per_lane); base = h.data(); }
-  uint8_t *kp = base, *nul = base + n * 32, *st = base + n * (per_lane - 3), *sp = st + n, *kidx = sp + n;
-  if (wire) { RingSel sel{keys, nkeys, out_key}; rc = verify_spend_cbor_impl(c, n, mem, nullptr, cbor, offsets, st, kp, nul, &sel); }
-  else rc = act_verify_spend_keyring_batch(c, n, mem, keys, nkeys, proof, st, out_key, kp);
-  if (rc) return rc;
-  const int rc_null = key_epochs ? act_nullifier_check_and_insert_epoch_batch(set, n, mem, wire ? nul : proof, wire ? 32 : pb, st, out_key, key_epochs, nkeys, sp)
-                                 : act_nullifier_check_and_insert_batch(set, n, mem, wire ? nul : proof, wire ? 32 : pb, st, sp);
+// Everything behind verification, over arrays of n lanes in `mem` memory: st = the verdicts, out_key = the matched ring indices,
+// kp = enc(K'), the nullifiers at nul + i * nul_stride; sp and kidx are scratch of n bytes each.  Check-and-insert with the verdicts
+// as skip mask, then the signatures; status[] / out are complete on every return (the failure contract of the header).  Shared by
+// redeem_keyring_impl and by the admission calls (admit_impl.inc), which hand it the survivors' compact arrays.
+static int redeem_keyring_tail(act_ctx* c, act_nullifier_set* set, size_t n, int mem, const uint8_t* keys, int nkeys, const uint32_t* key_epochs, int sign_key, bool wire,
+                               const uint8_t* nul, size_t nul_stride, const uint8_t* kp, uint8_t* st, uint8_t* sp, uint8_t* kidx, const uint8_t* rng, int rng_mode,
+                               uint8_t* out, uint8_t* status, uint8_t* out_key) {
+  const size_t out_b = wire ? act_cbor_size(c, ACT_CBOR_REFUND) : 128;
+  const int rc_null = key_epochs ? act_nullifier_check_and_insert_epoch_batch(set, n, mem, nul, nul_stride, st, out_key, key_epochs, nkeys, sp)
+                                 : act_nullifier_check_and_insert_batch(set, n, mem, nul, nul_stride, st, sp);
   std::string null_err;
   if (rc_null) {
     null_err = std::string("nullifier set: ") + act_nullifier_set_last_error(set);
@@ -98,6 +76,46 @@ static int redeem_keyring_impl(act_ctx* c, act_nullifier_set* set, size_t n, int
   }
   if (rc_null) c->err = null_err;
   return rc_null;
+}
+
+// what the ring redeem calls refuse as a whole before any GPU work (no status written, nothing recorded): shared with admit_impl.inc
+static int redeem_keyring_refused(act_ctx* c, act_nullifier_set* set, size_t n, const uint8_t* keys, int nkeys, const uint32_t* key_epochs, int sign_key, const uint8_t* proof,
+                                  const uint8_t* cbor, const uint8_t* rng, int rng_mode, const uint8_t* out, const uint8_t* status, const uint8_t* out_key) {
+  if (!c || !set || !keys || !rng || nkeys < 1 || nkeys > ACT_KEYRING_MAX || (n && ((!proof && !cbor) || !out || !status || !out_key))) return ACT_ERR_ARG;
+  if (sign_key != ACT_SIGN_MATCHED && (sign_key < 0 || sign_key >= nkeys)) return ACT_ERR_ARG;
+  if (rng_mode != ACT_RNG_PER_LANE && rng_mode != ACT_RNG_SEQUENTIAL && rng_mode != ACT_RNG_CALLBACK) return ACT_ERR_ARG;
+  if (set->device != c->device) { c->err = "act_redeem_keyring_batch: the nullifier set lives on another device"; return ACT_ERR_ARG; }
+  if (key_epochs) {      // refused before any verification work: nothing recorded, nothing signed, no status written
+    std::string why;
+    { std::lock_guard<std::mutex> lk(set->mu); why = null_epochs_refused(set, key_epochs, nkeys); }
+    if (!why.empty()) { c->err = "act_redeem_keyring_epochs_batch: " + why; return ACT_ERR_ARG; }
+  }
+  return ACT_OK;
+}
+
+static int redeem_keyring_impl(act_ctx* c, act_nullifier_set* set, size_t n, int mem, const uint8_t* keys, int nkeys, const uint32_t* key_epochs, int sign_key, const uint8_t* proof,
+                               const uint8_t* cbor, const uint64_t* offsets, const uint8_t* rng, int rng_mode, uint8_t* out, uint8_t* status, uint8_t* out_key) {
+  const bool wire = cbor != nullptr;
+  if (int bad = redeem_keyring_refused(c, set, n, keys, nkeys, key_epochs, sign_key, proof, cbor, rng, rng_mode, out, status, out_key)) return bad;
+  if (n == 0) {      // a bad ring fails the call whatever n
+    Call call(c, 0);
+    HIPCK(c, hipSetDevice(c->device));
+    const DevKey* d_ring = nullptr;
+    int rc0 = ring_set(c, keys, nkeys, &d_ring);
+    return rc0 ? rc0 : call.finish();
+  }
+  const size_t pb = act_spend_proof_bytes(c);
+  // K', verdicts, look-up answers, key indices and (wire form) the nullifiers beside the caller's arrays
+  const size_t per_lane = 35 + (wire ? 32 : 0);
+  std::vector<uint8_t> h; DevTmp d(c);
+  uint8_t* base; int rc;
+  if (mem == ACT_MEM_DEVICE) { if ((rc = d.alloc(n * per_lane))) return rc; base = d.p; }
+  else { h.resize(n * per_lane); base = h.data(); }
+  uint8_t *kp = base, *nul = base + n * 32, *st = base + n * (per_lane - 3), *sp = st + n, *kidx = sp + n;
+  if (wire) { RingSel sel{keys, nkeys, out_key}; rc = verify_spend_cbor_impl(c, n, mem, nullptr, cbor, offsets, st, kp, nul, &sel); }
+  else rc = act_verify_spend_keyring_batch(c, n, mem, keys, nkeys, proof, st, out_key, kp);
+  if (rc) return rc;
+  return redeem_keyring_tail(c, set, n, mem, keys, nkeys, key_epochs, sign_key, wire, wire ? nul : proof, wire ? 32 : pb, kp, st, sp, kidx, rng, rng_mode, out, status, out_key);
 }
 
 extern "C" int act_redeem_keyring_batch(act_ctx* c, act_nullifier_set* set, size_t n, int mem, const uint8_t* keys, int nkeys, int sign_key, const uint8_t* proof,

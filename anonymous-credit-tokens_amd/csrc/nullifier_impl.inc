@@ -24,6 +24,8 @@
 // passes none): clients choose their nullifiers, and without the key they cannot aim them at one probe chain.  The batch
 // table starts at the low half of the 64-bit hash, the persistent table at the high half.
 
+#include "null_probe.h"      // null_load_key, null_hash, null_eq, NullSalt, null_probe_contains
+
 namespace {
 
 struct NullArgs {
@@ -38,32 +40,6 @@ struct NullArgs {
 };
 // a lane whose epoch index names no table entry is left out of the batch altogether (as if masked) and answered undetermined
 __device__ __forceinline__ bool null_bad_index(const NullArgs& a, uint32_t i) { return a.eidx && a.eidx[i] >= a.n_epochs; }
-
-__device__ __forceinline__ void null_load_key(uint32_t w[8], const uint8_t* p) {
-  uint32_t r[8];
-  if ((reinterpret_cast<uintptr_t>(p) & 3u) == 0) { const uint32_t* q = reinterpret_cast<const uint32_t*>(p); for (int i = 0; i < 8; i++) r[i] = q[i]; }
-  else for (int i = 0; i < 8; i++) r[i] = (uint32_t)p[4 * i] | (uint32_t)p[4 * i + 1] << 8 | (uint32_t)p[4 * i + 2] << 16 | (uint32_t)p[4 * i + 3] << 24;
-  const act::sc k = act::sc_from_words(r);                                // Scalar::from_bytes_mod_order
-  for (int i = 0; i < 8; i++) w[i] = k.v[i];
-}
-// SipHash-1-3 (one compression round per 8-byte block, three finalisation rounds) of the 32-byte key under salt[0..3]
-__device__ __forceinline__ uint64_t null_hash(const uint32_t w[8], const uint32_t salt[4]) {
-  const uint64_t k0 = (uint64_t)salt[0] | (uint64_t)salt[1] << 32, k1 = (uint64_t)salt[2] | (uint64_t)salt[3] << 32;
-  uint64_t v0 = k0 ^ 0x736f6d6570736575ull, v1 = k1 ^ 0x646f72616e646f6dull, v2 = k0 ^ 0x6c7967656e657261ull, v3 = k1 ^ 0x7465646279746573ull;
-  auto rotl = [](uint64_t x, int b) { return (x << b) | (x >> (64 - b)); };
-  auto round = [&]() {
-    v0 += v1; v1 = rotl(v1, 13); v1 ^= v0; v0 = rotl(v0, 32);
-    v2 += v3; v3 = rotl(v3, 16); v3 ^= v2;
-    v0 += v3; v3 = rotl(v3, 21); v3 ^= v0;
-    v2 += v1; v1 = rotl(v1, 17); v1 ^= v2; v2 = rotl(v2, 32);
-  };
-  for (int i = 0; i < 4; i++) { const uint64_t m = (uint64_t)w[2 * i] | (uint64_t)w[2 * i + 1] << 32; v3 ^= m; round(); v0 ^= m; }
-  const uint64_t last = (uint64_t)32 << 56;                                // length byte, no tail bytes
-  v3 ^= last; round(); v0 ^= last;
-  v2 ^= 0xff; round(); round(); round();
-  return v0 ^ v1 ^ v2 ^ v3;
-}
-__device__ __forceinline__ bool null_eq(const uint32_t a[8], const uint32_t b[8]) { uint32_t d = 0; for (int i = 0; i < 8; i++) d |= a[i] ^ b[i]; return d == 0; }
 
 __global__ void __launch_bounds__(256) k_null_claim(NullArgs a) {
   uint32_t i = blockIdx.x * 256 + threadIdx.x;
@@ -156,7 +132,6 @@ __global__ void __launch_bounds__(256) k_null_count_state(const uint4* tab_state
   for (int off = 32; off; off >>= 1) mine += __shfl_down(mine, off);
   if (__lane_id() == 0 && mine) atomicAdd(counter, mine);
 }
-struct NullSalt { uint32_t w[4]; };
 // Every committed slot of the old table into the new one (same salt, same slot function, masked to the new capacity).  The keys are
 // known distinct, so a slot is claimed by a compare-and-swap 0 -> its old state word (committed, epoch carried over) and no key is
 // compared; nothing reads the new table before the kernel has finished.  `drop`: the state word of the slots that are left behind
@@ -192,19 +167,8 @@ __global__ void __launch_bounds__(256) k_null_contains(const uint8_t* keys, uint
                                                        const uint32_t* tab_state, uint32_t tab_cap, NullSalt salt, uint8_t* found) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  uint32_t w[8], o[8]; null_load_key(w, keys + (size_t)i * stride);
-  uint32_t t = (uint32_t)(null_hash(w, salt.w) >> 32) & (tab_cap - 1);
-  uint8_t f = 0;
-  for (uint32_t probes = 0; probes < tab_cap; probes++) {
-    const uint32_t st = tab_state[t];
-    if (st == 0u) break;
-    if ((st & 0xFFu) == 2u) {
-      const uint32_t* src = tab_keys + (size_t)t * 8;
-      for (int k = 0; k < 8; k++) o[k] = src[k];
-      if (null_eq(w, o)) { f = 1; break; }
-    }
-    t = (t + 1) & (tab_cap - 1);
-  }
+  uint32_t w[8]; null_load_key(w, keys + (size_t)i * stride);
+  const uint8_t f = null_probe_contains(w, tab_keys, tab_state, tab_cap, salt.w) ? 1 : 0;
   found[i] = f;
 }
 

@@ -645,6 +645,48 @@ int act_node_redeem_cbor_keyring_epochs_batch(act_node *node, act_node_nullifier
                                               const uint32_t *key_epochs, int sign_key, const uint8_t *cbor, const uint64_t *offsets,
                                               const uint8_t *rng, int rng_mode, uint8_t *out_refund_cbor, uint8_t *status, uint8_t *out_key);
 
+/* ======== admission before verification: the expected charge and the spent nullifiers first ========
+ * The redeem calls above verify, then look up and record, then sign: a replayed proof costs a whole verification before the set
+ * answers DoubleSpendError, and nothing compares SpendProof.s with what the request costs.  These two calls put an admission stage in
+ * front.  They are the superset forms (ring and epoch parameters); nkeys == 1 with key_epochs == NULL is the one-key call.  In lane
+ * order:
+ *     for i in 0..n:
+ *       1. wire form only: the message fails structurally -> exactly the code act_redeem_cbor_* gives (ACT_STATUS_CBOR_MALFORMED /
+ *          ACT_STATUS_CBOR_STRUCTURE, and 255 where an invalid point stands in front of the fault in wire order).  A well-shaped
+ *          message, its points not yet validated, goes on.  Every legal spelling is read, not only the canonical one.
+ *       2. charge != NULL and s_i != charge_i (both reduced mod l)      -> ACT_STATUS_WRONG_CHARGE: not looked up, not verified, not
+ *          recorded, not signed; no trace in the set -- the token can be redeemed later at the right price
+ *       3. k_i (reduced) is in the set when the call looks it up         -> ACT_STATUS_DOUBLE_SPEND, NOT verified
+ *       4. otherwise exactly act_redeem_(cbor_)keyring_epochs_batch: verification (255 / 6 / 7, out_key), check-and-insert (in the
+ *          set, or spent by an earlier ACCEPTED lane of this batch -> ACT_STATUS_DOUBLE_SPEND), recorded under the matched key's
+ *          epoch (untagged without key_epochs), signed
+ * charge: nullable; n scalars of 32 bytes in `mem` memory, laid out like SpendProof.s.
+ * What stays the same: with charge == NULL the accepted lanes, their refund bytes, their out_key, the nullifiers recorded with their
+ * epochs and what is drawn from the generator are byte for byte those of act_redeem_(cbor_)keyring_epochs_batch on an identical set --
+ * ACT_RNG_SEQUENTIAL slices go to the signed lanes in lane order, ACT_RNG_CALLBACK makes one draw of 128 x accepted bytes per call,
+ * ACT_RNG_PER_LANE uses the ORIGINAL lane's slice.
+ * What may differ: only the rejection code of a lane that is rejected for more than one reason.  A spent nullifier with a tampered or
+ * undecodable proof reports ACT_STATUS_DOUBLE_SPEND here and 7 / 255 there; a lane shed in steps 1-3 has out_key = ACT_KEY_NONE and an
+ * all-zero output record.
+ * Lanes that share a FRESH nullifier cannot be shed up front (the first VALID one wins): all of them are verified, as in the redeem calls.
+ * The look-up of step 3 is read-only.  The decision that records is still the check-and-insert behind verification: a nullifier that a
+ * concurrent caller records in between is caught there.
+ * Failure semantics are those of act_redeem_* (ACT_STATUS_NULLIFIER_UNDETERMINED / ACT_STATUS_RECORDED_UNSIGNED, status[] complete on
+ * return).  A HIP failure in the admission stage itself: nothing recorded, nothing signed, status[] not written.
+ * out_counts: nullable, HOST memory, ACT_ADMIT_COUNTS values: lanes, wire_rejected (step 1), wrong_charge, spent_before (step 3),
+ * verified (= lanes - wire_rejected - wrong_charge - spent_before: the lanes that cost a verification), rejected_by_verification,
+ * double_spend_after (step 4's check-and-insert), accepted. */
+#define ACT_STATUS_WRONG_CHARGE 250   /* admission: s != the expected charge; not verified, not recorded, not signed */
+#define ACT_ADMIT_COUNTS 8
+int act_redeem_admit_batch(act_ctx *ctx, act_nullifier_set *set, size_t n, int mem, const uint8_t *keys, int nkeys,
+                           const uint32_t *key_epochs /* nullable */, int sign_key, const uint8_t *proof, const uint8_t *charge /* nullable */,
+                           const uint8_t *rng, int rng_mode, uint8_t *out_refund, uint8_t *status, uint8_t *out_key,
+                           uint64_t *out_counts /* nullable, host */);
+int act_redeem_cbor_admit_batch(act_ctx *ctx, act_nullifier_set *set, size_t n, int mem, const uint8_t *keys, int nkeys,
+                                const uint32_t *key_epochs /* nullable */, int sign_key, const uint8_t *cbor, const uint64_t *offsets,
+                                const uint8_t *charge /* nullable */, const uint8_t *rng, int rng_mode, uint8_t *out_refund_cbor,
+                                uint8_t *status, uint8_t *out_key, uint64_t *out_counts /* nullable, host */);
+
 /* ======== row d and test infrastructure: debug hooks, measurement knobs, kernel timing, roofline probes (nothing here is on the product's path) ==== */
 /* Debug / test hook: the exact "spend" transcript pre-images of the last act_verify_spend_batch /
  * act_refund_batch chunk (n_last * act_spend_transcript_bytes, copied to host memory). */

@@ -26,6 +26,15 @@ pub struct ActNode {
 pub struct ActNodeNullifierSet {
     _private: [u8; 0],
 }
+/// One-GPU handles (`act_ctx`, `act_nullifier_set`): what the admission calls take.
+#[repr(C)]
+pub struct ActCtx {
+    _private: [u8; 0],
+}
+#[repr(C)]
+pub struct ActNullifierSet {
+    _private: [u8; 0],
+}
 /// `act_rng_source` (include/act_mi355x.h): the caller's generator handed to the library, which draws 128 bytes per lane it signs --
 /// once, after every verdict is known -- so the generator ends where a sequential loop over `refund` would have left it.
 #[repr(C)]
@@ -110,6 +119,12 @@ extern "C" {
     fn act_node_redeem_cbor_keyring_epochs_batch(node: *mut ActNode, set: *mut ActNodeNullifierSet, n: usize, keys: *const u8, nkeys: c_int,
                                                  key_epochs: *const u32, sign_key: c_int, cbor: *const u8, offsets: *const u64, rng: *const u8, rng_mode: c_int,
                                                  out_refund_cbor: *mut u8, status: *mut u8, out_key: *mut u8) -> c_int;
+    fn act_redeem_admit_batch(ctx: *mut ActCtx, set: *mut ActNullifierSet, n: usize, mem: c_int, keys: *const u8, nkeys: c_int, key_epochs: *const u32,
+                              sign_key: c_int, proof: *const u8, charge: *const u8, rng: *const u8, rng_mode: c_int, out_refund: *mut u8, status: *mut u8,
+                              out_key: *mut u8, out_counts: *mut u64) -> c_int;
+    fn act_redeem_cbor_admit_batch(ctx: *mut ActCtx, set: *mut ActNullifierSet, n: usize, mem: c_int, keys: *const u8, nkeys: c_int, key_epochs: *const u32,
+                                   sign_key: c_int, cbor: *const u8, offsets: *const u64, charge: *const u8, rng: *const u8, rng_mode: c_int,
+                                   out_refund_cbor: *mut u8, status: *mut u8, out_key: *mut u8, out_counts: *mut u64) -> c_int;
     fn act_node_device_stats(node: *mut ActNode, k: c_int, weight: *mut f64, last_lanes: *mut u64, last_seconds: *mut f64, last_calls: *mut u64) -> c_int;
 }
 
@@ -1035,6 +1050,67 @@ impl<'a> Keyring<'a> {
         let engine_failure = if rc != 0 { Some(unsafe { CStr::from_ptr(act_node_last_error(gpu.0)) }.to_string_lossy().into_owned()) } else { None };
         let lanes = (0..n).map(|i| if status[i] == 0 { Ok(Refund::from_record(&out[128 * i..128 * i + 128])) } else { Err(status_to_wire_error(status[i])) }).collect();
         RingRedeemed { redeemed: Redeemed { lanes, engine_failure }, matched: Self::matched(&out_key[..n]) }
+    }
+}
+
+/// `ACT_STATUS_WRONG_CHARGE`: the admission calls only -- `s` is not the expected charge; not verified, not recorded, not signed.
+pub const ACT_STATUS_WRONG_CHARGE: u8 = 250;
+pub const ACT_ADMIT_COUNTS: usize = 8;
+/// statuses, outputs (128-byte Refund records or `REFUND_CBOR_BYTES` messages, all zero where not signed), matched ring keys, and
+/// lanes / wire_rejected / wrong_charge / spent_before / verified / rejected_by_verification / double_spend_after / accepted
+pub struct Admitted {
+    pub rc: c_int,
+    pub status: Vec<u8>,
+    pub out: Vec<u8>,
+    pub out_key: Vec<u8>,
+    pub counts: [u64; ACT_ADMIT_COUNTS],
+}
+/// Admission before verification on ONE GPU (include/act_mi355x.h "admission before verification"): the ring redeem calls with a screen
+/// in front -- a proof whose charge `s` is not the expected one is answered `ACT_STATUS_WRONG_CHARGE` and a proof whose nullifier the
+/// set already holds `DoubleSpendError`, both WITHOUT being verified.  Thin: bytes in, bytes out, the statuses as the header lists them.
+/// The node-level forms do not exist yet; node callers compose `act_node_nullifier_contains_batch` in front of their redeem call.
+pub struct GpuAdmission {
+    ctx: *mut ActCtx,
+    set: *mut ActNullifierSet,
+}
+impl GpuAdmission {
+    /// # Safety
+    /// `ctx` and `set` are live handles on one device (`act_ctx_create` / `act_node_ctx`, `act_nullifier_set_create`) and outlive `self`.
+    pub unsafe fn from_raw(ctx: *mut ActCtx, set: *mut ActNullifierSet) -> Self {
+        GpuAdmission { ctx, set }
+    }
+    /// `keys`: nkeys records of 64 bytes; `proofs`: n records of `PROOF_BYTES`; `charges`: n scalars of 32 bytes, or None.
+    pub fn redeem_admit_batch(&self, keys: &[u8], key_epochs: Option<&[u32]>, sign_with: Option<usize>, proofs: &[u8], charges: Option<&[u8]>,
+                              mut rng: impl CryptoRngCore) -> Admitted {
+        let (n, nkeys) = (proofs.len() / PROOF_BYTES, keys.len() / 64);
+        assert!(proofs.len() == n * PROOF_BYTES && charges.map_or(true, |c| c.len() == 32 * n) && key_epochs.map_or(true, |e| e.len() == nkeys));
+        let src = rng_source(&mut rng);
+        let mut r = Admitted { rc: 0, status: vec![0u8; n + 1], out: vec![0u8; 128 * n + 1], out_key: vec![ACT_KEY_NONE; n + 1], counts: [0; ACT_ADMIT_COUNTS] };
+        r.rc = unsafe {
+            act_redeem_admit_batch(self.ctx, self.set, n, 0, keys.as_ptr(), nkeys as c_int, key_epochs.map_or(std::ptr::null(), |e| e.as_ptr()),
+                                   sign_with.map_or(ACT_SIGN_MATCHED, |i| i as c_int), proofs.as_ptr(), charges.map_or(std::ptr::null(), |c| c.as_ptr()),
+                                   &src as *const ActRngSource as *const u8, ACT_RNG_CALLBACK, r.out.as_mut_ptr(), r.status.as_mut_ptr(), r.out_key.as_mut_ptr(),
+                                   r.counts.as_mut_ptr())
+        };
+        r.status.truncate(n); r.out.truncate(128 * n); r.out_key.truncate(n);
+        r
+    }
+    /// The same on wire bytes: CBOR SpendProof messages in, CBOR Refund messages out.
+    pub fn redeem_cbor_admit_batch(&self, keys: &[u8], key_epochs: Option<&[u32]>, sign_with: Option<usize>, msgs: &[&[u8]], charges: Option<&[u8]>,
+                                   mut rng: impl CryptoRngCore) -> Admitted {
+        let (blob, offsets) = gather(msgs);
+        let (n, nkeys) = (msgs.len(), keys.len() / 64);
+        assert!(charges.map_or(true, |c| c.len() == 32 * n) && key_epochs.map_or(true, |e| e.len() == nkeys));
+        let src = rng_source(&mut rng);
+        let mut r = Admitted { rc: 0, status: vec![0u8; n + 1], out: vec![0u8; REFUND_CBOR_BYTES * n + 1], out_key: vec![ACT_KEY_NONE; n + 1], counts: [0; ACT_ADMIT_COUNTS] };
+        r.rc = unsafe {
+            act_redeem_cbor_admit_batch(self.ctx, self.set, n, 0, keys.as_ptr(), nkeys as c_int, key_epochs.map_or(std::ptr::null(), |e| e.as_ptr()),
+                                        sign_with.map_or(ACT_SIGN_MATCHED, |i| i as c_int), blob.as_ptr(), offsets.as_ptr(),
+                                        charges.map_or(std::ptr::null(), |c| c.as_ptr()), &src as *const ActRngSource as *const u8, ACT_RNG_CALLBACK,
+                                        r.out.as_mut_ptr(), r.status.as_mut_ptr(), r.out_key.as_mut_ptr(), r.counts.as_mut_ptr())
+        };
+        r.status.truncate(n); r.out.truncate(REFUND_CBOR_BYTES * n); r.out_key.truncate(n);
+        r
     }
 }
 
