@@ -264,15 +264,16 @@ class PrivateKey(_Cbor):
         return [out[i] if st[i] == 0 else _wire_error(st[i]) for i in range(len(msgs))]
 
     # ---- admission before verification: the expected charge and the spent nullifiers first ------------------
-    def redeem_admit_batch(self, params: Params, db: "NullifierDb", proofs: Sequence["SpendProof"], rng, charges: Sequence = None) -> List["Refund"]:
+    def redeem_admit_batch(self, params: Params, db: "NullifierDb", proofs: Sequence["SpendProof"], rng, charges: Sequence = None, unique: bool = False) -> List["Refund"]:
         """redeem_batch with the admission stage in front: entry i is a Refund, Error 250 (WrongCharge: proof i does not spend
         charges[i]; nothing was recorded, the token can still be redeemed at the right price) or the Errors of redeem_batch -- a
-        nullifier that is already recorded is answered DoubleSpendError WITHOUT the proof being verified."""
-        res, _ = Keyring([self]).redeem_admit_batch(params, db, proofs, rng, charges=charges)
+        nullifier that is already recorded is answered DoubleSpendError WITHOUT the proof being verified.  unique=True: a proof with
+        the bytes of an earlier proof of the batch is not verified either (act_redeem_admit_unique_batch); the same entries."""
+        res, _ = Keyring([self]).redeem_admit_batch(params, db, proofs, rng, charges=charges, unique=unique)
         return res
 
-    def redeem_admit_cbor_batch(self, params: Params, db: "NullifierDb", msgs: Sequence[bytes], rng, nbits: int = L, charges: Sequence = None) -> list:
-        res, _ = Keyring([self]).redeem_admit_cbor_batch(params, db, msgs, rng, nbits, charges=charges)
+    def redeem_admit_cbor_batch(self, params: Params, db: "NullifierDb", msgs: Sequence[bytes], rng, nbits: int = L, charges: Sequence = None, unique: bool = False) -> list:
+        res, _ = Keyring([self]).redeem_admit_cbor_batch(params, db, msgs, rng, nbits, charges=charges, unique=unique)
         return res
 
     def verify_spend_batch(self, params: Params, proofs: Sequence["SpendProof"]) -> bytes:
@@ -347,23 +348,25 @@ class Keyring:
         st, out, ok = _draw_signed(rng, len(msgs), lambda src, mode: e.redeem_cbor_keyring(db.set, self._records(), list(msgs), src, mode, self._sign_key(sign_with), key_epochs=self.epochs))
         return [out[i] if st[i] == 0 else _wire_error(st[i]) for i in range(len(msgs))], self._indices(st, ok)
 
-    def redeem_admit_batch(self, params: Params, db: "NullifierDb", proofs: Sequence["SpendProof"], rng, sign_with=None, charges: Sequence = None) -> Tuple[list, list]:
+    def redeem_admit_batch(self, params: Params, db: "NullifierDb", proofs: Sequence["SpendProof"], rng, sign_with=None, charges: Sequence = None, unique: bool = False) -> Tuple[list, list]:
         """redeem_batch behind the admission stage (act_redeem_admit_batch): `charges` (optional, one per proof) is what each request
         costs -- a proof whose s differs is answered Error 250 and is neither looked up, verified nor recorded; a proof whose nullifier
-        the database already holds is answered DoubleSpendError without being verified.  `self.last_admit_counts`: the call's counts."""
+        the database already holds is answered DoubleSpendError without being verified.  `self.last_admit_counts`: the call's counts.
+        unique=True (act_redeem_admit_unique_batch): byte-identical proofs of the batch are verified once; the results are the same
+        and the counts gain "copies"."""
         nbits = proofs[0].nbits if proofs else L
         e = params.engine(nbits)
         pb = b"".join(p.record for p in proofs)
         cc = b"".join(scalar(c) for c in charges) if charges is not None else None
         st, out, ok, self.last_admit_counts = _draw_signed(rng, len(proofs), lambda src, mode: e.redeem_admit(
-            db.set, self._records(), pb, src, mode, self._sign_key(sign_with), charges=cc, key_epochs=self.epochs))
+            db.set, self._records(), pb, src, mode, self._sign_key(sign_with), charges=cc, key_epochs=self.epochs, unique=unique))
         return [Refund(out[128 * i:128 * i + 128]) if st[i] == 0 else Error(st[i]) for i in range(len(proofs))], self._indices(st, ok)
 
-    def redeem_admit_cbor_batch(self, params: Params, db: "NullifierDb", msgs: Sequence[bytes], rng, nbits: int = L, sign_with=None, charges: Sequence = None) -> Tuple[list, list]:
+    def redeem_admit_cbor_batch(self, params: Params, db: "NullifierDb", msgs: Sequence[bytes], rng, nbits: int = L, sign_with=None, charges: Sequence = None, unique: bool = False) -> Tuple[list, list]:
         e = params.engine(nbits)
         cc = b"".join(scalar(c) for c in charges) if charges is not None else None
         st, out, ok, self.last_admit_counts = _draw_signed(rng, len(msgs), lambda src, mode: e.redeem_cbor_admit(
-            db.set, self._records(), list(msgs), src, mode, self._sign_key(sign_with), charges=cc, key_epochs=self.epochs))
+            db.set, self._records(), list(msgs), src, mode, self._sign_key(sign_with), charges=cc, key_epochs=self.epochs, unique=unique))
         return [out[i] if st[i] == 0 else _wire_error(st[i]) for i in range(len(msgs))], self._indices(st, ok)
 
 

@@ -17,6 +17,7 @@ TRANSCRIPT_HOST, TRANSCRIPT_DEVICE = 0, 1
 KEYRING_MAX, KEY_NONE, SIGN_MATCHED = 4, 255, -1      # act_*_keyring_batch: ring size, "no ring key matched", "sign with the matched key"
 STATUS_WRONG_CHARGE = 250                             # act_redeem_*admit_batch: s is not the expected charge
 ADMIT_COUNTS = ("lanes", "wire_rejected", "wrong_charge", "spent_before", "verified", "rejected_by_verification", "double_spend_after", "accepted")
+ADMIT_UNIQUE_COUNTS = ADMIT_COUNTS + ("copies",)      # act_redeem_*admit_unique_batch: lanes with the bytes of an earlier lane, not verified
 _ERRS = {1: "ACT_ERR_ARG", 2: "ACT_ERR_HIP", 3: "ACT_ERR_PARAMS", 4: "ACT_ERR_NO_DEVICE", 5: "ACT_ERR_RNG"}
 
 EXPORTS = [
@@ -46,7 +47,7 @@ EXPORTS = [
     "act_node_nullifier_check_and_insert_epoch_batch", "act_node_nullifier_set_epoch_len", "act_node_nullifier_set_retire_epoch",
     "act_node_nullifier_set_retired_epochs", "act_node_nullifier_set_export_epochs", "act_node_redeem_keyring_epochs_batch",
     "act_node_redeem_cbor_keyring_epochs_batch",
-    "act_redeem_admit_batch", "act_redeem_cbor_admit_batch",
+    "act_redeem_admit_batch", "act_redeem_cbor_admit_batch", "act_redeem_admit_unique_batch", "act_redeem_cbor_admit_unique_batch", "act_debug_copy_leaders",
     "act_issue_check_cbor_batch", "act_issue_sign_cbor_batch", "act_issue_cbor_batch",
     "act_node_issue_check_cbor_batch", "act_node_issue_sign_cbor_batch", "act_node_issue_cbor_batch",
     "act_ctx_host_hash_stats", "act_ctx_set_tiny_calls", "act_node_set_balance", "act_node_device_stats", "act_node_balance_state", "act_debug_set_slowdown", "act_debug_fail_next_signs",
@@ -227,6 +228,10 @@ def load() -> C.CDLL:
     # admission before verification: the expected charge and the spent nullifiers first (out_counts: ACT_ADMIT_COUNTS values, host)
     lib.act_redeem_admit_batch.argtypes = [vp, vp, sz, i32, u8p, i32, u32p, i32, u8p, u8p, u8p, i32, u8p, u8p, u8p, u64p]
     lib.act_redeem_cbor_admit_batch.argtypes = [vp, vp, sz, i32, u8p, i32, u32p, i32, u8p, vp, u8p, u8p, i32, u8p, u8p, u8p, u64p]
+    # the unique forms: byte-identical proofs of one batch are verified once (out_counts: ACT_ADMIT_UNIQUE_COUNTS values)
+    lib.act_redeem_admit_unique_batch.argtypes = lib.act_redeem_admit_batch.argtypes
+    lib.act_redeem_cbor_admit_unique_batch.argtypes = lib.act_redeem_cbor_admit_batch.argtypes
+    lib.act_debug_copy_leaders.argtypes = [vp, sz, u64p, vp, C.POINTER(C.c_double)]
     lib.act_issue_check_cbor_batch.argtypes = [vp, sz, i32, u8p, vp, u8p, u8p]
     lib.act_issue_sign_cbor_batch.argtypes = [vp, sz, i32, u8p, u8p, u8p, u8p, u8p, i32, u8p, u8p]
     lib.act_issue_cbor_batch.argtypes = [vp, sz, i32, u8p, u8p, vp, u8p, u8p, i32, u8p, u8p]
@@ -728,34 +733,40 @@ class Engine:
 
     # ---- admission before verification (act_redeem_admit_batch / act_redeem_cbor_admit_batch) ---------------------------------------
     def redeem_admit(self, nullifier_set, keys, proofs: bytes, rng, rng_mode: int = RNG_PER_LANE, sign_key: int = SIGN_MATCHED, charges: bytes = None,
-                     key_epochs=None, raw: bool = False):
+                     key_epochs=None, raw: bool = False, unique: bool = False):
         """redeem_keyring with the admission stage in front: a lane whose charge s is not charges[i] (STATUS_WRONG_CHARGE) or whose
         nullifier is already in the set (3) is answered without being verified.  -> (statuses, refunds, out_key, counts dict);
-        raw=True: (rc, statuses, refunds, out_key, counts), no exception."""
+        raw=True: (rc, statuses, refunds, out_key, counts), no exception.  unique=True: act_redeem_admit_unique_batch -- a lane with
+        the bytes of an earlier lane is not verified either; the same answers, and counts gains "copies"."""
         n = len(proofs) // self.proof_bytes; out = np.full(128 * n, 7 if raw else 0, np.uint8); st = np.zeros(n, np.uint8); ok = np.zeros(n, np.uint8)
         pk, kk = _in(b"".join(keys)); p0, k0 = _in(proofs, self.proof_bytes * n); p1, k1 = _rng_arg(rng)
         pc, kc = _in(charges, 32 * n) if charges is not None else (None, None)
         ke = _epoch_table(key_epochs, len(keys)) if key_epochs is not None else None
-        cnt = (C.c_uint64 * len(ADMIT_COUNTS))()
-        rc = self.lib.act_redeem_admit_batch(self.ctx, nullifier_set.h, n, MEM_HOST, pk, len(keys), ke.ctypes.data if ke is not None else None, sign_key, p0, pc, p1,
-                                             rng_mode, out.ctypes.data, st.ctypes.data, ok.ctypes.data, cnt)
-        counts = dict(zip(ADMIT_COUNTS, (int(v) for v in cnt)))
+        names = ADMIT_UNIQUE_COUNTS if unique else ADMIT_COUNTS
+        cnt = (C.c_uint64 * len(names))()
+        fn = self.lib.act_redeem_admit_unique_batch if unique else self.lib.act_redeem_admit_batch
+        rc = fn(self.ctx, nullifier_set.h, n, MEM_HOST, pk, len(keys), ke.ctypes.data if ke is not None else None, sign_key, p0, pc, p1,
+                rng_mode, out.ctypes.data, st.ctypes.data, ok.ctypes.data, cnt)
+        counts = dict(zip(names, (int(v) for v in cnt)))
         if raw:
             return rc, st.tobytes(), out.tobytes(), ok.tobytes(), counts
         self._ck(rc)
         return st.tobytes(), out.tobytes(), ok.tobytes(), counts
 
     def redeem_cbor_admit(self, nullifier_set, keys, messages: list, rng, rng_mode: int = RNG_SEQUENTIAL, sign_key: int = SIGN_MATCHED, charges: bytes = None,
-                          key_epochs=None, raw: bool = False):
-        """wire bytes in, wire bytes out -> (statuses, list of CBOR Refund messages (b"" where not signed), out_key, counts dict)"""
+                          key_epochs=None, raw: bool = False, unique: bool = False):
+        """wire bytes in, wire bytes out -> (statuses, list of CBOR Refund messages (b"" where not signed), out_key, counts dict);
+        unique=True: act_redeem_cbor_admit_unique_batch (a copy has the same length and the same bytes as an earlier message)"""
         n = len(messages); p0, k0, offs = _msgs(messages); ml = self.cbor_size("Refund")
         st = np.zeros(n, np.uint8); ok = np.zeros(n, np.uint8); out = np.zeros(ml * n, np.uint8); pk, kk = _in(b"".join(keys)); pr, kr = _rng_arg(rng)
         pc, kc = _in(charges, 32 * n) if charges is not None else (None, None)
         ke = _epoch_table(key_epochs, len(keys)) if key_epochs is not None else None
-        cnt = (C.c_uint64 * len(ADMIT_COUNTS))()
-        rc = self.lib.act_redeem_cbor_admit_batch(self.ctx, nullifier_set.h, n, MEM_HOST, pk, len(keys), ke.ctypes.data if ke is not None else None, sign_key, p0,
-                                                  offs.ctypes.data, pc, pr, rng_mode, out.ctypes.data, st.ctypes.data, ok.ctypes.data, cnt)
-        counts = dict(zip(ADMIT_COUNTS, (int(v) for v in cnt)))
+        names = ADMIT_UNIQUE_COUNTS if unique else ADMIT_COUNTS
+        cnt = (C.c_uint64 * len(names))()
+        fn = self.lib.act_redeem_cbor_admit_unique_batch if unique else self.lib.act_redeem_cbor_admit_batch
+        rc = fn(self.ctx, nullifier_set.h, n, MEM_HOST, pk, len(keys), ke.ctypes.data if ke is not None else None, sign_key, p0,
+                offs.ctypes.data, pc, pr, rng_mode, out.ctypes.data, st.ctypes.data, ok.ctypes.data, cnt)
+        counts = dict(zip(names, (int(v) for v in cnt)))
         b = out.tobytes()
         msgs = [b[i * ml:(i + 1) * ml] if st[i] == 0 else b"" for i in range(n)]
         if raw:
@@ -766,21 +777,31 @@ class Engine:
 
     def admit_ptr(self, fn: str, keys, n: int, mem: int, **p):
         """the admission calls on raw pointers of either kind: fn = redeem / redeem_cbor; p: set, proofs | cbor (+ offsets), charges,
-        rng, rng_mode, out, status, out_key, key_epochs, sign_key.  -> counts dict"""
+        rng, rng_mode, out, status, out_key, key_epochs, sign_key, unique (the act_redeem_*admit_unique_batch forms).  -> counts dict"""
         pk, kk = _in(b"".join(keys)); nk = len(keys)
         ke = _epoch_table(p["key_epochs"], nk) if p.get("key_epochs") is not None else None
         kep = ke.ctypes.data if ke is not None else None
-        cnt = (C.c_uint64 * len(ADMIT_COUNTS))()
+        unique = bool(p.get("unique"))
+        names = ADMIT_UNIQUE_COUNTS if unique else ADMIT_COUNTS
+        cnt = (C.c_uint64 * len(names))()
         if fn == "redeem":
-            rc = self.lib.act_redeem_admit_batch(self.ctx, p["set"].h, n, mem, pk, nk, kep, p.get("sign_key", SIGN_MATCHED), p["proofs"], p.get("charges") or None,
-                                                 p["rng"], p["rng_mode"], p["out"], p["status"], p["out_key"], cnt)
+            call = self.lib.act_redeem_admit_unique_batch if unique else self.lib.act_redeem_admit_batch
+            rc = call(self.ctx, p["set"].h, n, mem, pk, nk, kep, p.get("sign_key", SIGN_MATCHED), p["proofs"], p.get("charges") or None,
+                      p["rng"], p["rng_mode"], p["out"], p["status"], p["out_key"], cnt)
         else:
-            rc = self.lib.act_redeem_cbor_admit_batch(self.ctx, p["set"].h, n, mem, pk, nk, kep, p.get("sign_key", SIGN_MATCHED), p["cbor"], p.get("offsets") or None,
-                                                      p.get("charges") or None, p["rng"], p["rng_mode"], p["out"], p["status"], p["out_key"], cnt)
+            call = self.lib.act_redeem_cbor_admit_unique_batch if unique else self.lib.act_redeem_cbor_admit_batch
+            rc = call(self.ctx, p["set"].h, n, mem, pk, nk, kep, p.get("sign_key", SIGN_MATCHED), p["cbor"], p.get("offsets") or None,
+                      p.get("charges") or None, p["rng"], p["rng_mode"], p["out"], p["status"], p["out_key"], cnt)
         if not p.get("raw"):
             self._ck(rc)
-        counts = dict(zip(ADMIT_COUNTS, (int(v) for v in cnt)))
+        counts = dict(zip(names, (int(v) for v in cnt)))
         return (rc, counts) if p.get("raw") else counts
+
+    def copy_leaders(self, fps):
+        """act_debug_copy_leaders: the leader table of the unique admission forms over made-up fingerprints -> (leaders, milliseconds)"""
+        m = len(fps); a = np.asarray(fps, np.uint64); out = np.zeros(max(1, m), np.uint32); ms = C.c_double(0)
+        self._ck(self.lib.act_debug_copy_leaders(self.ctx, m, a.ctypes.data_as(C.POINTER(C.c_uint64)), out.ctypes.data, C.byref(ms)))
+        return out[:m].tolist(), ms.value
 
     # ---- issuance on wire bytes (act_issue_*cbor_batch): IssuanceRequest messages in, IssuanceResponse messages out ----------------
     def issue_cbor(self, sk: bytes, messages: list, c: bytes, rng, rng_mode: int = RNG_PER_LANE):

@@ -1,7 +1,8 @@
 // admit.h — launchers of the admission kernels (k_admit.hip; argument blocks and lane bodies in admit_lanes.h, engine side in
-// admit_impl.inc).
+// admit_impl.inc) and of the copy stage behind the screen (k_copies.hip; copy_lanes.h; copies_impl.inc).
 #pragma once
 #include "admit_lanes.h"
+#include "copy_lanes.h"
 
 namespace act {
 
@@ -14,6 +15,12 @@ void launch_admit_rows(const AdmitRowsArgs& a, hipStream_t s);
 void launch_admit_msgs(const AdmitMsgsArgs& a, hipStream_t s);
 void launch_admit_scatter(const AdmitScatterArgs& a, hipStream_t s);
 void launch_admit_patch(const AdmitPatchArgs& a, hipStream_t s);
+// the copy stage, over the m survivors of the screen in their compact order
+void launch_copy_fp(const CopyFpArgs& a, hipStream_t s);                // fp[j]: one wavefront per survivor
+void launch_copy_leaders(const CopyTableArgs& a, hipStream_t s);        // tab_fp zero and tab_j all-ones before; leader[j] = the smallest j with fp[j]
+void launch_copy_equal(const CopyEqualArgs& a, hipStream_t s);          // copy_of[j] = leader[j] when every byte is equal, else COPY_NONE
+void launch_copy_mark(const CopyMarkArgs& a, hipStream_t s);            // pre2 = a copy of pre and lead all-ones before
+void launch_copy_resolve(const CopyResolveArgs& a, hipStream_t s);      // behind launch_admit_scatter on the same stream
 #endif
 
 }  // namespace act

@@ -10,6 +10,8 @@
 //   5. scatter       statuses, out_key and refunds back to their lanes; shed lanes get all-zero records           [k_admit_scatter]
 // Nothing is shed (m == n): the caller's pointers go straight to redeem_keyring_impl; everything is shed: no verification kernel runs.
 // The decision that RECORDS is still the check-and-insert behind verification; the look-up of step 1 only spares work.
+// act_redeem_(cbor_)admit_unique_batch add the copy stage between steps 2 and 3 (copies_impl.inc, included behind this file): a
+// survivor whose input bytes are those of an earlier survivor is not verified and takes its answer from that lane      [k_copies.hip]
 namespace {
 
 constexpr size_t ADMIT_READ_WINDOW = 4096;       // messages per host-reader window (as WIRE_SETTLE_WINDOW)
@@ -68,13 +70,24 @@ void admit_counts_of(uint64_t* out_counts, size_t n, const uint8_t* pre, size_t 
   memcpy(out_counts, k, sizeof(k));
 }
 
+// the copy stage of the unique forms (copies_impl.inc): what it leaves for the rest of the call.  copies == 0: nothing below is used
+struct AdmitCopies {
+  act_ctx* c; DevTmp d;
+  size_t copies = 0, m2 = 0;                                  // m2 = the lanes that are verified
+  uint8_t* d_pre2 = nullptr; uint32_t *d_lead = nullptr, *d_idx2 = nullptr, *d_pos2 = nullptr;      // n entries each, in d
+  explicit AdmitCopies(act_ctx* c_) : c(c_), d(c_) {}
+  // span: the survivors' bytes in the caller's kind of memory (offsets in the same kind); h_idx: host-memory callers only
+  int run(hipStream_t stream, bool dev, size_t n, size_t m, const CopySpan& span, const uint8_t* d_pre, const uint32_t* d_idx, const uint32_t* h_idx,
+          const uint32_t salt[4]);
+};
+
 }  // namespace
 
 static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int mem, const uint8_t* keys, int nkeys, const uint32_t* key_epochs, int sign_key,
                              const uint8_t* proof, const uint8_t* cbor, const uint64_t* offsets, const uint8_t* charge, const uint8_t* rng, int rng_mode,
-                             uint8_t* out, uint8_t* status, uint8_t* out_key, uint64_t* out_counts) {
+                             uint8_t* out, uint8_t* status, uint8_t* out_key, uint64_t* out_counts, bool unique = false) {
   const bool wire = cbor != nullptr, dev = mem == ACT_MEM_DEVICE;
-  if (out_counts) memset(out_counts, 0, sizeof(uint64_t) * ACT_ADMIT_COUNTS);
+  if (out_counts) memset(out_counts, 0, sizeof(uint64_t) * (unique ? ACT_ADMIT_UNIQUE_COUNTS : ACT_ADMIT_COUNTS));
   if (!c || (mem != ACT_MEM_HOST && mem != ACT_MEM_DEVICE) || n > ((size_t)1 << 30)) return ACT_ERR_ARG;
   if (n && ((!proof && !cbor) || !out || !status || !out_key)) return ACT_ERR_ARG;
   if (wire && offsets) for (size_t i = 0; i < n; i++) if (offsets[i + 1] < offsets[i]) return ACT_ERR_ARG;
@@ -229,19 +242,37 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
   const size_t m = m32;
   if (m > n) { c->err = "admission: the compaction counted more survivors than lanes"; return ACT_ERR_HIP; }
 
+  // ---- step 3a (the unique forms): a survivor with the bytes of an earlier survivor is a copy and is not verified -----------------------
+  // mv lanes are verified: v_idx / v_pos / v_pre are the screen's arrays, or the copy stage's when it found copies
+  AdmitCopies cp(c);
+  std::vector<uint32_t> h_idx, h_lead;
+  const uint8_t* v_pre = d_pre; const uint32_t *v_idx = d_idx, *v_pos = d_pos; size_t mv = m;
+  if (unique && m >= 2) {
+    if (!dev) { h_idx.resize(m); ADCK(c, hipMemcpy(h_idx.data(), d_idx, m * 4, hipMemcpyDeviceToHost)); }
+    CopySpan span{wire ? cbor : proof, nullptr, wire ? ml : pb};
+    if (wire && offsets) span.offsets = dev ? reinterpret_cast<const uint64_t*>(d.p + o_off) : offsets;
+    uint32_t salt[4];
+    { std::lock_guard<std::mutex> lk(set->mu); memcpy(salt, set->salt, 16); }
+    if ((rc = cp.run(stream, dev, n, m, span, d_pre, d_idx, h_idx.data(), salt))) return rc;
+    if (cp.copies) {
+      v_pre = cp.d_pre2; v_idx = cp.d_idx2; v_pos = cp.d_pos2; mv = cp.m2;
+      if (!dev) { h_lead.resize(n); ADCK(c, hipMemcpy(h_lead.data(), cp.d_lead, n * 4, hipMemcpyDeviceToHost)); }
+    }
+  }
+
   // ---- nothing shed: the honest batch pays the screen and nothing else ------------------------------------------------------------------
-  if (m == n) {
+  if (mv == n) {
     rc = redeem_keyring_impl(c, set, n, mem, keys, nkeys, key_epochs, sign_key, proof, cbor, offsets, rng, rng_mode, out, status, out_key);
     if (out_counts && (rc == ACT_OK || rc == ACT_ERR_ARG)) {      // (ACT_ERR_ARG: the nullifier step refused lanes; status[] is complete)
       std::vector<uint8_t> hs;
       const uint8_t* s = status;
       if (dev) { hs.resize(n); if (hipMemcpy(hs.data(), status, n, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return rc; } s = hs.data(); }
-      admit_counts_of(out_counts, n, h_pre.data(), n, s);
+      admit_counts_of(out_counts, n, h_pre.data(), n, s);      // (copies: 0)
     }
     return rc;
   }
   // ---- everything shed: no verification, nothing recorded, no rng drawn -----------------------------------------------------------------
-  if (m == 0) {
+  if (mv == 0) {
     if ((rc = redeem_keyring_impl(c, set, 0, mem, keys, nkeys, key_epochs, sign_key, nullptr, nullptr, nullptr, rng, rng_mode, nullptr, nullptr, nullptr))) return rc;      // a bad ring fails the call whatever is shed
     if (dev) {
       ADCK(c, hipMemcpyAsync(status, d_pre, n, hipMemcpyDeviceToDevice, stream));
@@ -254,24 +285,25 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
   }
 
   // ---- step 3: the survivors, a window at a time -------------------------------------------------------------------------------------------
-  std::vector<uint32_t> h_idx(m), h_pos;
-  ADCK(c, hipMemcpy(h_idx.data(), d_idx, m * 4, hipMemcpyDeviceToHost));
-  if (!dev) { h_pos.resize(n); ADCK(c, hipMemcpy(h_pos.data(), d_pos, n * 4, hipMemcpyDeviceToHost)); }
+  std::vector<uint32_t> h_pos;
+  h_idx.resize(mv);
+  ADCK(c, hipMemcpy(h_idx.data(), v_idx, mv * 4, hipMemcpyDeviceToHost));
+  if (!dev) { h_pos.resize(n); ADCK(c, hipMemcpy(h_pos.data(), v_pos, n * 4, hipMemcpyDeviceToHost)); }
   // compact arrays in the caller's kind of memory: K' | nullifiers | verdicts | look-up answers | key indices | matched keys | statuses
   AdmitArr arr(c), cout(c);
-  if ((rc = arr.alloc(mem, m * 69))) { c->err = "admission: compact arrays"; return rc; }
-  if ((rc = cout.alloc(mem, m * out_b))) { c->err = "admission: compact output"; return rc; }
-  uint8_t *kp = arr.p, *knul = kp + m * 32, *st = knul + m * 32, *sp = st + m, *kidx = sp + m, *okey = kidx + m, *cst = okey + m;
+  if ((rc = arr.alloc(mem, mv * 69))) { c->err = "admission: compact arrays"; return rc; }
+  if ((rc = cout.alloc(mem, mv * out_b))) { c->err = "admission: compact output"; return rc; }
+  uint8_t *kp = arr.p, *knul = kp + mv * 32, *st = knul + mv * 32, *sp = st + mv, *kidx = sp + mv, *okey = kidx + mv, *cst = okey + mv;
   // a survivor's status that the tail leaves unwritten (it returns early only on a device failure BEHIND check-and-insert) must never
   // read as accepted: recorded, not signed
-  if (dev) { ADCK(c, hipMemset(cst, ACT_STATUS_RECORDED_UNSIGNED, m)); ADCK(c, hipDeviceSynchronize()); } else memset(cst, ACT_STATUS_RECORDED_UNSIGNED, m);
+  if (dev) { ADCK(c, hipMemset(cst, ACT_STATUS_RECORDED_UNSIGNED, mv)); ADCK(c, hipDeviceSynchronize()); } else memset(cst, ACT_STATUS_RECORDED_UNSIGNED, mv);
   {      // the reduced nullifiers of the survivors, as the screen left them
     DevTmp g(c); uint8_t* dst = knul;
-    if (!dev) { if ((rc = g.alloc(m * 32))) return rc; dst = g.p; }
-    AdmitRowsArgs ra{dst, d_kred, d_idx, (uint32_t)m, 32};
+    if (!dev) { if ((rc = g.alloc(mv * 32))) return rc; dst = g.p; }
+    AdmitRowsArgs ra{dst, d_kred, v_idx, (uint32_t)mv, 32};
     launch_admit_rows(ra, stream);
     ADCK(c, hipGetLastError());
-    if (!dev) ADCK(c, hipMemcpyAsync(knul, g.p, m * 32, hipMemcpyDeviceToHost, stream));
+    if (!dev) ADCK(c, hipMemcpyAsync(knul, g.p, mv * 32, hipMemcpyDeviceToHost, stream));
     ADCK(c, hipStreamSynchronize(stream));
   }
   // the per-lane rng slices follow their lanes (secret: staged in the context's own buffer or a host vector, wiped on every exit)
@@ -279,43 +311,43 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
   const uint8_t* c_rng = rng;
   if (rng_mode == ACT_RNG_PER_LANE) {
     if (dev) {
-      if ((rc = rng_dev.reserve(m * 128))) return rc;
-      AdmitRowsArgs ra{c->d_admit_rng, rng, d_idx, (uint32_t)m, 128};
+      if ((rc = rng_dev.reserve(mv * 128))) return rc;
+      AdmitRowsArgs ra{c->d_admit_rng, rng, v_idx, (uint32_t)mv, 128};
       launch_admit_rows(ra, stream);
       ADCK(c, hipGetLastError());
       ADCK(c, hipStreamSynchronize(stream));
       c_rng = c->d_admit_rng;
     } else {
-      rng_host.resize(m * 128);
-      for (size_t j = 0; j < m; j++) memcpy(rng_host.data() + j * 128, rng + (size_t)h_idx[j] * 128, 128);
+      rng_host.resize(mv * 128);
+      for (size_t j = 0; j < mv; j++) memcpy(rng_host.data() + j * 128, rng + (size_t)h_idx[j] * 128, 128);
       c_rng = rng_host.data();
     }
   }
   const size_t W = std::max<size_t>(1, ADMIT_WINDOW_BATCHES * c->max_batch);
-  DevTmp gd(c); std::vector<uint8_t> gh; size_t g_cap = 0;
+  DevTmp gd(c); std::unique_ptr<uint8_t[]> gh; size_t g_cap = 0;      // (host: not zero-filled -- the gather below writes every byte that is read)
   auto g_reserve = [&](size_t bytes) -> int {      // the gather buffer, in the caller's kind of memory
     if (bytes <= g_cap) return ACT_OK;
     if (dev) { if (gd.p) { std::lock_guard<std::mutex> lk(c->mu); ADCK(c, hipFree(gd.p)); gd.p = nullptr; gd.bytes = 0; } int r = gd.alloc(bytes); if (r) return r; }
-    else gh.resize(bytes);
+    else gh.reset(new uint8_t[bytes ? bytes : 1]);
     g_cap = bytes;
     return ACT_OK;
   };
   DevTmp d_moff(c);      // wire, device memory: a window's source starts and destination offsets
-  if (wire && dev && offsets && (rc = d_moff.alloc((2 * std::min(W, m) + 1) * 8))) return rc;
+  if (wire && dev && offsets && (rc = d_moff.alloc((2 * std::min(W, mv) + 1) * 8))) return rc;
   std::vector<uint64_t> dst_off, src_beg;
-  for (size_t w0 = 0; w0 < m; w0 += W) {
-    const size_t w = std::min(W, m - w0);
+  for (size_t w0 = 0; w0 < mv; w0 += W) {
+    const size_t w = std::min(W, mv - w0);
     const size_t row = wire ? ml : pb;
     if (!wire || !offsets) {      // rows of one size
       if ((rc = g_reserve(w * row))) return rc;
       const uint8_t* src = wire ? cbor : proof;
       if (dev) {
-        AdmitRowsArgs ra{gd.p, src, d_idx + w0, (uint32_t)w, row};
+        AdmitRowsArgs ra{gd.p, src, v_idx + w0, (uint32_t)w, row};
         launch_admit_rows(ra, stream);
         ADCK(c, hipGetLastError());
         ADCK(c, hipStreamSynchronize(stream));
       } else {
-        AdmitRowsJob job{gh.data(), src, h_idx.data() + w0, row};
+        AdmitRowsJob job{gh.get(), src, h_idx.data() + w0, row};
         act_host_parallel_for(w, 16, 0, [](void* p, size_t i0, size_t i1) {
           const AdmitRowsJob& j = *static_cast<const AdmitRowsJob*>(p);
           for (size_t k = i0; k < i1; k++) memcpy(j.dst + k * j.row, j.src + (size_t)j.idx[k] * j.row, j.row);
@@ -330,7 +362,7 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
       }
       if ((rc = g_reserve((size_t)dst_off[w]))) return rc;
       if (dev) {
-        uint64_t* d_src = reinterpret_cast<uint64_t*>(d_moff.p); uint64_t* d_dst = d_src + std::min(W, m);
+        uint64_t* d_src = reinterpret_cast<uint64_t*>(d_moff.p); uint64_t* d_dst = d_src + std::min(W, mv);
         ADCK(c, hipMemcpyAsync(d_src, src_beg.data(), w * 8, hipMemcpyHostToDevice, stream));
         ADCK(c, hipMemcpyAsync(d_dst, dst_off.data(), (w + 1) * 8, hipMemcpyHostToDevice, stream));
         AdmitMsgsArgs ma{gd.p, d_dst, cbor, d_src, (uint32_t)w, admit_pieces(longest)};
@@ -338,30 +370,31 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
         ADCK(c, hipGetLastError());
         ADCK(c, hipStreamSynchronize(stream));
       } else {
-        AdmitMsgsJob job{gh.data(), dst_off.data(), cbor, src_beg.data()};
+        AdmitMsgsJob job{gh.get(), dst_off.data(), cbor, src_beg.data()};
         act_host_parallel_for(w, 16, 0, [](void* p, size_t i0, size_t i1) {
           const AdmitMsgsJob& j = *static_cast<const AdmitMsgsJob*>(p);
           for (size_t k = i0; k < i1; k++) memcpy(j.dst + j.dst_off[k], j.src + j.src_beg[k], (size_t)(j.dst_off[k + 1] - j.dst_off[k]));
         }, &job);
       }
     }
-    const uint8_t* g = dev ? gd.p : gh.data();
+    const uint8_t* g = dev ? gd.p : gh.get();
     if (wire) { RingSel sel{keys, nkeys, okey + w0}; rc = verify_spend_cbor_impl(c, w, mem, nullptr, g, offsets ? dst_off.data() : nullptr, st + w0, kp + w0 * 32, nullptr, &sel); }
     else rc = act_verify_spend_keyring_batch(c, w, mem, keys, nkeys, g, st + w0, okey + w0, kp + w0 * 32);
     if (rc) return rc;            // as in the redeem calls: nothing recorded, status untouched
   }
 
   // ---- step 4: once per call, over the compact arrays ---------------------------------------------------------------------------------------
-  const int rc_tail = redeem_keyring_tail(c, set, m, mem, keys, nkeys, key_epochs, sign_key, wire, knul, 32, kp, st, sp, kidx, c_rng, rng_mode, cout.p, cst, okey);
+  const int rc_tail = redeem_keyring_tail(c, set, mv, mem, keys, nkeys, key_epochs, sign_key, wire, knul, 32, kp, st, sp, kidx, c_rng, rng_mode, cout.p, cst, okey);
 
   // ---- step 5: the answers back to their lanes (also behind a failure of step 4: status[] is complete on return) ----------------------------
   std::vector<uint8_t> h_cst;
   if (dev) {
-    AdmitScatterArgs sc{}; sc.n = (uint32_t)n; sc.out_bytes = out_b; sc.pos = d_pos; sc.pre = d_pre; sc.c_status = cst; sc.c_key = okey; sc.c_out = cout.p;
+    AdmitScatterArgs sc{}; sc.n = (uint32_t)n; sc.out_bytes = out_b; sc.pos = v_pos; sc.pre = v_pre; sc.c_status = cst; sc.c_key = okey; sc.c_out = cout.p;
     sc.status = status; sc.out_key = out_key; sc.out = out;
     launch_admit_scatter(sc, stream);
+    if (cp.copies) { CopyResolveArgs ra{cp.d_lead, (uint32_t)n, status, out_key}; launch_copy_resolve(ra, stream); }      // COPY_MARK leaves status[] here
     ADCK(c, hipGetLastError());
-    if (out_counts) { h_cst.resize(m); ADCK(c, hipMemcpyAsync(h_cst.data(), cst, m, hipMemcpyDeviceToHost, stream)); }
+    if (out_counts) { h_cst.resize(mv); ADCK(c, hipMemcpyAsync(h_cst.data(), cst, mv, hipMemcpyDeviceToHost, stream)); }
     ADCK(c, hipStreamSynchronize(stream));
   } else {
     for (size_t i = 0; i < n; i++) {
@@ -369,8 +402,10 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
       if (j == ADMIT_SHED) { status[i] = h_pre[i]; out_key[i] = ACT_KEY_NONE; memset(out + i * out_b, 0, out_b); }
       else { status[i] = cst[j]; out_key[i] = okey[j]; memcpy(out + i * out_b, cout.p + (size_t)j * out_b, out_b); }
     }
+    if (cp.copies) { CopyResolveArgs ra{h_lead.data(), (uint32_t)n, status, out_key}; for (size_t i = 0; i < n; i++) copy_resolve_lane(ra, (uint32_t)i); }
   }
-  admit_counts_of(out_counts, n, h_pre.data(), m, dev ? h_cst.data() : cst);
+  admit_counts_of(out_counts, n, h_pre.data(), mv, dev ? h_cst.data() : cst);
+  if (out_counts && unique) out_counts[ACT_ADMIT_COUNTS] = cp.copies;
   return rc_tail;
 }
 
@@ -387,4 +422,19 @@ extern "C" int act_redeem_cbor_admit_batch(act_ctx* c, act_nullifier_set* set, s
   static const uint8_t none = 0;
   return redeem_admit_impl(c, set, n, mem, keys, nkeys, key_epochs, sign_key, nullptr, cbor ? cbor : &none, offsets, charge, rng, rng_mode, out_refund_cbor, status,
                            out_key, out_counts);
+}
+extern "C" int act_redeem_admit_unique_batch(act_ctx* c, act_nullifier_set* set, size_t n, int mem, const uint8_t* keys, int nkeys, const uint32_t* key_epochs,
+                                             int sign_key, const uint8_t* proof, const uint8_t* charge, const uint8_t* rng, int rng_mode, uint8_t* out_refund,
+                                             uint8_t* status, uint8_t* out_key, uint64_t* out_counts) {
+  if (n && !proof) return ACT_ERR_ARG;
+  return redeem_admit_impl(c, set, n, mem, keys, nkeys, key_epochs, sign_key, proof, nullptr, nullptr, charge, rng, rng_mode, out_refund, status, out_key, out_counts,
+                           true);
+}
+extern "C" int act_redeem_cbor_admit_unique_batch(act_ctx* c, act_nullifier_set* set, size_t n, int mem, const uint8_t* keys, int nkeys, const uint32_t* key_epochs,
+                                                  int sign_key, const uint8_t* cbor, const uint64_t* offsets, const uint8_t* charge, const uint8_t* rng, int rng_mode,
+                                                  uint8_t* out_refund_cbor, uint8_t* status, uint8_t* out_key, uint64_t* out_counts) {
+  if (n && !cbor) return ACT_ERR_ARG;
+  static const uint8_t none = 0;
+  return redeem_admit_impl(c, set, n, mem, keys, nkeys, key_epochs, sign_key, nullptr, cbor ? cbor : &none, offsets, charge, rng, rng_mode, out_refund_cbor, status,
+                           out_key, out_counts, true);
 }

@@ -1290,3 +1290,4 @@ int act_refund_batch(act_ctx* c, size_t n, int mem, const uint8_t sk[64], const 
 #include "nullifier_impl.inc"
 #include "keyring_redeem_impl.inc"
 #include "admit_impl.inc"          // admission before verification: act_redeem_admit_batch, act_redeem_cbor_admit_batch
+#include "copies_impl.inc"         // its copy stage: act_redeem_admit_unique_batch, act_redeem_cbor_admit_unique_batch

@@ -687,6 +687,40 @@ int act_redeem_cbor_admit_batch(act_ctx *ctx, act_nullifier_set *set, size_t n, 
                                 const uint8_t *charge /* nullable */, const uint8_t *rng, int rng_mode, uint8_t *out_refund_cbor,
                                 uint8_t *status, uint8_t *out_key, uint64_t *out_counts /* nullable, host */);
 
+/* ======== admission, unique forms: byte-identical proofs of one batch are verified once ========
+ * The two calls above verify every lane that shares a FRESH nullifier, because any of them may be the first valid one.  Lanes with
+ * IDENTICAL input bytes have the same verdict and the same matched key by definition, so one verification answers all of them.  These
+ * two calls run the admission loop above with one more step between step 3 and step 4:
+ *       3a. lane i has passed steps 1-3, and an earlier lane j < i that has also passed them has the same input bytes -> lane i is a
+ *           COPY and is not verified.  Its leader is the smallest such j; a leader is never itself a copy.
+ *           Records form: the input bytes are the whole act_spend_proof_bytes record.  Wire form: the message's bytes
+ *           [offsets[i], offsets[i + 1]), the same length and the same content -- two different spellings of one proof, or one message
+ *           with and without a trailing byte, are NOT copies of each other (both are verified, as above).
+ * After the call's single check-and-insert and signing pass a copy is answered from its leader's FINAL status:
+ *       leader 255 / 6 / 7, ACT_STATUS_DOUBLE_SPEND, ACT_STATUS_NULLIFIER_UNDETERMINED   -> the same status
+ *       leader 0 or ACT_STATUS_RECORDED_UNSIGNED (its nullifier is recorded)           -> ACT_STATUS_DOUBLE_SPEND
+ * and in every case out_key[i] = out_key[j] (a verified lane that is then a double spend keeps the index it matched), an all-zero
+ * output record, and no rng slice: copies never sign, so ACT_RNG_SEQUENTIAL slices and the one ACT_RNG_CALLBACK draw are unchanged.
+ * What stays the same: every status, every out_key, every output byte, the nullifiers recorded with their epochs and what is drawn
+ * from the generator (all three conventions) are byte for byte those of act_redeem_(cbor_)admit_batch on the same batch and an
+ * identical set.  (Not promised where lanes end ACT_STATUS_NULLIFIER_UNDETERMINED: a set too small for the batch.)
+ * What differs: only out_counts.  ACT_ADMIT_UNIQUE_COUNTS values: the eight above, then copies.  verified = lanes - wire_rejected -
+ * wrong_charge - spent_before - copies; rejected_by_verification, double_spend_after and accepted count VERIFIED lanes only (their
+ * sum is verified when nothing is undetermined or unsigned).
+ * Equality is decided on the bytes themselves: a 64-bit fingerprint keyed with the set's salt only finds candidates, and a collision
+ * costs a verification and never changes an answer.  Whole-call refusals, failure semantics and the hygiene contract are those of the
+ * two calls above; nothing secret is staged (proofs, fingerprints and lane numbers are public).  A batch without copies in which
+ * nothing is shed still goes straight to the redeem call; a batch in which nothing survives still launches no verification kernel. */
+#define ACT_ADMIT_UNIQUE_COUNTS 9
+int act_redeem_admit_unique_batch(act_ctx *ctx, act_nullifier_set *set, size_t n, int mem, const uint8_t *keys, int nkeys,
+                                  const uint32_t *key_epochs /* nullable */, int sign_key, const uint8_t *proof, const uint8_t *charge /* nullable */,
+                                  const uint8_t *rng, int rng_mode, uint8_t *out_refund, uint8_t *status, uint8_t *out_key,
+                                  uint64_t *out_counts /* nullable, host */);
+int act_redeem_cbor_admit_unique_batch(act_ctx *ctx, act_nullifier_set *set, size_t n, int mem, const uint8_t *keys, int nkeys,
+                                       const uint32_t *key_epochs /* nullable */, int sign_key, const uint8_t *cbor, const uint64_t *offsets,
+                                       const uint8_t *charge /* nullable */, const uint8_t *rng, int rng_mode, uint8_t *out_refund_cbor,
+                                       uint8_t *status, uint8_t *out_key, uint64_t *out_counts /* nullable, host */);
+
 /* ======== row d and test infrastructure: debug hooks, measurement knobs, kernel timing, roofline probes (nothing here is on the product's path) ==== */
 /* Debug / test hook: the exact "spend" transcript pre-images of the last act_verify_spend_batch /
  * act_refund_batch chunk (n_last * act_spend_transcript_bytes, copied to host memory). */
@@ -702,6 +736,10 @@ int act_debug_set_slowdown(act_ctx *ctx, uint32_t ns_per_lane);
 /* Debug / test hook: the signature step of the next `count` act_redeem_batch / act_redeem_cbor_batch calls on this context fails after
  * the nullifiers have been recorded (the failure ACT_STATUS_RECORDED_UNSIGNED exists for; no input can provoke it). */
 int act_debug_fail_next_signs(act_ctx *ctx, int count);
+/* Debug / test hook: the leader table of the unique admission forms alone, on the device, over m fingerprints the caller makes up
+ * (HOST memory, none of them 0): out_leader[j] = the smallest index that carries fp[j].  out_ms (nullable): the time of the table's
+ * two launches -- every lane on one slot is the contention case. */
+int act_debug_copy_leaders(act_ctx *ctx, size_t m, const uint64_t *fp, uint32_t *out_leader, double *out_ms);
 /* Debug / test hook: out[i] = enc(scalars[i] * points[i]) (`RistrettoPoint * Scalar`, e.g. src/lib.rs:791) computed by the
  * engine's production variable-base chain, decode and encode; status[i] = 255 and a zero record when points[i] is not a
  * canonical encoding.  Exists so that third-party known answers can be replayed on the device one operation at a time

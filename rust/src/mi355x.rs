@@ -125,6 +125,12 @@ extern "C" {
     fn act_redeem_cbor_admit_batch(ctx: *mut ActCtx, set: *mut ActNullifierSet, n: usize, mem: c_int, keys: *const u8, nkeys: c_int, key_epochs: *const u32,
                                    sign_key: c_int, cbor: *const u8, offsets: *const u64, charge: *const u8, rng: *const u8, rng_mode: c_int,
                                    out_refund_cbor: *mut u8, status: *mut u8, out_key: *mut u8, out_counts: *mut u64) -> c_int;
+    fn act_redeem_admit_unique_batch(ctx: *mut ActCtx, set: *mut ActNullifierSet, n: usize, mem: c_int, keys: *const u8, nkeys: c_int, key_epochs: *const u32,
+                                     sign_key: c_int, proof: *const u8, charge: *const u8, rng: *const u8, rng_mode: c_int, out_refund: *mut u8, status: *mut u8,
+                                     out_key: *mut u8, out_counts: *mut u64) -> c_int;
+    fn act_redeem_cbor_admit_unique_batch(ctx: *mut ActCtx, set: *mut ActNullifierSet, n: usize, mem: c_int, keys: *const u8, nkeys: c_int, key_epochs: *const u32,
+                                          sign_key: c_int, cbor: *const u8, offsets: *const u64, charge: *const u8, rng: *const u8, rng_mode: c_int,
+                                          out_refund_cbor: *mut u8, status: *mut u8, out_key: *mut u8, out_counts: *mut u64) -> c_int;
     fn act_node_device_stats(node: *mut ActNode, k: c_int, weight: *mut f64, last_lanes: *mut u64, last_seconds: *mut f64, last_calls: *mut u64) -> c_int;
 }
 
@@ -1056,6 +1062,7 @@ impl<'a> Keyring<'a> {
 /// `ACT_STATUS_WRONG_CHARGE`: the admission calls only -- `s` is not the expected charge; not verified, not recorded, not signed.
 pub const ACT_STATUS_WRONG_CHARGE: u8 = 250;
 pub const ACT_ADMIT_COUNTS: usize = 8;
+pub const ACT_ADMIT_UNIQUE_COUNTS: usize = 9;
 /// statuses, outputs (128-byte Refund records or `REFUND_CBOR_BYTES` messages, all zero where not signed), matched ring keys, and
 /// lanes / wire_rejected / wrong_charge / spent_before / verified / rejected_by_verification / double_spend_after / accepted
 pub struct Admitted {
@@ -1064,6 +1071,9 @@ pub struct Admitted {
     pub out: Vec<u8>,
     pub out_key: Vec<u8>,
     pub counts: [u64; ACT_ADMIT_COUNTS],
+    /// the unique forms only: lanes with the bytes of an earlier lane of the batch, answered from that lane without being verified
+    /// (`counts[4]`, verified, is smaller by exactly this)
+    pub copies: u64,
 }
 /// Admission before verification on ONE GPU (include/act_mi355x.h "admission before verification"): the ring redeem calls with a screen
 /// in front -- a proof whose charge `s` is not the expected one is answered `ACT_STATUS_WRONG_CHARGE` and a proof whose nullifier the
@@ -1072,12 +1082,19 @@ pub struct Admitted {
 pub struct GpuAdmission {
     ctx: *mut ActCtx,
     set: *mut ActNullifierSet,
+    unique: bool,
 }
 impl GpuAdmission {
     /// # Safety
     /// `ctx` and `set` are live handles on one device (`act_ctx_create` / `act_node_ctx`, `act_nullifier_set_create`) and outlive `self`.
     pub unsafe fn from_raw(ctx: *mut ActCtx, set: *mut ActNullifierSet) -> Self {
-        GpuAdmission { ctx, set }
+        GpuAdmission { ctx, set, unique: false }
+    }
+    /// `true`: the calls go to `act_redeem_admit_unique_batch` / `act_redeem_cbor_admit_unique_batch` -- byte-identical proofs of one
+    /// batch are verified once.  Statuses, `out_key`, output bytes, what is recorded and what is drawn stay the same; `copies` is filled.
+    pub fn unique(mut self, on: bool) -> Self {
+        self.unique = on;
+        self
     }
     /// `keys`: nkeys records of 64 bytes; `proofs`: n records of `PROOF_BYTES`; `charges`: n scalars of 32 bytes, or None.
     pub fn redeem_admit_batch(&self, keys: &[u8], key_epochs: Option<&[u32]>, sign_with: Option<usize>, proofs: &[u8], charges: Option<&[u8]>,
@@ -1085,13 +1102,16 @@ impl GpuAdmission {
         let (n, nkeys) = (proofs.len() / PROOF_BYTES, keys.len() / 64);
         assert!(proofs.len() == n * PROOF_BYTES && charges.map_or(true, |c| c.len() == 32 * n) && key_epochs.map_or(true, |e| e.len() == nkeys));
         let src = rng_source(&mut rng);
-        let mut r = Admitted { rc: 0, status: vec![0u8; n + 1], out: vec![0u8; 128 * n + 1], out_key: vec![ACT_KEY_NONE; n + 1], counts: [0; ACT_ADMIT_COUNTS] };
+        let mut r = Admitted { rc: 0, status: vec![0u8; n + 1], out: vec![0u8; 128 * n + 1], out_key: vec![ACT_KEY_NONE; n + 1], counts: [0; ACT_ADMIT_COUNTS], copies: 0 };
+        let mut counts = [0u64; ACT_ADMIT_UNIQUE_COUNTS];
+        let call = if self.unique { act_redeem_admit_unique_batch } else { act_redeem_admit_batch };
         r.rc = unsafe {
-            act_redeem_admit_batch(self.ctx, self.set, n, 0, keys.as_ptr(), nkeys as c_int, key_epochs.map_or(std::ptr::null(), |e| e.as_ptr()),
+            call(self.ctx, self.set, n, 0, keys.as_ptr(), nkeys as c_int, key_epochs.map_or(std::ptr::null(), |e| e.as_ptr()),
                                    sign_with.map_or(ACT_SIGN_MATCHED, |i| i as c_int), proofs.as_ptr(), charges.map_or(std::ptr::null(), |c| c.as_ptr()),
                                    &src as *const ActRngSource as *const u8, ACT_RNG_CALLBACK, r.out.as_mut_ptr(), r.status.as_mut_ptr(), r.out_key.as_mut_ptr(),
-                                   r.counts.as_mut_ptr())
+                                   counts.as_mut_ptr())
         };
+        r.counts.copy_from_slice(&counts[..ACT_ADMIT_COUNTS]); r.copies = counts[ACT_ADMIT_COUNTS];
         r.status.truncate(n); r.out.truncate(128 * n); r.out_key.truncate(n);
         r
     }
@@ -1102,13 +1122,16 @@ impl GpuAdmission {
         let (n, nkeys) = (msgs.len(), keys.len() / 64);
         assert!(charges.map_or(true, |c| c.len() == 32 * n) && key_epochs.map_or(true, |e| e.len() == nkeys));
         let src = rng_source(&mut rng);
-        let mut r = Admitted { rc: 0, status: vec![0u8; n + 1], out: vec![0u8; REFUND_CBOR_BYTES * n + 1], out_key: vec![ACT_KEY_NONE; n + 1], counts: [0; ACT_ADMIT_COUNTS] };
+        let mut r = Admitted { rc: 0, status: vec![0u8; n + 1], out: vec![0u8; REFUND_CBOR_BYTES * n + 1], out_key: vec![ACT_KEY_NONE; n + 1], counts: [0; ACT_ADMIT_COUNTS], copies: 0 };
+        let mut counts = [0u64; ACT_ADMIT_UNIQUE_COUNTS];
+        let call = if self.unique { act_redeem_cbor_admit_unique_batch } else { act_redeem_cbor_admit_batch };
         r.rc = unsafe {
-            act_redeem_cbor_admit_batch(self.ctx, self.set, n, 0, keys.as_ptr(), nkeys as c_int, key_epochs.map_or(std::ptr::null(), |e| e.as_ptr()),
+            call(self.ctx, self.set, n, 0, keys.as_ptr(), nkeys as c_int, key_epochs.map_or(std::ptr::null(), |e| e.as_ptr()),
                                         sign_with.map_or(ACT_SIGN_MATCHED, |i| i as c_int), blob.as_ptr(), offsets.as_ptr(),
                                         charges.map_or(std::ptr::null(), |c| c.as_ptr()), &src as *const ActRngSource as *const u8, ACT_RNG_CALLBACK,
-                                        r.out.as_mut_ptr(), r.status.as_mut_ptr(), r.out_key.as_mut_ptr(), r.counts.as_mut_ptr())
+                                        r.out.as_mut_ptr(), r.status.as_mut_ptr(), r.out_key.as_mut_ptr(), counts.as_mut_ptr())
         };
+        r.counts.copy_from_slice(&counts[..ACT_ADMIT_COUNTS]); r.copies = counts[ACT_ADMIT_COUNTS];
         r.status.truncate(n); r.out.truncate(REFUND_CBOR_BYTES * n); r.out_key.truncate(n);
         r
     }
