@@ -14,6 +14,8 @@ LIB_PATH = os.environ.get("ACT_LIB_PATH") or os.path.join(_HERE, "libact_mi355x.
 MEM_HOST, MEM_DEVICE = 0, 1
 RNG_PER_LANE, RNG_SEQUENTIAL, RNG_CALLBACK = 0, 1, 2
 TRANSCRIPT_HOST, TRANSCRIPT_DEVICE = 0, 1
+WIRE_READER_HOST, WIRE_READER_DEVICE = 0, 1      # act_ctx_set_wire_reader: where a message that is not the canonical encoding is read
+WIRE_STATS = ("seen", "canonical", "read_on_device", "read_by_host")
 KEYRING_MAX, KEY_NONE, SIGN_MATCHED = 4, 255, -1      # act_*_keyring_batch: ring size, "no ring key matched", "sign with the matched key"
 STATUS_WRONG_CHARGE = 250                             # act_redeem_*admit_batch: s is not the expected charge
 ADMIT_COUNTS = ("lanes", "wire_rejected", "wrong_charge", "spent_before", "verified", "rejected_by_verification", "double_spend_after", "accepted")
@@ -27,7 +29,7 @@ EXPORTS = [
     "act_issue_batch", "act_issuance_to_credit_token_batch", "act_prove_spend_batch", "act_prove_spend_seeded_batch", "act_node_prove_spend_seeded_batch", "act_verify_spend_batch",
     "act_refund_batch", "act_refund_to_credit_token_batch", "act_debug_last_spend_transcripts", "act_debug_scalarmult_batch", "act_debug_secret_residue", "act_prof_enable",
     "act_prof_reset", "act_prof_kernel_count", "act_prof_kernel_name", "act_prof_get", "act_prof_get_busy", "act_ubench_mad_u64_u32", "act_ubench_random_read", "act_ubench_table_read",
-    "act_cbor_size", "act_cbor_record_bytes", "act_cbor_encode_batch", "act_cbor_decode_batch", "act_verify_spend_cbor_batch",
+    "act_cbor_size", "act_cbor_record_bytes", "act_cbor_encode_batch", "act_cbor_decode_batch", "act_cbor_read_batch", "act_ctx_set_wire_reader", "act_ctx_wire_stats", "act_node_set_wire_reader", "act_verify_spend_cbor_batch",
     "act_node_verify_spend_cbor_batch", "act_redeem_batch", "act_node_redeem_batch",
     "act_nullifier_set_create", "act_nullifier_set_destroy", "act_nullifier_set_len", "act_nullifier_set_last_error",
     "act_nullifier_check_and_insert_batch", "act_nullifier_set_reserve", "act_nullifier_set_export", "act_nullifier_contains_batch",
@@ -133,6 +135,10 @@ def load() -> C.CDLL:
         getattr(lib, f).restype = sz
     lib.act_cbor_encode_batch.argtypes = [vp, i32, sz, i32, u8p, u8p]
     lib.act_cbor_decode_batch.argtypes = [vp, i32, sz, i32, u8p, vp, u8p, u8p]
+    lib.act_cbor_read_batch.argtypes = [vp, i32, sz, i32, u8p, vp, u8p, u8p]
+    lib.act_ctx_set_wire_reader.argtypes = [vp, i32]
+    lib.act_ctx_wire_stats.argtypes = [vp, vp, i32]
+    lib.act_node_set_wire_reader.argtypes = [vp, i32]
     lib.act_verify_spend_cbor_batch.argtypes = [vp, sz, i32, u8p, u8p, vp, u8p, u8p]
     lib.act_node_verify_spend_cbor_batch.argtypes = [vp, sz, u8p, u8p, vp, u8p, u8p]
     lib.act_redeem_batch.argtypes = [vp, vp, sz, i32, u8p, u8p, u8p, i32, u8p, u8p]
@@ -577,6 +583,25 @@ class Engine:
         out = np.zeros(rb * n, np.uint8); st = np.zeros(n, np.uint8); p0, k0 = _in(blob)
         self._ck(self.lib.act_cbor_decode_batch(self.ctx, t, n, MEM_HOST, p0, offs.ctypes.data, out.ctypes.data, st.ctypes.data))
         return st.tobytes(), out.tobytes()
+
+    def cbor_read(self, type_name: str, messages: list):
+        """cbor_decode with every message read by the general reader on the GPU (act_cbor_read_batch): (status bytes, records bytes)."""
+        t = CBOR_TYPES[type_name]; rb = self.lib.act_cbor_record_bytes(self.ctx, t); n = len(messages)
+        offs = np.zeros(n + 1, np.uint64); offs[1:] = np.cumsum([len(m) for m in messages], dtype=np.uint64)
+        blob = b"".join(messages) + b"\0"
+        out = np.zeros(rb * n, np.uint8); st = np.zeros(n, np.uint8); p0, k0 = _in(blob)
+        self._ck(self.lib.act_cbor_read_batch(self.ctx, t, n, MEM_HOST, p0, offs.ctypes.data, out.ctypes.data, st.ctypes.data))
+        return st.tobytes(), out.tobytes()
+
+    def set_wire_reader(self, where: int):
+        """WIRE_READER_DEVICE (default) or WIRE_READER_HOST: where the spend wire calls and the admission screen read a message that
+        is not the canonical encoding"""
+        self._ck(self.lib.act_ctx_set_wire_reader(self.ctx, where))
+
+    def wire_stats(self, reset: bool = False) -> dict:
+        out = (C.c_uint64 * 4)()
+        self._ck(self.lib.act_ctx_wire_stats(self.ctx, C.cast(out, C.c_void_p), 1 if reset else 0))
+        return dict(zip(WIRE_STATS, (int(v) for v in out)))
 
     def redeem(self, nullifier_set, sk: bytes, proofs: bytes, rng: bytes, rng_mode: int = RNG_PER_LANE):
         """verify -> nullifier check-and-insert -> sign: statuses (3 = DoubleSpendError) and refunds."""

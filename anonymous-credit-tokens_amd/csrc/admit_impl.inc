@@ -2,8 +2,10 @@
 // k_admit.hip, lane bodies in admit_lanes.h).  act_redeem_admit_batch / act_redeem_cbor_admit_batch are the ring redeem calls with a
 // screen in front: per lane the charge is compared with the expected one and the nullifier is looked up (read only) BEFORE the proof
 // is verified, and only the lanes that pass go through verification -> check-and-insert -> sign.
-//   1. screen        k and s of every lane (records: fields 0 and 1; wire: the payloads of a canonical message, the host reader's
-//                    record of any other spelling, in windows of ADMIT_READ_WINDOW) -> pre-status, reduced k       [k_admit_screen]
+//   1. screen        k and s of every lane (records: fields 0 and 1; wire: the payloads of a canonical message, and of any other
+//                    spelling what the wire reader's reduced form gives -- cbor_lanes.h with keep_fields = 2, as a kernel for
+//                    device-memory callers and on the host workers for host-memory callers; under ACT_WIRE_READER_HOST the host
+//                    reader's record, in windows of ADMIT_READ_WINDOW) -> pre-status, reduced k                  [k_admit_screen]
 //   2. compaction    the survivors' lane numbers in lane order                                  [k_admit_count / _scan / _write]
 //   3. verification  of the survivors only, their records / messages gathered ADMIT_WINDOW_BATCHES * max_batch at a time
 //   4. once per call check-and-insert and signing over the compact 32-byte arrays (redeem_keyring_tail): one rng draw per call
@@ -52,6 +54,7 @@ struct AdmitArr {
 };
 
 struct AdmitWireJob { AdmitWireArgs a; };
+struct AdmitReadJob { CborReadArgs a; };
 struct AdmitRowsJob { uint8_t* dst; const uint8_t* src; const uint32_t* idx; size_t row; };
 struct AdmitMsgsJob { uint8_t* dst; const uint64_t* dst_off; const uint8_t* src; const uint64_t* src_beg; };
 
@@ -117,6 +120,8 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
   const size_t o_code = wire ? take(n) : 0, o_flags = (wire && dev) ? take(fcap) : 0, o_off = (wire && dev && offsets) ? take((n + 1) * 8) : 0;
   const size_t o_tmpl = (wire && dev) ? take(ml) : 0, o_pay = (wire && dev) ? take(nf * 4) : 0;
   const size_t o_pwhich = wire ? take(ADMIT_READ_WINDOW * 4) : 0, o_patch = wire ? take(ADMIT_READ_WINDOW * 64) : 0;
+  const bool dev_reader = wire && c->wire_reader.load() == ACT_WIRE_READER_DEVICE;
+  const size_t o_rcode = (dev_reader && dev) ? take(2 * n) : 0;      // the device reader's codes, then its infos
   DevTmp d(c);
   if ((rc = d.alloc(need))) return rc;
   ADCK(c, hipSetDevice(c->device));
@@ -147,6 +152,16 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
         a.tmpl = d.p + o_tmpl; a.pay_off = reinterpret_cast<const uint32_t*>(d.p + o_pay); a.ks = d_ks + off * 64; a.flags = d_flags + off;
         launch_admit_wire(a, stream);
       }
+      if (dev_reader) {      // every other spelling: the reader's reduced form over the flagged messages, k and s into d_ks, the codes for the screen
+        ADCK(c, hipMemsetAsync(d.p + o_rcode, 0, 2 * n, stream));
+        CborReadArgs ra{};
+        ra.T = *T; ra.L = c->L; ra.n = (uint32_t)n; ra.first = 0; ra.msg_len = (uint32_t)ml; ra.in = cbor; ra.offsets = offsets ? reinterpret_cast<const uint64_t*>(d.p + o_off) : nullptr;
+        ra.flags = d_flags; ra.rec = d_ks; ra.rec_stride = 64; ra.keep_fields = 2; ra.code = d.p + o_rcode; ra.info = d.p + o_rcode + n;
+        launch_cbor_read(ra, false, stream);
+        launch_cbor_read(ra, true, stream);
+        CborCodeArgs ca{(uint32_t)n, ra.code, ra.info, d.p + o_code};
+        launch_cbor_wire_code(ca, stream);
+      }
       ADCK(c, hipGetLastError());
       ADCK(c, hipMemcpyAsync(flags.data(), d_flags, fcap, hipMemcpyDeviceToHost, stream));
       ADCK(c, hipStreamSynchronize(stream));
@@ -163,14 +178,32 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
           a.flags[m] = canon ? 0 : 0x80;
         }
       }, &job);
+      h_code.assign(n, 0);
+      if (dev_reader) {      // the reader's lane body on the host workers, both passes of a message one behind the other
+        std::vector<uint8_t> rinfo(n, 0);
+        AdmitReadJob rj{};
+        rj.a.T = *T; rj.a.L = c->L; rj.a.n = (uint32_t)n; rj.a.first = 0; rj.a.msg_len = (uint32_t)ml; rj.a.in = cbor; rj.a.offsets = offsets;
+        rj.a.flags = flags.data(); rj.a.rec = h_ks.data(); rj.a.rec_stride = 64; rj.a.keep_fields = 2; rj.a.code = h_code.data(); rj.a.info = rinfo.data();
+        act_host_parallel_for(n, 64, 0, [](void* p, size_t i0, size_t i1) {
+          const CborReadArgs& a = static_cast<AdmitReadJob*>(p)->a;
+          uint32_t st[CBOR_MAX_DEPTH];
+          for (size_t m = i0; m < i1; m++) {
+            cbor_read_message_lane<false>(a, (uint32_t)m, st);
+            cbor_read_message_lane<true>(a, (uint32_t)m, st);
+            a.code[m] = cbor_code_status(a.code[m]);      // (an unflagged message keeps its 0)
+          }
+        }, &rj);
+      }
       ADCK(c, hipMemcpyAsync(d_ks, h_ks.data(), n * 64, hipMemcpyHostToDevice, stream));
       ADCK(c, hipStreamSynchronize(stream));
     }
     // every other spelling: the general reader, ADMIT_READ_WINDOW messages at a time.  A message that reads yields the record, and so
     // k and s; one that does not takes the code act_redeem_cbor_* gives it (the first error in wire order: cbor_settle_codes)
-    h_code.assign(n, 0);
+    if (h_code.size() != n) h_code.assign(n, 0);
     std::vector<size_t> which;
     for (size_t i = 0; i < n; i++) if (flags[i] & 0x80) which.push_back(i);
+    c->wire_stats[0] += n; c->wire_stats[1] += n - which.size(); c->wire_stats[dev_reader ? 2 : 3] += which.size();
+    if (dev_reader) which.clear();      // read already: the serial window loop below is the road of ACT_WIRE_READER_HOST
     std::vector<uint8_t> rec(pb), bytes, patch; std::vector<uint32_t> pwhich; std::vector<size_t> at;
     std::vector<int> codes; std::vector<CborCand> cands;
     for (size_t w0 = 0; w0 < which.size(); w0 += ADMIT_READ_WINDOW) {
@@ -218,7 +251,7 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
         ADCK(c, hipStreamSynchronize(stream));      // pwhich / patch are reused by the next window
       }
     }
-    ADCK(c, hipMemcpyAsync(d.p + o_code, h_code.data(), n, hipMemcpyHostToDevice, stream));
+    if (!(dev_reader && dev)) ADCK(c, hipMemcpyAsync(d.p + o_code, h_code.data(), n, hipMemcpyHostToDevice, stream));
     sa.ks = d_ks; sa.stride = 64; sa.wire_code = d.p + o_code;
   }
   if (charge) {

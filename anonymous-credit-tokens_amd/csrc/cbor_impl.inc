@@ -16,31 +16,9 @@
 // trailing bytes after the first item are not read.  Messages that are not byte-for-byte canonical take
 // the host reader below (cbor_read_message); canonical ones never leave the GPU.
 
+#include "cbor_reader.h"      // CborType, cbor_type(), CborReader, cbor_read_message: the host reader, shared with tests/hostcheck
+
 namespace {
-
-enum { CBOR_S = 0, CBOR_P = 1 };                 // field kinds
-enum { CBOR_OK = 0, CBOR_ERR_PARSE = 1, CBOR_ERR_STRUCTURE = 2, CBOR_ERR_VALUE = 3 };
-
-struct CborEntry { int key; int kind; int shape; };   // shape: 0 single, 1 array[L], 2 array[L] of pairs
-struct CborType { int n_entries; CborEntry e[17]; bool bare; };
-
-const CborType* cbor_type(int t) {
-  static const CborType T[10] = {
-    {0, {}, false},
-    /* 1 IssuanceRequest  */ {4, {{1, CBOR_P, 0}, {2, CBOR_S, 0}, {3, CBOR_S, 0}, {4, CBOR_S, 0}}, false},
-    /* 2 IssuanceResponse */ {5, {{1, CBOR_P, 0}, {2, CBOR_S, 0}, {3, CBOR_S, 0}, {4, CBOR_S, 0}, {5, CBOR_S, 0}}, false},
-    /* 3 SpendProof       */ {17, {{1, CBOR_S, 0}, {2, CBOR_S, 0}, {3, CBOR_P, 0}, {4, CBOR_P, 0}, {5, CBOR_P, 1}, {6, CBOR_S, 0}, {7, CBOR_S, 0},
-                                   {8, CBOR_S, 0}, {9, CBOR_S, 0}, {10, CBOR_S, 0}, {11, CBOR_S, 0}, {12, CBOR_S, 0}, {13, CBOR_S, 0}, {14, CBOR_S, 1},
-                                   {15, CBOR_S, 2}, {16, CBOR_S, 0}, {17, CBOR_S, 0}}, false},
-    /* 4 Refund           */ {4, {{1, CBOR_P, 0}, {2, CBOR_S, 0}, {3, CBOR_S, 0}, {4, CBOR_S, 0}}, false},
-    /* 5 PrivateKey       */ {2, {{1, CBOR_S, 0}, {2, CBOR_P, 0}}, false},
-    /* 6 PublicKey        */ {1, {{0, CBOR_P, 0}}, true},
-    /* 7 PreIssuance      */ {2, {{1, CBOR_S, 0}, {2, CBOR_S, 0}}, false},
-    /* 8 CreditToken      */ {5, {{1, CBOR_P, 0}, {2, CBOR_S, 0}, {3, CBOR_S, 0}, {4, CBOR_S, 0}, {5, CBOR_S, 0}}, false},
-    /* 9 PreRefund        */ {3, {{1, CBOR_S, 0}, {2, CBOR_S, 0}, {3, CBOR_S, 0}}, false},
-  };
-  return (t >= 1 && t <= 9) ? &T[t] : nullptr;
-}
 
 // canonical layout of one message type: template bytes + payload offset and kind of every record field
 struct CborLayout { std::vector<uint8_t> tmpl; std::vector<uint32_t> pay_off; std::vector<uint8_t> kind; std::vector<int> entry_first_field; };
@@ -63,177 +41,6 @@ CborLayout cbor_layout(const CborType& T, int L) {
     else { cbor_put_head(lay.tmpl, 4, (uint32_t)L); for (int j = 0; j < L; j++) { cbor_put_head(lay.tmpl, 4, 2); bstr32(T.e[i].kind); bstr32(T.e[i].kind); } }
   }
   return lay;
-}
-
-// ---- general RFC 8949 reader (host) ----------------------------------------------------------------------
-struct CborReader {
-  const uint8_t* p; size_t n, pos; int depth;
-  bool head(int& major, uint64_t& val, bool& indefinite) {
-    if (pos >= n) return false;
-    uint8_t b = p[pos++]; major = b >> 5; int ai = b & 31; indefinite = false;
-    if (ai < 24) { val = (uint64_t)ai; return true; }
-    if (ai == 31) { if (major == 0 || major == 1 || major == 6) return false; indefinite = true; val = 0; return true; }
-    if (ai > 27) return false;
-    int len = 1 << (ai - 24);
-    if (pos + (size_t)len > n) return false;
-    val = 0; for (int i = 0; i < len; i++) val = val << 8 | p[pos++];
-    return true;
-  }
-  bool is_break() const { return pos < n && p[pos] == 0xFF; }
-  // well-formed UTF-8 (RFC 3629: no overlongs, no surrogates, <= U+10FFFF): ciborium rejects text strings that are not
-  static bool utf8_ok(const uint8_t* s, size_t len) {
-    size_t i = 0;
-    while (i < len) {
-      const uint8_t b = s[i];
-      size_t need; uint32_t cp;
-      if (b < 0x80) { i++; continue; }
-      else if ((b & 0xE0) == 0xC0) { need = 1; cp = b & 0x1F; }
-      else if ((b & 0xF0) == 0xE0) { need = 2; cp = b & 0x0F; }
-      else if ((b & 0xF8) == 0xF0) { need = 3; cp = b & 0x07; }
-      else return false;
-      if (len - i <= need) return false;                        // truncated sequence
-      for (size_t k = 1; k <= need; k++) { const uint8_t c = s[i + k]; if ((c & 0xC0) != 0x80) return false; cp = (cp << 6) | (c & 0x3F); }
-      if ((need == 1 && cp < 0x80) || (need == 2 && cp < 0x800) || (need == 3 && cp < 0x10000) || cp > 0x10FFFF || (cp >= 0xD800 && cp <= 0xDFFF)) return false;
-      i += need + 1;
-    }
-    return true;
-  }
-  // reads a (possibly chunked) byte/text string into out (if non-null)
-  bool string_body(int major, uint64_t val, bool indefinite, std::vector<uint8_t>* out) {
-    if (!indefinite) {
-      if (val > n - pos) return false;
-      if (major == 3 && !utf8_ok(p + pos, (size_t)val)) return false;
-      if (out) out->insert(out->end(), p + pos, p + pos + val);
-      pos += (size_t)val; return true;
-    }
-    for (;;) {
-      if (pos >= n) return false;
-      if (is_break()) { pos++; return true; }
-      int m2; uint64_t v2; bool ind2;
-      if (!head(m2, v2, ind2) || m2 != major || ind2) return false;
-      if (v2 > n - pos) return false;
-      if (major == 3 && !utf8_ok(p + pos, (size_t)v2)) return false;      // every chunk of a text string is valid UTF-8 on its own
-      if (out) out->insert(out->end(), p + pos, p + pos + v2);
-      pos += (size_t)v2;
-    }
-  }
-  bool skip() {                                   // one complete data item
-    if (++depth > 256) return false;
-    int major; uint64_t val; bool ind;
-    if (!head(major, val, ind)) return false;
-    bool ok = true;
-    switch (major) {
-      case 0: case 1: break;
-      case 2: case 3: ok = string_body(major, val, ind, nullptr); break;
-      case 4: case 5: {
-        uint64_t items = major == 5 ? 2 : 1;
-        if (ind) { for (;;) { if (pos >= n) { ok = false; break; } if (is_break()) { pos++; break; } for (uint64_t k = 0; k < items && ok; k++) ok = skip(); if (!ok) break; } }
-        else { if (val > (n - pos)) { ok = false; break; } for (uint64_t i = 0; i < val * items && ok; i++) ok = skip(); }
-        break;
-      }
-      case 6: ok = skip(); break;
-      case 7: if (ind) ok = false; break;         // a stray break; floats / simple values carry no further bytes
-    }
-    depth--;
-    return ok;
-  }
-};
-
-// value at the reader = 32-byte byte string?  0 yes (copied to out), 2 structural mismatch, 1 malformed
-int cbor_read_bstr32(CborReader& r, uint8_t out[32]) {
-  size_t save = r.pos; int major; uint64_t val; bool ind;
-  if (!r.head(major, val, ind)) return CBOR_ERR_PARSE;
-  if (major != 2) { r.pos = save; return r.skip() ? CBOR_ERR_STRUCTURE : CBOR_ERR_PARSE; }
-  std::vector<uint8_t> b;
-  if (!r.string_body(2, val, ind, &b)) return CBOR_ERR_PARSE;
-  if (b.size() != 32) return CBOR_ERR_STRUCTURE;                               // "expected 32-byte array"
-  memcpy(out, b.data(), 32);
-  return CBOR_OK;
-}
-// array of `count` elements read by `elem`; ciborium parses the whole value before the codec looks at it, so a
-// malformed tail is a parse error even if the shape is already wrong
-template <class F>
-int cbor_read_array(CborReader& r, size_t count, bool* was_array, F&& elem) {
-  size_t save = r.pos; int major; uint64_t val; bool ind;
-  if (!r.head(major, val, ind)) return CBOR_ERR_PARSE;
-  if (major != 4) { r.pos = save; *was_array = false; return r.skip() ? CBOR_OK : CBOR_ERR_PARSE; }   // not an array: field silently absent
-  *was_array = true;
-  // every element is decoded, in order, BEFORE the length is looked at (src/cbor.rs:307-319: collect::<Result<Vec<_>, _>>()? and only
-  // then `len() == L`): `elem` also sees the indices >= count of an over-long array (it must not store those) until one fails
-  size_t got = 0; int first_err = CBOR_OK;
-  auto one = [&]() -> bool {
-    size_t s2 = r.pos;
-    if (first_err == CBOR_OK) { int e = elem(got); if (e == CBOR_ERR_PARSE) return false; if (e != CBOR_OK) first_err = e; }
-    else { r.pos = s2; if (!r.skip()) return false; }
-    got++; return true;
-  };
-  if (ind) { for (;;) { if (r.pos >= r.n) return CBOR_ERR_PARSE; if (r.is_break()) { r.pos++; break; } if (!one()) return CBOR_ERR_PARSE; } }
-  else { if (val > r.n - r.pos) return CBOR_ERR_PARSE; for (uint64_t i = 0; i < val; i++) if (!one()) return CBOR_ERR_PARSE; }
-  if (first_err != CBOR_OK) return first_err;
-  return got == count ? CBOR_OK : CBOR_ERR_STRUCTURE;                        // "... array wrong size"
-}
-
-// from_cbor returns the FIRST failure in wire order (src/cbor.rs:276-388: `?` inside `for (key, val) in map`), and a point is
-// validated where it is read (decode_point, :62-77).  The reader does not validate points (the GPU does), so it hands back what
-// the order depends on: `pts` = every point value read, in wire order, up to the reader's own return -- including values a later
-// duplicate key overwrites and the elements beyond L of an over-long array, which never reach the record -- and `irregular` = some
-// of them are not in the record.  The caller has the GPU validate `pts` when the reader stopped at a structural fault (an invalid
-// point in front of it is what the crate reports: InvalidValue) or when `irregular` (cbor_settle_codes below).
-struct CborCand { std::vector<uint8_t> pts; bool irregular = false; };
-
-// one message -> raw record (fields left unreduced / unvalidated: the GPU pass does that).  Mirrors from_cbor.
-int cbor_read_message(const CborType& T, int L, const uint8_t* msg, size_t len, uint8_t* rec, CborCand* cc = nullptr) {
-  CborReader r{msg, len, 0, 0};
-  if (T.bare) return cbor_read_bstr32(r, rec);                                  // PublicKey (src/cbor.rs:529-534)
-  // ciborium::from_reader parses the complete first item before the codec inspects it
-  { CborReader probe{msg, len, 0, 0}; if (!probe.skip()) return CBOR_ERR_PARSE; }
-  int major; uint64_t val; bool ind;
-  if (!r.head(major, val, ind)) return CBOR_ERR_PARSE;
-  if (major != 5) return CBOR_ERR_STRUCTURE;                                    // "expected CBOR map"
-  std::vector<int> first(T.n_entries); int nf = 0;
-  for (int i = 0; i < T.n_entries; i++) { first[i] = nf; nf += T.e[i].shape == 0 ? 1 : T.e[i].shape == 1 ? L : 2 * L; }
-  std::vector<uint8_t> present(T.n_entries, 0);
-  uint64_t remaining = val;
-  for (;;) {
-    if (ind) { if (r.is_break()) break; } else if (remaining-- == 0) break;
-    // key: only (unsigned) integers can match; everything else is skipped
-    size_t save = r.pos; int km; uint64_t kv; bool kind_;
-    if (!r.head(km, kv, kind_)) return CBOR_ERR_PARSE;
-    int ent = -1;
-    if (km == 0) { for (int i = 0; i < T.n_entries; i++) if ((uint64_t)T.e[i].key == kv) ent = i; }
-    else { r.pos = save; if (!r.skip()) return CBOR_ERR_PARSE; }
-    if (ent < 0) { if (!r.skip()) return CBOR_ERR_PARSE; continue; }
-    uint8_t* dst = rec + 32 * (size_t)first[ent];
-    int e;
-    const bool is_point = T.e[ent].kind == CBOR_P;
-    if (T.e[ent].shape == 0) {
-      e = cbor_read_bstr32(r, dst); if (e) return e;
-      if (is_point && cc) { cc->pts.insert(cc->pts.end(), dst, dst + 32); if (present[ent]) cc->irregular = true; }
-      present[ent] = 1;
-    } else {
-      bool was_array = true;
-      if (T.e[ent].shape == 1) e = cbor_read_array(r, (size_t)L, &was_array, [&](size_t j) {
-        uint8_t over[32];
-        uint8_t* d = j < (size_t)L ? dst + 32 * j : over;
-        const int be = cbor_read_bstr32(r, d);
-        if (be == CBOR_OK && is_point && cc) { cc->pts.insert(cc->pts.end(), d, d + 32); if (j >= (size_t)L || present[ent]) cc->irregular = true; }
-        return be;
-      });
-      else e = cbor_read_array(r, (size_t)L, &was_array, [&](size_t j) {
-        // z pair: an array of exactly two byte strings (src/cbor.rs:351-367; the pair's length is looked at before its elements)
-        bool pair_arr = true; uint8_t tmp[64], over[32];
-        int pe = cbor_read_array(r, 2, &pair_arr, [&](size_t k) { return cbor_read_bstr32(r, k < 2 ? tmp + 32 * k : over); });
-        if (!pair_arr) return (int)CBOR_ERR_STRUCTURE;                          // "expected array for z pair"
-        if (pe) return pe;                                                      // "z pair wrong size" / bad element
-        if (j < (size_t)L) memcpy(dst + 64 * j, tmp, 64);
-        return (int)CBOR_OK;
-      });
-      if (e) return e;
-      if (was_array) present[ent] = 1;
-    }
-  }
-  for (int i = 0; i < T.n_entries; i++) if (!present[i]) return CBOR_ERR_STRUCTURE;   // "missing field i"
-  return CBOR_OK;
 }
 
 // ---- GPU framing kernels: lane = (message, record field) -------------------------------------------------
@@ -560,6 +367,75 @@ int act_cbor_decode_batch(act_ctx* c, int type, size_t n, int mem, const uint8_t
   return call.finish();                                      // waits for both streams
 }
 
+// act_cbor_decode_batch's contract with every message going through the device reader: no canonical short cut, no host reader.
+// Per chunk, on the chunk's stream: the plain pass into the caller's records, the validating pass over the messages it names, then
+// per (message, field) the scalar reduction / point validation that k_cbor_unframe does, and zeros over what failed.  Nothing here
+// waits for the host, so the chunks of a host-memory caller alternate between the two slots like those of act_cbor_encode_batch.
+int act_cbor_read_batch(act_ctx* c, int type, size_t n, int mem, const uint8_t* cbor, const uint64_t* offsets, uint8_t* out_records,
+                        uint8_t* status) {
+  const CborType* T = cbor_type(type);
+  if (!c || !T || (n && (!cbor || !out_records || !status))) return ACT_ERR_ARG;
+  if (offsets) for (size_t i = 0; i < n; i++) if (offsets[i + 1] < offsets[i]) return ACT_ERR_ARG;     // message i = [offsets[i], offsets[i+1])
+  std::vector<uint64_t> rel[2];   // declared before `call`: on an early return its destructor waits for the streams while the copies' host buffers still exist
+  Call call(c, 0);
+  HIPCK(c, hipSetDevice(c->device));
+  CborDev d; int rc = cbor_dev_prepare(c, c->slots[0], type, &d); if (rc) return rc;
+  const size_t nf = d.lay.pay_off.size(), ml = d.lay.tmpl.size(), rb = nf * 32;
+  const size_t chunk = std::min(cbor_chunk_msgs(mem, nf, ml), (size_t)1 << 30);
+  const bool host = mem == ACT_MEM_HOST;
+  size_t k = 0;
+  for (size_t off = 0; off < n; off += chunk, k++) {
+    Slot& sl = c->slots[host ? (k & 1) : 0];
+    HIPCK(c, hipStreamSynchronize(sl.stream));               // the chunk before last has left this slot's staging areas
+    const size_t m = std::min(chunk, n - off), pad = (m + 3) & ~(size_t)3;
+    const size_t byte_beg = offsets ? (size_t)offsets[off] : off * ml, byte_end = offsets ? (size_t)offsets[off + m] : (off + m) * ml;
+    CborReadArgs ra{};
+    ra.T = *T; ra.L = c->L; ra.n = (uint32_t)m; ra.first = 0; ra.msg_len = (uint32_t)ml; ra.rec_stride = rb; ra.keep_fields = (uint32_t)nf;
+    if (host && (rc = copy_chain_wait(c, sl, false))) return rc;
+    if ((rc = dev_in(c, sl, 0, mem, cbor + byte_beg, byte_end - byte_beg, &ra.in))) return rc;
+    if (offsets) {
+      std::vector<uint64_t>& r = rel[host ? (k & 1) : 0];
+      r.resize(m + 1);
+      for (size_t i = 0; i <= m; i++) r[i] = offsets[off + i] - byte_beg;
+      if ((rc = stage_reserve(c, sl, 1, (m + 1) * 8))) return rc;
+      HIPCK(c, hipMemcpyAsync(sl.d_stage[1], r.data(), (m + 1) * 8, hipMemcpyHostToDevice, sl.stream));
+      ra.offsets = reinterpret_cast<const uint64_t*>(sl.d_stage[1]);
+    }
+    if (host && (rc = copy_chain_record(c, sl, false))) return rc;
+    if ((rc = dev_out_begin(c, sl, 2, mem, out_records + off * rb, m * rb, &ra.rec))) return rc;
+    if ((rc = stage_reserve(c, sl, 4, 2 * pad))) return rc;      // codes (padded: 32-bit OR in the field pass), then infos
+    ra.code = sl.d_stage[4]; ra.info = sl.d_stage[4] + pad;
+    HIPCK(c, hipMemsetAsync(sl.d_stage[4], 0, 2 * pad, sl.stream));
+    launch_cbor_read(ra, false, sl.stream);
+    launch_cbor_read(ra, true, sl.stream);
+    CborFixArgs fa{(uint32_t)m, (uint32_t)nf, d.kind, ra.rec, ra.code};
+    launch_cbor_fix(fa, sl.stream);
+    HIPCK(c, hipGetLastError());
+    if (host && (rc = copy_chain_wait(c, sl, true))) return rc;
+    if ((rc = dev_out_end(c, sl, mem, out_records + off * rb, ra.rec, m * rb))) return rc;
+    if (host && (rc = copy_chain_record(c, sl, true))) return rc;
+    HIPCK(c, hipMemcpyAsync(status + off, ra.code, m, host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, sl.stream));
+  }
+  return call.finish();                                      // waits for both streams
+}
+
+int act_ctx_set_wire_reader(act_ctx* c, int where) {
+  if (!c || (where != ACT_WIRE_READER_HOST && where != ACT_WIRE_READER_DEVICE)) return ACT_ERR_ARG;
+  c->wire_reader.store(where);
+  return ACT_OK;
+}
+// (here and not in node.cpp: it needs nothing of the node but its contexts, and the reader is this file's)
+int act_node_set_wire_reader(act_node* nd, int reader) {
+  if (!nd) return ACT_ERR_ARG;
+  for (int k = 0; k < act_node_device_count(nd); k++) { const int rc = act_ctx_set_wire_reader(act_node_ctx(nd, k), reader); if (rc) return rc; }
+  return ACT_OK;
+}
+int act_ctx_wire_stats(act_ctx* c, uint64_t out[4], int reset) {
+  if (!c || !out) return ACT_ERR_ARG;
+  for (int i = 0; i < 4; i++) out[i] = reset ? c->wire_stats[i].exchange(0) : c->wire_stats[i].load();
+  return ACT_OK;
+}
+
 
 // ---- wire bytes in, verdict out -----------------------------------------------------------------------------------------
 // SpendProof::from_cbor (src/cbor.rs:236-408) followed by PrivateKey::refund up to the challenge check (src/lib.rs:787-844) as ONE
@@ -567,6 +443,9 @@ int act_cbor_decode_batch(act_ctx* c, int type, size_t n, int mem, const uint8_t
 // each of the 130 points of a proof is decoded exactly once (by the kernel that needs it).  Messages that are not the canonical
 // encoding are flagged by the unframing kernel, verified as all-zero records for the moment, and settled after the pipeline has
 // drained: the general reader on the host (cbor_read_message), then a second, small verification call for those that parse.
+// That is the road of ACT_WIRE_READER_HOST.  Under ACT_WIRE_READER_DEVICE (the default) the flagged messages are read by
+// k_cbor_read_raw between the unframing kernel and the verification kernels of their own chunk: every spelling is verified once,
+// in the pipeline, and what is left for the end of the call is to give the messages the reader refused their wire status.
 static int wire_unframe_chunk(act_ctx* c, Slot& sl, const WireSrc& w, int mem, size_t off, uint32_t m, const uint8_t** d_records) {
   const ProofLayout pl{c->L};
   const size_t nf = pl.bytes() / 32;
@@ -590,6 +469,16 @@ static int wire_unframe_chunk(act_ctx* c, Slot& sl, const WireSrc& w, int mem, s
   CborArgs a{}; a.n = m; a.n_fields = (uint32_t)nf; a.msg_len = (uint32_t)w.msg_len; a.pay_off = d.pay_off; a.kind = d.kind; a.tmpl = d.tmpl;
   a.in = d_in; a.out = sl.d_stage[6]; a.offsets = d_offsets; a.status = c->d_wire_flags;
   hipLaunchKernelGGL(k_cbor_unframe_raw, dim3((unsigned)(((size_t)m * nf + 255) / 256)), dim3(256), 0, sl.stream, a, (uint32_t)off);
+  // the device reader: every flagged message of the chunk is read from the staged bytes into the record the unframing kernel would
+  // have filled, on the same stream and without a word to the host -- first the plain pass, then the validating pass over the
+  // messages the plain pass names (cbor_lanes.h); a lane of either returns at once unless its message is flagged
+  if (c->wire_read_code) {
+    CborReadArgs ra{};
+    ra.T = *cbor_type(ACT_CBOR_SPEND_PROOF); ra.L = c->L; ra.n = m; ra.first = (uint32_t)off; ra.msg_len = (uint32_t)w.msg_len; ra.in = d_in; ra.offsets = d_offsets;
+    ra.flags = c->d_wire_flags; ra.rec = sl.d_stage[6]; ra.rec_stride = pl.bytes(); ra.keep_fields = (uint32_t)nf; ra.keep_k_on_value = 1; ra.code = c->wire_read_code; ra.info = c->wire_read_info;
+    if ((rc = prof_launch(c, sl, PK_CBOR_READ, m, [&] { launch_cbor_read(ra, false, sl.stream); }))) return rc;
+    if ((rc = prof_launch(c, sl, PK_CBOR_READ_VALIDATE, m, [&] { launch_cbor_read(ra, true, sl.stream); }))) return rc;
+  }
   // the nullifier `k` is the first field of the record (src/cbor.rs:250): 32 bytes per proof to the caller's array
   if (w.out_nullifier)
     HIPCK(c, hipMemcpy2DAsync(w.out_nullifier + off * 32, 32, sl.d_stage[6], pl.bytes(), 32, m, mem == ACT_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, sl.stream));
@@ -629,18 +518,54 @@ static int verify_spend_cbor_impl(act_ctx* c, size_t n, int mem, const uint8_t s
     HIPCK(c, hipMalloc(&c->d_wire_flags, fcap)); c->d_wire_flags_cap = fcap;
   }
   HIPCK(c, hipMemsetAsync(c->d_wire_flags, 0, fcap, s0.stream));
+  const bool dev_reader = c->wire_reader.load() == ACT_WIRE_READER_DEVICE;
+  if (dev_reader) {
+    if (fcap > c->d_wire_codes_cap) {
+      if (c->d_wire_codes) HIPCK(c, hipFree(c->d_wire_codes));
+      c->d_wire_codes = nullptr; c->d_wire_codes_cap = 0;
+      HIPCK(c, hipMalloc(&c->d_wire_codes, 2 * fcap)); c->d_wire_codes_cap = fcap;
+    }
+    HIPCK(c, hipMemsetAsync(c->d_wire_codes, 0, 2 * c->d_wire_codes_cap, s0.stream));
+  }
   HIPCK(c, hipStreamSynchronize(s0.stream));                 // the other slot's stream reads the layout and the flags too
   WireSrc w{cbor, offsets, ml, out_nullifier};
   const DevKey* d_ring = nullptr;
   if (ring && (rc = ring_set(c, ring->keys, ring->nkeys, &d_ring))) { c->wire_layout = nullptr; return rc; }
+  if (dev_reader) { c->wire_read_code = c->d_wire_codes; c->wire_read_info = c->d_wire_codes + c->d_wire_codes_cap; }
   rc = ring ? ring_verify_locked(c, n, mem, d_ring, ring->nkeys, nullptr, status, ring->out_key, out_kprime, &w)
             : spend_batch_locked(c, n, mem, sk, nullptr, false, nullptr, ACT_RNG_PER_LANE, nullptr, status, out_kprime, &w);
-  c->wire_layout = nullptr;
+  c->wire_layout = nullptr; c->wire_read_code = c->wire_read_info = nullptr;
   if (rc) return rc;
+  if (dev_reader) {
+    // every message has been verified once, in the pipeline.  A message the reader refused was verified as the all-zero record the
+    // reader left: it takes its wire status, all-zero K' and nullifier and ACT_KEY_NONE -- what the settle loop below patches in
+    std::vector<uint8_t> ci(c->d_wire_codes_cap + n);      // codes and infos lie in one buffer: one copy
+    HIPCK(c, hipMemcpy(ci.data(), c->d_wire_codes, ci.size(), hipMemcpyDeviceToHost));
+    const uint8_t *code = ci.data(), *info = ci.data() + c->d_wire_codes_cap;
+    size_t read = 0, refused = 0;
+    for (size_t i = 0; i < n; i++) if (info[i] & act::CBOR_INFO_DEVICE) { read++; refused += code[i] != CBOR_OK; }
+    if (refused && mem == ACT_MEM_DEVICE) {
+      CborSettleArgs sa{(uint32_t)n, c->d_wire_codes, c->d_wire_codes + c->d_wire_codes_cap, status, out_kprime, out_nullifier, ring ? ring->out_key : nullptr};
+      launch_cbor_settle(sa, s0.stream);
+      HIPCK(c, hipGetLastError());
+      HIPCK(c, hipStreamSynchronize(s0.stream));
+    } else if (refused) {
+      for (size_t i = 0; i < n; i++) {
+        if (!(info[i] & act::CBOR_INFO_DEVICE) || code[i] == CBOR_OK) continue;
+        status[i] = act::cbor_code_status(code[i]);
+        if (out_kprime) memset(out_kprime + i * 32, 0, 32);
+        if (out_nullifier && !(info[i] & act::CBOR_INFO_KEPT_K)) memset(out_nullifier + i * 32, 0, 32);
+        if (ring) ring->out_key[i] = (uint8_t)ACT_KEY_NONE;
+      }
+    }
+    c->wire_stats[0] += n; c->wire_stats[1] += n - read; c->wire_stats[2] += read;
+    return call.finish();
+  }
   std::vector<uint8_t> flags(n), ok2, hok;
   HIPCK(c, hipMemcpy(flags.data(), c->d_wire_flags, n, hipMemcpyDeviceToHost));
   std::vector<size_t> which;
   for (size_t i = 0; i < n; i++) if (flags[i] & 0x80) which.push_back(i);
+  c->wire_stats[0] += n; c->wire_stats[1] += n - which.size(); c->wire_stats[3] += which.size();
   auto msg_beg = [&](size_t i) { return offsets ? (size_t)offsets[i] : i * ml; };
   auto msg_end = [&](size_t i) { return offsets ? (size_t)offsets[i + 1] : (i + 1) * ml; };
   const bool dev = mem == ACT_MEM_DEVICE;

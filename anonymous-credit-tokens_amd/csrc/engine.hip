@@ -20,6 +20,7 @@
 #include "kernels.h"
 #include "keyring.h"
 #include "admit.h"
+#include "cbor_lanes.h"
 #include "rng_source.h"
 #include "../../include/act_mi355x.h"
 
@@ -65,11 +66,11 @@ const uint8_t kGeneratorEnc[32] = {0xe2, 0xf2, 0xae, 0x0a, 0x6a, 0xbc, 0x4e, 0x7
 
 enum ProfId { PK_SPEND_PREP, PK_SPEND_PREP_A, PK_SPEND_PREP_B, PK_SPEND_PREP_C, PK_SPEND_PREP_JOIN, PK_SPEND_COORDS, PK_SPEND_BITS, PK_SPEND_ENC, PK_SPEND_TAIL, PK_HASH_SPEND, PK_SPEND_FINISH, PK_SIGN_A, PK_HASH_SMALL, PK_SIGN_B,
               PK_ISSUE_A, PK_ISSUE_CHECK, PK_REQUEST_A, PK_REQUEST_B, PK_PROVE_HEAD, PK_PROVE_BITS, PK_PROVE_ENC, PK_PROVE_TAIL, PK_PROVE_RESP,
-              PK_CLIENT, PK_COPY_H2D, PK_COPY_D2H, PK_ISSUE_A_WIRE, PK_SIGN_B_FRAME, PK_RING_CAND, PK_RING_HASH, PK_RING_FINISH, PK_COUNT };
+              PK_CLIENT, PK_COPY_H2D, PK_COPY_D2H, PK_ISSUE_A_WIRE, PK_SIGN_B_FRAME, PK_RING_CAND, PK_RING_HASH, PK_RING_FINISH, PK_CBOR_READ, PK_CBOR_READ_VALIDATE, PK_COUNT };
 const char* const kProfNames[PK_COUNT] = {"k_spend_prep", "k_spend_prep_a", "k_spend_prep_b", "k_spend_prep_c", "k_spend_prep_join", "k_spend_coords", "k_spend_bits", "k_spend_enc", "k_spend_tail", "k_hash_xof(spend)", "k_spend_finish",
                                           "k_sign_a", "k_hash_xof(small)", "k_sign_b", "k_issue_a", "k_issue_check", "k_request_a",
                                           "k_request_b", "k_prove_head", "k_prove_bits", "k_prove_enc", "k_prove_tail", "k_prove_resp", "k_client_verify",
-                                          "copy_h2d(bulk)", "copy_d2h(transcripts)", "k_issue_a_wire", "k_sign_b_frame", "k_ring_cand", "k_ring_hash", "k_ring_finish"};
+                                          "copy_h2d(bulk)", "copy_d2h(transcripts)", "k_issue_a_wire", "k_sign_b_frame", "k_ring_cand", "k_ring_hash", "k_ring_finish", "k_cbor_read_raw", "k_cbor_read_raw(validate)"};
 
 struct PendingProf { int id; hipEvent_t e0, e1; uint64_t lanes; };
 
@@ -143,6 +144,12 @@ struct act_ctx {
   uint8_t* d_tables_mf = nullptr;      // the four matrix-core table images (msm.h fixed_base_acc_mf)
   void* wire_layout = nullptr;         // the running wire-bytes call's CborDev (cbor_impl.inc)
   uint8_t* d_wire_flags = nullptr; size_t d_wire_flags_cap = 0;     // per message of a wire-bytes call: 0x80 = not the canonical encoding (cbor_impl.inc)
+  // the wire reader (act_ctx_set_wire_reader): where a message that is not the canonical encoding is read.  Device: per message of
+  // the running call a code byte and an info byte (cbor_lanes.h), written by the reader kernels in the chunk's own stream
+  std::atomic<int> wire_reader{ACT_WIRE_READER_DEVICE};
+  uint8_t* d_wire_codes = nullptr; size_t d_wire_codes_cap = 0;      // codes, then infos: 2 * cap bytes
+  uint8_t *wire_read_code = nullptr, *wire_read_info = nullptr;     // non-null while a call reads on the device (wire_unframe_chunk)
+  std::atomic<uint64_t> wire_stats[4] = {};                         // messages seen, canonical, read on the device, read by the host reader
   // key cache
   uint8_t sk_cached[64]{}; bool sk_valid = false; DevKey key{};
   uint8_t w_cached[32]{}; bool w_valid = false; ge w_pub{};
@@ -793,6 +800,7 @@ void act_ctx_destroy(act_ctx* c) {
   if (c->d_tables_ct) (void)hipFree(c->d_tables_ct);
   if (c->d_tables_mf) (void)hipFree(c->d_tables_mf);
   if (c->d_wire_flags) (void)hipFree(c->d_wire_flags);
+  if (c->d_wire_codes) (void)hipFree(c->d_wire_codes);
   if (c->d_admit_rng) { (void)hipMemset(c->d_admit_rng, 0, c->d_admit_rng_cap); (void)hipFree(c->d_admit_rng); }
   ring_ws_free(c);
   memset(&c->key, 0, sizeof(c->key)); memset(c->sk_cached, 0, 64);

@@ -289,6 +289,7 @@ act_ctx *act_node_ctx(act_node *node, int k);                  /* context k, e.g
 const char *act_node_last_error(const act_node *node);
 int act_node_set_transcript_mode(act_node *node, int mode);
 int act_node_set_host_threads(act_node *node, int per_gpu);    /* host BLAKE3 workers of every context */
+int act_node_set_wire_reader(act_node *node, int reader);      /* act_ctx_set_wire_reader on every context */
 int act_node_set_fixed_base_bits(act_node *node, int base, int bits);   /* act_ctx_set_fixed_base_bits on every context */
 /* Load balance.  The GPUs of a node are not equally fast (clocks differ by several percent between devices and move with
  * temperature) and a call ends when its slowest GPU does, so the cut is not n/N: (1) every throughput-sized call -- at least
@@ -341,7 +342,11 @@ int act_node_refund_to_credit_token_batch(act_node *node, size_t n, const uint8_
  * field is 3, behind it 2; array elements, those of an over-long array included, are decoded before the length is checked;
  * a value a later duplicate key overwrites still has to decode), and missing fields come last (:390-407).
  * Canonical messages are framed / unframed on the GPU (one lane per 32-byte field); others take a host reader, which hands the
- * points whose position matters to a validation kernel. */
+ * points whose position matters to a validation kernel.
+ * act_cbor_read_batch has the same contract -- all nine types, scalars reduced, points validated, the first failure in wire order,
+ * a zero record for a failed message -- with EVERY message read by the general RFC 8949 reader on the GPU (one lane per message,
+ * csrc/cbor_lanes.h): no canonical short cut and no host reader.  It is the reader the spend wire calls below run for messages that
+ * are not the canonical encoding, exposed on its own; chunked and staged like the decode call. */
 #define ACT_CBOR_ISSUANCE_REQUEST 1
 #define ACT_CBOR_ISSUANCE_RESPONSE 2
 #define ACT_CBOR_SPEND_PROOF 3
@@ -356,6 +361,8 @@ size_t act_cbor_record_bytes(const act_ctx *ctx, int type);
 int act_cbor_encode_batch(act_ctx *ctx, int type, size_t n, int mem, const uint8_t *records, uint8_t *out_cbor);
 int act_cbor_decode_batch(act_ctx *ctx, int type, size_t n, int mem, const uint8_t *cbor, const uint64_t *offsets,
                           uint8_t *out_records, uint8_t *status);
+int act_cbor_read_batch(act_ctx *ctx, int type, size_t n, int mem, const uint8_t *cbor, const uint64_t *offsets,
+                        uint8_t *out_records, uint8_t *status);
 
 /* Wire bytes in, verdict out: SpendProof::from_cbor (src/cbor.rs:236-408) + PrivateKey::refund up to the challenge check
  * (src/lib.rs:787-844) as ONE pass over n CBOR messages (delimited like act_cbor_decode_batch's: offsets[0..n] in host memory, or
@@ -365,10 +372,25 @@ int act_cbor_decode_batch(act_ctx *ctx, int type, size_t n, int mem, const uint8
  * 255 = a point that is not a canonical Ristretto encoding (from_cbor's CborError::InvalidValue);
  * ACT_STATUS_CBOR_MALFORMED = not well-formed CBOR (CborError::Ciborium); ACT_STATUS_CBOR_STRUCTURE = CborError::InvalidStructure
  * (not a map, missing field, wrong shape or length).  The status is the one from_cbor followed by refund gives, also for a message
- * that is wrong in several ways (the first failure in wire order, as described at act_cbor_decode_batch).  Non-canonical but valid
- * encodings take a host reader and a second, small verification call.  out_kprime (nullable) as in act_verify_spend_batch. */
+ * that is wrong in several ways (the first failure in wire order, as described at act_cbor_decode_batch).  A message that is not
+ * the canonical encoding -- an indefinite-length map, another key order, an unknown key, a chunked byte string ... -- is read by the
+ * general reader ON THE GPU, in its chunk's own stream between the unframing kernel and the verification kernels, and verified
+ * once, in the pipeline, like every other message; the same holds for every wire-level spend call below (refund, redeem, the ring
+ * and epoch forms) and for the admission screen.  out_kprime (nullable) as in act_verify_spend_batch.
+ *
+ * act_ctx_set_wire_reader chooses where such messages are read: ACT_WIRE_READER_DEVICE (the default) as described;
+ * ACT_WIRE_READER_HOST keeps the earlier road -- flagged messages verified as all-zero records, then read on the calling thread
+ * behind the pipeline and verified a second time -- as a fallback and as the baseline of comparisons.  The answers are the same.
+ * act_ctx_wire_stats: messages seen, canonical, read on the device, read by the host reader -- counted on the spend wire path and in
+ * the admission screen since the last reset.  The counters count READS, not distinct messages: an admission call counts every
+ * message once in its screen (where the reduced form, k and s, is read) and every survivor of the screen once more in the
+ * verification behind it, which reads the whole record. */
 #define ACT_STATUS_CBOR_MALFORMED 254
 #define ACT_STATUS_CBOR_STRUCTURE 253
+#define ACT_WIRE_READER_HOST 0
+#define ACT_WIRE_READER_DEVICE 1
+int act_ctx_set_wire_reader(act_ctx *ctx, int where);
+int act_ctx_wire_stats(act_ctx *ctx, uint64_t out[4], int reset);
 int act_verify_spend_cbor_batch(act_ctx *ctx, size_t n, int mem, const uint8_t sk[64], const uint8_t *cbor, const uint64_t *offsets,
                                 uint8_t *status, uint8_t *out_kprime);
 int act_node_verify_spend_cbor_batch(act_node *node, size_t n, const uint8_t sk[64], const uint8_t *cbor, const uint64_t *offsets,

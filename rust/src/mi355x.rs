@@ -54,6 +54,9 @@ const PROVE_RNG_BYTES: usize = 64 * (4 * L + 12); // 33 536: draw order of src/l
 extern "C" {
     fn act_node_create(h: *const u8, l: c_int, devices: *const c_int, n_devices: c_int, max_batch: usize, out: *mut *mut ActNode) -> c_int;
     fn act_node_destroy(node: *mut ActNode);
+    // where messages that are not the canonical encoding are read (1 = on the GPU, the default; 0 = the host reader): declared for
+    // deployments that want the fallback, called nowhere in this binding
+    fn act_node_set_wire_reader(node: *mut ActNode, reader: c_int) -> c_int;
     fn act_node_last_error(node: *const ActNode) -> *const c_char;
     fn act_node_request_batch(node: *mut ActNode, n: usize, pre: *const u8, rng: *const u8, out_req: *mut u8) -> c_int;
     fn act_node_issue_check_batch(node: *mut ActNode, n: usize, req: *const u8, status: *mut u8) -> c_int;
