@@ -594,8 +594,8 @@ class Engine:
         return st.tobytes(), out.tobytes()
 
     def set_wire_reader(self, where: int):
-        """WIRE_READER_DEVICE (default) or WIRE_READER_HOST: where the spend wire calls and the admission screen read a message that
-        is not the canonical encoding"""
+        """WIRE_READER_DEVICE (default) or WIRE_READER_HOST: where the spend wire calls, the admission screen and the issuance wire calls
+        read a message that is not the canonical encoding"""
         self._ck(self.lib.act_ctx_set_wire_reader(self.ctx, where))
 
     def wire_stats(self, reset: bool = False) -> dict:

@@ -21,6 +21,7 @@
 #include "keyring.h"
 #include "admit.h"
 #include "cbor_lanes.h"
+#include "issue_wire_lanes.h"
 #include "rng_source.h"
 #include "../../include/act_mi355x.h"
 
@@ -66,11 +67,11 @@ const uint8_t kGeneratorEnc[32] = {0xe2, 0xf2, 0xae, 0x0a, 0x6a, 0xbc, 0x4e, 0x7
 
 enum ProfId { PK_SPEND_PREP, PK_SPEND_PREP_A, PK_SPEND_PREP_B, PK_SPEND_PREP_C, PK_SPEND_PREP_JOIN, PK_SPEND_COORDS, PK_SPEND_BITS, PK_SPEND_ENC, PK_SPEND_TAIL, PK_HASH_SPEND, PK_SPEND_FINISH, PK_SIGN_A, PK_HASH_SMALL, PK_SIGN_B,
               PK_ISSUE_A, PK_ISSUE_CHECK, PK_REQUEST_A, PK_REQUEST_B, PK_PROVE_HEAD, PK_PROVE_BITS, PK_PROVE_ENC, PK_PROVE_TAIL, PK_PROVE_RESP,
-              PK_CLIENT, PK_COPY_H2D, PK_COPY_D2H, PK_ISSUE_A_WIRE, PK_SIGN_B_FRAME, PK_RING_CAND, PK_RING_HASH, PK_RING_FINISH, PK_CBOR_READ, PK_CBOR_READ_VALIDATE, PK_COUNT };
+              PK_CLIENT, PK_COPY_H2D, PK_COPY_D2H, PK_ISSUE_A_WIRE, PK_SIGN_B_FRAME, PK_RING_CAND, PK_RING_HASH, PK_RING_FINISH, PK_CBOR_READ, PK_CBOR_READ_VALIDATE, PK_ISSUE_WIRE_FLAG, PK_COUNT };
 const char* const kProfNames[PK_COUNT] = {"k_spend_prep", "k_spend_prep_a", "k_spend_prep_b", "k_spend_prep_c", "k_spend_prep_join", "k_spend_coords", "k_spend_bits", "k_spend_enc", "k_spend_tail", "k_hash_xof(spend)", "k_spend_finish",
                                           "k_sign_a", "k_hash_xof(small)", "k_sign_b", "k_issue_a", "k_issue_check", "k_request_a",
                                           "k_request_b", "k_prove_head", "k_prove_bits", "k_prove_enc", "k_prove_tail", "k_prove_resp", "k_client_verify",
-                                          "copy_h2d(bulk)", "copy_d2h(transcripts)", "k_issue_a_wire", "k_sign_b_frame", "k_ring_cand", "k_ring_hash", "k_ring_finish", "k_cbor_read_raw", "k_cbor_read_raw(validate)"};
+                                          "copy_h2d(bulk)", "copy_d2h(transcripts)", "k_issue_a_wire", "k_sign_b_frame", "k_ring_cand", "k_ring_hash", "k_ring_finish", "k_cbor_read_raw", "k_cbor_read_raw(validate)", "k_issue_wire_flag"};
 
 struct PendingProf { int id; hipEvent_t e0, e1; uint64_t lanes; };
 

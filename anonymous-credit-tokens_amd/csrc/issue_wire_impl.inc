@@ -6,8 +6,13 @@
 // without an IssuanceRequest, a RistrettoPoint or an IssuanceResponse on the host.  A chunk is ONE pipeline: k_issue_a_wire reads the
 // canonical messages in place (unframing, K decoded once, the records from_cbor returns left in the slot's staging for k_issue_check and
 // the signature), the transcript hash, k_issue_check, and -- for the whole endpoint -- the signature, whose phase B frames the
-// IssuanceResponse messages (k_sign_b_frame).  What is not byte-for-byte canonical is settled after the pipeline has drained, in windows of
-// WIRE_SETTLE_WINDOW, with the host reader of the spend path: cbor_read_message -> cbor_settle_codes -> one small act_issue_check_batch.
+// IssuanceResponse messages (k_sign_b_frame).  What is not byte-for-byte canonical:
+//   ACT_WIRE_READER_DEVICE (the default): k_issue_wire_flag marks it, k_cbor_read_raw reads it into the slot's records in the chunk's own
+//     stream, k_issue_a_wire_read takes the record up and the lane is checked, signed and framed beside its canonical neighbours;
+//     k_issue_check gives a message the reader refused its wire status (lane bodies: issue_wire_lanes.h).  Nothing is left for the end
+//     of the call but counting the flags for act_ctx_wire_stats.
+//   ACT_WIRE_READER_HOST: k_issue_a_wire flags it, and it is settled after the pipeline has drained, in windows of WIRE_SETTLE_WINDOW,
+//     with the host reader of the spend path: cbor_read_message -> cbor_settle_codes -> one small act_issue_check_batch.
 
 namespace {
 
@@ -32,6 +37,19 @@ int wire_flags_reserve(act_ctx* c, size_t n) {
   return ACT_OK;
 }
 
+// the device reader's code and info bytes, one each per message of the call, zero (CBOR_OK) until a reader kernel writes them (the
+// memset is on slot 0's stream: wire_flags_reserve, called next, waits for it)
+int wire_codes_reserve(act_ctx* c, size_t n) {
+  const size_t fcap = (n + 3) & ~(size_t)3;
+  if (fcap > c->d_wire_codes_cap) {
+    if (c->d_wire_codes) HIPCK(c, hipFree(c->d_wire_codes));
+    c->d_wire_codes = nullptr; c->d_wire_codes_cap = 0;
+    HIPCK(c, hipMalloc(&c->d_wire_codes, 2 * fcap)); c->d_wire_codes_cap = fcap;
+  }
+  HIPCK(c, hipMemsetAsync(c->d_wire_codes, 0, 2 * c->d_wire_codes_cap, c->slots[0].stream));
+  return ACT_OK;
+}
+
 // out_req: the record of an accepted lane, zero for any other (16 bytes per thread; the caller's pointer may have any alignment)
 __global__ void __launch_bounds__(256) k_issue_req_out(const uint8_t* rec, const uint8_t* status, uint8_t* out, uint32_t n) {
   const uint32_t gid = blockIdx.x * 256 + threadIdx.x;
@@ -41,10 +59,11 @@ __global__ void __launch_bounds__(256) k_issue_req_out(const uint8_t* rec, const
 }
 
 // Check (and with `sign` -- ACT_RNG_PER_LANE only, where no slice depends on another lane's verdict -- sign and frame) every canonical
-// message; chunks of max_batch alternate between the two slots as in issue_batch_impl.  A flagged message leaves with status 255, a zero
-// record and a zero slot.  The caller holds the context (Call).
-int issue_wire_pipeline(act_ctx* c, size_t n, int mem, const IssueWire& w, const uint8_t* camt, const uint8_t* rng, bool sign, uint8_t* out_resp,
-                        uint8_t* status, uint8_t* out_req) {
+// message; chunks of max_batch alternate between the two slots as in issue_batch_impl.  dev_reader: every flagged message is read in
+// front of phase A and goes through the same kernels.  Otherwise a flagged message leaves with status 255, a zero record and a zero
+// slot.  The caller holds the context (Call).
+int issue_wire_pipeline(act_ctx* c, size_t n, int mem, const IssueWire& w, const uint8_t* camt, const uint8_t* rng, bool sign, bool dev_reader,
+                        uint8_t* out_resp, uint8_t* status, uint8_t* out_req) {
   const size_t rl = w.resp.lay.tmpl.size();
   const FrameOut fo{w.resp.tmpl, w.resp.pay_off, (uint32_t)rl};
   size_t cursor = 0, chunk = 0; int rc;
@@ -68,7 +87,18 @@ int issue_wire_pipeline(act_ctx* c, size_t n, int mem, const IssueWire& w, const
     a.rec_out = sl.d_stage[6]; a.req = a.rec_out;
     a.tmpl = w.req.tmpl; a.pay_off = w.req.pay_off; a.msg_len = (uint32_t)w.ml; a.wire_flags = c->d_wire_flags; a.first = (uint32_t)off;
     if (sign && (rc = dev_in(c, sl, 1, mem, camt + off * 32, (size_t)m * 32, &a.c_amount))) return rc;      // (null: no X_A)
-    if ((rc = prof_launch(c, sl, PK_ISSUE_A_WIRE, m, [&] { launch_issue_a_wire(a, sl.stream); }))) return rc;
+    if (dev_reader) {
+      // flag pass, plain pass, validating pass (a lane of either reader kernel returns at once unless its message is flagged), then phase A
+      act::IssueWireFlagArgs fa{m, (uint32_t)off, (uint32_t)w.ml, a.wire, a.wire_off, a.tmpl, a.pay_off, c->d_wire_flags};
+      if ((rc = prof_launch(c, sl, PK_ISSUE_WIRE_FLAG, m, [&] { launch_issue_wire_flag(fa, sl.stream); }))) return rc;
+      CborReadArgs ra{};
+      ra.T = *cbor_type(ACT_CBOR_ISSUANCE_REQUEST); ra.L = c->L; ra.n = m; ra.first = (uint32_t)off; ra.msg_len = (uint32_t)w.ml; ra.in = a.wire; ra.offsets = a.wire_off;
+      ra.flags = c->d_wire_flags; ra.rec = a.rec_out; ra.rec_stride = 128; ra.keep_fields = 4; ra.code = c->d_wire_codes; ra.info = c->d_wire_codes + c->d_wire_codes_cap;
+      if ((rc = prof_launch(c, sl, PK_CBOR_READ, m, [&] { launch_cbor_read(ra, false, sl.stream); }))) return rc;
+      if ((rc = prof_launch(c, sl, PK_CBOR_READ_VALIDATE, m, [&] { launch_cbor_read(ra, true, sl.stream); }))) return rc;
+      a.wire_code = c->d_wire_codes;
+      if ((rc = prof_launch(c, sl, PK_ISSUE_A_WIRE, m, [&] { launch_issue_a_wire_read(a, sl.stream); }))) return rc;
+    } else if ((rc = prof_launch(c, sl, PK_ISSUE_A_WIRE, m, [&] { launch_issue_a_wire(a, sl.stream); }))) return rc;
     if ((rc = hash_step(c, sl, PK_HASH_SMALL, sl.d_trs, SMALL_TR_STRIDE, c->P.prefix_len[LABEL_REQUEST] + 80, m))) return rc;
     if ((rc = prof_launch(c, sl, PK_ISSUE_CHECK, m, [&] { launch_issue_check(a, sl.stream); }))) return rc;
     if (out_req) {
@@ -228,13 +258,24 @@ int flagged_lanes(act_ctx* c, size_t n, std::vector<size_t>& which) {
   return ACT_OK;
 }
 
+// how many lanes the flag pass marked (the device reader's road: only the count is wanted, for act_ctx_wire_stats)
+int flagged_count(act_ctx* c, size_t n, size_t* count) {
+  std::vector<uint8_t> flags(n);
+  HIPCK(c, hipMemcpy(flags.data(), c->d_wire_flags, n, hipMemcpyDeviceToHost));
+  size_t k = 0;
+  for (size_t i = 0; i < n; i++) k += flags[i] >> 7;
+  *count = k;
+  return ACT_OK;
+}
+
 int check_offsets(size_t n, const uint64_t* offsets) {
   if (n >= ((size_t)1 << 32)) return ACT_ERR_ARG;
   if (offsets) for (size_t i = 0; i < n; i++) if (offsets[i + 1] < offsets[i]) return ACT_ERR_ARG;     // message i = [offsets[i], offsets[i+1])
   return ACT_OK;
 }
 
-// the check half (and, with sk and ACT_RNG_PER_LANE bytes, the whole endpoint in one pipeline), settle included
+// the check half (and, with sk and ACT_RNG_PER_LANE bytes, the whole endpoint in one pipeline).  Device reader: the pipeline is the whole
+// call.  Host reader: the flagged lanes are settled behind it.
 int issue_wire_run(act_ctx* c, size_t n, int mem, const uint8_t sk[64], const uint8_t* cbor, const uint64_t* offsets, const uint8_t* camt,
                    const uint8_t* rng, uint8_t* out_resp, uint8_t* status, uint8_t* out_req) {
   IssueWire w; w.cbor = cbor; w.offsets = offsets;
@@ -243,11 +284,20 @@ int issue_wire_run(act_ctx* c, size_t n, int mem, const uint8_t sk[64], const ui
     Call call(c, n);
     HIPCK(c, hipSetDevice(c->device));
     int rc;
+    const bool dev_reader = c->wire_reader.load() == ACT_WIRE_READER_DEVICE;
     if (sk && (rc = set_key(c, sk))) return rc;
     if ((rc = issue_wire_prepare(c, w, true, sk != nullptr))) return rc;
+    if (dev_reader && (rc = wire_codes_reserve(c, n))) return rc;
     if ((rc = wire_flags_reserve(c, n))) return rc;
-    if ((rc = issue_wire_pipeline(c, n, mem, w, camt, rng, sk != nullptr, out_resp, status, out_req))) return rc;
+    if ((rc = issue_wire_pipeline(c, n, mem, w, camt, rng, sk != nullptr, dev_reader, out_resp, status, out_req))) return rc;
+    if (dev_reader) {
+      size_t read = 0;
+      if ((rc = flagged_count(c, n, &read))) return rc;
+      c->wire_stats[0] += n; c->wire_stats[1] += n - read; c->wire_stats[2] += read;
+      return call.finish();
+    }
     if ((rc = flagged_lanes(c, n, which))) return rc;
+    c->wire_stats[0] += n; c->wire_stats[1] += n - which.size(); c->wire_stats[3] += which.size();
     if ((rc = call.finish())) return rc;
   }
   return issue_wire_settle(c, mem, w, which, sk, camt, rng, out_resp, status, out_req);
@@ -297,6 +347,7 @@ int issue_cbor_tiny(act_ctx* c, size_t n, const uint8_t sk[64], const uint8_t* c
   if (rc) return rc;
   cbor_frame_refunds_host(cbor_layout(*cbor_type(ACT_CBOR_ISSUANCE_RESPONSE), c->L), n, resp.data(), st.data(), out_resp_cbor);
   memcpy(status, st.data(), n);
+  c->wire_stats[0] += n; c->wire_stats[1] += n;                  // (every message of a call that ends here is canonical)
   return ACT_OK;
 }
 

@@ -4,6 +4,7 @@
 // (SURVEY.md fact 0.9); the hash runs on the host or in k_hash_xof depending on the context's mode.
 #include "kernels.h"
 #include "keyring.h"
+#include "issue_wire_lanes.h"
 
 namespace act {
 
@@ -171,24 +172,30 @@ void launch_sign_b(const SignArgs& a, hipStream_t s) {
 // canonical encoding): its 13 framing bytes against the template, its four payloads with byte-aligned 16-byte loads; it writes the
 // record from_cbor returns (scalars reduced: decode_scalar) to rec_out and decodes K once, here.  A message that is not byte-for-byte
 // canonical gets wire flag 0x80, a zero record and status 255 for now: the host reader settles it (issue_wire_impl.inc).
-template <bool WIRE>
+// WIRE = 2 (k_issue_a_wire_read, ACT_WIRE_READER_DEVICE): k_issue_wire_flag has compared the framing bytes and k_cbor_read_raw has
+// read every flagged message into rec_out in front of this kernel (issue_wire_lanes.h): a canonical lane goes as above without the
+// comparison, a flagged one takes its fields from the reader's record, or leaves with a zero record when the reader refused it
+// (k_issue_check gives it its wire status).  The reader is NOT in here: its frame stack is 1 KiB of scratch per lane.
+template <int WIRE>
 __device__ __forceinline__ void issue_a_lane(const IssueArgs& a, uint32_t p) {
   uint32_t wk[8];
   sc gamma, k_bar, r_bar;
   if (WIRE) {
     const uint64_t beg = a.wire_off ? a.wire_off[p] : (uint64_t)p * a.msg_len, end = a.wire_off ? a.wire_off[p + 1] : beg + a.msg_len;
     const uint8_t* src = a.wire + beg;
-    bool canon = end - beg >= a.msg_len;                          // ciborium reads one item and ignores trailing bytes: a canonical prefix is enough
-    for (uint32_t f = 0, prev = 0; canon && f < 4; prev = a.pay_off[f] + 32, f++)
-      for (uint32_t i = prev; i < a.pay_off[f]; i++) canon = canon && src[i] == a.tmpl[i];
     uint8_t* rec = a.rec_out + (size_t)p * 128;
-    a.wire_flags[a.first + p] = canon ? 0 : 0x80;
-    if (!canon) { for (int i = 0; i < 128; i += 32) zero8(rec + i); a.flags[p] = FLAG_UNDECODABLE; return; }
-    uint32_t w[8];
-    load32_bytes(wk, src + a.pay_off[0]); store8(rec, wk);
-    load32_bytes(w, src + a.pay_off[1]); gamma = sc_from_words(w); store_sc(rec + 32, gamma);
-    load32_bytes(w, src + a.pay_off[2]); k_bar = sc_from_words(w); store_sc(rec + 64, k_bar);
-    load32_bytes(w, src + a.pay_off[3]); r_bar = sc_from_words(w); store_sc(rec + 96, r_bar);
+    bool canon;
+    if (WIRE == 2) canon = !(a.wire_flags[a.first + p] & 0x80);
+    else {
+      canon = end - beg >= a.msg_len;                             // ciborium reads one item and ignores trailing bytes: a canonical prefix is enough
+      for (uint32_t f = 0, prev = 0; canon && f < 4; prev = a.pay_off[f] + 32, f++)
+        for (uint32_t i = prev; i < a.pay_off[f]; i++) canon = canon && src[i] == a.tmpl[i];
+      a.wire_flags[a.first + p] = canon ? 0 : 0x80;
+    }
+    if (WIRE != 2 && !canon) { for (int i = 0; i < 128; i += 32) zero8(rec + i); a.flags[p] = FLAG_UNDECODABLE; return; }
+    if (!canon) {
+      if (!issue_wire_take_lane(rec, a.wire_code[a.first + p], wk, gamma, k_bar, r_bar)) { a.flags[p] = FLAG_UNDECODABLE; return; }
+    } else issue_wire_take_canonical(src, a.pay_off, rec, wk, gamma, k_bar, r_bar);
   } else {
     const uint8_t* rec = a.req + (size_t)p * 128;
     load8(wk, rec);
@@ -216,13 +223,20 @@ __device__ __forceinline__ void issue_a_lane(const IssueArgs& a, uint32_t p) {
 __global__ void __launch_bounds__(64, 2) k_issue_a(IssueArgs a) {
   uint32_t p = blockIdx.x * 64 + threadIdx.x;
   if (p >= a.n) return;
-  issue_a_lane<false>(a, p);
+  issue_a_lane<0>(a, p);
 }
 __global__ void __launch_bounds__(64, 2) k_issue_a_wire(IssueArgs a) {
   uint32_t p = blockIdx.x * 64 + threadIdx.x;
   if (p >= a.n) return;
-  issue_a_lane<true>(a, p);
+  issue_a_lane<1>(a, p);
 }
+__global__ void __launch_bounds__(64, 2) k_issue_a_wire_read(IssueArgs a) {
+  uint32_t p = blockIdx.x * 64 + threadIdx.x;
+  if (p >= a.n) return;
+  issue_a_lane<2>(a, p);
+}
+// the flag pass in front of the reader kernels: 13 byte loads and one byte store per message
+__global__ void __launch_bounds__(256) k_issue_wire_flag(IssueWireFlagArgs a) { issue_wire_flag_lane(a, blockIdx.x * 256 + threadIdx.x); }
 // X_A alone, for the sign-only entry points (act_issue_sign_batch / act_refund_sign_batch: the node dispatcher's second
 // phase): issue X_A = g + c h1 + K (:644) from the request, refund X_A = g + K' (:848) from the enc(K') that
 // act_verify_spend_batch returned.  Lanes whose status is already non-zero are left alone.
@@ -245,10 +259,13 @@ __global__ void __launch_bounds__(256) k_issue_check(IssueArgs a) {
   uint8_t stt = 0;
   if (a.flags[p] & FLAG_UNDECODABLE) stt = 255;
   else if (!sc_equal(sc_from_wide_words(w), gamma)) stt = 1;      // Error::InvalidIssuanceRequestProof (:638-640)
+  if (a.wire_code) stt = issue_wire_status(stt, a.wire_code[a.first + p]);      // (null for record callers and the host reader's road)
   a.status[p] = stt;
 }
 void launch_issue_a(const IssueArgs& a, hipStream_t s) { if (a.n) hipLaunchKernelGGL(k_issue_a, dim3((a.n + 63) / 64), dim3(64), 0, s, a); }
 void launch_issue_a_wire(const IssueArgs& a, hipStream_t s) { if (a.n) hipLaunchKernelGGL(k_issue_a_wire, dim3((a.n + 63) / 64), dim3(64), 0, s, a); }
+void launch_issue_a_wire_read(const IssueArgs& a, hipStream_t s) { if (a.n) hipLaunchKernelGGL(k_issue_a_wire_read, dim3((a.n + 63) / 64), dim3(64), 0, s, a); }
+void launch_issue_wire_flag(const IssueWireFlagArgs& a, hipStream_t s) { if (a.n) hipLaunchKernelGGL(k_issue_wire_flag, dim3((a.n + 255) / 256), dim3(256), 0, s, a); }
 void launch_issue_check(const IssueArgs& a, hipStream_t s) { if (a.n) hipLaunchKernelGGL(k_issue_check, dim3((a.n + 255) / 256), dim3(256), 0, s, a); }
 
 // ---- PreIssuance::request (:463-487) ---------------------------------------------------------------------

@@ -195,6 +195,9 @@ struct IssueArgs {
   uint8_t* rec_out;          // n * 128: the record from_cbor returns (K as on the wire, scalars reduced), what k_issue_check (req) and the sign phase read
   uint8_t* wire_flags;       // wire_flags[first + p] = 0x80: not the canonical encoding (record zero, status 255 until the host reader settles it)
   uint32_t first;
+  // the device reader's road (k_issue_a_wire_read, k_issue_check; issue_wire_lanes.h): wire_flags is an INPUT, written by k_issue_wire_flag,
+  // and wire_code[first + p] the reader's code for a flagged message (CBOR_OK for every other).  Null everywhere else.
+  const uint8_t* wire_code;
 };
 
 struct RequestArgs {
@@ -312,6 +315,7 @@ void launch_sign_xa(const SignXaArgs& a, hipStream_t s);
 void launch_sign_fused(const SignFusedArgs& a, bool check, hipStream_t s);
 void launch_issue_a(const IssueArgs& a, hipStream_t s);
 void launch_issue_a_wire(const IssueArgs& a, hipStream_t s);     // k_issue_a_wire: the same phase from wire bytes (IssueArgs wire mode)
+void launch_issue_a_wire_read(const IssueArgs& a, hipStream_t s);      // k_issue_a_wire_read: flagged lanes take the record k_cbor_read_raw left
 void launch_issue_check(const IssueArgs& a, hipStream_t s);
 void launch_request_a(const RequestArgs& a, hipStream_t s);
 void launch_request_b(const RequestArgs& a, hipStream_t s);

@@ -381,8 +381,9 @@ int act_cbor_read_batch(act_ctx *ctx, int type, size_t n, int mem, const uint8_t
  * act_ctx_set_wire_reader chooses where such messages are read: ACT_WIRE_READER_DEVICE (the default) as described;
  * ACT_WIRE_READER_HOST keeps the earlier road -- flagged messages verified as all-zero records, then read on the calling thread
  * behind the pipeline and verified a second time -- as a fallback and as the baseline of comparisons.  The answers are the same.
- * act_ctx_wire_stats: messages seen, canonical, read on the device, read by the host reader -- counted on the spend wire path and in
- * the admission screen since the last reset.  The counters count READS, not distinct messages: an admission call counts every
+ * The setting also governs act_issue_check_cbor_batch and act_issue_cbor_batch (below).
+ * act_ctx_wire_stats: messages seen, canonical, read on the device, read by the host reader -- counted on the spend wire path, in
+ * the admission screen and by the issuance wire calls (once per message and call) since the last reset.  The counters count READS, not distinct messages: an admission call counts every
  * message once in its screen (where the reduced form, k and s, is read) and every survivor of the screen once more in the
  * verification behind it, which reads the whole record. */
 #define ACT_STATUS_CBOR_MALFORMED 254
@@ -432,8 +433,11 @@ int act_node_refund_cbor_batch(act_node *node, size_t n, const uint8_t sk[64], c
  * message of an accepted lane, all zero for any other lane.  status[i]: 0; ACT_STATUS_INVALID_ISSUANCE_REQUEST_PROOF; 255 = K is not a
  * canonical Ristretto encoding (CborError::InvalidValue); ACT_STATUS_CBOR_MALFORMED; ACT_STATUS_CBOR_STRUCTURE -- from_cbor's code for
  * a message that is wrong in several ways (as described at act_cbor_decode_batch).  Canonical messages are unframed by the issue kernel
- * itself (the message is read once, K decoded once) and the responses framed by the signing kernel; other encodings take the host reader
- * and one small act_issue_check_batch call.
+ * itself (the message is read once, K decoded once) and the responses framed by the signing kernel.  Any other encoding -- an
+ * indefinite-length map, another key order, an unknown key, a chunked byte string ... -- is read by the general reader ON THE GPU, in
+ * its chunk's own stream in front of the issue kernel, and then checked, signed and framed in the same pipeline as its canonical
+ * neighbours (act_ctx_set_wire_reader: ACT_WIRE_READER_HOST keeps the earlier road, the host reader behind the pipeline and one small
+ * act_issue_check_batch / act_issue_sign_batch call per window, as a fallback and as the baseline of comparisons; same answers).
  *   act_issue_check_cbor_batch   from_cbor + the PoK check of issue (src/lib.rs:629-640): status, and out_req (nullable, n*128) = the
  *                                request as from_cbor returns it (K as on the wire, scalars reduced mod l), zero where status != 0 --
  *                                for a server that decides c after the verdicts
