@@ -15,6 +15,12 @@ int hc_admit_decide(int wire_code, int charge_given, int charge_equal, int found
   return admit_decide((uint8_t)wire_code, charge_given != 0, charge_equal != 0, [&]() { *probed = 1; return found != 0; });
 }
 
+// the set's slot hash of a 32-byte nullifier under a 16-byte salt, as the kernels compute it: reduce, then hash (both table starts come from it)
+uint64_t hc_null_hash(const uint8_t key[32], const uint8_t salt[16]) {
+  uint32_t w[8], s[4]; null_load_key(w, key); memcpy(s, salt, 16);
+  return null_hash(w, s);
+}
+
 // a committed slot for `key` (reduced here, as the set reduces it) under `epoch`: the set's slot function, linear probing.  0 = table full
 int hc_admit_table_insert(uint32_t* tab_keys, uint32_t* tab_state, uint32_t tab_cap, const uint8_t salt[16], const uint8_t key[32], uint32_t epoch) {
   uint32_t w[8], s[4]; null_load_key(w, key); memcpy(s, salt, 16);
