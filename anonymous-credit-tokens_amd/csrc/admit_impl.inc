@@ -8,7 +8,7 @@
 //                    reader's record, in windows of ADMIT_READ_WINDOW) -> pre-status, reduced k                  [k_admit_screen]
 //   2. compaction    the survivors' lane numbers in lane order                                  [k_admit_count / _scan / _write]
 //   3. verification  of the survivors only, their records / messages gathered ADMIT_WINDOW_BATCHES * max_batch at a time
-//   4. once per call check-and-insert and signing over the compact 32-byte arrays (redeem_keyring_tail): one rng draw per call
+//   4. once per call check-and-insert and signing over the compact 32-byte arrays (redeem_tail_ring, keyring_redeem_impl.inc): one rng draw per call
 //   5. scatter       statuses, out_key and refunds back to their lanes; shed lanes get all-zero records           [k_admit_scatter]
 // Nothing is shed (m == n): the caller's pointers go straight to redeem_keyring_impl; everything is shed: no verification kernel runs.
 // The decision that RECORDS is still the check-and-insert behind verification; the look-up of step 1 only spares work.
@@ -417,7 +417,7 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
   }
 
   // ---- step 4: once per call, over the compact arrays ---------------------------------------------------------------------------------------
-  const int rc_tail = redeem_keyring_tail(c, set, mv, mem, keys, nkeys, key_epochs, sign_key, wire, knul, 32, kp, st, sp, kidx, c_rng, rng_mode, cout.p, cst, okey);
+  const int rc_tail = redeem_tail_ring(c, set, mv, mem, keys, nkeys, key_epochs, sign_key, wire, knul, 32, kp, st, sp, kidx, c_rng, rng_mode, cout.p, cst, okey);
 
   // ---- step 5: the answers back to their lanes (also behind a failure of step 4: status[] is complete on return) ----------------------------
   std::vector<uint8_t> h_cst;

@@ -1,81 +1,44 @@
 // keyring_redeem_impl.inc — included by engine.hip after nullifier_impl.inc: the redemption step against a ring of issuer keys.
-// Composed as redeem_impl composes it (nullifier_impl.inc): ring verification -> check-and-insert with the verdicts as skip mask ->
-// sign what is left, each lane with the key `sign_key` names; the same failure contract (ACT_STATUS_NULLIFIER_UNDETERMINED,
-// ACT_STATUS_RECORDED_UNSIGNED, act_debug_fail_next_signs).  Membership in the nullifier set does not depend on the key.  No tiny form.
+// Ring verification, then redeem_tail (nullifier_impl.inc: the body every redeem entry point ends in, with its failure contract) over
+// the ring's steps: each lane is signed with the key `sign_key` names.  Membership in the nullifier set does not depend on the key.  No tiny form.
 // key_epochs (nullable, host memory, nkeys values): an accepted lane's nullifier is recorded under the epoch of the key it MATCHED --
 // out_key, as the ring verification leaves it, is the epoch index of the insert.
-// Everything behind verification, over arrays of n lanes in `mem` memory: st = the verdicts, out_key = the matched ring indices,
-// kp = enc(K'), the nullifiers at nul + i * nul_stride; sp and kidx are scratch of n bytes each.  Check-and-insert with the verdicts
-// as skip mask, then the signatures; status[] / out are complete on every return (the failure contract of the header).  Shared by
-// redeem_keyring_impl and by the admission calls (admit_impl.inc), which hand it the survivors' compact arrays.
-static int redeem_keyring_tail(act_ctx* c, act_nullifier_set* set, size_t n, int mem, const uint8_t* keys, int nkeys, const uint32_t* key_epochs, int sign_key, bool wire,
-                               const uint8_t* nul, size_t nul_stride, const uint8_t* kp, uint8_t* st, uint8_t* sp, uint8_t* kidx, const uint8_t* rng, int rng_mode,
-                               uint8_t* out, uint8_t* status, uint8_t* out_key) {
-  const size_t out_b = wire ? act_cbor_size(c, ACT_CBOR_REFUND) : 128;
-  const int rc_null = key_epochs ? act_nullifier_check_and_insert_epoch_batch(set, n, mem, nul, nul_stride, st, out_key, key_epochs, nkeys, sp)
-                                 : act_nullifier_check_and_insert_batch(set, n, mem, nul, nul_stride, st, sp);
-  std::string null_err;
-  if (rc_null) {
-    null_err = std::string("nullifier set: ") + act_nullifier_set_last_error(set);
-    if (rc_null == ACT_ERR_HIP) {
-      c->err = null_err + " (every verified lane is undetermined)";
-      if (mem == ACT_MEM_HOST) { for (size_t i = 0; i < n; i++) status[i] = st[i] ? st[i] : (uint8_t)ACT_STATUS_NULLIFIER_UNDETERMINED; memset(out, 0, n * out_b); }
-      else {
-        std::lock_guard<std::mutex> lk(c->mu);
-        (void)hipSetDevice(c->device);
-        hipLaunchKernelGGL(k_mark_undetermined_status, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, status, st, (uint32_t)n);
-        (void)hipMemsetAsync(out, 0, n * out_b, nullptr);
-        if (hipDeviceSynchronize() != hipSuccess) (void)hipGetLastError();
+// Arrays of n lanes in `mem` memory: st = the verdicts, out_key = the matched ring indices, kp = enc(K'), the nullifiers at
+// nul + i * nul_stride; sp and kidx are scratch of n bytes each.  The admission calls (admit_impl.inc) hand it the survivors' compact arrays.
+static int redeem_tail_ring(act_ctx* c, act_nullifier_set* set, size_t n, int mem, const uint8_t* keys, int nkeys, const uint32_t* key_epochs, int sign_key, bool wire,
+                            const uint8_t* nul, size_t nul_stride, const uint8_t* kp, uint8_t* st, uint8_t* sp, uint8_t* kidx, const uint8_t* rng, int rng_mode,
+                            uint8_t* out, uint8_t* status, uint8_t* out_key) {
+  return redeem_tail(c, set, n, mem, wire, st, sp, rng, rng_mode, out, status,
+    [&](const uint8_t* mask, uint8_t* spent) {
+      return key_epochs ? act_nullifier_check_and_insert_epoch_batch(set, n, mem, nul, nul_stride, mask, out_key, key_epochs, nkeys, spent)
+                        : act_nullifier_check_and_insert_batch(set, n, mem, nul, nul_stride, mask, spent);
+    },
+    [&] {      // the key every lane is signed with (out_key keeps what the lane matched)
+      if (mem == ACT_MEM_DEVICE) launch_ring_resolve_index(kidx, out_key, sign_key, (uint32_t)n, nullptr);
+      else for (size_t i = 0; i < n; i++) kidx[i] = sign_key >= 0 ? (uint8_t)sign_key : out_key[i];
+    },
+    [&](const uint8_t* verdict, const uint8_t* r, int r_mode, uint8_t* o, uint8_t* o_st) {
+      if (!wire) return act_refund_sign_keyring_batch(c, n, mem, keys, nkeys, kidx, kp, verdict, r, r_mode, o, o_st);
+      int rc_sign;
+      if (mem == ACT_MEM_HOST) {      // framed as act_refund_sign_cbor_batch frames: on the host workers, where the signatures landed
+        std::vector<uint8_t> rec(n * 128);
+        rc_sign = act_refund_sign_keyring_batch(c, n, mem, keys, nkeys, kidx, kp, verdict, r, r_mode, rec.data(), o_st);
+        if (!rc_sign) cbor_frame_refunds_host(cbor_layout(*cbor_type(ACT_CBOR_REFUND), c->L), n, rec.data(), o_st, o);
+        return rc_sign;
       }
-      return rc_null;
-    }
-  }
-  // the verdicts with the store's answers merged in, and the key every lane is signed with (out_key keeps what the lane matched)
-  if (mem == ACT_MEM_DEVICE) {
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCK(c, hipSetDevice(c->device));
-    hipLaunchKernelGGL(k_merge_double_spend, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, st, sp, (uint32_t)n);
-    launch_ring_resolve_index(kidx, out_key, sign_key, (uint32_t)n, nullptr);
-    if (hipDeviceSynchronize() != hipSuccess) { c->err = "k_merge_double_spend failed"; (void)hipGetLastError(); return ACT_ERR_HIP; }
-  } else {
-    for (size_t i = 0; i < n; i++) { st[i] = merge_spent(st[i], sp[i]); kidx[i] = sign_key >= 0 ? (uint8_t)sign_key : out_key[i]; }
-  }
-  ResolvedRng rr(c);
-  int rc_sign = rr.resolve(c, mem, st, n, rng, rng_mode);
-  const bool fail_sign = c->debug_fail_signs.load() > 0 && c->debug_fail_signs.fetch_sub(1) > 0;
-  if (!rc_sign) {
-    if (fail_sign) { rc_sign = ACT_ERR_HIP; c->err = "act_debug_fail_next_signs: simulated failure of the signature step"; }
-    else if (!wire) rc_sign = act_refund_sign_keyring_batch(c, n, mem, keys, nkeys, kidx, kp, st, rng, rng_mode, out, status);
-    else if (mem == ACT_MEM_HOST) {      // framed as act_refund_sign_cbor_batch frames: on the host workers, where the signatures landed
-      std::vector<uint8_t> rec(n * 128);
-      rc_sign = act_refund_sign_keyring_batch(c, n, mem, keys, nkeys, kidx, kp, st, rng, rng_mode, rec.data(), status);
-      if (!rc_sign) cbor_frame_refunds_host(cbor_layout(*cbor_type(ACT_CBOR_REFUND), c->L), n, rec.data(), status, out);
-    } else {
       DevTmp rec(c);
       rc_sign = rec.alloc(n * 128);
-      if (!rc_sign) rc_sign = act_refund_sign_keyring_batch(c, n, mem, keys, nkeys, kidx, kp, st, rng, rng_mode, rec.p, status);
-      if (!rc_sign) rc_sign = act_cbor_encode_batch(c, ACT_CBOR_REFUND, n, mem, rec.p, out);
+      if (!rc_sign) rc_sign = act_refund_sign_keyring_batch(c, n, mem, keys, nkeys, kidx, kp, verdict, r, r_mode, rec.p, o_st);
+      if (!rc_sign) rc_sign = act_cbor_encode_batch(c, ACT_CBOR_REFUND, n, mem, rec.p, o);
       if (!rc_sign) {
         std::lock_guard<std::mutex> lk(c->mu);
         (void)hipSetDevice(c->device);
-        hipLaunchKernelGGL(k_cbor_zero_failed, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->slots[0].stream, out, (uint32_t)out_b, status, (uint32_t)n);
+        const uint32_t out_b = (uint32_t)act_cbor_size(c, ACT_CBOR_REFUND);
+        hipLaunchKernelGGL(k_cbor_zero_failed, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->slots[0].stream, o, out_b, o_st, (uint32_t)n);
         if (hipStreamSynchronize(c->slots[0].stream) != hipSuccess) { (void)hipGetLastError(); c->err = "k_cbor_zero_failed failed"; rc_sign = ACT_ERR_HIP; }
       }
-    }
-  }
-  if (rc_sign) {
-    if (mem == ACT_MEM_HOST) { for (size_t i = 0; i < n; i++) status[i] = st[i] == 0 ? (uint8_t)ACT_STATUS_RECORDED_UNSIGNED : st[i]; memset(out, 0, n * out_b); }
-    else {
-      std::lock_guard<std::mutex> lk(c->mu);
-      (void)hipSetDevice(c->device);
-      hipLaunchKernelGGL(k_mark_recorded_unsigned, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, status, st, (uint32_t)n);
-      (void)hipMemsetAsync(out, 0, n * out_b, nullptr);
-      if (hipDeviceSynchronize() != hipSuccess) (void)hipGetLastError();
-    }
-    return rc_sign;
-  }
-  if (rc_null) c->err = null_err;
-  return rc_null;
+      return rc_sign;
+    });
 }
 
 // what the ring redeem calls refuse as a whole before any GPU work (no status written, nothing recorded): shared with admit_impl.inc
@@ -115,7 +78,7 @@ static int redeem_keyring_impl(act_ctx* c, act_nullifier_set* set, size_t n, int
   if (wire) { RingSel sel{keys, nkeys, out_key}; rc = verify_spend_cbor_impl(c, n, mem, nullptr, cbor, offsets, st, kp, nul, &sel); }
   else rc = act_verify_spend_keyring_batch(c, n, mem, keys, nkeys, proof, st, out_key, kp);
   if (rc) return rc;
-  return redeem_keyring_tail(c, set, n, mem, keys, nkeys, key_epochs, sign_key, wire, wire ? nul : proof, wire ? 32 : pb, kp, st, sp, kidx, rng, rng_mode, out, status, out_key);
+  return redeem_tail_ring(c, set, n, mem, keys, nkeys, key_epochs, sign_key, wire, wire ? nul : proof, wire ? 32 : pb, kp, st, sp, kidx, rng, rng_mode, out, status, out_key);
 }
 
 extern "C" int act_redeem_keyring_batch(act_ctx* c, act_nullifier_set* set, size_t n, int mem, const uint8_t* keys, int nkeys, int sign_key, const uint8_t* proof,

@@ -18,7 +18,9 @@
 #include <vector>
 #include "../../include/act_mi355x.h"
 #include "rng_source.h"
+#include "merge_spent.h"
 #include "node_nullifier.h"
+#include "node_redeem.h"
 
 struct act_node {
   std::vector<act_ctx*> ctx;
@@ -55,7 +57,7 @@ void small_call_err(act_node* nd, act_ctx* c) { const std::string text = act_las
 namespace {
 
 struct Shard { size_t off, m; };
-struct Piece { size_t k, off, m; int rc; };       // lanes [off, off + m) ran (or were to run: k == SIZE_MAX) on context k with result rc
+using namespace act_node_dispatch;      // Piece, at, count_zero (node_redeem.h)
 constexpr size_t kMinBalanceLanes = 4096;         // per device and piece: below this a call is latency, not throughput
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
@@ -149,8 +151,6 @@ int run(act_node* nd, size_t n, F fn, std::vector<Piece>* pieces = nullptr) {
   }
   return first_rc;
 }
-inline const uint8_t* at(const uint8_t* p, size_t off, size_t rec) { return p ? p + off * rec : nullptr; }
-inline uint8_t* at(uint8_t* p, size_t off, size_t rec) { return p ? p + off * rec : nullptr; }
 
 // accepted lanes in front of any lane: counts per block of 4096 lanes, the rest counted on demand
 struct AcceptedBefore {
@@ -313,7 +313,6 @@ static int refund_sign_locked(act_node* nd, size_t n, const uint8_t sk[64], cons
                 : act_refund_sign_batch(nd->ctx[k], m, ACT_MEM_HOST, sk, at(kprime, off, 32), checked.data() + off, r, rng_mode, at(out, off, out_rec), status + off);
   }, pieces);
 }
-static size_t count_zero(const uint8_t* st, size_t n) { size_t a = 0; for (size_t i = 0; i < n; i++) a += st[i] == 0; return a; }
 static int refund_sign_any(act_node* nd, size_t n, const uint8_t sk[64], const uint8_t* kprime, const uint8_t* status_in, const uint8_t* rng,
                            int rng_mode, bool cbor, uint8_t* out, uint8_t* status) {
   if (!nd || !sk || !rng || (n && (!kprime || !status_in || !out || !status))) return ACT_ERR_ARG;
@@ -432,13 +431,13 @@ int act_node_refund_cbor_batch(act_node* nd, size_t n, const uint8_t sk[64], con
   return refund_sign_any(nd, n, sk, kprime.data(), verdict.data(), rng, rng_mode, true, out_refund_cbor, status);
 }
 
-// The dispatcher for node forms that live in translation units of their own (node_issue_wire.cpp): `run` over the handle, under its
-// lock, fn(context, off, m) per piece.  (The CPU test builds link this file against a mock engine that has only the single-GPU calls used here.)
+// The dispatcher for node forms that live in translation units of their own (node_issue_wire.cpp, node_keyring.cpp): `run` over the
+// handle, under its lock, fn(context, off, m) per piece.  (The CPU test builds link this file against a mock engine that has only the single-GPU calls used here.)
 }  // extern "C"
 namespace act_node_dispatch {
-int run_pieces(act_node* nd, size_t n, const std::function<int(act_ctx*, size_t, size_t)>& fn) {
+int run_pieces(act_node* nd, size_t n, const std::function<int(act_ctx*, size_t, size_t)>& fn, std::vector<Piece>* pieces) {
   std::lock_guard<std::mutex> node_lock(nd->mu);
-  return run(nd, n, [&](size_t k, size_t off, size_t m) { return fn(nd->ctx[k], off, m); });
+  return run(nd, n, [&](size_t k, size_t off, size_t m) { return fn(nd->ctx[k], off, m); }, pieces);
 }
 }  // namespace act_node_dispatch
 extern "C" {
@@ -619,14 +618,35 @@ int act_node_nullifier_check_and_insert_batch(act_node_nullifier_set* ns, size_t
 
 }  // extern "C"
 
+// (node_redeem.h says what this is)
+int act_node_dispatch::redeem_tail(act_node* nd, act_node_nullifier_set* set, size_t n, size_t out_rec, uint8_t* verdict, const uint8_t* rng, int rng_mode, uint8_t* out,
+                                   uint8_t* status, const NullFn& null_step, const SignFn& sign_step) {
+  std::vector<uint8_t> spent(n);
+  const int rc_null = null_step(verdict, spent.data());
+  for (size_t i = 0; i < n; i++) verdict[i] = merge_spent(verdict[i], spent[i]);
+  // the caller's generator is touched only now, and only for the lanes that are signed
+  act::DrawnRng drawn;
+  int rc_sign = drawn.resolve(rng, rng_mode, rng_mode == ACT_RNG_CALLBACK ? count_zero(verdict, n) : 0);
+  std::vector<Piece> pieces;
+  if (!rc_sign) rc_sign = sign_step(verdict, rng, rng_mode, &pieces);
+  else pieces.push_back({(size_t)-1, 0, n, rc_sign});
+  if (rc_sign) {
+    for (const Piece& q : pieces) {
+      if (!q.rc) continue;
+      for (size_t i = q.off; i < q.off + q.m; i++) status[i] = verdict[i] == 0 ? ACT_STATUS_RECORDED_UNSIGNED : verdict[i];
+      memset(out + q.off * out_rec, 0, q.m * out_rec);
+    }
+    return rc_sign;
+  }
+  if (rc_null) { std::lock_guard<std::mutex> node_lock(nd->mu); set_node_err(nd, std::string("nullifier set: ") + act_node_nullifier_set_last_error(set)); }
+  return rc_null;
+}
+
 // The issuer's whole redemption step over the GPUs of a node (act_redeem_batch's meaning, include/act_mi355x.h): verification of
 // every lane, the node-level nullifier set over the whole batch in lane order (verdicts as skip mask), then the signatures --
 // ACT_RNG_SEQUENTIAL / ACT_RNG_CALLBACK draw only for lanes that are signed, from one stream, exactly as the sequential loop would.
 // Records in / records out (act_node_redeem_batch) and wire bytes in / wire bytes out (act_node_redeem_cbor_batch) share this body.
-// Failures after verification never lose a decision (same contract as act_redeem_batch): a device of the nullifier set that
-// fails leaves ITS lanes ACT_STATUS_NULLIFIER_UNDETERMINED (not recorded, not signed) while every other lane is finished; a GPU
-// that fails while signing leaves the lanes of ITS pieces that were to be signed ACT_STATUS_RECORDED_UNSIGNED (nullifier recorded,
-// refund owed); status[] and the output are complete for all other lanes and the error code says that something was left over.
+// Everything behind verification, and what a failure there leaves, is act_node_dispatch::redeem_tail (node_redeem.h).
 static int node_redeem(act_node* nd, act_node_nullifier_set* set, size_t n, const uint8_t sk[64], const uint8_t* proof, const uint8_t* cbor,
                        const uint64_t* offsets, const uint8_t* rng, int rng_mode, uint8_t* out, uint8_t* status) {
   const bool wire = cbor != nullptr;
@@ -649,37 +669,23 @@ static int node_redeem(act_node* nd, act_node_nullifier_set* set, size_t n, cons
     if (rc) { small_call_err(nd, c); return rc; }
     const int rc_null = act_node_nullifier_check_and_insert_batch(set, n, wire ? nl.data() : proof, wire ? 32 : pb, st.data(), sp.data());
     for (size_t i = 0; i < n; i++) {
-      if (st[i] == 0 && sp[i]) st[i] = sp[i] == 1 ? ACT_STATUS_DOUBLE_SPEND : ACT_STATUS_NULLIFIER_UNDETERMINED;
+      st[i] = merge_spent(st[i], sp[i]);
       if (st[i] == 0) memcpy(out + i * out_rec, rec.data() + i * out_rec, out_rec); else memset(out + i * out_rec, 0, out_rec);
       status[i] = st[i];
     }
     if (rc_null) { std::lock_guard<std::mutex> node_lock(nd->mu); set_node_err(nd, std::string("nullifier set: ") + act_node_nullifier_set_last_error(set)); }
     return rc_null;
   }
-  std::vector<uint8_t> kprime(n * 32), verdict(n), spent(n), nul(wire ? n * 32 : 0);
+  std::vector<uint8_t> kprime(n * 32), verdict(n), nul(wire ? n * 32 : 0);
   int rc = wire ? act_node_verify_spend_cbor_keys_batch(nd, n, sk, cbor, offsets, verdict.data(), kprime.data(), nul.data())
                 : act_node_verify_spend_batch(nd, n, sk, proof, verdict.data(), kprime.data());
   if (rc) return rc;
-  const int rc_null = act_node_nullifier_check_and_insert_batch(set, n, wire ? nul.data() : proof, wire ? 32 : pb, verdict.data(), spent.data());
-  for (size_t i = 0; i < n; i++)
-    if (verdict[i] == 0 && spent[i]) verdict[i] = spent[i] == 1 ? ACT_STATUS_DOUBLE_SPEND : ACT_STATUS_NULLIFIER_UNDETERMINED;
-  // the caller's generator is touched only now, and only for the lanes that are signed
-  act::DrawnRng drawn;
-  int rc_sign = drawn.resolve(rng, rng_mode, rng_mode == ACT_RNG_CALLBACK ? count_zero(verdict.data(), n) : 0);
-  std::lock_guard<std::mutex> node_lock(nd->mu);
-  std::vector<Piece> pieces;
-  if (!rc_sign) rc_sign = refund_sign_locked(nd, n, sk, kprime.data(), verdict.data(), rng, rng_mode, wire, out, status, &pieces);
-  else pieces.push_back({(size_t)-1, 0, n, rc_sign});
-  if (rc_sign) {
-    for (const Piece& q : pieces) {
-      if (!q.rc) continue;
-      for (size_t i = q.off; i < q.off + q.m; i++) status[i] = verdict[i] == 0 ? ACT_STATUS_RECORDED_UNSIGNED : verdict[i];
-      memset(out + q.off * out_rec, 0, q.m * out_rec);
-    }
-    return rc_sign;
-  }
-  if (rc_null) set_node_err(nd, std::string("nullifier set: ") + act_node_nullifier_set_last_error(set));
-  return rc_null;
+  return act_node_dispatch::redeem_tail(nd, set, n, out_rec, verdict.data(), rng, rng_mode, out, status,
+    [&](const uint8_t* mask, uint8_t* spent) { return act_node_nullifier_check_and_insert_batch(set, n, wire ? nul.data() : proof, wire ? 32 : pb, mask, spent); },
+    [&](const uint8_t* checked, const uint8_t* r, int r_mode, std::vector<Piece>* pieces) {
+      std::lock_guard<std::mutex> node_lock(nd->mu);
+      return refund_sign_locked(nd, n, sk, kprime.data(), checked, r, r_mode, wire, out, status, pieces);
+    });
 }
 extern "C" int act_node_redeem_batch(act_node* nd, act_node_nullifier_set* set, size_t n, const uint8_t sk[64], const uint8_t* proof, const uint8_t* rng,
                                      int rng_mode, uint8_t* out_refund, uint8_t* status) {

@@ -5,16 +5,11 @@
 #include <functional>
 #include <vector>
 #include "../../include/act_mi355x.h"
+#include "node_redeem.h"      // run_pieces, at, count_zero
 #include "rng_source.h"
 
-namespace act_node_dispatch {
-int run_pieces(act_node* nd, size_t n, const std::function<int(act_ctx*, size_t, size_t)>& fn);      // node.cpp
-}
-
 namespace {
-using act_node_dispatch::run_pieces;
-inline const uint8_t* at(const uint8_t* p, size_t off, size_t rec) { return p ? p + off * rec : nullptr; }
-inline uint8_t* at(uint8_t* p, size_t off, size_t rec) { return p ? p + off * rec : nullptr; }
+using namespace act_node_dispatch;
 // accepted lanes in front of every lane (ACT_RNG_SEQUENTIAL across pieces: a piece signs from its own offset into the stream)
 std::vector<size_t> accepted_before(const uint8_t* st, size_t n) {
   std::vector<size_t> a(n + 1, 0);
@@ -32,7 +27,6 @@ int issue_sign_cbor_pieces(act_node* nd, size_t n, const uint8_t sk[64], const u
                                      rng + (rng_mode == ACT_RNG_PER_LANE ? off : before[off]) * 128, rng_mode, at(out_resp_cbor, off, rl), status + off);
   });
 }
-size_t count_zero(const uint8_t* st, size_t n) { size_t a = 0; for (size_t i = 0; i < n; i++) a += st[i] == 0; return a; }
 }  // namespace
 
 extern "C" {

@@ -3,47 +3,35 @@
 // single-GPU calls node.cpp itself uses.  The pieces are cut by node.cpp's dispatcher (act_node_dispatch::run_pieces: weights, tail,
 // the handle's lock); out_key is cut per piece like status.
 //
-// Redemption is composed as node.cpp's node_redeem composes it: ring verification of every piece, the NODE-level nullifier set over
-// the whole batch in lane order (verdicts as skip mask; the set does not depend on the key), then the signatures with the per-lane
-// key index -- check -> count -> sign, so that ACT_RNG_SEQUENTIAL / ACT_RNG_CALLBACK hand out one stream exactly as the sequential loop
-// would.  The wire form reads the messages with act_cbor_decode_batch (its statuses are from_cbor's, the ones act_redeem_cbor_batch
+// Redemption: ring verification of every piece, then the body node.cpp's node_redeem ends in too (act_node_dispatch::redeem_tail,
+// node_redeem.h): the NODE-level nullifier set over the whole batch in lane order (verdicts as skip mask; the set does not depend on
+// the key), then the signatures, here with the per-lane key index -- check -> count -> sign, so that ACT_RNG_SEQUENTIAL /
+// ACT_RNG_CALLBACK hand out one stream exactly as the sequential loop would.  The wire form reads the messages with act_cbor_decode_batch (its statuses are from_cbor's, the ones act_redeem_cbor_batch
 // reports, in the codec's own numbering), block by block so that the host never holds more than a block of records, and frames with act_cbor_encode_batch.
 #include <algorithm>
 #include <cstring>
 #include <functional>
-#include <mutex>
 #include <string>
 #include <vector>
 #include "../../include/act_mi355x.h"
 #include "node_keyring.h"
-#include "rng_source.h"
-
-namespace act_node_dispatch {
-int run_pieces(act_node* nd, size_t n, const std::function<int(act_ctx*, size_t, size_t)>& fn);      // node.cpp
-}
+#include "node_redeem.h"
 
 namespace {
-using act_node_dispatch::run_pieces;
-inline const uint8_t* at(const uint8_t* p, size_t off, size_t rec) { return p ? p + off * rec : nullptr; }
-inline uint8_t* at(uint8_t* p, size_t off, size_t rec) { return p ? p + off * rec : nullptr; }
-size_t count_zero(const uint8_t* st, size_t n) { size_t a = 0; for (size_t i = 0; i < n; i++) a += st[i] == 0; return a; }
+using namespace act_node_dispatch;      // run_pieces, Piece, at (node_redeem.h)
 bool ring_ok(const uint8_t* keys, int nkeys) { return keys && nkeys >= 1 && nkeys <= ACT_KEYRING_MAX; }
 
-struct FailedPiece { size_t off, m; };
 // The sign half over the pieces.  rng is bytes.  A lane counts for the stream iff it is signed: status_in 0 AND key_index below nkeys.
-// `failed` (nullable): the pieces whose call failed (redeem marks their lanes RECORDED_UNSIGNED).
+// `pieces` (nullable): as run_pieces fills it.
 int sign_pieces(act_node* nd, size_t n, const uint8_t* keys, int nkeys, const uint8_t* key_index, const uint8_t* kprime, const uint8_t* status_in,
-                const uint8_t* rng, int rng_mode, uint8_t* out_refund, uint8_t* status, std::vector<FailedPiece>* failed) {
+                const uint8_t* rng, int rng_mode, uint8_t* out_refund, uint8_t* status, std::vector<Piece>* pieces) {
   const std::vector<uint8_t> checked(status_in, status_in + n), kidx(key_index, key_index + n);
   std::vector<size_t> before(n + 1, 0);
   for (size_t i = 0; i < n; i++) before[i + 1] = before[i] + (checked[i] == 0 && kidx[i] < nkeys);
-  std::mutex mu;
   return run_pieces(nd, n, [&](act_ctx* ctx, size_t off, size_t m) {
-    const int rc = act_refund_sign_keyring_batch(ctx, m, ACT_MEM_HOST, keys, nkeys, kidx.data() + off, at(kprime, off, 32), checked.data() + off,
-                                                 rng + (rng_mode == ACT_RNG_PER_LANE ? off : before[off]) * 128, rng_mode, at(out_refund, off, 128), status + off);
-    if (rc && failed) { std::lock_guard<std::mutex> lk(mu); failed->push_back({off, m}); }
-    return rc;
-  });
+    return act_refund_sign_keyring_batch(ctx, m, ACT_MEM_HOST, keys, nkeys, kidx.data() + off, at(kprime, off, 32), checked.data() + off,
+                                         rng + (rng_mode == ACT_RNG_PER_LANE ? off : before[off]) * 128, rng_mode, at(out_refund, off, 128), status + off);
+  }, pieces);
 }
 
 constexpr size_t WIRE_BLOCK = (size_t)1 << 16;      // messages decoded into host records at a time (1.1 GB at L = 128)
@@ -61,7 +49,7 @@ int act_node_keyring::redeem(act_node* nd, act_node_nullifier_set* set, size_t n
   act_ctx* c0 = act_node_ctx(nd, 0);
   if (n == 0) return act_verify_spend_keyring_batch(c0, 0, ACT_MEM_HOST, keys, nkeys, nullptr, nullptr, nullptr, nullptr);      // a bad ring fails the call whatever n
   const size_t pb = act_spend_proof_bytes(c0), out_rec = wire ? act_cbor_size(c0, ACT_CBOR_REFUND) : 128;
-  std::vector<uint8_t> kprime(n * 32), verdict(n), spent(n), nul(wire ? n * 32 : 0);
+  std::vector<uint8_t> kprime(n * 32), verdict(n), nul(wire ? n * 32 : 0);
   int rc;
   if (!wire) {
     rc = run_pieces(nd, n, [&](act_ctx* ctx, size_t off, size_t m) {
@@ -93,36 +81,24 @@ int act_node_keyring::redeem(act_node* nd, act_node_nullifier_set* set, size_t n
       }
     }
   }
-  const int rc_null = null_step ? (*null_step)(set, n, wire ? nul.data() : proof, wire ? 32 : pb, verdict.data(), out_key, spent.data())
-                                : act_node_nullifier_check_and_insert_batch(set, n, wire ? nul.data() : proof, wire ? 32 : pb, verdict.data(), spent.data());
-  std::vector<uint8_t> kidx(n);
-  for (size_t i = 0; i < n; i++) {
-    if (verdict[i] == 0 && spent[i]) verdict[i] = spent[i] == 1 ? ACT_STATUS_DOUBLE_SPEND : ACT_STATUS_NULLIFIER_UNDETERMINED;
-    kidx[i] = sign_key >= 0 ? (uint8_t)sign_key : out_key[i];
-  }
-  // the caller's generator is touched only now, and only for the lanes that are signed
-  act::DrawnRng drawn;
-  int rc_sign = drawn.resolve(rng, rng_mode, rng_mode == ACT_RNG_CALLBACK ? count_zero(verdict.data(), n) : 0);
-  std::vector<FailedPiece> failed;
-  std::vector<uint8_t> rec(wire ? n * 128 : 0);
-  if (!rc_sign) rc_sign = sign_pieces(nd, n, keys, nkeys, kidx.data(), kprime.data(), verdict.data(), rng, rng_mode, wire ? rec.data() : out, status, &failed);
-  else failed.push_back({0, n});
-  if (!rc_sign && wire) {
-    rc_sign = run_pieces(nd, n, [&](act_ctx* ctx, size_t off, size_t m) {
-      return act_cbor_encode_batch(ctx, ACT_CBOR_REFUND, m, ACT_MEM_HOST, rec.data() + off * 128, out + off * out_rec);
+  const uint8_t* nullifiers = wire ? nul.data() : proof;
+  const size_t stride = wire ? 32 : pb;
+  return act_node_dispatch::redeem_tail(nd, set, n, out_rec, verdict.data(), rng, rng_mode, out, status,
+    [&](const uint8_t* mask, uint8_t* spent) {
+      return null_step ? (*null_step)(set, n, nullifiers, stride, mask, out_key, spent) : act_node_nullifier_check_and_insert_batch(set, n, nullifiers, stride, mask, spent);
+    },
+    [&](const uint8_t* checked, const uint8_t* r, int r_mode, std::vector<Piece>* pieces) {
+      std::vector<uint8_t> kidx(n), rec(wire ? n * 128 : 0);
+      for (size_t i = 0; i < n; i++) kidx[i] = sign_key >= 0 ? (uint8_t)sign_key : out_key[i];
+      int rc_sign = sign_pieces(nd, n, keys, nkeys, kidx.data(), kprime.data(), checked, r, r_mode, wire ? rec.data() : out, status, pieces);
+      if (rc_sign || !wire) return rc_sign;
+      rc_sign = run_pieces(nd, n, [&](act_ctx* ctx, size_t off, size_t m) {
+        return act_cbor_encode_batch(ctx, ACT_CBOR_REFUND, m, ACT_MEM_HOST, rec.data() + off * 128, out + off * out_rec);
+      });
+      if (rc_sign) pieces->push_back({(size_t)-1, 0, n, rc_sign});      // no lane has its message: every signature is owed
+      else for (size_t i = 0; i < n; i++) if (status[i]) memset(out + i * out_rec, 0, out_rec);      // an unsigned lane's slot is all zero
+      return rc_sign;
     });
-    if (rc_sign) failed.push_back({0, n});
-    else for (size_t i = 0; i < n; i++) if (status[i]) memset(out + i * out_rec, 0, out_rec);      // an unsigned lane's slot is all zero
-  }
-  if (rc_sign) {
-    if (failed.empty()) failed.push_back({0, n});
-    for (const FailedPiece& q : failed) {
-      for (size_t i = q.off; i < q.off + q.m; i++) status[i] = verdict[i] == 0 ? ACT_STATUS_RECORDED_UNSIGNED : verdict[i];
-      memset(out + q.off * out_rec, 0, q.m * out_rec);
-    }
-    return rc_sign;
-  }
-  return rc_null;
 }
 using act_node_keyring::redeem;
 

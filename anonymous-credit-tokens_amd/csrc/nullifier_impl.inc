@@ -25,6 +25,7 @@
 // table starts at the low half of the 64-bit hash, the persistent table at the high half.
 
 #include "null_probe.h"      // null_load_key, null_hash, null_eq, NullSalt, null_probe_contains
+#include "merge_spent.h"     // merge_spent
 
 namespace {
 
@@ -524,11 +525,6 @@ int act_nullifier_contains_batch(act_nullifier_set* s, size_t n, int mem, const 
 // before it calls refund and unwraps: for valid proofs the two orders give the same result; for invalid ones the example panics.)
 // Composed from the public entry points above: verify -> check-and-insert with the verdicts as skip mask -> sign the rest.
 namespace {
-// verdict 0 + spent 1 -> DoubleSpendError; verdict 0 + undetermined -> ACT_STATUS_NULLIFIER_UNDETERMINED (neither recorded nor signed)
-__device__ __host__ inline uint8_t merge_spent(uint8_t verdict, uint8_t spent) {
-  if (verdict != 0 || spent == 0) return verdict;
-  return spent == 1 ? (uint8_t)ACT_STATUS_DOUBLE_SPEND : (uint8_t)ACT_STATUS_NULLIFIER_UNDETERMINED;
-}
 __global__ void __launch_bounds__(256) k_merge_double_spend(uint8_t* status, const uint8_t* spent, uint32_t n) {
   uint32_t i = blockIdx.x * 256 + threadIdx.x;
   if (i < n) status[i] = merge_spent(status[i], spent[i]);
@@ -556,6 +552,59 @@ __global__ void __launch_bounds__(256) k_mark_undetermined_status(uint8_t* statu
   if (i < n) status[i] = verdict[i] ? verdict[i] : (uint8_t)ACT_STATUS_NULLIFIER_UNDETERMINED;
 }
 }  // namespace
+
+// Everything behind verification, ONCE for every redeem entry point (one key here; ring, epochs and admission: keyring_redeem_impl.inc),
+// over arrays of n lanes in `mem` memory: st = the verdicts, sp = scratch for the store's answers.  What differs is handed in:
+//   null_step(skip_mask = st, out_spent = sp) -> rc     the plain check-and-insert or the epoch insert
+//   beside_merge()                                      the caller's share of the merge's pass: in device memory it runs under c->mu and
+//                                                       may launch on the null stream, in front of the merge's synchronisation
+//   sign_step(st, rng, rng_mode, out, status) -> rc     the signatures, rng already resolved, framed or not as the call's output is
+template <class NullStep, class BesideMerge, class SignStep>
+static int redeem_tail(act_ctx* c, act_nullifier_set* set, size_t n, int mem, bool wire, uint8_t* st, uint8_t* sp, const uint8_t* rng, int rng_mode,
+                       uint8_t* out, uint8_t* status, NullStep null_step, BesideMerge beside_merge, SignStep sign_step) {
+  const size_t out_b = wire ? act_cbor_size(c, ACT_CBOR_REFUND) : 128;
+  const int rc_null = null_step(st, sp);
+  // a step failed as a whole: every lane that verified says `what`, the others their verdict, and there is no output.  (Device memory:
+  // best effort on a device that may just have failed a call -- the header promises a status for every lane.)
+  auto give_up = [&](uint8_t what, void (*k_mark)(uint8_t*, const uint8_t*, uint32_t)) {
+    if (mem == ACT_MEM_HOST) { for (size_t i = 0; i < n; i++) status[i] = st[i] ? st[i] : what; memset(out, 0, n * out_b); return; }
+    std::lock_guard<std::mutex> lk(c->mu);
+    (void)hipSetDevice(c->device);
+    hipLaunchKernelGGL(k_mark, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, status, st, (uint32_t)n);
+    (void)hipMemsetAsync(out, 0, n * out_b, nullptr);
+    if (hipDeviceSynchronize() != hipSuccess) (void)hipGetLastError();
+  };
+  std::string null_err;
+  if (rc_null) {
+    null_err = std::string("nullifier set: ") + act_nullifier_set_last_error(set);
+    if (rc_null == ACT_ERR_HIP) {           // the device itself failed: no per-lane answer can be trusted; nothing is signed
+      c->err = null_err + " (every verified lane is undetermined)";
+      give_up(ACT_STATUS_NULLIFIER_UNDETERMINED, k_mark_undetermined_status);
+      return rc_null;
+    }
+  }
+  if (mem == ACT_MEM_DEVICE) {
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIPCK(c, hipSetDevice(c->device));
+    hipLaunchKernelGGL(k_merge_double_spend, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, st, sp, (uint32_t)n);
+    beside_merge();
+    if (hipDeviceSynchronize() != hipSuccess) { c->err = "k_merge_double_spend failed"; (void)hipGetLastError(); return ACT_ERR_HIP; }
+  } else {
+    for (size_t i = 0; i < n; i++) st[i] = merge_spent(st[i], sp[i]);
+    beside_merge();
+  }
+  // the generator is touched only now, for the lanes that are signed (the reference draws e, alpha after its checks, src/lib.rs:842-852)
+  ResolvedRng rr(c);
+  int rc_sign = rr.resolve(c, mem, st, n, rng, rng_mode);
+  const bool fail_sign = c->debug_fail_signs.load() > 0 && c->debug_fail_signs.fetch_sub(1) > 0;      // error-path test hook (act_debug_fail_next_signs)
+  if (!rc_sign) {
+    if (fail_sign) { rc_sign = ACT_ERR_HIP; c->err = "act_debug_fail_next_signs: simulated failure of the signature step"; }
+    else rc_sign = sign_step(st, rng, rng_mode, out, status);
+  }
+  if (rc_sign) { give_up(ACT_STATUS_RECORDED_UNSIGNED, k_mark_recorded_unsigned); return rc_sign; }      // the nullifiers ARE recorded: the refunds are owed
+  if (rc_null) c->err = null_err;
+  return rc_null;
+}
 
 static int redeem_impl(act_ctx* c, act_nullifier_set* set, size_t n, int mem, const uint8_t sk[64], const uint8_t* proof, const uint8_t* cbor,
                        const uint64_t* offsets, const uint8_t* rng, int rng_mode, uint8_t* out, uint8_t* status) {
@@ -600,57 +649,16 @@ static int redeem_impl(act_ctx* c, act_nullifier_set* set, size_t n, int mem, co
   if (mem == ACT_MEM_DEVICE) { if ((rc = d.alloc(n * per_lane))) return rc; base = d.p; }
   else { h.resize(n * per_lane); base = h.data(); }
   uint8_t *kp = base, *nul = base + n * 32, *st = base + n * (per_lane - 2), *sp = st + n;
-  auto set_err = [&](const std::string& m) { c->err = m; };
   rc = wire ? verify_spend_cbor_impl(c, n, mem, sk, cbor, offsets, st, kp, nul) : act_verify_spend_batch(c, n, mem, sk, proof, st, kp);
   if (rc) return rc;
-  // records: `k` is the first field of a SpendProof record; wire: the 32-byte fields the verification call gathered
-  const int rc_null = act_nullifier_check_and_insert_batch(set, n, mem, wire ? nul : proof, wire ? 32 : pb, st, sp);
-  std::string null_err;
-  if (rc_null) {
-    null_err = std::string("nullifier set: ") + act_nullifier_set_last_error(set);
-    if (rc_null == ACT_ERR_HIP) {           // the device itself failed: no per-lane answer can be trusted; nothing is signed
-      set_err(null_err + " (every verified lane is undetermined)");
-      if (mem == ACT_MEM_HOST) { for (size_t i = 0; i < n; i++) status[i] = st[i] ? st[i] : (uint8_t)ACT_STATUS_NULLIFIER_UNDETERMINED; memset(out, 0, n * out_b); }
-      else {      // best effort on a device that has just failed a call: the header promises a status for every lane
-        std::lock_guard<std::mutex> lk(c->mu);
-        (void)hipSetDevice(c->device);
-        hipLaunchKernelGGL(k_mark_undetermined_status, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, status, st, (uint32_t)n);
-        (void)hipMemsetAsync(out, 0, n * out_b, nullptr);
-        if (hipDeviceSynchronize() != hipSuccess) (void)hipGetLastError();
-      }
-      return rc_null;
-    }
-  }
-  if (mem == ACT_MEM_DEVICE) {
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIPCK(c, hipSetDevice(c->device));
-    hipLaunchKernelGGL(k_merge_double_spend, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, st, sp, (uint32_t)n);
-    if (hipDeviceSynchronize() != hipSuccess) { c->err = "k_merge_double_spend failed"; (void)hipGetLastError(); return ACT_ERR_HIP; }
-  } else {
-    for (size_t i = 0; i < n; i++) st[i] = merge_spent(st[i], sp[i]);
-  }
-  // the generator is touched only now, for the lanes that are signed (the reference draws e, alpha after its checks, src/lib.rs:842-852)
-  ResolvedRng rr(c);
-  int rc_sign = rr.resolve(c, mem, st, n, rng, rng_mode);
-  const bool fail_sign = c->debug_fail_signs.load() > 0 && c->debug_fail_signs.fetch_sub(1) > 0;      // error-path test hook (act_debug_fail_next_signs)
-  if (!rc_sign) {
-    if (fail_sign) { rc_sign = ACT_ERR_HIP; set_err("act_debug_fail_next_signs: simulated failure of the signature step"); }
-    else rc_sign = wire ? act_refund_sign_cbor_batch(c, n, mem, sk, kp, st, rng, rng_mode, out, status)
-                        : act_refund_sign_batch(c, n, mem, sk, kp, st, rng, rng_mode, out, status);
-  }
-  if (rc_sign) {
-    if (mem == ACT_MEM_HOST) { for (size_t i = 0; i < n; i++) status[i] = st[i] == 0 ? (uint8_t)ACT_STATUS_RECORDED_UNSIGNED : st[i]; memset(out, 0, n * out_b); }
-    else {
-      std::lock_guard<std::mutex> lk(c->mu);
-      (void)hipSetDevice(c->device);
-      hipLaunchKernelGGL(k_mark_recorded_unsigned, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, status, st, (uint32_t)n);
-      (void)hipMemsetAsync(out, 0, n * out_b, nullptr);
-      if (hipDeviceSynchronize() != hipSuccess) (void)hipGetLastError();
-    }
-    return rc_sign;
-  }
-  if (rc_null) set_err(null_err);
-  return rc_null;
+  return redeem_tail(c, set, n, mem, wire, st, sp, rng, rng_mode, out, status,
+                     [&](const uint8_t* mask, uint8_t* spent) {      // records: `k` is the first field of a SpendProof record; wire: the fields the verification call gathered
+                       return act_nullifier_check_and_insert_batch(set, n, mem, wire ? nul : proof, wire ? 32 : pb, mask, spent);
+                     },
+                     [] {},
+                     [&](const uint8_t* verdict, const uint8_t* r, int r_mode, uint8_t* o, uint8_t* o_st) {
+                       return wire ? act_refund_sign_cbor_batch(c, n, mem, sk, kp, verdict, r, r_mode, o, o_st) : act_refund_sign_batch(c, n, mem, sk, kp, verdict, r, r_mode, o, o_st);
+                     });
 }
 
 extern "C" int act_redeem_batch(act_ctx* c, act_nullifier_set* set, size_t n, int mem, const uint8_t sk[64], const uint8_t* proof, const uint8_t* rng,

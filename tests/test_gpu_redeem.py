@@ -204,3 +204,88 @@ def test_redeem_failures_keep_every_decision(engine_factory, oracle, bench_param
                                          rf.ctypes.data, st2.ctypes.data) == 0
     assert rf.tobytes() == b"".join(want[1][128 * i:128 * i + 128] for i in owed)
     ns.close()
+
+
+@pytest.fixture(scope="module")
+def failing_case(engine_factory, oracle, bench_params):
+    """minted once: the 14-lane batch with one of each verdict, as records and as wire messages, and the loop's answer"""
+    from act_amd import capi
+    L = 8
+    eng = engine_factory(bench_params, L, max_batch=5, transcript=capi.TRANSCRIPT_DEVICE)
+    sk = eng.private_key_random(shake("rd-sk", 64))
+    other = eng.private_key_random(shake("rd-sk-other", 64))
+    first, _ = _batches(eng, sk, L)
+    rng = shake("rdt-rng", 128 * 32)
+    want = _sequential_loop(oracle.ctx(bench_params, L), sk, first, rng, set())
+    assert list(want[0]) == [0, 0, 7, 0, 0, 6, 0, 255, 0, 0, 0, 0, 3, 3]
+    return eng, sk, other, first, eng.cbor_encode("SpendProof", b"".join(first)), rng, want[0]
+
+
+@pytest.mark.parametrize("fault", ["capacity", "sign"])
+@pytest.mark.parametrize("mem", ["host", "device"])
+@pytest.mark.parametrize("wire", [False, True], ids=["records", "wire"])
+@pytest.mark.parametrize("form", ["one key", "ring", "ring with epochs"])
+def test_every_redeem_form_finishes_a_failed_call_alike(failing_case, form, wire, mem, fault):
+    """The steps behind verification, from every entry point and from either memory.  The set is full (the nullifier step refuses the
+    batch) or the signature step fails behind the recorded nullifiers (act_debug_fail_next_signs): status[] is the sequential loop's
+    with 0 -> 252 or 0 -> 251, every output slot is zero, the set is unchanged or holds every accepted nullifier, the call fails, and
+    the ring forms leave the out_key of the call without the fault.
+    (Capacity: the store refuses the batch before it looks at a lane, so lanes 12 and 13 -- DoubleSpend in the loop only because
+    lanes 0 and 3 of the SAME batch came first -- are undetermined like them, as test_redeem_failures_keep_every_decision has it.)"""
+    import torch
+    from act_amd import capi
+    eng, sk, other, first, msgs, rng, loop = failing_case
+    eng.set_transcript_mode(capi.TRANSCRIPT_DEVICE)                 # (the session's engines are shared: whatever ran in between)
+    n = len(first)
+    keys = [other, sk]                                              # the signing key is entry 1; ACT_SIGN_MATCHED
+    out_b = eng.cbor_size("Refund") if wire else 128
+    p_in, keep_in, offs = capi._msgs(msgs) if wire else capi._in(b"".join(first)) + (None,)
+    p_rng, keep_rng = capi._in(rng)
+    st = np.full(n, 99, np.uint8); out = np.full(out_b * n, 7, np.uint8); ok = np.full(n, 99, np.uint8)
+    if mem == "device":
+        dev = [torch.from_numpy(a.copy()).cuda() for a in (keep_in, keep_rng, st, out, ok)]
+        torch.cuda.synchronize()
+        p_in, p_rng, p_st, p_out, p_ok = (t.data_ptr() for t in dev)
+    else:
+        p_st, p_out, p_ok = st.ctypes.data, out.ctypes.data, ok.ctypes.data
+    m = capi.MEM_DEVICE if mem == "device" else capi.MEM_HOST
+    src = (p_in, offs.ctypes.data) if wire else (p_in,)
+    ke = capi._epoch_table([3, 4])
+
+    def call(ns):
+        tail = src + (p_rng, capi.RNG_SEQUENTIAL, p_out, p_st)
+        if form == "one key":
+            fn = eng.lib.act_redeem_cbor_batch if wire else eng.lib.act_redeem_batch
+            rc = fn(eng.ctx, ns.h, n, m, capi._in(sk, 64)[0], *tail)
+        else:
+            pk, kk = capi._in(b"".join(keys))
+            name = "act_redeem_%skeyring_%sbatch" % ("cbor_" if wire else "", "epochs_" if form == "ring with epochs" else "")
+            head = (pk, 2, ke.ctypes.data) if form == "ring with epochs" else (pk, 2)
+            rc = getattr(eng.lib, name)(eng.ctx, ns.h, n, m, *head, capi.SIGN_MATCHED, *tail, p_ok)
+        if mem == "device":
+            got = [t.cpu().numpy() for t in dev[2:]]
+        else:
+            got = [st, out, ok]
+        return rc, got[0].tobytes(), got[1].copy(), got[2].tobytes()
+
+    ns = capi.NullifierSet(1000)
+    rc, status, refunds, want_key = call(ns)                        # without the fault
+    assert rc == 0 and status == loop and len(ns) == loop.count(0)
+    ns.close()
+    if fault == "capacity":      # a set made for 4 nullifiers holds 1024 slots / 2 = 512: filled to the brim
+        ns = capi.NullifierSet(4)
+        assert ns.check_and_insert(b"".join((10**9 + i).to_bytes(32, "little") for i in range(505))) == bytes(505)
+        want, grown = bytes(252 if s in (0, 3) else s for s in loop), 0
+    else:
+        ns = capi.NullifierSet(1000)
+        assert eng.lib.act_debug_fail_next_signs(eng.ctx, 1) == 0
+        want, grown = bytes(251 if s == 0 else s for s in loop), loop.count(0)
+    before = len(ns)
+    rc, status, refunds, got_key = call(ns)
+    assert rc != 0
+    assert status == want
+    assert not refunds.any()
+    assert len(ns) == before + grown
+    if form != "one key":
+        assert got_key == want_key
+    ns.close()

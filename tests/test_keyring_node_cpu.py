@@ -182,3 +182,66 @@ def test_a_failing_generator_or_gpu_signs_nothing(lib):
     assert sorted(unsigned + done) == [i for i in range(n) if verdict[i] == 0]
     lib.act_node_nullifier_set_destroy(ns)
     lib.act_node_destroy(nd)
+
+
+@pytest.mark.parametrize("fault", ["nullifier device", "signing device", "generator"])
+def test_one_key_and_a_ring_of_one_finish_a_failed_redemption_alike(lib, fault):
+    """The steps behind verification are the same for act_node_redeem_batch and act_node_redeem_keyring_batch: under the same fault,
+    on fresh sets, the two calls agree on every status byte, on which output slots are all zero, on the set's length and on whether
+    the call failed.  (n = 40 with a stream generator: the general path of the one-key call, not its road for a few items.)"""
+    ndev, n, bad = 3, 40, 1
+    nd = make_node(lib, ndev)
+    devs = (C.c_int * ndev)(*range(ndev))
+    proofs = bytearray(records(n, PB, 123))
+    for i in range(n):                                             # the mocks reject an odd first byte: every third lane
+        proofs[PB * i] = (proofs[PB * i] & 0xfe) | (i % 3 == 1)
+    proofs = bytes(proofs)
+    verdict = bytes(7 if i % 3 == 1 else 0 for i in range(n))
+    acc = verdict.count(0)
+    rng = records(n, 128, 124)
+    keys = ring(1)
+    got = {}
+    for form in ("one key", "ring"):
+        ns = C.c_void_p()
+        assert lib.act_node_nullifier_set_create(devs, ndev, C.c_size_t(1000), b"0123456789abcdef", C.byref(ns)) == 0
+        short = _Replay(rng[:128 * acc - 1])                       # one byte too few: draw() returns non-zero and writes nothing
+        src, mode = (short.ptr, 2) if fault == "generator" else (rng, 1)
+        lib.act_mock_fail(bad if fault == "nullifier device" else -1, bad if fault == "signing device" else -1)
+        lib.act_mock_keyring_fail(bad if fault == "signing device" else -1)
+        out, st, ok = bufs(n, 128, 1, 1)
+        if form == "one key":
+            rc = lib.act_node_redeem_batch(nd, ns, C.c_size_t(n), bytes(64), proofs, src, mode, out, st)
+        else:
+            rc = lib.act_node_redeem_keyring_batch(nd, ns, C.c_size_t(n), keys, 1, -1, proofs, src, mode, out, st, ok)
+            assert ok.raw[:n] == bytes(255 if v else 0 for v in verdict)
+        lib.act_mock_fail(-1, -1)
+        lib.act_mock_keyring_fail(-1)
+        status, refunds = st.raw[:n], [out.raw[128 * i:128 * (i + 1)] for i in range(n)]
+        # every signed lane against its own mock's rule, every other slot all zero.  The slices are the sequential loop's: a lane that
+        # was to be signed has its slice whether or not its device then failed (251), a lane the store could not answer has none (252)
+        checked = bytes(0 if s == 251 else s for s in status)
+        want = expect_signed(proofs, keys, bytes(n), checked, rng, 1, 1)
+        cur = 0
+        for i in range(n):
+            if status[i]:
+                assert refunds[i] == bytes(128), (form, i)
+            elif form == "ring":
+                assert refunds[i] == want[1][128 * i:128 * (i + 1)], (form, i)
+            else:
+                assert refunds[i][:8] == proofs[PB * i:PB * i + 8] and refunds[i][8:16] == rng[128 * cur:128 * cur + 8], (form, i)
+            cur += checked[i] == 0
+        assert short.draws == []
+        got[form] = (status, [r == bytes(128) for r in refunds], lib.act_node_nullifier_set_len(ns), rc != 0)
+        lib.act_node_nullifier_set_destroy(ns)
+    lib.act_node_destroy(nd)
+    assert got["one key"] == got["ring"]
+    status, _, recorded, failed = got["ring"]
+    assert failed and all(status[i] == 7 for i in range(n) if verdict[i])
+    accepted = [status[i] for i in range(n) if verdict[i] == 0]
+    if fault == "nullifier device":        # the lost device's lanes are undetermined and not recorded, every other lane is finished
+        assert set(accepted) == {0, 252} and recorded == accepted.count(0)
+    elif fault == "signing device":        # the accepted lanes of the failed device's piece are recorded and unsigned
+        a, b = n * bad // ndev, n * (bad + 1) // ndev
+        assert status == bytes(v if v else (251 if a <= i < b else 0) for i, v in enumerate(verdict)) and recorded == acc
+    else:                                  # nothing was drawn: every accepted lane is recorded and unsigned
+        assert status == bytes(v if v else 251 for v in verdict) and recorded == acc
