@@ -5,7 +5,7 @@
 //   1. screen        k and s of every lane (records: fields 0 and 1; wire: the payloads of a canonical message, and of any other
 //                    spelling what the wire reader's reduced form gives -- cbor_lanes.h with keep_fields = 2, as a kernel for
 //                    device-memory callers and on the host workers for host-memory callers; under ACT_WIRE_READER_HOST the host
-//                    reader's record, in windows of ADMIT_READ_WINDOW) -> pre-status, reduced k                  [k_admit_screen]
+//                    reader's record, in windows of WIRE_SETTLE_WINDOW: wire_window_read, cbor_impl.inc) -> pre-status, reduced k [k_admit_screen]
 //   2. compaction    the survivors' lane numbers in lane order                                  [k_admit_count / _scan / _write]
 //   3. verification  of the survivors only, their records / messages gathered ADMIT_WINDOW_BATCHES * max_batch at a time
 //   4. once per call check-and-insert and signing over the compact 32-byte arrays (redeem_tail_ring, keyring_redeem_impl.inc): one rng draw per call
@@ -16,7 +16,6 @@
 // survivor whose input bytes are those of an earlier survivor is not verified and takes its answer from that lane      [k_copies.hip]
 namespace {
 
-constexpr size_t ADMIT_READ_WINDOW = 4096;       // messages per host-reader window (as WIRE_SETTLE_WINDOW)
 constexpr size_t ADMIT_WINDOW_BATCHES = 4;       // survivors gathered and verified at a time, in units of max_batch
 constexpr size_t ADMIT_WIRE_LAUNCH = (size_t)1 << 20;      // messages per launch of the framing compare
 
@@ -106,8 +105,7 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
   const CborType* T = cbor_type(ACT_CBOR_SPEND_PROOF);
   CborLayout lay; if (wire) lay = cbor_layout(*T, c->L);
   const size_t ml = lay.tmpl.size(), nf = lay.pay_off.size();
-  auto msg_beg = [&](size_t i) { return offsets ? (size_t)offsets[i] : i * ml; };
-  auto msg_end = [&](size_t i) { return offsets ? (size_t)offsets[i + 1] : (i + 1) * ml; };
+  const WireExtent ext{cbor, offsets, ml};      // where message i lies (wire callers)
   hipStream_t stream = set->stream;
 
   // ---- the stage's own device memory (public data: lane numbers, codes, nullifiers, charges) -------------------------------------------
@@ -119,7 +117,7 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
   const size_t o_ks = own_ks ? take(n * 64) : 0, o_charge = (charge && !dev) ? take(n * 32) : 0;
   const size_t o_code = wire ? take(n) : 0, o_flags = (wire && dev) ? take(fcap) : 0, o_off = (wire && dev && offsets) ? take((n + 1) * 8) : 0;
   const size_t o_tmpl = (wire && dev) ? take(ml) : 0, o_pay = (wire && dev) ? take(nf * 4) : 0;
-  const size_t o_pwhich = wire ? take(ADMIT_READ_WINDOW * 4) : 0, o_patch = wire ? take(ADMIT_READ_WINDOW * 64) : 0;
+  const size_t o_pwhich = wire ? take(WIRE_SETTLE_WINDOW * 4) : 0, o_patch = wire ? take(WIRE_SETTLE_WINDOW * 64) : 0;
   const bool dev_reader = wire && c->wire_reader.load() == ACT_WIRE_READER_DEVICE;
   const size_t o_rcode = (dev_reader && dev) ? take(2 * n) : 0;      // the device reader's codes, then its infos
   DevTmp d(c);
@@ -197,52 +195,25 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
       ADCK(c, hipMemcpyAsync(d_ks, h_ks.data(), n * 64, hipMemcpyHostToDevice, stream));
       ADCK(c, hipStreamSynchronize(stream));
     }
-    // every other spelling: the general reader, ADMIT_READ_WINDOW messages at a time.  A message that reads yields the record, and so
-    // k and s; one that does not takes the code act_redeem_cbor_* gives it (the first error in wire order: cbor_settle_codes)
+    // every other spelling: the general reader, a window at a time (wire_window_read).  A message that reads yields the record, and so
+    // k and s; one that does not takes the status act_redeem_cbor_* gives it (the first error in wire order: cbor_settle_codes)
     if (h_code.size() != n) h_code.assign(n, 0);
     std::vector<size_t> which;
     for (size_t i = 0; i < n; i++) if (flags[i] & 0x80) which.push_back(i);
     c->wire_stats[0] += n; c->wire_stats[1] += n - which.size(); c->wire_stats[dev_reader ? 2 : 3] += which.size();
     if (dev_reader) which.clear();      // read already: the serial window loop below is the road of ACT_WIRE_READER_HOST
-    std::vector<uint8_t> rec(pb), bytes, patch; std::vector<uint32_t> pwhich; std::vector<size_t> at;
-    std::vector<int> codes; std::vector<CborCand> cands;
-    for (size_t w0 = 0; w0 < which.size(); w0 += ADMIT_READ_WINDOW) {
-      const size_t w1 = std::min(which.size(), w0 + ADMIT_READ_WINDOW), cnt = w1 - w0;
-      at.assign(cnt, 0);
-      if (dev) {      // the window's bytes: one copy of the span when its messages lie close together, one per message when not
-        size_t sum = 0;
-        for (size_t k = 0; k < cnt; k++) sum += msg_end(which[w0 + k]) - msg_beg(which[w0 + k]);
-        const size_t span_beg = msg_beg(which[w0]), span_end = msg_end(which[w1 - 1]);
-        if (span_end - span_beg <= 2 * sum + ((size_t)1 << 20)) {
-          bytes.resize(span_end - span_beg);
-          if (!bytes.empty()) ADCK(c, hipMemcpy(bytes.data(), cbor + span_beg, bytes.size(), hipMemcpyDeviceToHost));
-          for (size_t k = 0; k < cnt; k++) at[k] = msg_beg(which[w0 + k]) - span_beg;
-        } else {
-          bytes.resize(sum);
-          size_t o = 0;
-          for (size_t k = 0; k < cnt; k++) {
-            const size_t b = msg_beg(which[w0 + k]), l = msg_end(which[w0 + k]) - b;
-            if (l) ADCK(c, hipMemcpy(bytes.data() + o, cbor + b, l, hipMemcpyDeviceToHost));
-            at[k] = o; o += l;
-          }
-        }
-      }
-      codes.assign(cnt, CBOR_OK); cands.assign(cnt, CborCand{}); patch.assign(cnt * 64, 0); pwhich.clear();
-      std::vector<size_t> good;
+    WireWindow win; std::vector<uint8_t> patch; std::vector<uint32_t> pwhich;
+    for (size_t w0 = 0; w0 < which.size(); w0 += WIRE_SETTLE_WINDOW) {
+      const size_t cnt = std::min(which.size(), w0 + WIRE_SETTLE_WINDOW) - w0;
+      const size_t* lanes = which.data() + w0;
+      if ((rc = wire_window_read(c, stream, *T, ext, dev, lanes, cnt, pb, win))) return rc;
+      patch.clear(); pwhich.clear();
       for (size_t k = 0; k < cnt; k++) {
-        const size_t i = which[w0 + k], beg = msg_beg(i), end = msg_end(i);
-        std::fill(rec.begin(), rec.end(), 0);
-        codes[k] = cbor_read_message(*T, c->L, dev ? bytes.data() + at[k] : cbor + beg, end - beg, rec.data(), &cands[k]);
-        if (codes[k] == CBOR_OK) memcpy(patch.data() + k * 64, rec.data(), 64);
+        if (win.codes[k] != CBOR_OK) { h_code[lanes[k]] = win.status[k]; continue; }
+        patch.insert(patch.end(), win.recs.data() + k * pb, win.recs.data() + k * pb + 64);      // k and s: the record's first two fields
+        pwhich.push_back((uint32_t)lanes[k]);
       }
-      if ((rc = cbor_settle_codes(c, stream, codes, cands))) return rc;
-      size_t np = 0;
-      for (size_t k = 0; k < cnt; k++) {
-        const size_t i = which[w0 + k];
-        if (codes[k] == CBOR_OK) { if (np != k) memmove(patch.data() + np * 64, patch.data() + k * 64, 64); pwhich.push_back((uint32_t)i); np++; }
-        else h_code[i] = codes[k] == CBOR_ERR_VALUE ? (uint8_t)ACT_STATUS_UNDECODABLE : codes[k] == CBOR_ERR_PARSE ? (uint8_t)ACT_STATUS_CBOR_MALFORMED : (uint8_t)ACT_STATUS_CBOR_STRUCTURE;
-      }
-      if (np) {
+      if (const size_t np = pwhich.size()) {
         ADCK(c, hipMemcpyAsync(d.p + o_pwhich, pwhich.data(), np * 4, hipMemcpyHostToDevice, stream));
         ADCK(c, hipMemcpyAsync(d.p + o_patch, patch.data(), np * 64, hipMemcpyHostToDevice, stream));
         AdmitPatchArgs pa{d_ks, reinterpret_cast<const uint32_t*>(d.p + o_pwhich), d.p + o_patch, (uint32_t)np};
@@ -390,8 +361,8 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
       dst_off.assign(w + 1, 0); src_beg.assign(w, 0);
       size_t longest = 0;
       for (size_t k = 0; k < w; k++) {
-        const size_t i = h_idx[w0 + k], len = msg_end(i) - msg_beg(i);
-        src_beg[k] = msg_beg(i); dst_off[k + 1] = dst_off[k] + len; longest = std::max(longest, len);
+        const size_t i = h_idx[w0 + k], len = ext.end(i) - ext.beg(i);
+        src_beg[k] = ext.beg(i); dst_off[k + 1] = dst_off[k] + len; longest = std::max(longest, len);
       }
       if ((rc = g_reserve((size_t)dst_off[w]))) return rc;
       if (dev) {

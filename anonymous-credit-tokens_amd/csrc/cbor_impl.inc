@@ -14,9 +14,11 @@
 // CBOR item (RFC 8949) whose top level is a map; integer keys select fields, unknown keys and non-matching
 // value shapes are ignored, a later duplicate key overwrites an earlier one, errors surface in map order,
 // trailing bytes after the first item are not read.  Messages that are not byte-for-byte canonical take
-// the host reader below (cbor_read_message); canonical ones never leave the GPU.
+// the host reader below (cbor_read_message); canonical ones never leave the GPU.  The wire calls that settle such messages after their
+// pipeline (ACT_WIRE_READER_HOST: spend, admission, issuance) do it through one window: wire_window.h and wire_window_read below.
 
 #include "cbor_reader.h"      // CborType, cbor_type(), CborReader, cbor_read_message: the host reader, shared with tests/hostcheck
+#include "wire_window.h"      // one window of the host reader's road (ACT_WIRE_READER_HOST): gather plan, parse step, lane-patch plan
 
 namespace {
 
@@ -192,6 +194,65 @@ int cbor_settle_codes(act_ctx* c, hipStream_t stream, std::vector<int>& codes, c
   if (d_bad) (void)hipFree(d_bad);
   HIPCK(c, he);
   for (size_t i = 0; i < owner.size(); i++) if (bad[i]) codes[owner[i]] = CBOR_ERR_VALUE;
+  return ACT_OK;
+}
+
+// One window of the host reader's road, for its three settles (verify_spend_cbor_impl below, issue_wire_settle, the admission
+// screen): the flagged messages which[0..cnt) are brought to the host (device-memory callers; wire_window.h has the rule), read by
+// cbor_read_message, and their codes ordered as from_cbor orders them (cbor_settle_codes).  It leaves codes[k], status[k] -- the
+// lane status of a message that is refused, 0 for one that reads -- and the raw record recs[k * rb ...] of every message that READ,
+// all zero otherwise; a record can have read and still be refused (CBOR_ERR_VALUE from a point that never reaches it).
+// Nothing here or in wire_patch_lanes takes the context's lock: the spend settle runs inside its call, which holds it (the admission
+// screen is serialised by the context's admission lock); issue_wire_settle runs between calls and takes it around each of the two
+// (issue_wire_impl.inc).
+struct WireWindow { WireGather g; std::vector<uint8_t> bytes, recs, status; std::vector<int> codes; std::vector<CborCand> cands; };
+int wire_window_read(act_ctx* c, hipStream_t stream, const CborType& T, const WireExtent& x, bool dev, const size_t* which, size_t cnt, size_t rb, WireWindow& w) {
+  if (dev) {
+    wire_gather_plan(x, which, cnt, w.g);
+    w.bytes.resize(w.g.bytes);
+    const int rc = wire_gather_run(w.g, w.bytes.data(), [&](uint8_t* dst, size_t src, size_t len) -> int { HIPCK(c, hipMemcpy(dst, x.cbor + src, len, hipMemcpyDeviceToHost)); return ACT_OK; });
+    if (rc) return rc;
+  }
+  wire_window_parse(T, c->L, x, which, cnt, dev ? w.bytes.data() : nullptr, w.g.at, rb, w.recs, w.codes, w.cands);
+  // the first error in wire order, as from_cbor reports it: an invalid point in front of a structural fault, or in a value that a
+  // duplicate key or an over-long array keeps out of the record, is InvalidValue (status 255)
+  if (const int rc = cbor_settle_codes(c, stream, w.codes, w.cands)) return rc;
+  w.status.resize(cnt);
+  for (size_t k = 0; k < cnt; k++) w.status[k] = act::cbor_code_status((uint8_t)w.codes[k]);
+  return ACT_OK;
+}
+// lanes[0..cnt) of a caller's array (host or device memory; null: nothing to do) take vals[k * stride ...]
+int wire_patch_lanes(act_ctx* c, int mem, uint8_t* base, size_t stride, const size_t* lanes, size_t cnt, const uint8_t* vals, bool span_only = false) {
+  if (!base) return ACT_OK;
+  if (mem == ACT_MEM_HOST) { for (size_t k = 0; k < cnt; k++) memcpy(base + lanes[k] * stride, vals + k * stride, stride); return ACT_OK; }
+  return wire_patch_run(lanes, cnt, stride, vals,
+    [&](uint8_t* dst, size_t off, size_t len) -> int { HIPCK(c, hipMemcpy(dst, base + off, len, hipMemcpyDeviceToHost)); return ACT_OK; },
+    [&](size_t off, const uint8_t* src, size_t len) -> int { HIPCK(c, hipMemcpy(base + off, src, len, hipMemcpyHostToDevice)); return ACT_OK; }, span_only);
+}
+
+// one flag byte per message of a wire-bytes call, accumulated with 32-bit atomics, zero when this returns (slot 0's stream has drained:
+// the other slot's stream reads the flags, and the layout, too)
+int wire_flags_reserve(act_ctx* c, size_t n) {
+  const size_t fcap = (n + 3) & ~(size_t)3;
+  if (fcap > c->d_wire_flags_cap) {
+    if (c->d_wire_flags) HIPCK(c, hipFree(c->d_wire_flags));
+    c->d_wire_flags = nullptr; c->d_wire_flags_cap = 0;
+    HIPCK(c, hipMalloc(&c->d_wire_flags, fcap)); c->d_wire_flags_cap = fcap;
+  }
+  HIPCK(c, hipMemsetAsync(c->d_wire_flags, 0, fcap, c->slots[0].stream));
+  HIPCK(c, hipStreamSynchronize(c->slots[0].stream));
+  return ACT_OK;
+}
+// the device reader's code and info bytes, one each per message of the call, zero (CBOR_OK) until a reader kernel writes them (the
+// memset is on slot 0's stream: wire_flags_reserve, called next, waits for it)
+int wire_codes_reserve(act_ctx* c, size_t n) {
+  const size_t fcap = (n + 3) & ~(size_t)3;
+  if (fcap > c->d_wire_codes_cap) {
+    if (c->d_wire_codes) HIPCK(c, hipFree(c->d_wire_codes));
+    c->d_wire_codes = nullptr; c->d_wire_codes_cap = 0;
+    HIPCK(c, hipMalloc(&c->d_wire_codes, 2 * fcap)); c->d_wire_codes_cap = fcap;
+  }
+  HIPCK(c, hipMemsetAsync(c->d_wire_codes, 0, 2 * c->d_wire_codes_cap, c->slots[0].stream));
   return ACT_OK;
 }
 
@@ -486,15 +547,9 @@ static int wire_unframe_chunk(act_ctx* c, Slot& sl, const WireSrc& w, int mem, s
   return ACT_OK;
 }
 
-namespace {
-// Settling the messages that were not byte-for-byte canonical.  Untrusted clients choose the encoding, so there can be two of them
-// at the ends of a 2^20-message batch or a million of them: the flagged messages are taken in windows of at most WIRE_SETTLE_WINDOW,
-// each window reads only its own messages (one copy of the span that holds them when they lie close together, one copy per message
-// when they do not), parses them with the general reader, verifies those that parse in one small call and patches the caller's
-// arrays over its own lane range -- the host never holds more than one window of records, whatever the batch looks like.
-constexpr size_t WIRE_SETTLE_WINDOW = 4096;
-}  // namespace
-
+// Settling the messages that were not byte-for-byte canonical (ACT_WIRE_READER_HOST): in windows of at most WIRE_SETTLE_WINDOW, each
+// read by wire_window_read above; here the window's records that read are verified in one small call and the caller's arrays patched
+// over the window's lanes -- the host never holds more than one window of records, whatever the batch looks like.
 // `ring` (keyring_impl.inc): the same pass against a ring of issuer keys instead of sk -- ring_verify_locked in place of
 // spend_batch_locked, and ring->out_key patched beside the statuses
 static int verify_spend_cbor_impl(act_ctx* c, size_t n, int mem, const uint8_t sk[64], const uint8_t* cbor, const uint64_t* offsets,
@@ -510,24 +565,9 @@ static int verify_spend_cbor_impl(act_ctx* c, size_t n, int mem, const uint8_t s
   CborDev d; int rc = cbor_dev_prepare(c, s0, ACT_CBOR_SPEND_PROOF, &d); if (rc) return rc;
   c->wire_layout = &d;
   const size_t ml = d.lay.tmpl.size(), pb = ProofLayout{c->L}.bytes();
-  // one flag byte per message, accumulated with 32-bit atomics
-  const size_t fcap = (n + 3) & ~(size_t)3;
-  if (fcap > c->d_wire_flags_cap) {
-    if (c->d_wire_flags) HIPCK(c, hipFree(c->d_wire_flags));
-    c->d_wire_flags = nullptr; c->d_wire_flags_cap = 0;
-    HIPCK(c, hipMalloc(&c->d_wire_flags, fcap)); c->d_wire_flags_cap = fcap;
-  }
-  HIPCK(c, hipMemsetAsync(c->d_wire_flags, 0, fcap, s0.stream));
   const bool dev_reader = c->wire_reader.load() == ACT_WIRE_READER_DEVICE;
-  if (dev_reader) {
-    if (fcap > c->d_wire_codes_cap) {
-      if (c->d_wire_codes) HIPCK(c, hipFree(c->d_wire_codes));
-      c->d_wire_codes = nullptr; c->d_wire_codes_cap = 0;
-      HIPCK(c, hipMalloc(&c->d_wire_codes, 2 * fcap)); c->d_wire_codes_cap = fcap;
-    }
-    HIPCK(c, hipMemsetAsync(c->d_wire_codes, 0, 2 * c->d_wire_codes_cap, s0.stream));
-  }
-  HIPCK(c, hipStreamSynchronize(s0.stream));                 // the other slot's stream reads the layout and the flags too
+  if (dev_reader && (rc = wire_codes_reserve(c, n))) return rc;
+  if ((rc = wire_flags_reserve(c, n))) return rc;             // (waits for both memsets: the other slot's stream reads the layout and the flags too)
   WireSrc w{cbor, offsets, ml, out_nullifier};
   const DevKey* d_ring = nullptr;
   if (ring && (rc = ring_set(c, ring->keys, ring->nkeys, &d_ring))) { c->wire_layout = nullptr; return rc; }
@@ -561,94 +601,47 @@ static int verify_spend_cbor_impl(act_ctx* c, size_t n, int mem, const uint8_t s
     c->wire_stats[0] += n; c->wire_stats[1] += n - read; c->wire_stats[2] += read;
     return call.finish();
   }
-  std::vector<uint8_t> flags(n), ok2, hok;
+  std::vector<uint8_t> flags(n);
   HIPCK(c, hipMemcpy(flags.data(), c->d_wire_flags, n, hipMemcpyDeviceToHost));
   std::vector<size_t> which;
   for (size_t i = 0; i < n; i++) if (flags[i] & 0x80) which.push_back(i);
   c->wire_stats[0] += n; c->wire_stats[1] += n - which.size(); c->wire_stats[3] += which.size();
-  auto msg_beg = [&](size_t i) { return offsets ? (size_t)offsets[i] : i * ml; };
-  auto msg_end = [&](size_t i) { return offsets ? (size_t)offsets[i + 1] : (i + 1) * ml; };
-  const bool dev = mem == ACT_MEM_DEVICE;
-  std::vector<uint8_t> recs, bytes, st2, kp2, verdict, hs, hk, hn;
-  std::vector<size_t> good, pos, at;
-  std::vector<int> codes; std::vector<CborCand> cands;
+  const WireExtent x{cbor, offsets, ml};
+  WireWindow win;
+  std::vector<uint8_t> st2, kp2, ok2, verdict, kprime, nul, key;
+  std::vector<size_t> good;
   for (size_t w0 = 0; w0 < which.size(); w0 += WIRE_SETTLE_WINDOW) {
-    const size_t w1 = std::min(which.size(), w0 + WIRE_SETTLE_WINDOW), cnt = w1 - w0;
-    // the window's message bytes (device-memory callers): `at[k]` = where message which[w0 + k] starts in `bytes`
-    at.assign(cnt, 0);
-    if (dev) {
-      size_t sum = 0;
-      for (size_t k = 0; k < cnt; k++) sum += msg_end(which[w0 + k]) - msg_beg(which[w0 + k]);
-      const size_t span_beg = msg_beg(which[w0]), span_end = msg_end(which[w1 - 1]);       // offsets are monotone (checked above)
-      if (span_end - span_beg <= 2 * sum + ((size_t)1 << 20)) {
-        bytes.resize(span_end - span_beg);
-        if (!bytes.empty()) HIPCK(c, hipMemcpy(bytes.data(), cbor + span_beg, bytes.size(), hipMemcpyDeviceToHost));
-        for (size_t k = 0; k < cnt; k++) at[k] = msg_beg(which[w0 + k]) - span_beg;
-      } else {
-        bytes.resize(sum);
-        size_t o = 0;
-        for (size_t k = 0; k < cnt; k++) {
-          const size_t b = msg_beg(which[w0 + k]), l = msg_end(which[w0 + k]) - b;
-          if (l) HIPCK(c, hipMemcpy(bytes.data() + o, cbor + b, l, hipMemcpyDeviceToHost));
-          at[k] = o; o += l;
-        }
-      }
-    }
-    recs.assign(cnt * pb, 0); st2.assign(cnt, 0); verdict.assign(cnt, 0); pos.assign(cnt, (size_t)-1); good.clear();
-    if (out_kprime) kp2.assign(cnt * 32, 0);
-    codes.assign(cnt, CBOR_OK); cands.assign(cnt, CborCand{});
+    const size_t cnt = std::min(which.size(), w0 + WIRE_SETTLE_WINDOW) - w0;
+    const size_t* lanes = which.data() + w0;
+    if ((rc = wire_window_read(c, s0.stream, *T, x, mem == ACT_MEM_DEVICE, lanes, cnt, pb, win))) return rc;
+    // a refused message: its wire status, all-zero K' and ACT_KEY_NONE, and its `k` (the record's first field) as it stood on the wire
+    // if every field read; then the records of the messages that read move to the front, one behind the other, for the small call
+    verdict = win.status; kprime.assign(cnt * 32, 0); key.assign(cnt, (uint8_t)ACT_KEY_NONE); nul.resize(cnt * 32); good.clear();
     for (size_t k = 0; k < cnt; k++) {
-      const size_t i = which[w0 + k], beg = msg_beg(i), end = msg_end(i);
-      const uint8_t* src = dev ? bytes.data() + at[k] : cbor + beg;
-      const int e = codes[k] = cbor_read_message(*T, c->L, src, end - beg, recs.data() + good.size() * pb, &cands[k]);
-      if (e == CBOR_OK) { pos[k] = good.size(); good.push_back(k); }
-      else memset(recs.data() + good.size() * pb, 0, pb);
+      memcpy(nul.data() + k * 32, win.recs.data() + k * pb, 32);
+      if (win.codes[k] != CBOR_OK) continue;
+      if (good.size() != k) memcpy(win.recs.data() + good.size() * pb, win.recs.data() + k * pb, pb);
+      good.push_back(k);
     }
-    // the first error in wire order, as from_cbor reports it: an invalid point in front of a structural fault, or in a value that a
-    // duplicate key or an over-long array keeps out of the record, is InvalidValue (status 255)
-    if ((rc = cbor_settle_codes(c, s0.stream, codes, cands))) return rc;
     if (!good.empty()) {
-      if (ring) ok2.assign(cnt, ACT_KEY_NONE);
-      rc = ring ? ring_verify_locked(c, good.size(), ACT_MEM_HOST, d_ring, ring->nkeys, recs.data(), st2.data(), ok2.data(), out_kprime ? kp2.data() : nullptr)
-                : spend_batch_locked(c, good.size(), ACT_MEM_HOST, sk, recs.data(), false, nullptr, ACT_RNG_PER_LANE, nullptr, st2.data(), out_kprime ? kp2.data() : nullptr);
+      st2.assign(good.size(), 0); ok2.assign(good.size(), (uint8_t)ACT_KEY_NONE);
+      if (out_kprime) kp2.assign(good.size() * 32, 0);
+      rc = ring ? ring_verify_locked(c, good.size(), ACT_MEM_HOST, d_ring, ring->nkeys, win.recs.data(), st2.data(), ok2.data(), out_kprime ? kp2.data() : nullptr)
+                : spend_batch_locked(c, good.size(), ACT_MEM_HOST, sk, win.recs.data(), false, nullptr, ACT_RNG_PER_LANE, nullptr, st2.data(), out_kprime ? kp2.data() : nullptr);
       if (rc) return rc;
-      for (size_t g = 0; g < good.size(); g++) verdict[good[g]] = st2[g];
-    }
-    for (size_t k = 0; k < cnt; k++) {
-      if (codes[k] == CBOR_ERR_VALUE) verdict[k] = ACT_STATUS_UNDECODABLE;
-      else if (codes[k] != CBOR_OK) verdict[k] = codes[k] == CBOR_ERR_PARSE ? ACT_STATUS_CBOR_MALFORMED : ACT_STATUS_CBOR_STRUCTURE;
-    }
-    const uint8_t zero32[32] = {0};
-    auto kprime_of = [&](size_t k) { return (pos[k] != (size_t)-1 && verdict[k] == 0) ? kp2.data() + pos[k] * 32 : zero32; };
-    auto null_of = [&](size_t k) { return pos[k] != (size_t)-1 ? recs.data() + pos[k] * pb : zero32; };          // `k` is the record's first field
-    auto key_of = [&](size_t k) { return (pos[k] != (size_t)-1 && verdict[k] == 0) ? ok2[pos[k]] : (uint8_t)ACT_KEY_NONE; };
-    if (dev) {
-      // the lanes [first, last] of the caller's device arrays: read once, patched on the host, written back once
-      const size_t first = which[w0], lanes = which[w1 - 1] - first + 1;
-      hs.resize(lanes);
-      HIPCK(c, hipMemcpy(hs.data(), status + first, lanes, hipMemcpyDeviceToHost));
-      if (out_kprime) { hk.resize(lanes * 32); HIPCK(c, hipMemcpy(hk.data(), out_kprime + first * 32, lanes * 32, hipMemcpyDeviceToHost)); }
-      if (out_nullifier) { hn.resize(lanes * 32); HIPCK(c, hipMemcpy(hn.data(), out_nullifier + first * 32, lanes * 32, hipMemcpyDeviceToHost)); }
-      if (ring) { hok.resize(lanes); HIPCK(c, hipMemcpy(hok.data(), ring->out_key + first, lanes, hipMemcpyDeviceToHost)); }
-      for (size_t k = 0; k < cnt; k++) {
-        const size_t l = which[w0 + k] - first;
-        hs[l] = verdict[k];
-        if (out_kprime) memcpy(hk.data() + l * 32, kprime_of(k), 32);
-        if (out_nullifier) memcpy(hn.data() + l * 32, null_of(k), 32);
-        if (ring) hok[l] = key_of(k);
-      }
-      if (ring) HIPCK(c, hipMemcpy(ring->out_key + first, hok.data(), lanes, hipMemcpyHostToDevice));
-      HIPCK(c, hipMemcpy(status + first, hs.data(), lanes, hipMemcpyHostToDevice));
-      if (out_kprime) HIPCK(c, hipMemcpy(out_kprime + first * 32, hk.data(), lanes * 32, hipMemcpyHostToDevice));
-      if (out_nullifier) HIPCK(c, hipMemcpy(out_nullifier + first * 32, hn.data(), lanes * 32, hipMemcpyHostToDevice));
-    } else {
-      for (size_t k = 0; k < cnt; k++) {
-        status[which[w0 + k]] = verdict[k];
-        if (out_kprime) memcpy(out_kprime + which[w0 + k] * 32, kprime_of(k), 32);
-        if (out_nullifier) memcpy(out_nullifier + which[w0 + k] * 32, null_of(k), 32);
-        if (ring) ring->out_key[which[w0 + k]] = key_of(k);
+      for (size_t g = 0; g < good.size(); g++) {
+        const size_t k = good[g];
+        if ((verdict[k] = st2[g])) continue;
+        if (out_kprime) memcpy(kprime.data() + k * 32, kp2.data() + g * 32, 32);
+        key[k] = ok2[g];
       }
     }
+    // (the span of the window's lanes, read once and written back once, as before: with one message in 64 respelled the lane-by-lane
+    // road of the issuance settle measured 27 % slower here -- 512 blocking copies of 1 to 32 bytes in place of four of the span)
+    if ((rc = wire_patch_lanes(c, mem, status, 1, lanes, cnt, verdict.data(), true))) return rc;
+    if ((rc = wire_patch_lanes(c, mem, out_kprime, 32, lanes, cnt, kprime.data(), true))) return rc;
+    if ((rc = wire_patch_lanes(c, mem, out_nullifier, 32, lanes, cnt, nul.data(), true))) return rc;
+    if ((rc = wire_patch_lanes(c, mem, ring ? ring->out_key : nullptr, 1, lanes, cnt, key.data(), true))) return rc;
   }
   return call.finish();
 }
@@ -779,14 +772,7 @@ static int refund_cbor_tiny_records(act_ctx* c, size_t n, const uint8_t sk[64], 
     Slot& s0 = c->slots[0];
     CborDev d; int rc = cbor_dev_prepare(c, s0, ACT_CBOR_SPEND_PROOF, &d); if (rc) return rc;
     c->wire_layout = &d;
-    const size_t fcap = (n + 3) & ~(size_t)3;
-    if (fcap > c->d_wire_flags_cap) {
-      if (c->d_wire_flags) HIPCK(c, hipFree(c->d_wire_flags));
-      c->d_wire_flags = nullptr; c->d_wire_flags_cap = 0;
-      HIPCK(c, hipMalloc(&c->d_wire_flags, fcap)); c->d_wire_flags_cap = fcap;
-    }
-    HIPCK(c, hipMemsetAsync(c->d_wire_flags, 0, fcap, s0.stream));
-    HIPCK(c, hipStreamSynchronize(s0.stream));
+    if ((rc = wire_flags_reserve(c, n))) return rc;
     WireSrc w{cbor, offsets, d.lay.tmpl.size(), out_nullifier};
     rc = spend_batch_locked(c, n, ACT_MEM_HOST, sk, nullptr, true, rng, rng_mode, rec.data(), st.data(), nullptr, &w);
     c->wire_layout = nullptr;

@@ -12,7 +12,8 @@
 //     k_issue_check gives a message the reader refused its wire status (lane bodies: issue_wire_lanes.h).  Nothing is left for the end
 //     of the call but counting the flags for act_ctx_wire_stats.
 //   ACT_WIRE_READER_HOST: k_issue_a_wire flags it, and it is settled after the pipeline has drained, in windows of WIRE_SETTLE_WINDOW,
-//     with the host reader of the spend path: cbor_read_message -> cbor_settle_codes -> one small act_issue_check_batch.
+//     through the window of the spend path (wire_window_read in cbor_impl.inc over wire_window.h: gather, cbor_read_message,
+//     cbor_settle_codes), then one small act_issue_check_batch.
 
 namespace {
 
@@ -23,30 +24,6 @@ int issue_wire_prepare(act_ctx* c, IssueWire& w, bool want_req, bool want_resp) 
   if (want_req && (rc = cbor_dev_prepare(c, c->slots[0], ACT_CBOR_ISSUANCE_REQUEST, &w.req))) return rc;
   if (want_resp && (rc = cbor_dev_prepare(c, c->slots[1], ACT_CBOR_ISSUANCE_RESPONSE, &w.resp))) return rc;
   w.ml = w.req.lay.tmpl.size();
-  return ACT_OK;
-}
-int wire_flags_reserve(act_ctx* c, size_t n) {
-  const size_t fcap = (n + 3) & ~(size_t)3;
-  if (fcap > c->d_wire_flags_cap) {
-    if (c->d_wire_flags) HIPCK(c, hipFree(c->d_wire_flags));
-    c->d_wire_flags = nullptr; c->d_wire_flags_cap = 0;
-    HIPCK(c, hipMalloc(&c->d_wire_flags, fcap)); c->d_wire_flags_cap = fcap;
-  }
-  HIPCK(c, hipMemsetAsync(c->d_wire_flags, 0, fcap, c->slots[0].stream));
-  HIPCK(c, hipStreamSynchronize(c->slots[0].stream));
-  return ACT_OK;
-}
-
-// the device reader's code and info bytes, one each per message of the call, zero (CBOR_OK) until a reader kernel writes them (the
-// memset is on slot 0's stream: wire_flags_reserve, called next, waits for it)
-int wire_codes_reserve(act_ctx* c, size_t n) {
-  const size_t fcap = (n + 3) & ~(size_t)3;
-  if (fcap > c->d_wire_codes_cap) {
-    if (c->d_wire_codes) HIPCK(c, hipFree(c->d_wire_codes));
-    c->d_wire_codes = nullptr; c->d_wire_codes_cap = 0;
-    HIPCK(c, hipMalloc(&c->d_wire_codes, 2 * fcap)); c->d_wire_codes_cap = fcap;
-  }
-  HIPCK(c, hipMemsetAsync(c->d_wire_codes, 0, 2 * c->d_wire_codes_cap, c->slots[0].stream));
   return ACT_OK;
 }
 
@@ -145,23 +122,18 @@ int issue_sign_frame_locked(act_ctx* c, size_t n, int mem, const IssueWire& w, c
   return sync_all(c);
 }
 
-// Lanes of a caller's array (host or device memory) rewritten one window at a time: dense windows as one read-modify-write of their lane
-// span, sparse ones (two messages at the two ends of a large device batch) lane by lane.
-int patch_lanes(act_ctx* c, int mem, uint8_t* base, size_t stride, const std::vector<size_t>& lanes, const uint8_t* vals) {
-  if (lanes.empty() || !base) return ACT_OK;
-  if (mem == ACT_MEM_HOST) { for (size_t k = 0; k < lanes.size(); k++) memcpy(base + lanes[k] * stride, vals + k * stride, stride); return ACT_OK; }
+// issue_wire_settle runs between calls, with no lock held (its small calls take the context themselves): the locking forms of the
+// window and of the lane patch (wire_window_read, wire_patch_lanes: cbor_impl.inc).  They are defined here, behind the spend path,
+// which runs with the context held and must not see them.
+int window_read_locked(act_ctx* c, const CborType& T, const WireExtent& x, int mem, const size_t* which, size_t cnt, WireWindow& w) {
   std::lock_guard<std::mutex> lk(c->mu);
   HIPCK(c, hipSetDevice(c->device));
-  const size_t first = lanes.front(), span = lanes.back() - first + 1;
-  if (span <= 2 * lanes.size() + 64) {
-    std::vector<uint8_t> h(span * stride);
-    HIPCK(c, hipMemcpy(h.data(), base + first * stride, h.size(), hipMemcpyDeviceToHost));
-    for (size_t k = 0; k < lanes.size(); k++) memcpy(h.data() + (lanes[k] - first) * stride, vals + k * stride, stride);
-    HIPCK(c, hipMemcpy(base + first * stride, h.data(), h.size(), hipMemcpyHostToDevice));
-  } else {
-    for (size_t k = 0; k < lanes.size(); k++) HIPCK(c, hipMemcpy(base + lanes[k] * stride, vals + k * stride, stride, hipMemcpyHostToDevice));
-  }
-  return ACT_OK;
+  return wire_window_read(c, c->slots[0].stream, T, x, mem == ACT_MEM_DEVICE, which, cnt, 128, w);
+}
+int patch_lanes(act_ctx* c, int mem, uint8_t* base, size_t stride, const size_t* lanes, size_t cnt, const uint8_t* vals) {
+  std::lock_guard<std::mutex> lk(c->mu);
+  HIPCK(c, hipSetDevice(c->device));
+  return wire_patch_lanes(c, mem, base, stride, lanes, cnt, vals);
 }
 // `bytes` of caller memory at p (host or device) into dst
 int read_caller(act_ctx* c, int mem, const uint8_t* p, size_t bytes, uint8_t* dst) {
@@ -173,44 +145,31 @@ int read_caller(act_ctx* c, int mem, const uint8_t* p, size_t bytes, uint8_t* ds
   return ACT_OK;
 }
 
-// Settling the messages the pipeline flagged, after it has drained (no lock held: the small calls take it themselves).  A window reads
-// only its own messages, parses them with the spend path's reader, orders the codes as from_cbor does (cbor_settle_codes), checks the
-// records that parse in one small act_issue_check_batch and patches the window's lanes of status / out_req.  With `sk` (the whole
-// endpoint, ACT_RNG_PER_LANE) the accepted ones are also signed from their own rng slices and framed into out_resp.
+// Settling the messages the pipeline flagged, after it has drained (no lock held: the small calls take it themselves).  A window is
+// read by the spend path's window (its own messages only, the codes ordered as from_cbor does); here the records that read are checked
+// in one small act_issue_check_batch and the window's lanes of status / out_req patched.  With `sk` (the whole endpoint,
+// ACT_RNG_PER_LANE) the accepted ones are also signed from their own rng slices and framed into out_resp.
 int issue_wire_settle(act_ctx* c, int mem, const IssueWire& w, const std::vector<size_t>& which, const uint8_t sk[64], const uint8_t* camt,
                       const uint8_t* rng, uint8_t* out_resp, uint8_t* status, uint8_t* out_req) {
   const CborType* T = cbor_type(ACT_CBOR_ISSUANCE_REQUEST);
   const CborLayout rlay = cbor_layout(*cbor_type(ACT_CBOR_ISSUANCE_RESPONSE), c->L);
   const size_t rl = rlay.tmpl.size();
-  auto msg_beg = [&](size_t i) { return w.offsets ? (size_t)w.offsets[i] : i * w.ml; };
-  auto msg_end = [&](size_t i) { return w.offsets ? (size_t)w.offsets[i + 1] : (i + 1) * w.ml; };
+  const WireExtent x{w.cbor, w.offsets, w.ml};
+  WireWindow win;
   int rc;
   for (size_t w0 = 0; w0 < which.size(); w0 += WIRE_SETTLE_WINDOW) {
-    const size_t w1 = std::min(which.size(), w0 + WIRE_SETTLE_WINDOW), cnt = w1 - w0;
-    std::vector<size_t> lanes(which.begin() + w0, which.begin() + w1);
-    std::vector<uint8_t> msg; std::vector<int> codes(cnt); std::vector<CborCand> cands(cnt);
-    std::vector<uint8_t> recs(cnt * 128, 0), good_recs; std::vector<size_t> good;
+    const size_t cnt = std::min(which.size(), w0 + WIRE_SETTLE_WINDOW) - w0;
+    const size_t* lanes = which.data() + w0;
+    if ((rc = window_read_locked(c, *T, x, mem, lanes, cnt, win))) return rc;
+    std::vector<uint8_t>& recs = win.recs;
+    std::vector<uint8_t> good_recs; std::vector<size_t> good;
     for (size_t k = 0; k < cnt; k++) {
-      const size_t i = lanes[k], len = msg_end(i) - msg_beg(i);
-      msg.resize(len);
-      if ((rc = read_caller(c, mem, w.cbor + msg_beg(i), len, msg.data()))) return rc;
-      codes[k] = cbor_read_message(*T, c->L, msg.data(), len, recs.data() + k * 128, &cands[k]);
-    }
-    {
-      std::lock_guard<std::mutex> lk(c->mu);
-      HIPCK(c, hipSetDevice(c->device));
-      if ((rc = cbor_settle_codes(c, c->slots[0].stream, codes, cands))) return rc;      // the first error in wire order
-    }
-    for (size_t k = 0; k < cnt; k++) {
-      if (codes[k] != CBOR_OK) { memset(recs.data() + k * 128, 0, 128); continue; }
+      if (win.codes[k] != CBOR_OK) continue;
       for (int f = 1; f < 4; f++) store_sc(recs.data() + k * 128 + 32 * f, load_sc(recs.data() + k * 128 + 32 * f));      // decode_scalar
       good.push_back(k);
       good_recs.insert(good_recs.end(), recs.data() + k * 128, recs.data() + (k + 1) * 128);
     }
-    std::vector<uint8_t> verdict(cnt), st(good.size()), resp(cnt * rl, 0);
-    for (size_t k = 0; k < cnt; k++)
-      verdict[k] = codes[k] == CBOR_OK ? 0 : codes[k] == CBOR_ERR_VALUE ? (uint8_t)ACT_STATUS_UNDECODABLE
-                 : codes[k] == CBOR_ERR_PARSE ? (uint8_t)ACT_STATUS_CBOR_MALFORMED : (uint8_t)ACT_STATUS_CBOR_STRUCTURE;
+    std::vector<uint8_t> verdict(win.status), st(good.size()), resp(cnt * rl, 0);
     if (!good.empty()) {
       if ((rc = act_issue_check_batch(c, good.size(), ACT_MEM_HOST, good_recs.data(), st.data()))) return rc;
       for (size_t g = 0; g < good.size(); g++) verdict[good[g]] = st[g];
@@ -242,9 +201,9 @@ int issue_wire_settle(act_ctx* c, int mem, const IssueWire& w, const std::vector
       }
     }
     for (size_t k = 0; k < cnt; k++) if (verdict[k]) { memset(recs.data() + k * 128, 0, 128); memset(resp.data() + k * rl, 0, rl); }
-    if ((rc = patch_lanes(c, mem, status, 1, lanes, verdict.data()))) return rc;
-    if (out_req && (rc = patch_lanes(c, mem, out_req, 128, lanes, recs.data()))) return rc;
-    if (sk && (rc = patch_lanes(c, mem, out_resp, rl, lanes, resp.data()))) return rc;
+    if ((rc = patch_lanes(c, mem, status, 1, lanes, cnt, verdict.data()))) return rc;
+    if (out_req && (rc = patch_lanes(c, mem, out_req, 128, lanes, cnt, recs.data()))) return rc;
+    if (sk && (rc = patch_lanes(c, mem, out_resp, rl, lanes, cnt, resp.data()))) return rc;
   }
   return ACT_OK;
 }
