@@ -276,6 +276,18 @@ class PrivateKey(_Cbor):
         res, _ = Keyring([self]).redeem_admit_cbor_batch(params, db, msgs, rng, nbits, charges=charges, unique=unique)
         return res
 
+    # ---- replayable redemption: a retried SpendProof gets its Refund again ----------------------------------
+    def redeem_replay_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", proofs: Sequence["SpendProof"], nonce_key: bytes) -> Tuple[list, list]:
+        """redeem_batch without a generator: the nonces are derived from `nonce_key` (32 secret bytes the issuer keeps), this key, the
+        nullifier and K', and `receipts` (a second NullifierDb) remembers which K' a nullifier was spent for -- a proof that is sent
+        again gets the same Refund, byte for byte, instead of DoubleSpendError.  -> (results, replayed flags)"""
+        res, _, replayed = Keyring([self]).redeem_replay_batch(params, db, receipts, proofs, nonce_key)
+        return res, replayed
+
+    def redeem_replay_cbor_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", msgs: Sequence[bytes], nonce_key: bytes, nbits: int = L) -> Tuple[list, list]:
+        res, _, replayed = Keyring([self]).redeem_replay_cbor_batch(params, db, receipts, msgs, nonce_key, nbits)
+        return res, replayed
+
     def verify_spend_batch(self, params: Params, proofs: Sequence["SpendProof"]) -> bytes:
         nbits = proofs[0].nbits if proofs else L
         return params.engine(nbits).verify_spend(self.record, b"".join(p.record for p in proofs))
@@ -368,6 +380,24 @@ class Keyring:
         st, out, ok, self.last_admit_counts = _draw_signed(rng, len(msgs), lambda src, mode: e.redeem_cbor_admit(
             db.set, self._records(), list(msgs), src, mode, self._sign_key(sign_with), charges=cc, key_epochs=self.epochs, unique=unique))
         return [out[i] if st[i] == 0 else _wire_error(st[i]) for i in range(len(msgs))], self._indices(st, ok)
+
+    def redeem_replay_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", proofs: Sequence["SpendProof"], nonce_key: bytes, sign_with=None) -> Tuple[list, list, list]:
+        """redeem_batch made retry-safe (act_redeem_replay_batch): no generator -- the nonces are derived from `nonce_key`, the key a
+        lane is signed with, the nullifier and K' -- and `receipts`, a second NullifierDb, records for which K' every nullifier was
+        spent.  A proof that is sent again (same ring key to sign with, same nonce_key) gets the same Refund, byte for byte; another
+        proof for the same nullifier is DoubleSpendError as before.  Retire an epoch on both databases.
+        -> (results, matched ring indices, replayed flags); `self.last_replay_counts`: the call's counts."""
+        nbits = proofs[0].nbits if proofs else L
+        st, out, ok, rep, self.last_replay_counts = params.engine(nbits).redeem_replay(
+            db.set, receipts.set, self._records(), b"".join(p.record for p in proofs), nonce_key, self._sign_key(sign_with), key_epochs=self.epochs)
+        return [Refund(out[128 * i:128 * i + 128]) if st[i] == 0 else Error(st[i]) for i in range(len(proofs))], self._indices(st, ok), [bool(r) for r in rep]
+
+    def redeem_replay_cbor_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", msgs: Sequence[bytes], nonce_key: bytes, nbits: int = L,
+                                 sign_with=None) -> Tuple[list, list, list]:
+        """the same on wire bytes (act_redeem_cbor_replay_batch): a retry may be another CBOR spelling of the same proof"""
+        st, out, ok, rep, self.last_replay_counts = params.engine(nbits).redeem_cbor_replay(
+            db.set, receipts.set, self._records(), list(msgs), nonce_key, self._sign_key(sign_with), key_epochs=self.epochs)
+        return [out[i] if st[i] == 0 else _wire_error(st[i]) for i in range(len(msgs))], self._indices(st, ok), [bool(r) for r in rep]
 
 
 class PreIssuance(_Cbor):

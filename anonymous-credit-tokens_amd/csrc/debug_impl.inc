@@ -124,6 +124,7 @@ int act_debug_secret_residue(act_ctx* c, size_t* nonzero_bytes) {
   for (Slot& sl : c->slots) regions.emplace_back(sl.d_trs, std::min<size_t>(4096, c->max_batch) * SMALL_TR_STRIDE);      // the small transcripts (first lanes): a rejected lane's signature (sign-beside-the-check kernels) must not survive the call
   if (c->d_tiny) { regions.emplace_back(c->d_tiny, TINY_OUT); for (size_t i = 0; i < TINY_OUT; i++) nz += c->h_tiny[i] != 0; }      // staged inputs of the tiny calls (device + pinned)
   if (c->d_admit_rng) regions.emplace_back(c->d_admit_rng, c->d_admit_rng_cap);      // the gathered per-lane rng slices of the admission calls
+  if (c->d_replay) regions.emplace_back(c->d_replay, c->d_replay_cap);      // the staged nonce_key and the derived nonces of the replay calls
   if (c->d_small) regions.emplace_back(c->d_small, c->d_small_cap);      // the small-batch schedule's partial sums and bucket sets (what single-item calls use)
   for (auto& r : regions) total += r.second;
   if (total > ((size_t)1 << 30)) { c->err = "act_debug_secret_residue: context too large to read back (use a small max_batch)"; return ACT_ERR_ARG; }

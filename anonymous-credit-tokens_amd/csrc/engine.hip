@@ -20,6 +20,7 @@
 #include "kernels.h"
 #include "keyring.h"
 #include "admit.h"
+#include "replay_lanes.h"
 #include "cbor_lanes.h"
 #include "issue_wire_lanes.h"
 #include "rng_source.h"
@@ -184,6 +185,8 @@ struct act_ctx {
   std::atomic<int> debug_fail_signs{0};          // act_debug_fail_next_signs (test hook of the redeem failure contract)
   std::mutex admit_mu;                 // an admission call holds it from start to end (admit_impl.inc): d_admit_rng below belongs to ONE call at a time; taken before mu, never under it
   uint8_t* d_admit_rng = nullptr; size_t d_admit_rng_cap = 0;      // the survivors' per-lane rng slices of an admission call (admit_impl.inc): wiped when the call ends
+  std::mutex replay_mu;                // a replay call holds it from start to end (replay_impl.inc): d_replay below belongs to ONE call at a time; taken before mu, never under it
+  uint8_t* d_replay = nullptr; size_t d_replay_cap = 0;            // the staged nonce_key and ring records, then the derived per-lane nonces of a replay call: wiped when the call ends
   struct RingWs* ring_ws = nullptr;              // key-ring side buffers, allocated by the context's first ring call (keyring_impl.inc)
 };
 static void ring_ws_free(act_ctx* c);            // keyring_impl.inc
@@ -803,6 +806,7 @@ void act_ctx_destroy(act_ctx* c) {
   if (c->d_wire_flags) (void)hipFree(c->d_wire_flags);
   if (c->d_wire_codes) (void)hipFree(c->d_wire_codes);
   if (c->d_admit_rng) { (void)hipMemset(c->d_admit_rng, 0, c->d_admit_rng_cap); (void)hipFree(c->d_admit_rng); }
+  if (c->d_replay) { (void)hipMemset(c->d_replay, 0, c->d_replay_cap); (void)hipFree(c->d_replay); }
   ring_ws_free(c);
   memset(&c->key, 0, sizeof(c->key)); memset(c->sk_cached, 0, 64);
   delete c;
@@ -1300,3 +1304,4 @@ int act_refund_batch(act_ctx* c, size_t n, int mem, const uint8_t sk[64], const 
 #include "keyring_redeem_impl.inc"
 #include "admit_impl.inc"          // admission before verification: act_redeem_admit_batch, act_redeem_cbor_admit_batch
 #include "copies_impl.inc"         // its copy stage: act_redeem_admit_unique_batch, act_redeem_cbor_admit_unique_batch
+#include "replay_impl.inc"         // replayable redemption: act_redeem_replay_batch, act_redeem_cbor_replay_batch, act_replay_derive_batch

@@ -5,6 +5,35 @@
 // out_key, as the ring verification leaves it, is the epoch index of the insert.
 // Arrays of n lanes in `mem` memory: st = the verdicts, out_key = the matched ring indices, kp = enc(K'), the nullifiers at
 // nul + i * nul_stride; sp and kidx are scratch of n bytes each.  The admission calls (admit_impl.inc) hand it the survivors' compact arrays.
+// the signatures of a ring redemption, each lane with ring key kidx[i], framed as Refund messages for the wire form (redeem_tail's sign_step)
+static int ring_sign_step(act_ctx* c, size_t n, int mem, const uint8_t* keys, int nkeys, bool wire, const uint8_t* kidx, const uint8_t* kp, const uint8_t* verdict,
+                          const uint8_t* r, int r_mode, uint8_t* o, uint8_t* o_st) {
+  if (!wire) return act_refund_sign_keyring_batch(c, n, mem, keys, nkeys, kidx, kp, verdict, r, r_mode, o, o_st);
+  int rc_sign;
+  if (mem == ACT_MEM_HOST) {      // framed as act_refund_sign_cbor_batch frames: on the host workers, where the signatures landed
+    std::vector<uint8_t> rec(n * 128);
+    rc_sign = act_refund_sign_keyring_batch(c, n, mem, keys, nkeys, kidx, kp, verdict, r, r_mode, rec.data(), o_st);
+    if (!rc_sign) cbor_frame_refunds_host(cbor_layout(*cbor_type(ACT_CBOR_REFUND), c->L), n, rec.data(), o_st, o);
+    return rc_sign;
+  }
+  DevTmp rec(c);
+  rc_sign = rec.alloc(n * 128);
+  if (!rc_sign) rc_sign = act_refund_sign_keyring_batch(c, n, mem, keys, nkeys, kidx, kp, verdict, r, r_mode, rec.p, o_st);
+  if (!rc_sign) rc_sign = act_cbor_encode_batch(c, ACT_CBOR_REFUND, n, mem, rec.p, o);
+  if (!rc_sign) {
+    std::lock_guard<std::mutex> lk(c->mu);
+    (void)hipSetDevice(c->device);
+    const uint32_t out_b = (uint32_t)act_cbor_size(c, ACT_CBOR_REFUND);
+    hipLaunchKernelGGL(k_cbor_zero_failed, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->slots[0].stream, o, out_b, o_st, (uint32_t)n);
+    if (hipStreamSynchronize(c->slots[0].stream) != hipSuccess) { (void)hipGetLastError(); c->err = "k_cbor_zero_failed failed"; rc_sign = ACT_ERR_HIP; }
+  }
+  return rc_sign;
+}
+// the key every lane is signed with (out_key keeps what the lane matched): redeem_tail's beside_merge of the ring calls
+static void ring_sign_index(int mem, uint8_t* kidx, const uint8_t* out_key, int sign_key, size_t n) {
+  if (mem == ACT_MEM_DEVICE) launch_ring_resolve_index(kidx, out_key, sign_key, (uint32_t)n, nullptr);
+  else for (size_t i = 0; i < n; i++) kidx[i] = sign_key >= 0 ? (uint8_t)sign_key : out_key[i];
+}
 static int redeem_tail_ring(act_ctx* c, act_nullifier_set* set, size_t n, int mem, const uint8_t* keys, int nkeys, const uint32_t* key_epochs, int sign_key, bool wire,
                             const uint8_t* nul, size_t nul_stride, const uint8_t* kp, uint8_t* st, uint8_t* sp, uint8_t* kidx, const uint8_t* rng, int rng_mode,
                             uint8_t* out, uint8_t* status, uint8_t* out_key) {
@@ -13,31 +42,9 @@ static int redeem_tail_ring(act_ctx* c, act_nullifier_set* set, size_t n, int me
       return key_epochs ? act_nullifier_check_and_insert_epoch_batch(set, n, mem, nul, nul_stride, mask, out_key, key_epochs, nkeys, spent)
                         : act_nullifier_check_and_insert_batch(set, n, mem, nul, nul_stride, mask, spent);
     },
-    [&] {      // the key every lane is signed with (out_key keeps what the lane matched)
-      if (mem == ACT_MEM_DEVICE) launch_ring_resolve_index(kidx, out_key, sign_key, (uint32_t)n, nullptr);
-      else for (size_t i = 0; i < n; i++) kidx[i] = sign_key >= 0 ? (uint8_t)sign_key : out_key[i];
-    },
+    [&] { ring_sign_index(mem, kidx, out_key, sign_key, n); },
     [&](const uint8_t* verdict, const uint8_t* r, int r_mode, uint8_t* o, uint8_t* o_st) {
-      if (!wire) return act_refund_sign_keyring_batch(c, n, mem, keys, nkeys, kidx, kp, verdict, r, r_mode, o, o_st);
-      int rc_sign;
-      if (mem == ACT_MEM_HOST) {      // framed as act_refund_sign_cbor_batch frames: on the host workers, where the signatures landed
-        std::vector<uint8_t> rec(n * 128);
-        rc_sign = act_refund_sign_keyring_batch(c, n, mem, keys, nkeys, kidx, kp, verdict, r, r_mode, rec.data(), o_st);
-        if (!rc_sign) cbor_frame_refunds_host(cbor_layout(*cbor_type(ACT_CBOR_REFUND), c->L), n, rec.data(), o_st, o);
-        return rc_sign;
-      }
-      DevTmp rec(c);
-      rc_sign = rec.alloc(n * 128);
-      if (!rc_sign) rc_sign = act_refund_sign_keyring_batch(c, n, mem, keys, nkeys, kidx, kp, verdict, r, r_mode, rec.p, o_st);
-      if (!rc_sign) rc_sign = act_cbor_encode_batch(c, ACT_CBOR_REFUND, n, mem, rec.p, o);
-      if (!rc_sign) {
-        std::lock_guard<std::mutex> lk(c->mu);
-        (void)hipSetDevice(c->device);
-        const uint32_t out_b = (uint32_t)act_cbor_size(c, ACT_CBOR_REFUND);
-        hipLaunchKernelGGL(k_cbor_zero_failed, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->slots[0].stream, o, out_b, o_st, (uint32_t)n);
-        if (hipStreamSynchronize(c->slots[0].stream) != hipSuccess) { (void)hipGetLastError(); c->err = "k_cbor_zero_failed failed"; rc_sign = ACT_ERR_HIP; }
-      }
-      return rc_sign;
+      return ring_sign_step(c, n, mem, keys, nkeys, wire, kidx, kp, verdict, r, r_mode, o, o_st);
     });
 }
 

@@ -747,6 +747,67 @@ int act_redeem_cbor_admit_unique_batch(act_ctx *ctx, act_nullifier_set *set, siz
                                        const uint8_t *charge /* nullable */, const uint8_t *rng, int rng_mode, uint8_t *out_refund_cbor,
                                        uint8_t *status, uint8_t *out_key, uint64_t *out_counts /* nullable, host */);
 
+/* ======== replayable redemption: a retried SpendProof gets its Refund again ========
+ * The redeem calls above record the nullifier and then sign; the refund exists only in the call's output buffer.  A client whose
+ * response was lost resends the same SpendProof, gets DoubleSpendError and loses its remaining credits.  These two calls are
+ * act_redeem_(cbor_)keyring_epochs_batch (key_epochs nullable; nkeys == 1 is the one-key call) made retry-safe without storing a refund:
+ *   derived nonces  the lane's 128 nonce bytes are not drawn from a generator (there is no rng / rng_mode) but derived from the
+ *                   issuer's `nonce_key`, the key the lane is SIGNED with, the nullifier and enc(K'): signing the same spend again
+ *                   gives the same refund byte for byte, a different spend gets independent nonces.
+ *   receipts        a second, ordinary act_nullifier_set records one 32-byte tag per recorded nullifier: WHICH K' it was spent for.
+ * Exact definitions (BLAKE3, default mode; every input has a fixed length, so nothing is length-prefixed; k_i = the lane's
+ * nullifier reduced mod l, 32 bytes little-endian; key_j = the 64-byte record x | enc(w) of the key lane i is signed with):
+ *     tag_i   = BLAKE3("act-mi355x/receipt/v1" zero-padded to 32 bytes | k_i | enc(K'_i))[0:32] with byte 31 &= 0x0F
+ *     nonce_i = BLAKE3-XOF("act-mi355x/refund-nonce/v1" zero-padded to 32 bytes | nonce_key | key_j | k_i | enc(K'_i), 128 bytes)
+ * The refund of lane i is byte for byte act_refund_sign_keyring_batch over enc(K'_i) with nonce_i as its ACT_RNG_PER_LANE slice.
+ * In lane order:
+ *     1. verification exactly as in the ring redeem call, records or wire (every legal spelling, read as act_ctx_set_wire_reader
+ *        says; 255 / 6 / 7 and the CBOR codes unchanged; out_key unchanged)
+ *     2. check-and-insert of k into `set`, under the matched key's epoch when key_epochs is given
+ *     3. k was fresh: the lane's tag is recorded in `receipts` under the same epoch (ONLY then: a double spender cannot plant a tag)
+ *     4. k was spent -- before the call or by an earlier lane of this batch -- and the tag is in `receipts`: this is the very spend
+ *        that was recorded, a REPLAY: status 0, out_replayed[i] = 1, signed again.  Tag absent: another spend of the same token,
+ *        ACT_STATUS_DOUBLE_SPEND and a zero record as in the redeem calls (the lane keeps the out_key it matched).
+ *     5. fresh and replayed lanes are signed with nonce_i, by ring key sign_key or the matched key (ACT_SIGN_MATCHED); the wire form
+ *        frames Refund messages.
+ * Why this is safe: the refund depends only on K', and K' commits to the new nullifier k*, to r* and to c - s.  Handing the same
+ * refund out twice gives the holder ONE token with nullifier k*, which can be spent once.  A second proof for the same k with another
+ * K' -- the actual double spend -- has another tag and is refused.  A replay is verified again: it costs what a double spend costs.
+ * What follows:
+ *   - a retry after the original call returned gets the identical refund bytes as long as the signing key and nonce_key are the same
+ *     -- also on another context, after export / restore of BOTH sets, and when the retry is another CBOR spelling of the same proof.
+ *   - if sign_key has moved in between, the retry gets a different refund, valid under the new key for the same K'; likewise a
+ *     rotated nonce_key gives a different, still valid refund.  (Either way the client holds one K' and can finish one of them.)
+ *   - a retry that races its original call may still see ACT_STATUS_DOUBLE_SPEND once (k recorded, receipt not yet).
+ *   - failures are those of act_redeem_*: ACT_STATUS_NULLIFIER_UNDETERMINED lanes are not recorded and get no receipt; after a failed
+ *     signature step lanes say ACT_STATUS_RECORDED_UNSIGNED, and their repair is now TO CALL THIS CALL AGAIN with the same lanes (the
+ *     receipt was written before signing).  A failure of the receipts step after k was recorded never withholds a refund: the lanes
+ *     are signed, the call returns the receipts set's error with its text, and only the retry of those lanes is lost.
+ *   - retire an epoch on BOTH sets.  The existing act_redeem_* calls, and a set that never sees one of these calls, are unchanged.
+ * Refused as a whole before any GPU work (nothing verified, nothing recorded, status[] not written), ACT_ERR_ARG: everything the ring
+ * redeem calls refuse; receipts NULL, the same handle as set, or on another device; nonce_key NULL; an epoch table either set
+ * refuses; a receipts set that cannot take n more keys by the set's own room rule (len + n > slots / 2: act_nullifier_set_reserve it).
+ * out_replayed: nullable, n bytes in `mem` memory.  out_counts: nullable, HOST memory, ACT_REPLAY_COUNTS values: lanes,
+ * rejected_by_verification, fresh (recorded and signed), replayed, double_spend, unanswered (UNDETERMINED or RECORDED_UNSIGNED).
+ * One replay call runs at a time per context; nonce_key, the ring and the derived nonces are staged in buffers of the context that
+ * are wiped on every exit.  Always the pipelined chunk schedule, whatever n. */
+#define ACT_REPLAY_COUNTS 6
+int act_redeem_replay_batch(act_ctx *ctx, act_nullifier_set *set, act_nullifier_set *receipts, size_t n, int mem, const uint8_t *keys, int nkeys,
+                            const uint32_t *key_epochs /* nullable */, int sign_key, const uint8_t *proof, const uint8_t nonce_key[32],
+                            uint8_t *out_refund, uint8_t *status, uint8_t *out_key, uint8_t *out_replayed /* nullable */,
+                            uint64_t *out_counts /* nullable, host */);
+int act_redeem_cbor_replay_batch(act_ctx *ctx, act_nullifier_set *set, act_nullifier_set *receipts, size_t n, int mem, const uint8_t *keys, int nkeys,
+                                 const uint32_t *key_epochs /* nullable */, int sign_key, const uint8_t *cbor, const uint64_t *offsets,
+                                 const uint8_t nonce_key[32], uint8_t *out_refund_cbor, uint8_t *status, uint8_t *out_key,
+                                 uint8_t *out_replayed /* nullable */, uint64_t *out_counts /* nullable, host */);
+/* The building block of the two calls above, for callers that compose the same thing from act_node_verify_spend_keyring_batch, two
+ * node-level sets and act_node_refund_sign_keyring_batch: out_tags[i] (32 bytes) and out_nonces[i] (128 bytes) of every lane with
+ * status_in[i] == 0 and key_index[i] < nkeys (the key the lane is to be SIGNED with); every other lane gets zeros.  nullifiers:
+ * lane i at nullifiers + i * stride (stride >= 32; reduced here).  All arrays in `mem` memory; keys and nonce_key in host memory. */
+int act_replay_derive_batch(act_ctx *ctx, size_t n, int mem, const uint8_t *keys, int nkeys, const uint8_t *key_index,
+                            const uint8_t nonce_key[32], const uint8_t *nullifiers, size_t stride, const uint8_t *kprime,
+                            const uint8_t *status_in, uint8_t *out_tags /* nullable */, uint8_t *out_nonces /* nullable */);
+
 /* ======== row d and test infrastructure: debug hooks, measurement knobs, kernel timing, roofline probes (nothing here is on the product's path) ==== */
 /* Debug / test hook: the exact "spend" transcript pre-images of the last act_verify_spend_batch /
  * act_refund_batch chunk (n_last * act_spend_transcript_bytes, copied to host memory). */

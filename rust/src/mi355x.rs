@@ -134,6 +134,14 @@ extern "C" {
     fn act_redeem_cbor_admit_unique_batch(ctx: *mut ActCtx, set: *mut ActNullifierSet, n: usize, mem: c_int, keys: *const u8, nkeys: c_int, key_epochs: *const u32,
                                           sign_key: c_int, cbor: *const u8, offsets: *const u64, charge: *const u8, rng: *const u8, rng_mode: c_int,
                                           out_refund_cbor: *mut u8, status: *mut u8, out_key: *mut u8, out_counts: *mut u64) -> c_int;
+    fn act_redeem_replay_batch(ctx: *mut ActCtx, set: *mut ActNullifierSet, receipts: *mut ActNullifierSet, n: usize, mem: c_int, keys: *const u8, nkeys: c_int,
+                               key_epochs: *const u32, sign_key: c_int, proof: *const u8, nonce_key: *const u8, out_refund: *mut u8, status: *mut u8,
+                               out_key: *mut u8, out_replayed: *mut u8, out_counts: *mut u64) -> c_int;
+    fn act_redeem_cbor_replay_batch(ctx: *mut ActCtx, set: *mut ActNullifierSet, receipts: *mut ActNullifierSet, n: usize, mem: c_int, keys: *const u8, nkeys: c_int,
+                                    key_epochs: *const u32, sign_key: c_int, cbor: *const u8, offsets: *const u64, nonce_key: *const u8, out_refund_cbor: *mut u8,
+                                    status: *mut u8, out_key: *mut u8, out_replayed: *mut u8, out_counts: *mut u64) -> c_int;
+    fn act_replay_derive_batch(ctx: *mut ActCtx, n: usize, mem: c_int, keys: *const u8, nkeys: c_int, key_index: *const u8, nonce_key: *const u8,
+                               nullifiers: *const u8, stride: usize, kprime: *const u8, status_in: *const u8, out_tags: *mut u8, out_nonces: *mut u8) -> c_int;
     fn act_node_device_stats(node: *mut ActNode, k: c_int, weight: *mut f64, last_lanes: *mut u64, last_seconds: *mut f64, last_calls: *mut u64) -> c_int;
 }
 
@@ -1137,6 +1145,77 @@ impl GpuAdmission {
         r.counts.copy_from_slice(&counts[..ACT_ADMIT_COUNTS]); r.copies = counts[ACT_ADMIT_COUNTS];
         r.status.truncate(n); r.out.truncate(REFUND_CBOR_BYTES * n); r.out_key.truncate(n);
         r
+    }
+}
+
+pub const ACT_REPLAY_COUNTS: usize = 6;
+/// statuses, outputs (128-byte Refund records or `REFUND_CBOR_BYTES` messages, all zero where not signed), matched ring keys, the
+/// replay marks, and lanes / rejected_by_verification / fresh / replayed / double_spend / unanswered
+pub struct Replayed {
+    pub rc: c_int,
+    pub status: Vec<u8>,
+    pub out: Vec<u8>,
+    pub out_key: Vec<u8>,
+    pub replayed: Vec<u8>,
+    pub counts: [u64; ACT_REPLAY_COUNTS],
+}
+/// Replayable redemption on ONE GPU (include/act_mi355x.h "replayable redemption"): the ring redeem calls without a generator -- the
+/// nonces are derived from `nonce_key`, the signing key, the nullifier and K' -- and with a second set, the receipts, that records for
+/// which K' a nullifier was spent.  A `SpendProof` that is sent again gets the same `Refund`, byte for byte, instead of
+/// `DoubleSpendError`; another proof for the same nullifier is refused as before.  Retire an epoch on BOTH sets.  Thin: bytes in, bytes
+/// out.  The node-level forms do not exist yet; node callers compose `derive` with their verify, set and sign calls.
+pub struct GpuReplay {
+    ctx: *mut ActCtx,
+    set: *mut ActNullifierSet,
+    receipts: *mut ActNullifierSet,
+    nonce_key: [u8; 32],
+}
+impl GpuReplay {
+    /// # Safety
+    /// `ctx`, `set` and `receipts` are live handles on one device, `set != receipts`, and all three outlive `self`.
+    pub unsafe fn from_raw(ctx: *mut ActCtx, set: *mut ActNullifierSet, receipts: *mut ActNullifierSet, nonce_key: [u8; 32]) -> Self {
+        GpuReplay { ctx, set, receipts, nonce_key }
+    }
+    /// `keys`: nkeys records of 64 bytes; `proofs`: n records of `PROOF_BYTES`.
+    pub fn redeem_replay_batch(&self, keys: &[u8], key_epochs: Option<&[u32]>, sign_with: Option<usize>, proofs: &[u8]) -> Replayed {
+        let (n, nkeys) = (proofs.len() / PROOF_BYTES, keys.len() / 64);
+        assert!(proofs.len() == n * PROOF_BYTES && key_epochs.map_or(true, |e| e.len() == nkeys));
+        let mut r = Replayed { rc: 0, status: vec![0u8; n + 1], out: vec![0u8; 128 * n + 1], out_key: vec![ACT_KEY_NONE; n + 1], replayed: vec![0u8; n + 1], counts: [0; ACT_REPLAY_COUNTS] };
+        r.rc = unsafe {
+            act_redeem_replay_batch(self.ctx, self.set, self.receipts, n, 0, keys.as_ptr(), nkeys as c_int, key_epochs.map_or(std::ptr::null(), |e| e.as_ptr()),
+                                    sign_with.map_or(ACT_SIGN_MATCHED, |i| i as c_int), proofs.as_ptr(), self.nonce_key.as_ptr(), r.out.as_mut_ptr(),
+                                    r.status.as_mut_ptr(), r.out_key.as_mut_ptr(), r.replayed.as_mut_ptr(), r.counts.as_mut_ptr())
+        };
+        r.status.truncate(n); r.out.truncate(128 * n); r.out_key.truncate(n); r.replayed.truncate(n);
+        r
+    }
+    /// The same on wire bytes: CBOR SpendProof messages in (a retry may be another spelling of the same proof), CBOR Refund messages out.
+    pub fn redeem_cbor_replay_batch(&self, keys: &[u8], key_epochs: Option<&[u32]>, sign_with: Option<usize>, msgs: &[&[u8]]) -> Replayed {
+        let (blob, offsets) = gather(msgs);
+        let (n, nkeys) = (msgs.len(), keys.len() / 64);
+        assert!(key_epochs.map_or(true, |e| e.len() == nkeys));
+        let mut r = Replayed { rc: 0, status: vec![0u8; n + 1], out: vec![0u8; REFUND_CBOR_BYTES * n + 1], out_key: vec![ACT_KEY_NONE; n + 1], replayed: vec![0u8; n + 1],
+                               counts: [0; ACT_REPLAY_COUNTS] };
+        r.rc = unsafe {
+            act_redeem_cbor_replay_batch(self.ctx, self.set, self.receipts, n, 0, keys.as_ptr(), nkeys as c_int, key_epochs.map_or(std::ptr::null(), |e| e.as_ptr()),
+                                         sign_with.map_or(ACT_SIGN_MATCHED, |i| i as c_int), blob.as_ptr(), offsets.as_ptr(), self.nonce_key.as_ptr(),
+                                         r.out.as_mut_ptr(), r.status.as_mut_ptr(), r.out_key.as_mut_ptr(), r.replayed.as_mut_ptr(), r.counts.as_mut_ptr())
+        };
+        r.status.truncate(n); r.out.truncate(REFUND_CBOR_BYTES * n); r.out_key.truncate(n); r.replayed.truncate(n);
+        r
+    }
+    /// The building block: per lane with `status_in[i] == 0` and `key_index[i] < nkeys` the 32-byte receipt tag and the 128 nonce
+    /// bytes (`ACT_RNG_PER_LANE` slices for the sign call); zeros elsewhere.  `nullifiers`: n dense 32-byte values.  -> (rc, tags, nonces)
+    pub fn derive(&self, keys: &[u8], key_index: &[u8], nullifiers: &[u8], kprime: &[u8], status_in: &[u8]) -> (c_int, Vec<u8>, Vec<u8>) {
+        let n = status_in.len();
+        assert!(key_index.len() == n && nullifiers.len() == 32 * n && kprime.len() == 32 * n);
+        let (mut tags, mut nonces) = (vec![0u8; 32 * n + 1], vec![0u8; 128 * n + 1]);
+        let rc = unsafe {
+            act_replay_derive_batch(self.ctx, n, 0, keys.as_ptr(), (keys.len() / 64) as c_int, key_index.as_ptr(), self.nonce_key.as_ptr(), nullifiers.as_ptr(), 32,
+                                    kprime.as_ptr(), status_in.as_ptr(), tags.as_mut_ptr(), nonces.as_mut_ptr())
+        };
+        tags.truncate(32 * n); nonces.truncate(128 * n);
+        (rc, tags, nonces)
     }
 }
 
