@@ -277,15 +277,17 @@ class PrivateKey(_Cbor):
         return res
 
     # ---- replayable redemption: a retried SpendProof gets its Refund again ----------------------------------
-    def redeem_replay_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", proofs: Sequence["SpendProof"], nonce_key: bytes) -> Tuple[list, list]:
+    def redeem_replay_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", proofs: Sequence["SpendProof"], nonce_key: bytes,
+                            admit: bool = False, charges: Sequence = None) -> Tuple[list, list]:
         """redeem_batch without a generator: the nonces are derived from `nonce_key` (32 secret bytes the issuer keeps), this key, the
         nullifier and K', and `receipts` (a second NullifierDb) remembers which K' a nullifier was spent for -- a proof that is sent
-        again gets the same Refund, byte for byte, instead of DoubleSpendError.  -> (results, replayed flags)"""
-        res, _, replayed = Keyring([self]).redeem_replay_batch(params, db, receipts, proofs, nonce_key)
+        again gets the same Refund, byte for byte, instead of DoubleSpendError.  admit / charges: Keyring.redeem_replay_batch.  -> (results, replayed flags)"""
+        res, _, replayed = Keyring([self]).redeem_replay_batch(params, db, receipts, proofs, nonce_key, admit=admit, charges=charges)
         return res, replayed
 
-    def redeem_replay_cbor_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", msgs: Sequence[bytes], nonce_key: bytes, nbits: int = L) -> Tuple[list, list]:
-        res, _, replayed = Keyring([self]).redeem_replay_cbor_batch(params, db, receipts, msgs, nonce_key, nbits)
+    def redeem_replay_cbor_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", msgs: Sequence[bytes], nonce_key: bytes, nbits: int = L,
+                                 admit: bool = False, charges: Sequence = None) -> Tuple[list, list]:
+        res, _, replayed = Keyring([self]).redeem_replay_cbor_batch(params, db, receipts, msgs, nonce_key, nbits, admit=admit, charges=charges)
         return res, replayed
 
     def verify_spend_batch(self, params: Params, proofs: Sequence["SpendProof"]) -> bytes:
@@ -381,22 +383,42 @@ class Keyring:
             db.set, self._records(), list(msgs), src, mode, self._sign_key(sign_with), charges=cc, key_epochs=self.epochs, unique=unique))
         return [out[i] if st[i] == 0 else _wire_error(st[i]) for i in range(len(msgs))], self._indices(st, ok)
 
-    def redeem_replay_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", proofs: Sequence["SpendProof"], nonce_key: bytes, sign_with=None) -> Tuple[list, list, list]:
+    def redeem_replay_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", proofs: Sequence["SpendProof"], nonce_key: bytes, sign_with=None,
+                            admit: bool = False, charges: Sequence = None) -> Tuple[list, list, list]:
         """redeem_batch made retry-safe (act_redeem_replay_batch): no generator -- the nonces are derived from `nonce_key`, the key a
         lane is signed with, the nullifier and K' -- and `receipts`, a second NullifierDb, records for which K' every nullifier was
         spent.  A proof that is sent again (same ring key to sign with, same nonce_key) gets the same Refund, byte for byte; another
         proof for the same nullifier is DoubleSpendError as before.  Retire an epoch on both databases.
+        admit=True (act_redeem_admit_replay_batch): the admission screen in front -- `charges` (optional, one per proof; Error 250 for
+        a proof whose s differs) and the spent nullifiers first: a proof whose nullifier is spent and whose receipt is not its own is
+        DoubleSpendError WITHOUT being verified, a retry is verified and served.  Accepted lanes, refunds and both databases end as
+        without it; the counts are capi.ADMIT_REPLAY_COUNTS.
         -> (results, matched ring indices, replayed flags); `self.last_replay_counts`: the call's counts."""
         nbits = proofs[0].nbits if proofs else L
-        st, out, ok, rep, self.last_replay_counts = params.engine(nbits).redeem_replay(
-            db.set, receipts.set, self._records(), b"".join(p.record for p in proofs), nonce_key, self._sign_key(sign_with), key_epochs=self.epochs)
+        if charges is not None and not admit:
+            raise ValueError("charges are compared by the admission screen: admit=True")
+        e, pb = params.engine(nbits), b"".join(p.record for p in proofs)
+        if admit:
+            cc = b"".join(scalar(c) for c in charges) if charges is not None else None
+            st, out, ok, rep, self.last_replay_counts = e.redeem_admit_replay(
+                db.set, receipts.set, self._records(), pb, nonce_key, self._sign_key(sign_with), key_epochs=self.epochs, charges=cc)
+        else:
+            st, out, ok, rep, self.last_replay_counts = e.redeem_replay(db.set, receipts.set, self._records(), pb, nonce_key, self._sign_key(sign_with), key_epochs=self.epochs)
         return [Refund(out[128 * i:128 * i + 128]) if st[i] == 0 else Error(st[i]) for i in range(len(proofs))], self._indices(st, ok), [bool(r) for r in rep]
 
     def redeem_replay_cbor_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", msgs: Sequence[bytes], nonce_key: bytes, nbits: int = L,
-                                 sign_with=None) -> Tuple[list, list, list]:
-        """the same on wire bytes (act_redeem_cbor_replay_batch): a retry may be another CBOR spelling of the same proof"""
-        st, out, ok, rep, self.last_replay_counts = params.engine(nbits).redeem_cbor_replay(
-            db.set, receipts.set, self._records(), list(msgs), nonce_key, self._sign_key(sign_with), key_epochs=self.epochs)
+                                 sign_with=None, admit: bool = False, charges: Sequence = None) -> Tuple[list, list, list]:
+        """the same on wire bytes (act_redeem_cbor_replay_batch; admit=True: act_redeem_cbor_admit_replay_batch): a retry may be another
+        CBOR spelling of the same proof"""
+        if charges is not None and not admit:
+            raise ValueError("charges are compared by the admission screen: admit=True")
+        e = params.engine(nbits)
+        if admit:
+            cc = b"".join(scalar(c) for c in charges) if charges is not None else None
+            st, out, ok, rep, self.last_replay_counts = e.redeem_cbor_admit_replay(
+                db.set, receipts.set, self._records(), list(msgs), nonce_key, self._sign_key(sign_with), key_epochs=self.epochs, charges=cc)
+        else:
+            st, out, ok, rep, self.last_replay_counts = e.redeem_cbor_replay(db.set, receipts.set, self._records(), list(msgs), nonce_key, self._sign_key(sign_with), key_epochs=self.epochs)
         return [out[i] if st[i] == 0 else _wire_error(st[i]) for i in range(len(msgs))], self._indices(st, ok), [bool(r) for r in rep]
 
 

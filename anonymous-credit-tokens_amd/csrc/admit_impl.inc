@@ -14,6 +14,8 @@
 // The decision that RECORDS is still the check-and-insert behind verification; the look-up of step 1 only spares work.
 // act_redeem_(cbor_)admit_unique_batch add the copy stage between steps 2 and 3 (copies_impl.inc, included behind this file): a
 // survivor whose input bytes are those of an earlier survivor is not verified and takes its answer from that lane      [k_copies.hip]
+// act_redeem_(cbor_)admit_replay_batch (admit_replay_impl.inc, included behind replay_impl.inc; DESIGN 4.9) add a stage between steps 1
+// and 2 -- a spent lane whose receipt is this proof's own is a retry candidate and survives -- and end in the replay tail, not the ring's
 namespace {
 
 constexpr size_t ADMIT_WINDOW_BATCHES = 4;       // survivors gathered and verified at a time, in units of max_batch
@@ -57,6 +59,74 @@ struct AdmitReadJob { CborReadArgs a; };
 struct AdmitRowsJob { uint8_t* dst; const uint8_t* src; const uint32_t* idx; size_t row; };
 struct AdmitMsgsJob { uint8_t* dst; const uint64_t* dst_off; const uint8_t* src; const uint64_t* src_beg; };
 
+// One window of lanes gathered into the caller's kind of memory (step 3's survivors; the spent lanes of the replay form,
+// admit_replay_impl.inc): records or canonical-size messages as rows of one size, messages between monotone offsets with offsets of
+// their own.  d_idx: the window's lane numbers in device memory (device-memory callers); h_idx: the same on the host.
+struct AdmitGather {
+  act_ctx* c; hipStream_t stream; bool dev; const uint8_t* src; size_t row; const WireExtent* ext;      // ext: messages between offsets, else rows
+  DevTmp gd, d_moff; std::unique_ptr<uint8_t[]> gh; size_t g_cap = 0, moff_cap = 0;      // (host: not zero-filled -- the gather writes every byte that is read)
+  std::vector<uint64_t> dst_off, src_beg;
+  AdmitGather(act_ctx* c_, hipStream_t s, bool dev_, const uint8_t* src_, size_t row_, const WireExtent* ext_) : c(c_), stream(s), dev(dev_), src(src_), row(row_), ext(ext_), gd(c_), d_moff(c_) {}
+  const uint8_t* data() const { return dev ? gd.p : gh.get(); }
+  const uint64_t* offsets() const { return ext ? dst_off.data() : nullptr; }
+  const uint64_t* dev_offsets() const { return (ext && dev) ? reinterpret_cast<const uint64_t*>(d_moff.p) + moff_cap : nullptr; }      // the same in device memory (device-memory callers)
+  static int regrow(act_ctx* c, DevTmp& t, size_t bytes) {
+    if (t.p) { std::lock_guard<std::mutex> lk(c->mu); ADCK(c, hipFree(t.p)); t.p = nullptr; t.bytes = 0; }
+    return t.alloc(bytes);
+  }
+  int reserve(size_t bytes) {      // the gather buffer, in the caller's kind of memory
+    if (bytes <= g_cap) return ACT_OK;
+    if (dev) { if (int r = regrow(c, gd, bytes)) return r; }
+    else gh.reset(new uint8_t[bytes ? bytes : 1]);
+    g_cap = bytes;
+    return ACT_OK;
+  }
+  int run(const uint32_t* d_idx, const uint32_t* h_idx, size_t w) {
+    int rc;
+    if (!ext) {      // rows of one size
+      if ((rc = reserve(w * row))) return rc;
+      if (dev) {
+        AdmitRowsArgs ra{gd.p, src, d_idx, (uint32_t)w, row};
+        launch_admit_rows(ra, stream);
+        ADCK(c, hipGetLastError());
+        ADCK(c, hipStreamSynchronize(stream));
+      } else {
+        AdmitRowsJob job{gh.get(), src, h_idx, row};
+        act_host_parallel_for(w, 16, 0, [](void* p, size_t i0, size_t i1) {
+          const AdmitRowsJob& j = *static_cast<const AdmitRowsJob*>(p);
+          for (size_t k = i0; k < i1; k++) memcpy(j.dst + k * j.row, j.src + (size_t)j.idx[k] * j.row, j.row);
+        }, &job);
+      }
+      return ACT_OK;
+    }
+    // messages between monotone offsets, gathered with offsets of their own
+    dst_off.assign(w + 1, 0); src_beg.assign(w, 0);
+    size_t longest = 0;
+    for (size_t k = 0; k < w; k++) {
+      const size_t i = h_idx[k], len = ext->end(i) - ext->beg(i);
+      src_beg[k] = ext->beg(i); dst_off[k + 1] = dst_off[k] + len; longest = std::max(longest, len);
+    }
+    if ((rc = reserve((size_t)dst_off[w]))) return rc;
+    if (dev) {      // a window's source starts and destination offsets
+      if (w > moff_cap) { if ((rc = regrow(c, d_moff, (2 * w + 1) * 8))) return rc; moff_cap = w; }
+      uint64_t* d_src = reinterpret_cast<uint64_t*>(d_moff.p); uint64_t* d_dst = d_src + moff_cap;
+      ADCK(c, hipMemcpyAsync(d_src, src_beg.data(), w * 8, hipMemcpyHostToDevice, stream));
+      ADCK(c, hipMemcpyAsync(d_dst, dst_off.data(), (w + 1) * 8, hipMemcpyHostToDevice, stream));
+      AdmitMsgsArgs ma{gd.p, d_dst, src, d_src, (uint32_t)w, admit_pieces(longest)};
+      launch_admit_msgs(ma, stream);
+      ADCK(c, hipGetLastError());
+      ADCK(c, hipStreamSynchronize(stream));
+    } else {
+      AdmitMsgsJob job{gh.get(), dst_off.data(), src, src_beg.data()};
+      act_host_parallel_for(w, 16, 0, [](void* p, size_t i0, size_t i1) {
+        const AdmitMsgsJob& j = *static_cast<const AdmitMsgsJob*>(p);
+        for (size_t k = i0; k < i1; k++) memcpy(j.dst + j.dst_off[k], j.src + j.src_beg[k], (size_t)(j.dst_off[k + 1] - j.dst_off[k]));
+      }, &job);
+    }
+    return ACT_OK;
+  }
+};
+
 void admit_counts_of(uint64_t* out_counts, size_t n, const uint8_t* pre, size_t m, const uint8_t* cst) {
   if (!out_counts) return;
   uint64_t k[ACT_ADMIT_COUNTS] = {n, 0, 0, 0, m, 0, 0, 0};
@@ -83,13 +153,38 @@ struct AdmitCopies {
           const uint32_t salt[4]);
 };
 
+// the replay form (act_redeem_(cbor_)admit_replay_batch, DESIGN 4.9; admit_replay_impl.inc, included behind replay_impl.inc): what it
+// hands to redeem_admit_impl and what its stage between the screen and the compaction leaves
+struct AdmitReplay {
+  act_nullifier_set* receipts; const uint8_t* nonce_key; uint8_t* out_replayed; uint64_t* out_counts;
+  size_t candidates = 0;              // spent lanes whose tag the receipts hold: verified like fresh lanes
+};
+// the stage's view of the call: the screen's arrays and, as scratch until the survivors' compaction overwrites them, the compaction's
+struct AdmitReplayStage {
+  hipStream_t stream; size_t n; bool dev, wire, dev_reader; const uint8_t* proof; const uint8_t* cbor; const WireExtent* ext; bool offsets;
+  uint8_t* d_pre; const uint8_t* d_kred; uint32_t *d_blk, *d_idx, *d_pos, *d_total;
+};
+
 }  // namespace
 
+static int admit_replay_stage(act_ctx* c, AdmitReplay& rp, const AdmitReplayStage& g);
+static void admit_replay_counts_of(uint64_t* out_counts, size_t n, const uint8_t* pre, size_t candidates, size_t m, const uint64_t* tail_counts);
+static int replay_refused(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, const uint8_t* nonce_key, size_t n, const uint32_t* key_epochs, int nkeys);
+static int replay_tail(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys, int nkeys, const uint32_t* key_epochs,
+                       int sign_key, bool wire, const uint8_t* k_at, size_t k_stride, const uint8_t* kp, uint8_t* st, const uint8_t* nonce_key, uint8_t* out,
+                       uint8_t* status, uint8_t* out_key, uint8_t* out_replayed, uint64_t* out_counts, bool* began = nullptr);
+static int redeem_replay_locked(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys, int nkeys,
+                                const uint32_t* key_epochs, int sign_key, const uint8_t* proof, const uint8_t* cbor, const uint64_t* offsets, const uint8_t* nonce_key,
+                                uint8_t* out, uint8_t* status, uint8_t* out_key, uint8_t* out_replayed, uint64_t* out_counts);
+
+// rp (the replay form): rng / rng_mode are the derived nonces' stand-in (one byte, ACT_RNG_PER_LANE) and out_counts is null -- the
+// form's own counts are rp->out_counts
 static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int mem, const uint8_t* keys, int nkeys, const uint32_t* key_epochs, int sign_key,
                              const uint8_t* proof, const uint8_t* cbor, const uint64_t* offsets, const uint8_t* charge, const uint8_t* rng, int rng_mode,
-                             uint8_t* out, uint8_t* status, uint8_t* out_key, uint64_t* out_counts, bool unique = false) {
+                             uint8_t* out, uint8_t* status, uint8_t* out_key, uint64_t* out_counts, bool unique = false, AdmitReplay* rp = nullptr) {
   const bool wire = cbor != nullptr, dev = mem == ACT_MEM_DEVICE;
   if (out_counts) memset(out_counts, 0, sizeof(uint64_t) * (unique ? ACT_ADMIT_UNIQUE_COUNTS : ACT_ADMIT_COUNTS));
+  if (rp && rp->out_counts) memset(rp->out_counts, 0, sizeof(uint64_t) * ACT_ADMIT_REPLAY_COUNTS);
   if (!c || (mem != ACT_MEM_HOST && mem != ACT_MEM_DEVICE) || n > ((size_t)1 << 30)) return ACT_ERR_ARG;
   if (n && ((!proof && !cbor) || !out || !status || !out_key)) return ACT_ERR_ARG;
   if (wire && offsets) for (size_t i = 0; i < n; i++) if (offsets[i + 1] < offsets[i]) return ACT_ERR_ARG;
@@ -98,9 +193,12 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
   // (or, for a batch that is shed completely, the empty ring call below) before anything is written
   int rc = redeem_keyring_refused(c, set, 0, keys, nkeys, key_epochs, sign_key, nullptr, nullptr, rng, rng_mode, nullptr, nullptr, nullptr);
   if (rc) return rc;
+  if (rp && (rc = replay_refused(c, set, rp->receipts, rp->nonce_key, n, key_epochs, nkeys))) return rc;
   if (n == 0) return redeem_keyring_impl(c, set, 0, mem, keys, nkeys, key_epochs, sign_key, nullptr, nullptr, nullptr, rng, rng_mode, nullptr, nullptr, nullptr);
   // one admission call at a time per context: the gathered rng slices live in the context's own buffer (d_admit_rng)
   std::lock_guard<std::mutex> admission(c->admit_mu);
+  std::unique_lock<std::mutex> replay;      // the replay form: the staged secrets and the derived nonces of its tail (d_replay)
+  if (rp) replay = std::unique_lock<std::mutex>(c->replay_mu);
   const size_t pb = act_spend_proof_bytes(c), out_b = wire ? act_cbor_size(c, ACT_CBOR_REFUND) : 128;
   const CborType* T = cbor_type(ACT_CBOR_SPEND_PROOF);
   CborLayout lay; if (wire) lay = cbor_layout(*T, c->L);
@@ -237,6 +335,17 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
     std::lock_guard<std::mutex> lk(set->mu);
     sa.tab_keys = set->tab_keys; sa.tab_state = set->tab_state; sa.tab_cap = set->tab_cap; memcpy(sa.salt.w, set->salt, 16);
     launch_admit_screen(sa, stream);
+    if (!rp) launch_admit_compact(d_pre, (uint32_t)n, d_blk, d_idx, d_pos, d_total, stream);
+    ADCK(c, hipGetLastError());
+    if (!rp) {
+      ADCK(c, hipMemcpyAsync(&m32, d_total, 4, hipMemcpyDeviceToHost, stream));
+      ADCK(c, hipMemcpyAsync(h_pre.data(), d_pre, n, hipMemcpyDeviceToHost, stream));
+    }
+    ADCK(c, hipStreamSynchronize(stream));
+  }
+  if (rp) {      // the spent lanes: retry candidates go on, the others stay double spends; then the compaction over what that leaves
+    const AdmitReplayStage g{stream, n, dev, wire, dev_reader, proof, cbor, &ext, offsets != nullptr, d_pre, d_kred, d_blk, d_idx, d_pos, d_total};
+    if ((rc = admit_replay_stage(c, *rp, g))) return rc;
     launch_admit_compact(d_pre, (uint32_t)n, d_blk, d_idx, d_pos, d_total, stream);
     ADCK(c, hipGetLastError());
     ADCK(c, hipMemcpyAsync(&m32, d_total, 4, hipMemcpyDeviceToHost, stream));
@@ -265,6 +374,13 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
   }
 
   // ---- nothing shed: the honest batch pays the screen and nothing else ------------------------------------------------------------------
+  if (mv == n && rp) {
+    uint64_t tc[ACT_REPLAY_COUNTS] = {0, 0, 0, 0, 0, 0};
+    rc = redeem_replay_locked(c, set, rp->receipts, n, mem, keys, nkeys, key_epochs, sign_key, proof, cbor, offsets, rp->nonce_key, out, status, out_key, rp->out_replayed,
+                              rp->out_counts ? tc : nullptr);
+    if (rp->out_counts && tc[0] == n) admit_replay_counts_of(rp->out_counts, n, h_pre.data(), rp->candidates, n, tc);      // (tc[0] == 0: the call ended before its tail)
+    return rc;
+  }
   if (mv == n) {
     rc = redeem_keyring_impl(c, set, n, mem, keys, nkeys, key_epochs, sign_key, proof, cbor, offsets, rng, rng_mode, out, status, out_key);
     if (out_counts && (rc == ACT_OK || rc == ACT_ERR_ARG)) {      // (ACT_ERR_ARG: the nullifier step refused lanes; status[] is complete)
@@ -282,9 +398,11 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
       ADCK(c, hipMemcpyAsync(status, d_pre, n, hipMemcpyDeviceToDevice, stream));
       ADCK(c, hipMemsetAsync(out_key, ACT_KEY_NONE, n, stream));
       ADCK(c, hipMemsetAsync(out, 0, n * out_b, stream));
+      if (rp && rp->out_replayed) ADCK(c, hipMemsetAsync(rp->out_replayed, 0, n, stream));
       ADCK(c, hipStreamSynchronize(stream));
-    } else { memcpy(status, h_pre.data(), n); memset(out_key, ACT_KEY_NONE, n); memset(out, 0, n * out_b); }
+    } else { memcpy(status, h_pre.data(), n); memset(out_key, ACT_KEY_NONE, n); memset(out, 0, n * out_b); if (rp && rp->out_replayed) memset(rp->out_replayed, 0, n); }
     admit_counts_of(out_counts, n, h_pre.data(), 0, nullptr);
+    if (rp && rp->out_counts) admit_replay_counts_of(rp->out_counts, n, h_pre.data(), 0, 0, nullptr);
     return ACT_OK;
   }
 
@@ -295,9 +413,10 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
   if (!dev) { h_pos.resize(n); ADCK(c, hipMemcpy(h_pos.data(), v_pos, n * 4, hipMemcpyDeviceToHost)); }
   // compact arrays in the caller's kind of memory: K' | nullifiers | verdicts | look-up answers | key indices | matched keys | statuses
   AdmitArr arr(c), cout(c);
-  if ((rc = arr.alloc(mem, mv * 69))) { c->err = "admission: compact arrays"; return rc; }
+  if ((rc = arr.alloc(mem, mv * (rp ? 70 : 69)))) { c->err = "admission: compact arrays"; return rc; }
   if ((rc = cout.alloc(mem, mv * out_b))) { c->err = "admission: compact output"; return rc; }
-  uint8_t *kp = arr.p, *knul = kp + mv * 32, *st = knul + mv * 32, *sp = st + mv, *kidx = sp + mv, *okey = kidx + mv, *cst = okey + mv;
+  uint8_t *kp = arr.p, *knul = kp + mv * 32, *st = knul + mv * 32, *sp = st + mv, *kidx = sp + mv, *okey = kidx + mv, *cst = okey + mv,
+          *crepl = cst + mv;      // (the replay form: the survivors' replay marks)
   // a survivor's status that the tail leaves unwritten (it returns early only on a device failure BEHIND check-and-insert) must never
   // read as accepted: recorded, not signed
   if (dev) { ADCK(c, hipMemset(cst, ACT_STATUS_RECORDED_UNSIGNED, mv)); ADCK(c, hipDeviceSynchronize()); } else memset(cst, ACT_STATUS_RECORDED_UNSIGNED, mv);
@@ -313,7 +432,7 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
   // the per-lane rng slices follow their lanes (secret: staged in the context's own buffer or a host vector, wiped on every exit)
   AdmitRngDev rng_dev(c); std::vector<uint8_t> rng_host; AdmitHostWipe rng_wipe{rng_host};
   const uint8_t* c_rng = rng;
-  if (rng_mode == ACT_RNG_PER_LANE) {
+  if (rng_mode == ACT_RNG_PER_LANE && !rp) {
     if (dev) {
       if ((rc = rng_dev.reserve(mv * 128))) return rc;
       AdmitRowsArgs ra{c->d_admit_rng, rng, v_idx, (uint32_t)mv, 128};
@@ -328,68 +447,23 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
     }
   }
   const size_t W = std::max<size_t>(1, ADMIT_WINDOW_BATCHES * c->max_batch);
-  DevTmp gd(c); std::unique_ptr<uint8_t[]> gh; size_t g_cap = 0;      // (host: not zero-filled -- the gather below writes every byte that is read)
-  auto g_reserve = [&](size_t bytes) -> int {      // the gather buffer, in the caller's kind of memory
-    if (bytes <= g_cap) return ACT_OK;
-    if (dev) { if (gd.p) { std::lock_guard<std::mutex> lk(c->mu); ADCK(c, hipFree(gd.p)); gd.p = nullptr; gd.bytes = 0; } int r = gd.alloc(bytes); if (r) return r; }
-    else gh.reset(new uint8_t[bytes ? bytes : 1]);
-    g_cap = bytes;
-    return ACT_OK;
-  };
-  DevTmp d_moff(c);      // wire, device memory: a window's source starts and destination offsets
-  if (wire && dev && offsets && (rc = d_moff.alloc((2 * std::min(W, mv) + 1) * 8))) return rc;
-  std::vector<uint64_t> dst_off, src_beg;
+  AdmitGather gather(c, stream, dev, wire ? cbor : proof, wire ? ml : pb, (wire && offsets) ? &ext : nullptr);
   for (size_t w0 = 0; w0 < mv; w0 += W) {
     const size_t w = std::min(W, mv - w0);
-    const size_t row = wire ? ml : pb;
-    if (!wire || !offsets) {      // rows of one size
-      if ((rc = g_reserve(w * row))) return rc;
-      const uint8_t* src = wire ? cbor : proof;
-      if (dev) {
-        AdmitRowsArgs ra{gd.p, src, v_idx + w0, (uint32_t)w, row};
-        launch_admit_rows(ra, stream);
-        ADCK(c, hipGetLastError());
-        ADCK(c, hipStreamSynchronize(stream));
-      } else {
-        AdmitRowsJob job{gh.get(), src, h_idx.data() + w0, row};
-        act_host_parallel_for(w, 16, 0, [](void* p, size_t i0, size_t i1) {
-          const AdmitRowsJob& j = *static_cast<const AdmitRowsJob*>(p);
-          for (size_t k = i0; k < i1; k++) memcpy(j.dst + k * j.row, j.src + (size_t)j.idx[k] * j.row, j.row);
-        }, &job);
-      }
-    } else {                      // messages between monotone offsets, gathered with offsets of their own
-      dst_off.assign(w + 1, 0); src_beg.assign(w, 0);
-      size_t longest = 0;
-      for (size_t k = 0; k < w; k++) {
-        const size_t i = h_idx[w0 + k], len = ext.end(i) - ext.beg(i);
-        src_beg[k] = ext.beg(i); dst_off[k + 1] = dst_off[k] + len; longest = std::max(longest, len);
-      }
-      if ((rc = g_reserve((size_t)dst_off[w]))) return rc;
-      if (dev) {
-        uint64_t* d_src = reinterpret_cast<uint64_t*>(d_moff.p); uint64_t* d_dst = d_src + std::min(W, mv);
-        ADCK(c, hipMemcpyAsync(d_src, src_beg.data(), w * 8, hipMemcpyHostToDevice, stream));
-        ADCK(c, hipMemcpyAsync(d_dst, dst_off.data(), (w + 1) * 8, hipMemcpyHostToDevice, stream));
-        AdmitMsgsArgs ma{gd.p, d_dst, cbor, d_src, (uint32_t)w, admit_pieces(longest)};
-        launch_admit_msgs(ma, stream);
-        ADCK(c, hipGetLastError());
-        ADCK(c, hipStreamSynchronize(stream));
-      } else {
-        AdmitMsgsJob job{gh.get(), dst_off.data(), cbor, src_beg.data()};
-        act_host_parallel_for(w, 16, 0, [](void* p, size_t i0, size_t i1) {
-          const AdmitMsgsJob& j = *static_cast<const AdmitMsgsJob*>(p);
-          for (size_t k = i0; k < i1; k++) memcpy(j.dst + j.dst_off[k], j.src + j.src_beg[k], (size_t)(j.dst_off[k + 1] - j.dst_off[k]));
-        }, &job);
-      }
-    }
-    const uint8_t* g = dev ? gd.p : gh.get();
-    if (wire) { RingSel sel{keys, nkeys, okey + w0}; rc = verify_spend_cbor_impl(c, w, mem, nullptr, g, offsets ? dst_off.data() : nullptr, st + w0, kp + w0 * 32, nullptr, &sel); }
+    if ((rc = gather.run(v_idx + w0, h_idx.data() + w0, w))) return rc;
+    const uint8_t* g = gather.data();
+    if (wire) { RingSel sel{keys, nkeys, okey + w0}; rc = verify_spend_cbor_impl(c, w, mem, nullptr, g, gather.offsets(), st + w0, kp + w0 * 32, nullptr, &sel); }
     else rc = act_verify_spend_keyring_batch(c, w, mem, keys, nkeys, g, st + w0, okey + w0, kp + w0 * 32);
     if (rc) return rc;            // as in the redeem calls: nothing recorded, status untouched
   }
 
   // ---- step 4: once per call, over the compact arrays ---------------------------------------------------------------------------------------
-  const int rc_tail = redeem_tail_ring(c, set, mv, mem, keys, nkeys, key_epochs, sign_key, wire, knul, 32, kp, st, sp, kidx, c_rng, rng_mode, cout.p, cst, okey);
+  uint64_t tc[ACT_REPLAY_COUNTS] = {0, 0, 0, 0, 0, 0};
+  bool began = false;
+  const int rc_tail = rp ? replay_tail(c, set, rp->receipts, mv, mem, keys, nkeys, key_epochs, sign_key, wire, knul, 32, kp, st, rp->nonce_key, cout.p, cst, okey, crepl, tc, &began)
+                         : redeem_tail_ring(c, set, mv, mem, keys, nkeys, key_epochs, sign_key, wire, knul, 32, kp, st, sp, kidx, c_rng, rng_mode, cout.p, cst, okey);
 
+  if (rp && rc_tail && !began) return rc_tail;      // staging its buffers failed: as a failed verification -- nothing recorded, status untouched
   // ---- step 5: the answers back to their lanes (also behind a failure of step 4: status[] is complete on return) ----------------------------
   std::vector<uint8_t> h_cst;
   if (dev) {
@@ -397,6 +471,10 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
     sc.status = status; sc.out_key = out_key; sc.out = out;
     launch_admit_scatter(sc, stream);
     if (cp.copies) { CopyResolveArgs ra{cp.d_lead, (uint32_t)n, status, out_key}; launch_copy_resolve(ra, stream); }      // COPY_MARK leaves status[] here
+    if (rp && rp->out_replayed) {      // the replay marks ride the same scatter as one-byte records (a shed lane: 0)
+      AdmitScatterArgs sr = sc; sr.out_bytes = 1; sr.c_out = crepl; sr.out = rp->out_replayed;
+      launch_admit_scatter(sr, stream);
+    }
     ADCK(c, hipGetLastError());
     if (out_counts) { h_cst.resize(mv); ADCK(c, hipMemcpyAsync(h_cst.data(), cst, mv, hipMemcpyDeviceToHost, stream)); }
     ADCK(c, hipStreamSynchronize(stream));
@@ -405,10 +483,12 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
       const uint32_t j = h_pos[i];
       if (j == ADMIT_SHED) { status[i] = h_pre[i]; out_key[i] = ACT_KEY_NONE; memset(out + i * out_b, 0, out_b); }
       else { status[i] = cst[j]; out_key[i] = okey[j]; memcpy(out + i * out_b, cout.p + (size_t)j * out_b, out_b); }
+      if (rp && rp->out_replayed) rp->out_replayed[i] = j == ADMIT_SHED ? 0 : crepl[j];
     }
     if (cp.copies) { CopyResolveArgs ra{h_lead.data(), (uint32_t)n, status, out_key}; for (size_t i = 0; i < n; i++) copy_resolve_lane(ra, (uint32_t)i); }
   }
   admit_counts_of(out_counts, n, h_pre.data(), mv, dev ? h_cst.data() : cst);
+  if (rp && rp->out_counts && tc[0] == mv) admit_replay_counts_of(rp->out_counts, n, h_pre.data(), rp->candidates, mv, tc);
   if (out_counts && unique) out_counts[ACT_ADMIT_COUNTS] = cp.copies;
   return rc_tail;
 }

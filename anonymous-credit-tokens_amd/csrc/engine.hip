@@ -21,6 +21,7 @@
 #include "keyring.h"
 #include "admit.h"
 #include "replay_lanes.h"
+#include "admit_replay_lanes.h"
 #include "cbor_lanes.h"
 #include "issue_wire_lanes.h"
 #include "rng_source.h"
@@ -1305,3 +1306,4 @@ int act_refund_batch(act_ctx* c, size_t n, int mem, const uint8_t sk[64], const 
 #include "admit_impl.inc"          // admission before verification: act_redeem_admit_batch, act_redeem_cbor_admit_batch
 #include "copies_impl.inc"         // its copy stage: act_redeem_admit_unique_batch, act_redeem_cbor_admit_unique_batch
 #include "replay_impl.inc"         // replayable redemption: act_redeem_replay_batch, act_redeem_cbor_replay_batch, act_replay_derive_batch
+#include "admit_replay_impl.inc"   // its admission form: act_redeem_admit_replay_batch, act_redeem_cbor_admit_replay_batch

@@ -78,44 +78,40 @@ void replay_counts_of(uint64_t* out_counts, size_t n, const uint8_t* status, con
 
 }  // namespace
 
-static int redeem_replay_impl(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys, int nkeys,
-                              const uint32_t* key_epochs, int sign_key, const uint8_t* proof, const uint8_t* cbor, const uint64_t* offsets, const uint8_t* nonce_key,
-                              uint8_t* out, uint8_t* status, uint8_t* out_key, uint8_t* out_replayed, uint64_t* out_counts) {
-  const bool wire = cbor != nullptr, dev = mem == ACT_MEM_DEVICE;
-  if (out_counts) memset(out_counts, 0, sizeof(uint64_t) * ACT_REPLAY_COUNTS);
-  if (!c || (mem != ACT_MEM_HOST && mem != ACT_MEM_DEVICE) || n > ((size_t)1 << 30)) return ACT_ERR_ARG;
-  // everything the ring redeem call refuses as a whole, in the same words (the nonces stand where its rng stands), then this call's own
-  static const uint8_t derived = 0;
-  if (int bad = redeem_keyring_refused(c, set, n, keys, nkeys, key_epochs, sign_key, proof, cbor, &derived, ACT_RNG_PER_LANE, out, status, out_key)) return bad;
+// Everything the replay calls refuse as a whole on top of the ring redeem call's refusals: the receipts handle, nonce_key, the epoch table
+// against the receipts set, and the receipts' room for n more keys.  (Also in front of the admission form, admit_replay_impl.inc.)
+static int replay_refused(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, const uint8_t* nonce_key, size_t n, const uint32_t* key_epochs, int nkeys) {
   if (!receipts || !nonce_key || receipts == set) return ACT_ERR_ARG;
   if (receipts->device != c->device) { c->err = "act_redeem_replay_batch: the receipts set lives on another device"; return ACT_ERR_ARG; }
-  {
-    std::lock_guard<std::mutex> lk(receipts->mu);
-    if (key_epochs) {
-      const std::string why = null_epochs_refused(receipts, key_epochs, nkeys);
-      if (!why.empty()) { c->err = "act_redeem_replay_batch: the receipts set: " + why; return ACT_ERR_ARG; }
-    }
-    if (receipts->len + n > receipts->tab_cap / 2) {
-      c->err = "act_redeem_replay_batch: the receipts set has no room for " + std::to_string(n) + " more keys (act_nullifier_set_reserve)";
-      return ACT_ERR_ARG;
-    }
+  std::lock_guard<std::mutex> lk(receipts->mu);
+  if (key_epochs) {
+    const std::string why = null_epochs_refused(receipts, key_epochs, nkeys);
+    if (!why.empty()) { c->err = "act_redeem_replay_batch: the receipts set: " + why; return ACT_ERR_ARG; }
   }
-  if (n == 0) return redeem_keyring_impl(c, set, 0, mem, keys, nkeys, key_epochs, sign_key, nullptr, nullptr, nullptr, &derived, ACT_RNG_PER_LANE, nullptr, nullptr, nullptr);
-  // one replay call at a time per context: the staged secrets and the derived nonces live in the context's own buffer (d_replay)
-  std::lock_guard<std::mutex> replay(c->replay_mu);
-  const size_t pb = act_spend_proof_bytes(c);
-  // K', tags and (wire form) the nullifiers; verdicts, merged answers, key indices, the two sets' answers, the receipts mask and its answers, the replay marks
-  const size_t per_lane = 64 + 8 + (wire ? 32 : 0);
+  if (receipts->len + n > receipts->tab_cap / 2) {
+    c->err = "act_redeem_replay_batch: the receipts set has no room for " + std::to_string(n) + " more keys (act_nullifier_set_reserve)";
+    return ACT_ERR_ARG;
+  }
+  return ACT_OK;
+}
+
+// The replay tail: everything behind the verification, over dense arrays in `mem` memory -- the nullifiers at k_at + i * k_stride, enc(K')
+// kp, the verdicts st (merged in place), the matched keys out_key.  Tags, both set steps, resolve, derived nonces, the sign step and the
+// counts (ACT_REPLAY_COUNTS values, nullable).  The replay calls end in it over the caller's lanes, the admission form over its
+// survivors.  The caller holds replay_mu.  began (nullable): set once nothing in front of the tail proper can fail any more -- a return
+// with it unset has recorded nothing and written no status.
+static int replay_tail(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys, int nkeys, const uint32_t* key_epochs,
+                       int sign_key, bool wire, const uint8_t* k_at, size_t k_stride, const uint8_t* kp, uint8_t* st, const uint8_t* nonce_key, uint8_t* out,
+                       uint8_t* status, uint8_t* out_key, uint8_t* out_replayed, uint64_t* out_counts, bool* began) {
+  const bool dev = mem == ACT_MEM_DEVICE;
+  // tags; merged answers, key indices, the two sets' answers, the receipts mask and its answers, the replay marks
+  const size_t per_lane = 32 + 7;
   std::vector<uint8_t> h; DevTmp d(c);
   uint8_t* base; int rc;
   if (dev) { if ((rc = d.alloc(n * per_lane))) return rc; base = d.p; }
   else { h.resize(n * per_lane); base = h.data(); }
-  uint8_t *kp = base, *tag = base + n * 32, *nul = base + n * 64, *st = base + n * (per_lane - 8), *sp = st + n, *kidx = sp + n, *spent = kidx + n, *found = spent + n,
-          *skip = found + n, *r_ans = skip + n, *repl = out_replayed ? out_replayed : r_ans + n;
-  if (wire) { RingSel sel{keys, nkeys, out_key}; rc = verify_spend_cbor_impl(c, n, mem, nullptr, cbor, offsets, st, kp, nul, &sel); }
-  else rc = act_verify_spend_keyring_batch(c, n, mem, keys, nkeys, proof, st, out_key, kp);
-  if (rc) return rc;
-  const uint8_t* k_at = wire ? nul : proof; const size_t k_stride = wire ? 32 : pb;
+  uint8_t *tag = base, *sp = base + n * 32, *kidx = sp + n, *spent = kidx + n, *found = spent + n, *skip = found + n, *r_ans = skip + n,
+          *repl = out_replayed ? out_replayed : r_ans + n;
 
   ReplaySecretsDev sec_dev(c); ReplaySecretsHost sec_host;
   const uint8_t* secrets; uint8_t* nonces;
@@ -125,6 +121,7 @@ static int redeem_replay_impl(act_ctx* c, act_nullifier_set* set, act_nullifier_
 
   hipStream_t stream = set->stream;
   int rc_receipts = ACT_OK; std::string receipts_err;
+  if (began) *began = true;      // from here on status[] is complete on return, whatever fails
   const int rc_tail = redeem_tail(c, set, n, mem, wire, st, sp, nonces, ACT_RNG_PER_LANE, out, status,
     [&](const uint8_t* mask, uint8_t* sp_out) -> int {
       // the tags first: they depend on the verification alone, and behind the insert of k nothing but the receipts may fail
@@ -180,6 +177,41 @@ static int redeem_replay_impl(act_ctx* c, act_nullifier_set* set, act_nullifier_
   if (rc_tail) return rc_tail;
   if (rc_receipts) { c->err = "receipts set: " + receipts_err + " (every refund was handed out; a retry of this batch's fresh lanes may be refused)"; return rc_receipts; }
   return ACT_OK;
+}
+
+// the verification and the tail over the caller's lanes; the caller has made the whole-call refusals and holds replay_mu
+static int redeem_replay_locked(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys, int nkeys,
+                                const uint32_t* key_epochs, int sign_key, const uint8_t* proof, const uint8_t* cbor, const uint64_t* offsets, const uint8_t* nonce_key,
+                                uint8_t* out, uint8_t* status, uint8_t* out_key, uint8_t* out_replayed, uint64_t* out_counts) {
+  const bool wire = cbor != nullptr, dev = mem == ACT_MEM_DEVICE;
+  const size_t pb = act_spend_proof_bytes(c);
+  // K', the verdicts and (wire form) the nullifiers
+  const size_t per_lane = 32 + 1 + (wire ? 32 : 0);
+  std::vector<uint8_t> h; DevTmp d(c);
+  uint8_t* base; int rc;
+  if (dev) { if ((rc = d.alloc(n * per_lane))) return rc; base = d.p; }
+  else { h.resize(n * per_lane); base = h.data(); }
+  uint8_t *kp = base, *nul = base + n * 32, *st = base + n * (per_lane - 1);
+  if (wire) { RingSel sel{keys, nkeys, out_key}; rc = verify_spend_cbor_impl(c, n, mem, nullptr, cbor, offsets, st, kp, nul, &sel); }
+  else rc = act_verify_spend_keyring_batch(c, n, mem, keys, nkeys, proof, st, out_key, kp);
+  if (rc) return rc;
+  return replay_tail(c, set, receipts, n, mem, keys, nkeys, key_epochs, sign_key, wire, wire ? nul : proof, wire ? 32 : pb, kp, st, nonce_key, out, status, out_key,
+                     out_replayed, out_counts);
+}
+
+static int redeem_replay_impl(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys, int nkeys,
+                              const uint32_t* key_epochs, int sign_key, const uint8_t* proof, const uint8_t* cbor, const uint64_t* offsets, const uint8_t* nonce_key,
+                              uint8_t* out, uint8_t* status, uint8_t* out_key, uint8_t* out_replayed, uint64_t* out_counts) {
+  if (out_counts) memset(out_counts, 0, sizeof(uint64_t) * ACT_REPLAY_COUNTS);
+  if (!c || (mem != ACT_MEM_HOST && mem != ACT_MEM_DEVICE) || n > ((size_t)1 << 30)) return ACT_ERR_ARG;
+  // everything the ring redeem call refuses as a whole, in the same words (the nonces stand where its rng stands), then this call's own
+  static const uint8_t derived = 0;
+  if (int bad = redeem_keyring_refused(c, set, n, keys, nkeys, key_epochs, sign_key, proof, cbor, &derived, ACT_RNG_PER_LANE, out, status, out_key)) return bad;
+  if (int bad = replay_refused(c, set, receipts, nonce_key, n, key_epochs, nkeys)) return bad;
+  if (n == 0) return redeem_keyring_impl(c, set, 0, mem, keys, nkeys, key_epochs, sign_key, nullptr, nullptr, nullptr, &derived, ACT_RNG_PER_LANE, nullptr, nullptr, nullptr);
+  // one replay call at a time per context: the staged secrets and the derived nonces live in the context's own buffer (d_replay)
+  std::lock_guard<std::mutex> replay(c->replay_mu);
+  return redeem_replay_locked(c, set, receipts, n, mem, keys, nkeys, key_epochs, sign_key, proof, cbor, offsets, nonce_key, out, status, out_key, out_replayed, out_counts);
 }
 
 extern "C" int act_redeem_replay_batch(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys, int nkeys,

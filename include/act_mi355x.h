@@ -808,6 +808,55 @@ int act_replay_derive_batch(act_ctx *ctx, size_t n, int mem, const uint8_t *keys
                             const uint8_t nonce_key[32], const uint8_t *nullifiers, size_t stride, const uint8_t *kprime,
                             const uint8_t *status_in, uint8_t *out_tags /* nullable */, uint8_t *out_nonces /* nullable */);
 
+/* ======== admission for the replayable redemption: retries are recognised BEFORE they are verified ========
+ * Behind the admission calls an honest retry is ACT_STATUS_DOUBLE_SPEND; behind the replay calls every lane whose nullifier is spent is
+ * verified at full price before the receipts can say whether it is a retry.  These two calls are act_redeem_(cbor_)replay_batch with
+ * the admission screen in front, and the screen asks the receipts: tag_i (defined above) needs only k_i and enc(K'_i), and
+ * K'_i = sum_j 2^j Com_j is a function of the proof's bytes alone -- L point decodings, one Horner run and one encoding; no key, no
+ * transcript, no range kernel.  In lane order:
+ *     for i in 0..n:
+ *       1. wire form only: the message fails structurally -> exactly the code act_redeem_cbor_* gives, under either
+ *          act_ctx_set_wire_reader setting, for every legal spelling
+ *       2. charge != NULL and s_i != charge_i (both reduced mod l)      -> ACT_STATUS_WRONG_CHARGE: not looked up, not verified, no
+ *          trace in either set
+ *       3. k_i (reduced) is in `set` when the call looks it up: enc(K'_i) is computed from the lane's Com_j, tag_i from it, and tag_i is
+ *          looked up in `receipts`, read only
+ *          3a. a Com_j does not decode, or the tag is absent            -> ACT_STATUS_DOUBLE_SPEND, NOT verified, ACT_KEY_NONE and an
+ *              all-zero record
+ *          3b. the tag is present: the lane is a retry CANDIDATE and goes on
+ *       4. every remaining lane, fresh or candidate: exactly act_redeem_(cbor_)replay_batch over those lanes in lane order --
+ *          verification, check-and-insert under the matched key's epoch, a receipt only where k was fresh, a replay where the tag is
+ *          found, derived nonces, signing, out_replayed
+ * Why 3a is safe: a receipt for k is written only by the lane that found k fresh.  k was spent before this call's look-up, so no lane
+ * of this batch can write one: a lane whose k is in the set and whose tag is not in `receipts` can only end 3 / 6 / 7 / 255 in the
+ * replay call, never 0.  The screen never accepts anything: every refund is still behind a full verification, the check-and-insert
+ * and the receipts look-up of step 4.
+ * What stays the same: with charge == NULL every accepted lane and its refund bytes, out_key, out_replayed and the keys and epochs
+ * both sets hold afterwards are byte for byte those of act_redeem_(cbor_)replay_batch on the same batch and identical sets.
+ * What may differ: only the rejection code of a lane rejected for more than one reason -- a foreign spend (step 3a) that is also
+ * tampered or undecodable reports ACT_STATUS_DOUBLE_SPEND here and 7 / 255 there; a lane shed in steps 1-3 has out_key = ACT_KEY_NONE.
+ * A retry that races its original call may see ACT_STATUS_DOUBLE_SPEND once: both look-ups of step 3 are read-only, and the race the
+ * replay calls document (k recorded, receipt not yet) also exists at the screen.
+ * Refused as a whole: everything the admission calls and the replay calls refuse, the receipts' room rule computed with n included.
+ * Failure semantics (ACT_STATUS_NULLIFIER_UNDETERMINED / ACT_STATUS_RECORDED_UNSIGNED, status[] complete on return, a receipts
+ * failure never withholds a refund) are those of the replay calls; a HIP failure inside the screen leaves nothing recorded, nothing
+ * signed and status[] not written.  A batch in which nothing is shed goes straight to the replay implementation with the caller's
+ * pointers; a batch in which nothing survives launches no verification kernel.  One call at a time per context (the admission calls'
+ * lock, then the replay calls').
+ * out_counts: nullable, HOST memory, ACT_ADMIT_REPLAY_COUNTS values: lanes, wire_rejected (step 1), wrong_charge (step 2),
+ * foreign_spend (step 3a), retry_candidates (step 3b), verified (= lanes - wire_rejected - wrong_charge - foreign_spend),
+ * rejected_by_verification, fresh (recorded and signed), replayed (signed again from a found receipt), double_spend_after (step 4's
+ * check-and-insert), unanswered (UNDETERMINED or RECORDED_UNSIGNED). */
+#define ACT_ADMIT_REPLAY_COUNTS 11
+int act_redeem_admit_replay_batch(act_ctx *ctx, act_nullifier_set *set, act_nullifier_set *receipts, size_t n, int mem, const uint8_t *keys, int nkeys,
+                                  const uint32_t *key_epochs /* nullable */, int sign_key, const uint8_t *proof, const uint8_t *charge /* nullable */,
+                                  const uint8_t nonce_key[32], uint8_t *out_refund, uint8_t *status, uint8_t *out_key,
+                                  uint8_t *out_replayed /* nullable */, uint64_t *out_counts /* nullable, host */);
+int act_redeem_cbor_admit_replay_batch(act_ctx *ctx, act_nullifier_set *set, act_nullifier_set *receipts, size_t n, int mem, const uint8_t *keys, int nkeys,
+                                       const uint32_t *key_epochs /* nullable */, int sign_key, const uint8_t *cbor, const uint64_t *offsets,
+                                       const uint8_t *charge /* nullable */, const uint8_t nonce_key[32], uint8_t *out_refund_cbor, uint8_t *status,
+                                       uint8_t *out_key, uint8_t *out_replayed /* nullable */, uint64_t *out_counts /* nullable, host */);
+
 /* ======== row d and test infrastructure: debug hooks, measurement knobs, kernel timing, roofline probes (nothing here is on the product's path) ==== */
 /* Debug / test hook: the exact "spend" transcript pre-images of the last act_verify_spend_batch /
  * act_refund_batch chunk (n_last * act_spend_transcript_bytes, copied to host memory). */
