@@ -30,7 +30,7 @@ EXPORTS = [
     "act_ctx_set_host_threads", "act_host_usable_cpus", "act_host_hash_many", "act_host_parallel_for", "act_host_pool_stats", "act_ctx_streams_overlap", "act_ctx_set_pipeline_depth", "act_ctx_set_small_batch_max", "act_ctx_set_fixed_base_bits", "act_node_set_fixed_base_bits", "act_tuning_set", "act_build_has_ct_secret_tables", "act_ctx_fixed_base_bits", "act_last_error", "act_spend_proof_bytes", "act_prove_rng_bytes",
     "act_spend_transcript_bytes", "act_private_key_random", "act_pre_issuance_random_batch", "act_request_batch",
     "act_issue_batch", "act_issuance_to_credit_token_batch", "act_prove_spend_batch", "act_prove_spend_seeded_batch", "act_node_prove_spend_seeded_batch", "act_verify_spend_batch",
-    "act_refund_batch", "act_refund_to_credit_token_batch", "act_debug_last_spend_transcripts", "act_debug_scalarmult_batch", "act_debug_secret_residue", "act_prof_enable",
+    "act_refund_batch", "act_refund_to_credit_token_batch", "act_debug_last_spend_transcripts", "act_debug_scalarmult_batch", "act_debug_fixed_base_batch", "act_debug_secret_residue", "act_prof_enable",
     "act_prof_reset", "act_prof_kernel_count", "act_prof_kernel_name", "act_prof_get", "act_prof_get_busy", "act_ubench_mad_u64_u32", "act_ubench_random_read", "act_ubench_table_read",
     "act_cbor_size", "act_cbor_record_bytes", "act_cbor_encode_batch", "act_cbor_decode_batch", "act_cbor_read_batch", "act_ctx_set_wire_reader", "act_ctx_wire_stats", "act_node_set_wire_reader", "act_verify_spend_cbor_batch",
     "act_node_verify_spend_cbor_batch", "act_redeem_batch", "act_node_redeem_batch",
@@ -134,6 +134,7 @@ def load() -> C.CDLL:
     lib.act_refund_to_credit_token_batch.argtypes = [vp, sz, i32, u8p, u8p, u8p, u8p, u8p, u8p]
     lib.act_debug_last_spend_transcripts.argtypes = [vp, sz, u8p, C.POINTER(sz)]
     lib.act_debug_scalarmult_batch.argtypes = [vp, sz, i32, u8p, u8p, u8p, u8p]
+    lib.act_debug_fixed_base_batch.argtypes = [vp, i32, sz, i32, u8p, u8p]
     lib.act_debug_secret_residue.argtypes = [vp, C.POINTER(sz)]
     for f in ("act_cbor_size", "act_cbor_record_bytes"):
         getattr(lib, f).argtypes = [vp, i32]
@@ -575,6 +576,13 @@ class Engine:
         p0, k0 = _in(points, 32 * n); p1, k1 = _in(scalars, 32 * n)
         self._ck(self.lib.act_debug_scalarmult_batch(self.ctx, n, MEM_HOST, p0, p1, out.ctypes.data, st.ctypes.data))
         return st.tobytes(), out.tobytes()
+
+    def debug_fixed_base(self, base: int, scalars: bytes) -> bytes:
+        """enc(s_i * B) for the fixed base 0..3 (g, h1, h2, h3) through this context's table of B at its current window width."""
+        n = len(scalars) // 32; out = np.zeros(32 * n, np.uint8)
+        p0, k0 = _in(scalars, 32 * n)
+        self._ck(self.lib.act_debug_fixed_base_batch(self.ctx, base, n, MEM_HOST, p0, out.ctypes.data))
+        return out.tobytes()
 
     # ---- CBOR wire codec (src/cbor.rs) -----------------------------------------------------------------
     def cbor_size(self, type_name: str) -> int:

@@ -108,6 +108,25 @@ int act_debug_scalarmult_batch(act_ctx* c, size_t n, int mem, const uint8_t* poi
   return call.finish();
 }
 
+// out[i] = enc(scalars[i] * B), B = base 0..3 (g, h1, h2, h3), through fixed_base_acc on the table and window width the context holds
+// for B at this moment (act_ctx_set_fixed_base_bits)
+int act_debug_fixed_base_batch(act_ctx* c, int base, size_t n, int mem, const uint8_t* scalars, uint8_t* out) {
+  if (!c || base < 0 || base > 3 || (n && (!scalars || !out))) return ACT_ERR_ARG;
+  Call call(c, n);
+  HIPCK(c, hipSetDevice(c->device));
+  Slot& sl = c->slots[0];
+  for (size_t off = 0; off < n; off += c->max_batch) {
+    uint32_t m = (uint32_t)std::min(c->max_batch, n - off);
+    const uint8_t* d_s; uint8_t* d_o; int rc;
+    if ((rc = dev_in(c, sl, 0, mem, scalars + off * 32, (size_t)m * 32, &d_s))) return rc;
+    if ((rc = dev_out_begin(c, sl, 1, mem, out + off * 32, (size_t)m * 32, &d_o))) return rc;
+    launch_debug_fixed_base(c->P.tab[base], d_s, m, d_o, sl.stream);
+    if ((rc = dev_out_end(c, sl, mem, out + off * 32, d_o, (size_t)m * 32))) return rc;
+    HIPCK(c, hipStreamSynchronize(sl.stream));
+  }
+  return call.finish();
+}
+
 // Test hook: bytes that are not zero in the context's secret-bearing buffers (what finish_call wipes), read back to the host.
 int act_debug_secret_residue(act_ctx* c, size_t* nonzero_bytes) {
   if (!c || !nonzero_bytes) return ACT_ERR_ARG;

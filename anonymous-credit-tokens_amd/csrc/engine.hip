@@ -837,13 +837,22 @@ int act_ctx_set_fixed_base_bits(act_ctx* c, int base, int bits) {
     }
   }
   hipStream_t s0 = c->slots[0].stream;
-  uint8_t* d_enc = nullptr; uint32_t *d_ext = nullptr, *d_ok = nullptr;
-  HIPCK(c, hipMalloc(&d_enc, 32)); HIPCK(c, hipMalloc(&d_ext, GE_WORDS * 4)); HIPCK(c, hipMalloc(&d_ok, 4));
-  HIPCK(c, hipMemcpyAsync(d_enc, enc, 32, hipMemcpyHostToDevice, s0));
-  launch_decode_points(d_enc, 1, d_ext, d_ok, s0);
+  // one allocation for the three scratch pieces (nothing to leak when a later one would have failed): encoding | decode verdict | point
+  uint8_t* d_tmp = nullptr;
+  HIPCK(c, hipMalloc(&d_tmp, 64 + GE_WORDS * 4));
+  uint8_t* d_enc = d_tmp; uint32_t *d_ok = reinterpret_cast<uint32_t*>(d_tmp + 32), *d_ext = reinterpret_cast<uint32_t*>(d_tmp + 64);
+  uint32_t ok = 0;
+  hipError_t se = hipMemcpyAsync(d_enc, enc, 32, hipMemcpyHostToDevice, s0);
+  if (se == hipSuccess) { launch_decode_points(d_enc, 1, d_ext, d_ok, s0); se = hipMemcpyAsync(&ok, d_ok, 4, hipMemcpyDeviceToHost, s0); }
+  if (se == hipSuccess) se = hipStreamSynchronize(s0);
+  if (se != hipSuccess || !ok) {
+    (void)hipFree(d_tmp); (void)hipGetLastError();
+    if (se != hipSuccess) { c->err = "act_ctx_set_fixed_base_bits: decoding the base failed"; return ACT_ERR_HIP; }
+    c->err = "act_ctx_set_fixed_base_bits: the base is not a canonical Ristretto encoding"; return ACT_ERR_PARAMS;
+  }
   uint32_t* t = table_acquire(c->device, enc, bits, d_ext, s0, nullptr);
-  const hipError_t se = hipStreamSynchronize(s0);
-  (void)hipFree(d_enc); (void)hipFree(d_ext); (void)hipFree(d_ok);
+  se = hipStreamSynchronize(s0);
+  (void)hipFree(d_tmp);
   if (!t || se != hipSuccess) {
     (void)hipGetLastError();
     if (t) table_release(c->device, t);

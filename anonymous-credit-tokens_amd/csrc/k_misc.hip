@@ -4,24 +4,12 @@
 
 namespace act {
 
-// T[pos][e] = e * 2^(w*pos) * B as affine Niels (msm.h).  lane = (pos, e): w*pos doublings of B, a
-// w-bit double-and-add, one inversion.  Runs once per context (cf. RistrettoBasepointTable::create,
-// /root/reference/src/lib.rs:311-313).
+// T[pos][e] = e * 2^(w*pos) * B as affine Niels (msm.h fb_table_entry).  lane = (pos, e).  Runs once per
+// (device, base, width) (cf. RistrettoBasepointTable::create in the upstream crate, src/lib.rs:311-313).
 __global__ void __launch_bounds__(256) k_build_table(const uint32_t* base_ext, uint32_t* table, uint32_t wbits) {
   uint32_t gid = blockIdx.x * 256 + threadIdx.x;
   if (gid >= fb_windows(wbits) << wbits) return;
-  uint32_t pos = gid >> wbits, e = gid & ((1u << wbits) - 1u);
-  ge b = ge_load(base_ext);
-  for (uint32_t i = 0; i < wbits * pos; i++) b = ge_double(b);
-  ge acc = ge_identity();
-  ge_cached bc = ge_to_cached(b);
-  for (int bit = (int)wbits - 1; bit >= 0; bit--) {
-    acc = ge_double(acc);
-    if ((e >> bit) & 1u) acc = ge_add_cached(acc, bc);
-  }
-  fe zi = fe_invert(acc.Z);
-  ge af; af.X = fe_mul(acc.X, zi); af.Y = fe_mul(acc.Y, zi); af.Z = fe_one(); af.T = fe_mul(af.X, af.Y);
-  niels_store(table + (size_t)gid * NIELS_WORDS, niels_from_affine(af));
+  niels_store(table + (size_t)gid * NIELS_WORDS, fb_table_entry(ge_load(base_ext), wbits, gid));
 }
 void launch_build_table(const uint32_t* base_ext, uint32_t* table, uint32_t wbits, hipStream_t s) {
   const uint32_t lanes = fb_windows(wbits) << wbits;
@@ -155,6 +143,20 @@ __global__ void __launch_bounds__(64, 2) k_debug_scalarmult(const uint8_t* pts, 
 }
 void launch_debug_scalarmult(const uint8_t* pts, const uint8_t* scs, uint32_t n, uint32_t* pbk, uint8_t* out, uint8_t* status, hipStream_t s) {
   if (n) hipLaunchKernelGGL(k_debug_scalarmult, dim3((n + 63) / 64), dim3(64), 0, s, pts, scs, n, pbk, out, status);
+}
+
+// Test hook (act_debug_fixed_base_batch): out[i] = enc(s_i * B) through the production fixed-base product (msm.h fixed_base_acc)
+// on the table and window width the context holds for B right now, and the production encode: one product per lane, so that every
+// window and entry of a table of any width can be aimed at with a chosen scalar.
+__global__ void __launch_bounds__(64) k_debug_fixed_base(FbTab tab, const uint8_t* scs, uint32_t n, uint8_t* out) {
+  uint32_t i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  ge r = fixed_base_acc(ge_identity(), tab, load_sc(scs + (size_t)i * 32));
+  uint32_t e[8]; ristretto_encode(e, r);
+  store8(out + (size_t)i * 32, e);
+}
+void launch_debug_fixed_base(FbTab tab, const uint8_t* scs, uint32_t n, uint8_t* out, hipStream_t s) {
+  if (n) hipLaunchKernelGGL(k_debug_fixed_base, dim3((n + 63) / 64), dim3(64), 0, s, tab, scs, n, out);
 }
 
 // ALU roofline probe: 8 register-resident accumulators per lane, each advanced by one block of 10 dependent v_mad_u64_u32

@@ -272,6 +272,7 @@ void launch_ubench_random_read(const uint32_t* buf, uint64_t lines, uint32_t blo
 constexpr int UBENCH_MADS_PER_ITER = 80;    // 8 chains x 10 dependent multiply-accumulates (k_misc.hip k_ubench_mad)
 void launch_ubench_mad(uint32_t* out, uint32_t blocks, uint32_t iters, hipStream_t s);
 void launch_debug_scalarmult(const uint8_t* pts, const uint8_t* scs, uint32_t n, uint32_t* pbk, uint8_t* out, uint8_t* status, hipStream_t s);
+void launch_debug_fixed_base(FbTab tab, const uint8_t* scs, uint32_t n, uint8_t* out, hipStream_t s);
 void launch_spend_prep(const SpendArgs& a, hipStream_t s);
 void launch_spend_prep_role(const SpendArgs& a, int role /* 0 A, 1 B, 2 C, 3 join, 4 C1 (what k_spend_bits waits for), 5 C2 */, hipStream_t s);
 void launch_spend_enc_small(const SpendArgs& a, hipStream_t s);

@@ -78,6 +78,22 @@ struct FbTab { const uint32_t* p; uint32_t wbits; uint32_t id; };
 ACT_HD uint32_t fb_windows(uint32_t wbits) { return (253u + wbits - 1u) / wbits; }      // scalars are canonical: < l < 2^253
 ACT_HD size_t fb_table_words(uint32_t wbits) { return (size_t)fb_windows(wbits) * ((size_t)1 << wbits) * NIELS_WORDS; }
 
+// Entry `gid` = (pos, e) of B's table at width wbits, T[pos][e] = e * 2^(wbits*pos) * B as affine Niels: wbits*pos doublings of B, a
+// wbits-bit double-and-add, one inversion.  One lane of k_build_table (k_misc.hip); the host test build fills its tables with it too.
+ACT_HD ge_niels fb_table_entry(ge b, uint32_t wbits, uint32_t gid) {
+  uint32_t pos = gid >> wbits, e = gid & ((1u << wbits) - 1u);
+  for (uint32_t i = 0; i < wbits * pos; i++) b = ge_double(b);
+  ge acc = ge_identity();
+  ge_cached bc = ge_to_cached(b);
+  for (int bit = (int)wbits - 1; bit >= 0; bit--) {
+    acc = ge_double(acc);
+    if ((e >> bit) & 1u) acc = ge_add_cached(acc, bc);
+  }
+  fe zi = fe_invert(acc.Z);
+  ge af; af.X = fe_mul(acc.X, zi); af.Y = fe_mul(acc.Y, zi); af.Z = fe_one(); af.T = fe_mul(af.X, af.Y);
+  return niels_from_affine(af);
+}
+
 // acc += s * B using B's table; s canonical (< l).  fb_windows(wbits) mixed additions, no doublings.  The entry of window
 // pos+1 is loaded before the addition of window pos (the tables live in L2 / Infinity Cache / HBM: ~550-cycle loads).
 ACT_HD uint32_t fb_next_digit(uint32_t w[8], uint32_t wbits) {

@@ -882,6 +882,12 @@ int act_debug_copy_leaders(act_ctx *ctx, size_t m, const uint64_t *fp, uint32_t 
  * (tests/golden/sodium_primitives.json). */
 int act_debug_scalarmult_batch(act_ctx *ctx, size_t n, int mem, const uint8_t *points, const uint8_t *scalars, uint8_t *out,
                                uint8_t *status);
+/* Debug / test hook: out[i] = enc(scalars[i] * B) for the fixed base B = `base` 0..3 (g, h1, h2, h3) (`&table * &scalar`, e.g.
+ * src/lib.rs:224-228), computed by the engine's production fixed-base product on the table and window width the context holds for
+ * that base at the time of the call (act_ctx_set_fixed_base_bits), and the production encode.  Scalars are 32 bytes each and are
+ * reduced mod l on load.  Exists so that every window and entry of a table of any width can be aimed at with a chosen scalar.
+ * ACT_ERR_ARG for a base outside 0..3. */
+int act_debug_fixed_base_batch(act_ctx *ctx, int base, size_t n, int mem, const uint8_t *scalars, uint8_t *out);
 
 /* Measurement hook: A/B switches and size overrides of tools/ and tests/ (csrc/kernels.h TuneKey: "no_mapped_reads", "no_fused_tiny",
  * "no_taper", "no_wide_sign", "no_wide_prove", "no_wide_client", "no_lds_isolation", "no_stream_probe", "small_sub", "small_in_flight",

@@ -111,6 +111,31 @@ int hc_fixed_base(const uint8_t* pt, const uint8_t* s, uint8_t* o) {
   ristretto_encode(r, acc); st(o, r);
   return 1;
 }
+// the same at a RUN-TIME window width, the table filled entry by entry with the lane body of k_build_table (msm.h fb_table_entry):
+// out[i] = enc(scalars[i] * pt) for n scalars of 32 bytes.  Only the entries these scalars read are built (found with the product's own
+// digit walk, so what is built is what is read): an entry costs wbits * pos doublings, and the 47 104 of an 11-bit table take
+// seconds where the ~3 000 that are read take a fraction of one; an entry nobody reads is checked by nobody either way.
+// 0 = pt does not decode or wbits is outside what the ABI accepts.
+int hc_fixed_base_w(const uint8_t* pt, int wbits, size_t n, const uint8_t* scalars, uint8_t* out) {
+  uint32_t w[8], r[8]; ld(w, pt); ge b; if (!ristretto_decode(b, w)) return 0;
+  if (wbits < 4 || wbits > 24) return 0;
+  const uint32_t wb = (uint32_t)wbits, nw = fb_windows(wb);
+  std::vector<uint32_t> tab(fb_table_words(wb));
+  std::vector<bool> built((size_t)nw << wb, false);
+  for (size_t i = 0; i < n; i++) {
+    const sc s = sc_in(scalars + 32 * i);
+    uint32_t d[8]; for (int k = 0; k < 8; k++) d[k] = s.v[k];
+    for (uint32_t pos = 0; pos < nw; pos++) {
+      const uint32_t gid = (pos << wb) + fb_next_digit(d, wb);
+      if (!built[gid]) { niels_store(&tab[(size_t)gid * NIELS_WORDS], fb_table_entry(b, wb, gid)); built[gid] = true; }
+    }
+  }
+  const FbTab t{tab.data(), wb, 0u};
+  for (size_t i = 0; i < n; i++) {
+    ristretto_encode(r, fixed_base_acc(ge_identity(), t, sc_in(scalars + 32 * i))); st(out + 32 * i, r);
+  }
+  return 1;
+}
 int hc_add_sub_dbl(const uint8_t* a, const uint8_t* b, uint8_t* o_add, uint8_t* o_sub, uint8_t* o_dbl) {
   uint32_t w[8], r[8]; ge p, q; ld(w, a); if (!ristretto_decode(p, w)) return 0; ld(w, b); if (!ristretto_decode(q, w)) return 0;
   ristretto_encode(r, ge_add(p, q)); st(o_add, r);

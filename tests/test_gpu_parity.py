@@ -3,6 +3,7 @@ against the C oracle on the same seeded inputs.  Bit-exact (integer / byte work)
 import pytest
 
 from conftest import ELL, load_golden, shake, scb
+from fixed_base_cases import crafted_spend_proofs
 
 pytestmark = pytest.mark.gpu
 
@@ -161,16 +162,7 @@ def test_crafted_scalars_reproduce_the_oracle_transcript(engine_factory, oracle,
     st, proof, _ = eng.prove_spend(tok, scb(321), shake("cs-pr", octx.prove_rng_bytes))
     assert st == b"\0"
     pb = octx.proof_bytes
-    recs = []
-    for n, v in enumerate(pats):
-        t = bytearray(proof)
-        t[32 * (4 + L):32 * (5 + L)] = scb(v)                                           # gamma
-        for j in range(L):
-            w = pats[(n + j) % N]
-            t[32 * (12 + L + j):32 * (13 + L + j)] = scb(w)                             # gamma0_j
-            t[32 * (12 + 2 * L + 2 * j):32 * (13 + 2 * L + 2 * j)] = scb(pats[(n + 2 * j + 1) % N])       # z_j0
-        recs.append(bytes(t))
-    nc = bytearray(recs[3]); nc[32 * (4 + L):32 * (5 + L)] = ((1 << 253) - 1).to_bytes(32, "little"); recs[3] = bytes(nc)   # gamma >= l
+    recs = crafted_spend_proofs(proof, L, pats)      # gamma, gamma0_j, z_j0 from pats; record 3 with gamma >= l (tests/fixed_base_cases.py)
     batch = b"".join(recs)
     want = [octx.verify_spend(sk, r, True) for r in recs]
     try:
