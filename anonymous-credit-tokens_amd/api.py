@@ -443,6 +443,14 @@ class PreIssuance(_Cbor):
             raise Error(st[0])
         return CreditToken(out)
 
+    def to_credit_token_ring(self, params: Params, publics: Sequence[PublicKey], request: "IssuanceRequest", response: "IssuanceResponse") -> Tuple["CreditToken", int]:
+        """to_credit_token against the issuer's published keys (1 .. 4, in the caller's order of preference) while it rotates them:
+        -> (token, index of the first ring key the response verifies under); the one-key error when none does."""
+        st, out, ok = params.engine().issuance_to_credit_token_ring(self.record, [p.w for p in publics], request.record, response.record)
+        if st[0]:
+            raise Error(st[0])
+        return CreditToken(out), ok[0]
+
 
 class IssuanceRequest(_Cbor):
     CBOR_TYPE = "IssuanceRequest"
@@ -510,6 +518,14 @@ class PreRefund(_Cbor):
         if st[0]:
             raise Error(st[0])
         return CreditToken(out)
+
+    def to_credit_token_ring(self, params: Params, spend_proof: SpendProof, refund: "Refund", publics: Sequence[PublicKey]) -> Tuple[CreditToken, int]:
+        """to_credit_token against the issuer's published keys: a Refund names no key, and Keyring.refund_batch(sign_with=i) moves a
+        client onto key i without telling it.  -> (token, index of the first ring key the refund verifies under)."""
+        st, out, ok = params.engine(spend_proof.nbits).refund_to_credit_token_ring(self.record, spend_proof.record, refund.record, [p.w for p in publics])
+        if st[0]:
+            raise Error(st[0])
+        return CreditToken(out), ok[0]
 
 
 class Refund(_Cbor):

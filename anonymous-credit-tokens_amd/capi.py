@@ -55,6 +55,7 @@ EXPORTS = [
     "act_redeem_admit_batch", "act_redeem_cbor_admit_batch", "act_redeem_admit_unique_batch", "act_redeem_cbor_admit_unique_batch", "act_debug_copy_leaders",
     "act_redeem_replay_batch", "act_redeem_cbor_replay_batch", "act_replay_derive_batch",
     "act_redeem_admit_replay_batch", "act_redeem_cbor_admit_replay_batch",
+    "act_issuance_to_credit_token_keyring_batch", "act_refund_to_credit_token_keyring_batch",
     "act_issue_check_cbor_batch", "act_issue_sign_cbor_batch", "act_issue_cbor_batch",
     "act_node_issue_check_cbor_batch", "act_node_issue_sign_cbor_batch", "act_node_issue_cbor_batch",
     "act_ctx_host_hash_stats", "act_ctx_set_tiny_calls", "act_node_set_balance", "act_node_device_stats", "act_node_balance_state", "act_debug_set_slowdown", "act_debug_fail_next_signs",
@@ -132,6 +133,8 @@ def load() -> C.CDLL:
     lib.act_verify_spend_batch.argtypes = [vp, sz, i32, u8p, u8p, u8p, u8p]
     lib.act_refund_batch.argtypes = [vp, sz, i32, u8p, u8p, u8p, i32, u8p, u8p]
     lib.act_refund_to_credit_token_batch.argtypes = [vp, sz, i32, u8p, u8p, u8p, u8p, u8p, u8p]
+    lib.act_issuance_to_credit_token_keyring_batch.argtypes = [vp, sz, i32, u8p, u8p, C.c_uint32, u8p, u8p, u8p, u8p, u8p]
+    lib.act_refund_to_credit_token_keyring_batch.argtypes = [vp, sz, i32, u8p, u8p, u8p, u8p, C.c_uint32, u8p, u8p, u8p]
     lib.act_debug_last_spend_transcripts.argtypes = [vp, sz, u8p, C.POINTER(sz)]
     lib.act_debug_scalarmult_batch.argtypes = [vp, sz, i32, u8p, u8p, u8p, u8p]
     lib.act_debug_fixed_base_batch.argtypes = [vp, i32, sz, i32, u8p, u8p]
@@ -753,6 +756,35 @@ class Engine:
         b = out.tobytes()
         assert all(st[i] == 0 or not out[i * ml:(i + 1) * ml].any() for i in range(n)), "a failed lane's slot is not zero"
         return st.tobytes(), [b[i * ml:(i + 1) * ml] if st[i] == 0 else b"" for i in range(n)], ok.tobytes()
+
+    # ---- key rotation, the client's side: to_credit_token against a ring of issuer PUBLIC keys (publics = list of 32-byte w) ----------
+    def issuance_to_credit_token_ring(self, pre: bytes, publics, req: bytes, resp: bytes, raw: bool = False):
+        """-> (statuses, tokens, out_key bytes: the smallest ring index every accepted lane verifies under, KEY_NONE elsewhere).
+        raw=True: (rc, statuses, tokens, out_key), no exception."""
+        n = len(pre) // 64; out = np.zeros(160 * n, np.uint8); st = np.zeros(n, np.uint8); ok = np.zeros(n, np.uint8)
+        p0, k0 = _in(pre, 64 * n); pw, kw = _in(b"".join(publics)); p1, k1 = _in(req, 128 * n); p2, k2 = _in(resp, 160 * n)
+        rc = self.lib.act_issuance_to_credit_token_keyring_batch(self.ctx, n, MEM_HOST, p0, pw, len(publics), p1, p2, out.ctypes.data, st.ctypes.data, ok.ctypes.data)
+        if raw:
+            return rc, st.tobytes(), out.tobytes(), ok.tobytes()
+        self._ck(rc)
+        return st.tobytes(), out.tobytes(), ok.tobytes()
+
+    def refund_to_credit_token_ring(self, prerefund: bytes, proofs: bytes, refund: bytes, publics, raw: bool = False):
+        n = len(prerefund) // 96; out = np.zeros(160 * n, np.uint8); st = np.zeros(n, np.uint8); ok = np.zeros(n, np.uint8)
+        p0, k0 = _in(prerefund, 96 * n); p1, k1 = _in(proofs, self.proof_bytes * n); p2, k2 = _in(refund, 128 * n); pw, kw = _in(b"".join(publics))
+        rc = self.lib.act_refund_to_credit_token_keyring_batch(self.ctx, n, MEM_HOST, p0, p1, p2, pw, len(publics), out.ctypes.data, st.ctypes.data, ok.ctypes.data)
+        if raw:
+            return rc, st.tobytes(), out.tobytes(), ok.tobytes()
+        self._ck(rc)
+        return st.tobytes(), out.tobytes(), ok.tobytes()
+
+    def client_ring_ptr(self, fn: str, publics, n: int, mem: int, **p):
+        """the same on raw pointers of either kind (device-memory callers): fn = issuance / refund; the ring itself is host bytes"""
+        pw, kw = _in(b"".join(publics)); nk = len(publics)
+        if fn == "issuance":
+            self._ck(self.lib.act_issuance_to_credit_token_keyring_batch(self.ctx, n, mem, p["pre"], pw, nk, p["req"], p["resp"], p["out"], p["status"], p["out_key"]))
+        else:
+            self._ck(self.lib.act_refund_to_credit_token_keyring_batch(self.ctx, n, mem, p["pre"], p["proofs"], p["refund"], pw, nk, p["out"], p["status"], p["out_key"]))
 
     def keyring_ptr(self, fn: str, keys, n: int, mem: int, **p):
         """the ring calls on raw pointers of either kind (device-memory callers): fn = verify / sign / redeem / redeem_cbor"""

@@ -19,6 +19,7 @@
 #include <vector>
 #include "kernels.h"
 #include "keyring.h"
+#include "client_ring_lanes.h"
 #include "admit.h"
 #include "replay_lanes.h"
 #include "admit_replay_lanes.h"
@@ -189,8 +190,10 @@ struct act_ctx {
   std::mutex replay_mu;                // a replay call holds it from start to end (replay_impl.inc): d_replay below belongs to ONE call at a time; taken before mu, never under it
   uint8_t* d_replay = nullptr; size_t d_replay_cap = 0;            // the staged nonce_key and ring records, then the derived per-lane nonces of a replay call: wiped when the call ends
   struct RingWs* ring_ws = nullptr;              // key-ring side buffers, allocated by the context's first ring call (keyring_impl.inc)
+  struct ClientRingWs* client_ring_ws = nullptr; // the client's ring tables and side buffers, allocated by the context's first client-ring call (client_ring_impl.inc)
 };
 static void ring_ws_free(act_ctx* c);            // keyring_impl.inc
+static void client_ring_ws_free(act_ctx* c);     // client_ring_impl.inc
 
 namespace {
 
@@ -809,6 +812,7 @@ void act_ctx_destroy(act_ctx* c) {
   if (c->d_admit_rng) { (void)hipMemset(c->d_admit_rng, 0, c->d_admit_rng_cap); (void)hipFree(c->d_admit_rng); }
   if (c->d_replay) { (void)hipMemset(c->d_replay, 0, c->d_replay_cap); (void)hipFree(c->d_replay); }
   ring_ws_free(c);
+  client_ring_ws_free(c);
   memset(&c->key, 0, sizeof(c->key)); memset(c->sk_cached, 0, 64);
   delete c;
 }
@@ -1304,6 +1308,7 @@ int act_refund_batch(act_ctx* c, size_t n, int mem, const uint8_t sk[64], const 
 #include "keyring_impl.inc"     // key rotation: verification and signing against a ring of issuer keys
 
 #include "client_impl.inc"      // prove_spend and the two to_credit_token calls
+#include "client_ring_impl.inc" // the two to_credit_token calls against a ring of issuer public keys
 
 #include "debug_impl.inc"       // act_debug_*, act_ubench_*, act_prof_*
 }  // extern "C"

@@ -671,6 +671,29 @@ int act_node_redeem_cbor_keyring_epochs_batch(act_node *node, act_node_nullifier
                                               const uint32_t *key_epochs, int sign_key, const uint8_t *cbor, const uint64_t *offsets,
                                               const uint8_t *rng, int rng_mode, uint8_t *out_refund_cbor, uint8_t *status, uint8_t *out_key);
 
+/* ======== key rotation, the client's side: to_credit_token against a ring of issuer PUBLIC keys ========================================
+ * Neither an IssuanceResponse nor a Refund names the key it was signed with, and with sign_key the server moves a client onto a new key
+ * with its next refund.  These two calls verify every item ONCE and say per lane under WHICH published key it verified: w enters the
+ * client's check only through X_g and Y_g, so an extra key costs two fixed-base products on g, one on an 8-bit table of w_k, a mixed
+ * addition, two encodings and one single-chunk BLAKE3 per item (0.4 of one variable-base product) instead of a whole verification -- and no key identifier, which
+ * would be a tagging channel chosen by the server, has to travel beside the message.
+ *   ring_w    nkeys encodings of 32 bytes, 1 <= nkeys <= ACT_KEYRING_MAX, in the caller's order of preference; always HOST memory, like w
+ *             in the one-key calls.  nkeys out of range, a null ring or an entry that is not a canonical encoding: ACT_ERR_ARG before
+ *             anything is launched.  Duplicate entries are legal: the first one wins.
+ *   out_key   per lane: the SMALLEST ring index under which the one-key call accepts the item; ACT_KEY_NONE on every lane whose status
+ *             is not 0.
+ *   status, out_token   those of the one-key call under that key: 255 = undecodable, whatever the ring; 2 (issuance) / 4 (refund) = no
+ *             ring key verifies; a rejected lane's token is all zero.
+ * nkeys == 1 gives the bytes of the one-key call.  The secret pre records are staged and wiped as there; the ring's tables and side
+ * buffers (public data) are allocated by a context's first call of this kind.  There is no tiny or fused road for rings: always the
+ * chunked launches, whatever n. */
+int act_issuance_to_credit_token_keyring_batch(act_ctx *ctx, size_t n, int mem, const uint8_t *pre, const uint8_t *ring_w, uint32_t nkeys,
+                                               const uint8_t *req, const uint8_t *resp, uint8_t *out_token, uint8_t *status,
+                                               uint8_t *out_key);
+int act_refund_to_credit_token_keyring_batch(act_ctx *ctx, size_t n, int mem, const uint8_t *prerefund, const uint8_t *proof,
+                                             const uint8_t *refund, const uint8_t *ring_w, uint32_t nkeys, uint8_t *out_token,
+                                             uint8_t *status, uint8_t *out_key);
+
 /* ======== admission before verification: the expected charge and the spent nullifiers first ========
  * The redeem calls above verify, then look up and record, then sign: a replayed proof costs a whole verification before the set
  * answers DoubleSpendError, and nothing compares SpendProof.s with what the request costs.  These two calls put an admission stage in
