@@ -278,16 +278,16 @@ class PrivateKey(_Cbor):
 
     # ---- replayable redemption: a retried SpendProof gets its Refund again ----------------------------------
     def redeem_replay_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", proofs: Sequence["SpendProof"], nonce_key: bytes,
-                            admit: bool = False, charges: Sequence = None) -> Tuple[list, list]:
+                            admit: bool = False, charges: Sequence = None, unique: bool = False) -> Tuple[list, list]:
         """redeem_batch without a generator: the nonces are derived from `nonce_key` (32 secret bytes the issuer keeps), this key, the
         nullifier and K', and `receipts` (a second NullifierDb) remembers which K' a nullifier was spent for -- a proof that is sent
-        again gets the same Refund, byte for byte, instead of DoubleSpendError.  admit / charges: Keyring.redeem_replay_batch.  -> (results, replayed flags)"""
-        res, _, replayed = Keyring([self]).redeem_replay_batch(params, db, receipts, proofs, nonce_key, admit=admit, charges=charges)
+        again gets the same Refund, byte for byte, instead of DoubleSpendError.  admit / charges / unique: Keyring.redeem_replay_batch.  -> (results, replayed flags)"""
+        res, _, replayed = Keyring([self]).redeem_replay_batch(params, db, receipts, proofs, nonce_key, admit=admit, charges=charges, unique=unique)
         return res, replayed
 
     def redeem_replay_cbor_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", msgs: Sequence[bytes], nonce_key: bytes, nbits: int = L,
-                                 admit: bool = False, charges: Sequence = None) -> Tuple[list, list]:
-        res, _, replayed = Keyring([self]).redeem_replay_cbor_batch(params, db, receipts, msgs, nonce_key, nbits, admit=admit, charges=charges)
+                                 admit: bool = False, charges: Sequence = None, unique: bool = False) -> Tuple[list, list]:
+        res, _, replayed = Keyring([self]).redeem_replay_cbor_batch(params, db, receipts, msgs, nonce_key, nbits, admit=admit, charges=charges, unique=unique)
         return res, replayed
 
     def verify_spend_batch(self, params: Params, proofs: Sequence["SpendProof"]) -> bytes:
@@ -384,7 +384,7 @@ class Keyring:
         return [out[i] if st[i] == 0 else _wire_error(st[i]) for i in range(len(msgs))], self._indices(st, ok)
 
     def redeem_replay_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", proofs: Sequence["SpendProof"], nonce_key: bytes, sign_with=None,
-                            admit: bool = False, charges: Sequence = None) -> Tuple[list, list, list]:
+                            admit: bool = False, charges: Sequence = None, unique: bool = False) -> Tuple[list, list, list]:
         """redeem_batch made retry-safe (act_redeem_replay_batch): no generator -- the nonces are derived from `nonce_key`, the key a
         lane is signed with, the nullifier and K' -- and `receipts`, a second NullifierDb, records for which K' every nullifier was
         spent.  A proof that is sent again (same ring key to sign with, same nonce_key) gets the same Refund, byte for byte; another
@@ -393,30 +393,37 @@ class Keyring:
         a proof whose s differs) and the spent nullifiers first: a proof whose nullifier is spent and whose receipt is not its own is
         DoubleSpendError WITHOUT being verified, a retry is verified and served.  Accepted lanes, refunds and both databases end as
         without it; the counts are capi.ADMIT_REPLAY_COUNTS.
+        unique=True (with admit=True; act_redeem_admit_replay_unique_batch): byte-identical proofs of the batch are verified and signed
+        once and the copies get the same Refund; the results are the same and the counts gain "copies" and "copies_served".
         -> (results, matched ring indices, replayed flags); `self.last_replay_counts`: the call's counts."""
         nbits = proofs[0].nbits if proofs else L
         if charges is not None and not admit:
             raise ValueError("charges are compared by the admission screen: admit=True")
+        if unique and not admit:
+            raise ValueError("copies are found behind the admission screen: admit=True")
         e, pb = params.engine(nbits), b"".join(p.record for p in proofs)
         if admit:
             cc = b"".join(scalar(c) for c in charges) if charges is not None else None
             st, out, ok, rep, self.last_replay_counts = e.redeem_admit_replay(
-                db.set, receipts.set, self._records(), pb, nonce_key, self._sign_key(sign_with), key_epochs=self.epochs, charges=cc)
+                db.set, receipts.set, self._records(), pb, nonce_key, self._sign_key(sign_with), key_epochs=self.epochs, charges=cc, unique=unique)
         else:
             st, out, ok, rep, self.last_replay_counts = e.redeem_replay(db.set, receipts.set, self._records(), pb, nonce_key, self._sign_key(sign_with), key_epochs=self.epochs)
         return [Refund(out[128 * i:128 * i + 128]) if st[i] == 0 else Error(st[i]) for i in range(len(proofs))], self._indices(st, ok), [bool(r) for r in rep]
 
     def redeem_replay_cbor_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", msgs: Sequence[bytes], nonce_key: bytes, nbits: int = L,
-                                 sign_with=None, admit: bool = False, charges: Sequence = None) -> Tuple[list, list, list]:
+                                 sign_with=None, admit: bool = False, charges: Sequence = None, unique: bool = False) -> Tuple[list, list, list]:
         """the same on wire bytes (act_redeem_cbor_replay_batch; admit=True: act_redeem_cbor_admit_replay_batch): a retry may be another
-        CBOR spelling of the same proof"""
+        CBOR spelling of the same proof.  unique=True (with admit=True): act_redeem_cbor_admit_replay_unique_batch -- a copy is a message
+        of the same length and the same bytes; another spelling is verified on its own"""
         if charges is not None and not admit:
             raise ValueError("charges are compared by the admission screen: admit=True")
+        if unique and not admit:
+            raise ValueError("copies are found behind the admission screen: admit=True")
         e = params.engine(nbits)
         if admit:
             cc = b"".join(scalar(c) for c in charges) if charges is not None else None
             st, out, ok, rep, self.last_replay_counts = e.redeem_cbor_admit_replay(
-                db.set, receipts.set, self._records(), list(msgs), nonce_key, self._sign_key(sign_with), key_epochs=self.epochs, charges=cc)
+                db.set, receipts.set, self._records(), list(msgs), nonce_key, self._sign_key(sign_with), key_epochs=self.epochs, charges=cc, unique=unique)
         else:
             st, out, ok, rep, self.last_replay_counts = e.redeem_cbor_replay(db.set, receipts.set, self._records(), list(msgs), nonce_key, self._sign_key(sign_with), key_epochs=self.epochs)
         return [out[i] if st[i] == 0 else _wire_error(st[i]) for i in range(len(msgs))], self._indices(st, ok), [bool(r) for r in rep]

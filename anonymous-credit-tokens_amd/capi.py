@@ -23,6 +23,7 @@ ADMIT_UNIQUE_COUNTS = ADMIT_COUNTS + ("copies",)      # act_redeem_*admit_unique
 REPLAY_COUNTS = ("lanes", "rejected_by_verification", "fresh", "replayed", "double_spend", "unanswered")      # act_redeem_*replay_batch
 ADMIT_REPLAY_COUNTS = ("lanes", "wire_rejected", "wrong_charge", "foreign_spend", "retry_candidates", "verified", "rejected_by_verification", "fresh", "replayed",
                        "double_spend_after", "unanswered")      # act_redeem_*admit_replay_batch
+ADMIT_REPLAY_UNIQUE_COUNTS = ADMIT_REPLAY_COUNTS + ("copies", "copies_served")      # act_redeem_*admit_replay_unique_batch: copies, and those whose leader ended 0
 _ERRS = {1: "ACT_ERR_ARG", 2: "ACT_ERR_HIP", 3: "ACT_ERR_PARAMS", 4: "ACT_ERR_NO_DEVICE", 5: "ACT_ERR_RNG"}
 
 EXPORTS = [
@@ -54,7 +55,7 @@ EXPORTS = [
     "act_node_redeem_cbor_keyring_epochs_batch",
     "act_redeem_admit_batch", "act_redeem_cbor_admit_batch", "act_redeem_admit_unique_batch", "act_redeem_cbor_admit_unique_batch", "act_debug_copy_leaders",
     "act_redeem_replay_batch", "act_redeem_cbor_replay_batch", "act_replay_derive_batch",
-    "act_redeem_admit_replay_batch", "act_redeem_cbor_admit_replay_batch",
+    "act_redeem_admit_replay_batch", "act_redeem_cbor_admit_replay_batch", "act_redeem_admit_replay_unique_batch", "act_redeem_cbor_admit_replay_unique_batch",
     "act_issuance_to_credit_token_keyring_batch", "act_refund_to_credit_token_keyring_batch",
     "act_issue_check_cbor_batch", "act_issue_sign_cbor_batch", "act_issue_cbor_batch",
     "act_node_issue_check_cbor_batch", "act_node_issue_sign_cbor_batch", "act_node_issue_cbor_batch",
@@ -254,6 +255,9 @@ def load() -> C.CDLL:
     # its admission form: the screen asks the receipts before anything is verified (out_counts: ACT_ADMIT_REPLAY_COUNTS values, host)
     lib.act_redeem_admit_replay_batch.argtypes = [vp, vp, vp, sz, i32, u8p, i32, u32p, i32, u8p, u8p, u8p, u8p, u8p, u8p, u8p, u64p]
     lib.act_redeem_cbor_admit_replay_batch.argtypes = [vp, vp, vp, sz, i32, u8p, i32, u32p, i32, u8p, vp, u8p, u8p, u8p, u8p, u8p, u8p, u64p]
+    # its unique forms: byte-identical proofs of one batch are verified and signed once (out_counts: ACT_ADMIT_REPLAY_UNIQUE_COUNTS values)
+    lib.act_redeem_admit_replay_unique_batch.argtypes = lib.act_redeem_admit_replay_batch.argtypes
+    lib.act_redeem_cbor_admit_replay_unique_batch.argtypes = lib.act_redeem_cbor_admit_replay_batch.argtypes
     lib.act_issue_check_cbor_batch.argtypes = [vp, sz, i32, u8p, vp, u8p, u8p]
     lib.act_issue_sign_cbor_batch.argtypes = [vp, sz, i32, u8p, u8p, u8p, u8p, u8p, i32, u8p, u8p]
     lib.act_issue_cbor_batch.argtypes = [vp, sz, i32, u8p, u8p, vp, u8p, u8p, i32, u8p, u8p]
@@ -929,36 +933,42 @@ class Engine:
 
     # ---- admission for the replayable redemption (act_redeem_admit_replay_batch / act_redeem_cbor_admit_replay_batch) ----------------
     def redeem_admit_replay(self, nullifier_set, receipts, keys, proofs: bytes, nonce_key: bytes, sign_key: int = SIGN_MATCHED, key_epochs=None, charges: bytes = None,
-                            raw: bool = False):
+                            raw: bool = False, unique: bool = False):
         """redeem_replay with the admission screen in front: a wrong charge (STATUS_WRONG_CHARGE) and a spent nullifier whose receipt is
         not this proof's (STATUS_DOUBLE_SPEND) are answered unverified; a retry is verified and served.
-        -> (statuses, refunds, out_key, replayed, counts dict); raw=True: (rc, ...), no exception"""
+        -> (statuses, refunds, out_key, replayed, counts dict); raw=True: (rc, ...), no exception.  unique=True:
+        act_redeem_admit_replay_unique_batch -- a lane with the bytes of an earlier lane is not verified and takes that lane's answer"""
+        names = ADMIT_REPLAY_UNIQUE_COUNTS if unique else ADMIT_REPLAY_COUNTS
+        fn = self.lib.act_redeem_admit_replay_unique_batch if unique else self.lib.act_redeem_admit_replay_batch
         n = len(proofs) // self.proof_bytes; out = np.full(128 * n, 7 if raw else 0, np.uint8)
         st = np.full(n, 99 if raw else 0, np.uint8); ok = np.zeros(n, np.uint8); rp = np.zeros(n, np.uint8)
         pk, kk = _in(b"".join(keys)); p0, k0 = _in(proofs, self.proof_bytes * n); pn, kn = _in(nonce_key, 32)
         pc, kc = _in(charges, 32 * n) if charges is not None else (None, None)
         ke = _epoch_table(key_epochs, len(keys)) if key_epochs is not None else None
-        cnt = (C.c_uint64 * len(ADMIT_REPLAY_COUNTS))()
-        rc = self.lib.act_redeem_admit_replay_batch(self.ctx, nullifier_set.h, receipts.h, n, MEM_HOST, pk, len(keys), ke.ctypes.data if ke is not None else None, sign_key,
-                                                    p0, pc, pn, out.ctypes.data, st.ctypes.data, ok.ctypes.data, rp.ctypes.data, cnt)
-        counts = dict(zip(ADMIT_REPLAY_COUNTS, (int(v) for v in cnt)))
+        cnt = (C.c_uint64 * len(names))()
+        rc = fn(self.ctx, nullifier_set.h, receipts.h, n, MEM_HOST, pk, len(keys), ke.ctypes.data if ke is not None else None, sign_key,
+                p0, pc, pn, out.ctypes.data, st.ctypes.data, ok.ctypes.data, rp.ctypes.data, cnt)
+        counts = dict(zip(names, (int(v) for v in cnt)))
         if raw:
             return rc, st.tobytes(), out.tobytes(), ok.tobytes(), rp.tobytes(), counts
         self._ck(rc)
         return st.tobytes(), out.tobytes(), ok.tobytes(), rp.tobytes(), counts
 
     def redeem_cbor_admit_replay(self, nullifier_set, receipts, keys, messages: list, nonce_key: bytes, sign_key: int = SIGN_MATCHED, key_epochs=None,
-                                 charges: bytes = None, raw: bool = False):
-        """wire bytes in, wire bytes out -> (statuses, list of CBOR Refund messages (b"" where not signed), out_key, replayed, counts dict)"""
+                                 charges: bytes = None, raw: bool = False, unique: bool = False):
+        """wire bytes in, wire bytes out -> (statuses, list of CBOR Refund messages (b"" where not signed), out_key, replayed, counts dict)
+        unique=True: act_redeem_cbor_admit_replay_unique_batch (a copy has the same length and the same bytes as an earlier message)"""
+        names = ADMIT_REPLAY_UNIQUE_COUNTS if unique else ADMIT_REPLAY_COUNTS
+        fn = self.lib.act_redeem_cbor_admit_replay_unique_batch if unique else self.lib.act_redeem_cbor_admit_replay_batch
         n = len(messages); p0, k0, offs = _msgs(messages); ml = self.cbor_size("Refund")
         st = np.full(n, 99 if raw else 0, np.uint8); ok = np.zeros(n, np.uint8); rp = np.zeros(n, np.uint8); out = np.zeros(ml * n, np.uint8)
         pk, kk = _in(b"".join(keys)); pn, kn = _in(nonce_key, 32)
         pc, kc = _in(charges, 32 * n) if charges is not None else (None, None)
         ke = _epoch_table(key_epochs, len(keys)) if key_epochs is not None else None
-        cnt = (C.c_uint64 * len(ADMIT_REPLAY_COUNTS))()
-        rc = self.lib.act_redeem_cbor_admit_replay_batch(self.ctx, nullifier_set.h, receipts.h, n, MEM_HOST, pk, len(keys), ke.ctypes.data if ke is not None else None,
-                                                         sign_key, p0, offs.ctypes.data, pc, pn, out.ctypes.data, st.ctypes.data, ok.ctypes.data, rp.ctypes.data, cnt)
-        counts = dict(zip(ADMIT_REPLAY_COUNTS, (int(v) for v in cnt)))
+        cnt = (C.c_uint64 * len(names))()
+        rc = fn(self.ctx, nullifier_set.h, receipts.h, n, MEM_HOST, pk, len(keys), ke.ctypes.data if ke is not None else None,
+                sign_key, p0, offs.ctypes.data, pc, pn, out.ctypes.data, st.ctypes.data, ok.ctypes.data, rp.ctypes.data, cnt)
+        counts = dict(zip(names, (int(v) for v in cnt)))
         b = out.tobytes()
         msgs = [b[i * ml:(i + 1) * ml] if st[i] == 0 else b"" for i in range(n)]
         if raw:
@@ -969,21 +979,26 @@ class Engine:
 
     def admit_replay_ptr(self, fn: str, keys, n: int, mem: int, **p):
         """the two calls on raw pointers of either kind: fn = redeem / redeem_cbor; p: set, receipts, proofs | cbor (+ offsets), charges, nonce_key,
-        out, status, out_key, replayed, key_epochs, sign_key, raw.  -> counts dict, or (rc, counts) with raw"""
+        out, status, out_key, replayed, key_epochs, sign_key, raw, unique (the act_redeem_*admit_replay_unique_batch forms).
+        -> counts dict, or (rc, counts) with raw"""
         pk, kk = _in(b"".join(keys)); nk = len(keys); pn, kn = _in(p["nonce_key"], 32)
         ke = _epoch_table(p["key_epochs"], nk) if p.get("key_epochs") is not None else None
         kep = ke.ctypes.data if ke is not None else None
-        cnt = (C.c_uint64 * len(ADMIT_REPLAY_COUNTS))()
+        unique = bool(p.get("unique", False))
+        names = ADMIT_REPLAY_UNIQUE_COUNTS if unique else ADMIT_REPLAY_COUNTS
+        cnt = (C.c_uint64 * len(names))()
         if fn == "redeem":
-            rc = self.lib.act_redeem_admit_replay_batch(self.ctx, p["set"].h, p["receipts"].h, n, mem, pk, nk, kep, p.get("sign_key", SIGN_MATCHED), p["proofs"],
-                                                        p.get("charges") or None, pn, p["out"], p["status"], p["out_key"], p.get("replayed") or None, cnt)
+            call = self.lib.act_redeem_admit_replay_unique_batch if unique else self.lib.act_redeem_admit_replay_batch
+            rc = call(self.ctx, p["set"].h, p["receipts"].h, n, mem, pk, nk, kep, p.get("sign_key", SIGN_MATCHED), p["proofs"],
+                      p.get("charges") or None, pn, p["out"], p["status"], p["out_key"], p.get("replayed") or None, cnt)
         else:
-            rc = self.lib.act_redeem_cbor_admit_replay_batch(self.ctx, p["set"].h, p["receipts"].h, n, mem, pk, nk, kep, p.get("sign_key", SIGN_MATCHED), p["cbor"],
-                                                             p.get("offsets") or None, p.get("charges") or None, pn, p["out"], p["status"], p["out_key"],
-                                                             p.get("replayed") or None, cnt)
+            call = self.lib.act_redeem_cbor_admit_replay_unique_batch if unique else self.lib.act_redeem_cbor_admit_replay_batch
+            rc = call(self.ctx, p["set"].h, p["receipts"].h, n, mem, pk, nk, kep, p.get("sign_key", SIGN_MATCHED), p["cbor"],
+                      p.get("offsets") or None, p.get("charges") or None, pn, p["out"], p["status"], p["out_key"],
+                      p.get("replayed") or None, cnt)
         if not p.get("raw"):
             self._ck(rc)
-        counts = dict(zip(ADMIT_REPLAY_COUNTS, (int(v) for v in cnt)))
+        counts = dict(zip(names, (int(v) for v in cnt)))
         return (rc, counts) if p.get("raw") else counts
 
     def replay_derive(self, keys, key_index: bytes, nonce_key: bytes, nullifiers: bytes, kprime: bytes, status_in: bytes, stride: int = 32):

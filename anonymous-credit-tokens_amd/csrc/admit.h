@@ -21,6 +21,7 @@ void launch_copy_leaders(const CopyTableArgs& a, hipStream_t s);        // tab_f
 void launch_copy_equal(const CopyEqualArgs& a, hipStream_t s);          // copy_of[j] = leader[j] when every byte is equal, else COPY_NONE
 void launch_copy_mark(const CopyMarkArgs& a, hipStream_t s);            // pre2 = a copy of pre and lead all-ones before
 void launch_copy_resolve(const CopyResolveArgs& a, hipStream_t s);      // behind launch_admit_scatter on the same stream
+void launch_copy_serve(const CopyServeArgs& a, hipStream_t s);          // the replay unique forms: behind BOTH scatters (rows and replay marks)
 #endif
 
 }  // namespace act

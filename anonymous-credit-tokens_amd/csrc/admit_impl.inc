@@ -16,6 +16,8 @@
 // survivor whose input bytes are those of an earlier survivor is not verified and takes its answer from that lane      [k_copies.hip]
 // act_redeem_(cbor_)admit_replay_batch (admit_replay_impl.inc, included behind replay_impl.inc; DESIGN 4.9) add a stage between steps 1
 // and 2 -- a spent lane whose receipt is this proof's own is a retry candidate and survives -- and end in the replay tail, not the ring's
+// act_redeem_(cbor_)admit_replay_unique_batch are both at once (unique && rp): the copy stage runs over fresh lanes and retry candidates
+// alike, and behind the scatters a copy is SERVED -- it takes its leader's refund -- where the unique forms above resolve it  [k_copy_serve]
 namespace {
 
 constexpr size_t ADMIT_WINDOW_BATCHES = 4;       // survivors gathered and verified at a time, in units of max_batch
@@ -184,7 +186,7 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
                              uint8_t* out, uint8_t* status, uint8_t* out_key, uint64_t* out_counts, bool unique = false, AdmitReplay* rp = nullptr) {
   const bool wire = cbor != nullptr, dev = mem == ACT_MEM_DEVICE;
   if (out_counts) memset(out_counts, 0, sizeof(uint64_t) * (unique ? ACT_ADMIT_UNIQUE_COUNTS : ACT_ADMIT_COUNTS));
-  if (rp && rp->out_counts) memset(rp->out_counts, 0, sizeof(uint64_t) * ACT_ADMIT_REPLAY_COUNTS);
+  if (rp && rp->out_counts) memset(rp->out_counts, 0, sizeof(uint64_t) * (unique ? ACT_ADMIT_REPLAY_UNIQUE_COUNTS : ACT_ADMIT_REPLAY_COUNTS));
   if (!c || (mem != ACT_MEM_HOST && mem != ACT_MEM_DEVICE) || n > ((size_t)1 << 30)) return ACT_ERR_ARG;
   if (n && ((!proof && !cbor) || !out || !status || !out_key)) return ACT_ERR_ARG;
   if (wire && offsets) for (size_t i = 0; i < n; i++) if (offsets[i + 1] < offsets[i]) return ACT_ERR_ARG;
@@ -465,18 +467,25 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
 
   if (rp && rc_tail && !began) return rc_tail;      // staging its buffers failed: as a failed verification -- nothing recorded, status untouched
   // ---- step 5: the answers back to their lanes (also behind a failure of step 4: status[] is complete on return) ----------------------------
-  std::vector<uint8_t> h_cst;
+  std::vector<uint8_t> h_cst, h_fin;      // h_fin: the final statuses of a device-memory caller (the replay unique forms' copies_served)
   if (dev) {
     AdmitScatterArgs sc{}; sc.n = (uint32_t)n; sc.out_bytes = out_b; sc.pos = v_pos; sc.pre = v_pre; sc.c_status = cst; sc.c_key = okey; sc.c_out = cout.p;
     sc.status = status; sc.out_key = out_key; sc.out = out;
     launch_admit_scatter(sc, stream);
-    if (cp.copies) { CopyResolveArgs ra{cp.d_lead, (uint32_t)n, status, out_key}; launch_copy_resolve(ra, stream); }      // COPY_MARK leaves status[] here
+    if (cp.copies && !rp) { CopyResolveArgs ra{cp.d_lead, (uint32_t)n, status, out_key}; launch_copy_resolve(ra, stream); }      // COPY_MARK leaves status[] here
     if (rp && rp->out_replayed) {      // the replay marks ride the same scatter as one-byte records (a shed lane: 0)
       AdmitScatterArgs sr = sc; sr.out_bytes = 1; sr.c_out = crepl; sr.out = rp->out_replayed;
       launch_admit_scatter(sr, stream);
     }
+    // the replay unique forms: behind both scatters the rows of leaders are final; a copy takes its leader's whole answer
+    if (cp.copies && rp) { CopyServeArgs va{cp.d_lead, (uint32_t)n, out_b, status, out_key, out, rp->out_replayed}; launch_copy_serve(va, stream); }
     ADCK(c, hipGetLastError());
     if (out_counts) { h_cst.resize(mv); ADCK(c, hipMemcpyAsync(h_cst.data(), cst, mv, hipMemcpyDeviceToHost, stream)); }
+    if (cp.copies && rp && rp->out_counts) {      // copies_served is counted on the final statuses
+      h_lead.resize(n); h_fin.resize(n);
+      ADCK(c, hipMemcpyAsync(h_lead.data(), cp.d_lead, n * 4, hipMemcpyDeviceToHost, stream));
+      ADCK(c, hipMemcpyAsync(h_fin.data(), status, n, hipMemcpyDeviceToHost, stream));
+    }
     ADCK(c, hipStreamSynchronize(stream));
   } else {
     for (size_t i = 0; i < n; i++) {
@@ -485,11 +494,18 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
       else { status[i] = cst[j]; out_key[i] = okey[j]; memcpy(out + i * out_b, cout.p + (size_t)j * out_b, out_b); }
       if (rp && rp->out_replayed) rp->out_replayed[i] = j == ADMIT_SHED ? 0 : crepl[j];
     }
-    if (cp.copies) { CopyResolveArgs ra{h_lead.data(), (uint32_t)n, status, out_key}; for (size_t i = 0; i < n; i++) copy_resolve_lane(ra, (uint32_t)i); }
+    if (cp.copies && !rp) { CopyResolveArgs ra{h_lead.data(), (uint32_t)n, status, out_key}; for (size_t i = 0; i < n; i++) copy_resolve_lane(ra, (uint32_t)i); }
+    if (cp.copies && rp) { CopyServeArgs va{h_lead.data(), (uint32_t)n, out_b, status, out_key, out, rp->out_replayed}; for (size_t i = 0; i < n; i++) copy_serve_lane(va, (uint32_t)i); }
   }
   admit_counts_of(out_counts, n, h_pre.data(), mv, dev ? h_cst.data() : cst);
   if (rp && rp->out_counts && tc[0] == mv) admit_replay_counts_of(rp->out_counts, n, h_pre.data(), rp->candidates, mv, tc);
   if (out_counts && unique) out_counts[ACT_ADMIT_COUNTS] = cp.copies;
+  if (rp && rp->out_counts && unique && cp.copies && tc[0] == mv) {      // copies, then the copies whose leader ended 0
+    const uint8_t* fin = dev ? h_fin.data() : status;
+    uint64_t served = 0;
+    for (size_t i = 0; i < n; i++) served += h_lead[i] != COPY_NONE && fin[i] == 0;
+    rp->out_counts[ACT_ADMIT_REPLAY_COUNTS] = cp.copies; rp->out_counts[ACT_ADMIT_REPLAY_COUNTS + 1] = served;
+  }
   return rc_tail;
 }
 

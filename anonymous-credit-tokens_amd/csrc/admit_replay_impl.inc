@@ -163,11 +163,12 @@ static int admit_replay_stage(act_ctx* c, AdmitReplay& rp, const AdmitReplayStag
 
 static int redeem_admit_replay_impl(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys, int nkeys,
                                     const uint32_t* key_epochs, int sign_key, const uint8_t* proof, const uint8_t* cbor, const uint64_t* offsets, const uint8_t* charge,
-                                    const uint8_t* nonce_key, uint8_t* out, uint8_t* status, uint8_t* out_key, uint8_t* out_replayed, uint64_t* out_counts) {
+                                    const uint8_t* nonce_key, uint8_t* out, uint8_t* status, uint8_t* out_key, uint8_t* out_replayed, uint64_t* out_counts,
+                                    bool unique = false) {
   static const uint8_t derived = 0;      // the nonces stand where the admission calls' rng stands
   AdmitReplay rp{receipts, nonce_key, out_replayed, out_counts};
   return redeem_admit_impl(c, set, n, mem, keys, nkeys, key_epochs, sign_key, proof, cbor, offsets, charge, &derived, ACT_RNG_PER_LANE, out, status, out_key, nullptr,
-                           false, &rp);
+                           unique, &rp);
 }
 
 extern "C" int act_redeem_admit_replay_batch(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys, int nkeys,
@@ -185,4 +186,23 @@ extern "C" int act_redeem_cbor_admit_replay_batch(act_ctx* c, act_nullifier_set*
   static const uint8_t none = 0;
   return redeem_admit_replay_impl(c, set, receipts, n, mem, keys, nkeys, key_epochs, sign_key, nullptr, cbor ? cbor : &none, offsets, charge, nonce_key, out_refund_cbor,
                                   status, out_key, out_replayed, out_counts);
+}
+
+// the unique forms: the copy stage of the admission unique forms (copies_impl.inc) behind this screen, and copies SERVED from their
+// leader's answer (copy_serve_lane; out_counts: ACT_ADMIT_REPLAY_UNIQUE_COUNTS values)
+extern "C" int act_redeem_admit_replay_unique_batch(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys, int nkeys,
+                                                    const uint32_t* key_epochs, int sign_key, const uint8_t* proof, const uint8_t* charge, const uint8_t nonce_key[32],
+                                                    uint8_t* out_refund, uint8_t* status, uint8_t* out_key, uint8_t* out_replayed, uint64_t* out_counts) {
+  if (n && !proof) return ACT_ERR_ARG;
+  return redeem_admit_replay_impl(c, set, receipts, n, mem, keys, nkeys, key_epochs, sign_key, proof, nullptr, nullptr, charge, nonce_key, out_refund, status, out_key,
+                                  out_replayed, out_counts, true);
+}
+extern "C" int act_redeem_cbor_admit_replay_unique_batch(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys,
+                                                         int nkeys, const uint32_t* key_epochs, int sign_key, const uint8_t* cbor, const uint64_t* offsets,
+                                                         const uint8_t* charge, const uint8_t nonce_key[32], uint8_t* out_refund_cbor, uint8_t* status, uint8_t* out_key,
+                                                         uint8_t* out_replayed, uint64_t* out_counts) {
+  if (n && !cbor) return ACT_ERR_ARG;
+  static const uint8_t none = 0;
+  return redeem_admit_replay_impl(c, set, receipts, n, mem, keys, nkeys, key_epochs, sign_key, nullptr, cbor ? cbor : &none, offsets, charge, nonce_key, out_refund_cbor,
+                                  status, out_key, out_replayed, out_counts, true);
 }

@@ -6,7 +6,8 @@
 //   c. compare       copy_of[j] = leader[j] iff every byte is equal: k_copy_equal, or the host workers (4 bytes per lane come down)
 //   d. mark          pre2 = pre with COPY_MARK on the copies, lead[lane] = a copy's leader lane       k_copy_mark
 //   e. compaction    launch_admit_compact over pre2: the lanes that are verified, in lane order
-// The caller goes on with idx2 / pos2 / pre2 in place of the screen's arrays and launches k_copy_resolve behind the scatter.
+// The caller goes on with idx2 / pos2 / pre2 in place of the screen's arrays and launches k_copy_resolve behind the scatter -- or, in
+// the replay unique forms (act_redeem_(cbor_)admit_replay_unique_batch), k_copy_serve behind both scatters: a copy gets its leader's refund.
 // Everything staged here is public (proof bytes never leave the caller's memory; fingerprints and lane numbers are derived from them).
 namespace {
 

@@ -12,6 +12,8 @@
 //                                                      verification and never changes an answer
 //   copy_mark_lane     lane = survivor                 the side array of the second compaction and every copy's leader LANE
 //   copy_resolve_lane  lane = item                     a copy's status and out_key from its leader's final ones
+//   copy_serve_lane    lane = item                     the replay unique forms: a copy's status, out_key, replay mark and output row
+//                                                      from its leader's final ones (copy_serve_piece: one 16-byte piece of the row)
 // Nothing here is secret: proofs, fingerprints and lane numbers are public.
 #pragma once
 #include "admit_lanes.h"
@@ -174,6 +176,35 @@ ACT_HD void copy_resolve_lane(const CopyResolveArgs& a, uint32_t i) {
   const uint32_t l = a.lead[i];
   if (l == COPY_NONE) return;                                 // leaders are never copies: status[l] is final, one pass suffices
   a.status[i] = copy_status(a.status[l]); a.out_key[i] = a.out_key[l];
+}
+
+// ---- a copy's answer under replay semantics (act_redeem_(cbor_)admit_replay_unique_batch) ----------------------------------------------
+// the table of the header: a leader that ends 0 (fresh or replayed) hands its output record on byte for byte and its copy is a replay;
+// every other leader hands its status on and the copy's record stays all-zero.  Rows start at out + i * out_b at ANY byte address (the
+// framed Refund is not a multiple of 4 long and the caller's base is free), so a row moves in byte-aligned pieces: copy_load16's
+// counterpart for stores, and no row pointer is ever cast to a wider type.
+ACT_HD void copy_store16(uint8_t* p, const uint64_t w[2], uint32_t bytes) {
+  const uint32_t t[4] = {(uint32_t)w[0], (uint32_t)(w[0] >> 32), (uint32_t)w[1], (uint32_t)(w[1] >> 32)};
+  if (bytes == 16) __builtin_memcpy(p, t, 16);
+  else for (uint32_t i = 0; i < bytes; i++) p[i] = (uint8_t)(t[i >> 2] >> (8 * (i & 3u)));
+}
+// out_replayed: nullable.  Reads rows of leaders only and writes rows of copies only (a leader is never a copy): any order, no atomics
+struct CopyServeArgs { const uint32_t* lead; uint32_t n; uint64_t out_b; uint8_t* status; uint8_t* out_key; uint8_t* out; uint8_t* out_replayed; };
+// piece q of lane i's row (the device runs one thread per piece; piece 0 also writes the lane's three bytes)
+ACT_HD void copy_serve_piece(const CopyServeArgs& a, uint32_t i, uint32_t q) {
+  if (i >= a.n) return;
+  const uint32_t l = a.lead[i];
+  if (l == COPY_NONE) return;
+  const uint8_t s = a.status[l];                              // (a leader's: final, and no lane of this pass writes it)
+  if (q == 0) { a.status[i] = s; a.out_key[i] = a.out_key[l]; if (a.out_replayed) a.out_replayed[i] = s == 0 ? 1 : 0; }
+  const uint32_t bytes = admit_piece_bytes(a.out_b, q);
+  uint64_t w[2] = {0, 0};
+  if (s == 0) copy_load16(w, a.out + (uint64_t)l * a.out_b + (uint64_t)q * 16, bytes);
+  copy_store16(a.out + (uint64_t)i * a.out_b + (uint64_t)q * 16, w, bytes);
+}
+ACT_HD void copy_serve_lane(const CopyServeArgs& a, uint32_t i) {
+  const uint32_t pieces = admit_pieces(a.out_b);
+  for (uint32_t q = 0; q < pieces; q++) copy_serve_piece(a, i, q);
 }
 
 }  // namespace act

@@ -1,5 +1,6 @@
 // k_copies.hip — the copy stage of admission: byte-identical proofs of one batch are verified once (act_redeem_admit_unique_batch /
-// act_redeem_cbor_admit_unique_batch; lane bodies in copy_lanes.h, which says what they compute; engine side in copies_impl.inc).
+// act_redeem_cbor_admit_unique_batch; lane bodies in copy_lanes.h, which says what they compute; engine side in copies_impl.inc), and
+// the serve pass of act_redeem_(cbor_)admit_replay_unique_batch, where a copy gets its leader's refund.
 // Nothing here is on the verification path.
 #include "copy_lanes.h"
 #include "admit.h"
@@ -44,6 +45,15 @@ __global__ void __launch_bounds__(64 * COPY_WAVES) k_copy_equal(CopyEqualArgs a)
 __global__ void __launch_bounds__(256) k_copy_mark(CopyMarkArgs a) { copy_mark_lane(a, blockIdx.x * 256 + threadIdx.x); }
 __global__ void __launch_bounds__(256) k_copy_resolve(CopyResolveArgs a) { copy_resolve_lane(a, blockIdx.x * 256 + threadIdx.x); }
 
+// The replay unique forms: one thread per 16-byte piece of an item's output row, so the threads of a copy read consecutive pieces of
+// its leader's row and write consecutive pieces of its own.  Rows of leaders are read, rows of copies are written, a leader is never a
+// copy: no thread reads what another writes.  The caller's full-size arrays (a leader may lie in an earlier gather window).
+__global__ void __launch_bounds__(256) k_copy_serve(CopyServeArgs a, uint32_t pieces) {
+  const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  const uint64_t i = p / pieces;
+  if (i < a.n) copy_serve_piece(a, (uint32_t)i, (uint32_t)(p % pieces));
+}
+
 static unsigned copy_grid(uint64_t lanes, uint32_t per_block) { return (unsigned)((lanes + per_block - 1) / per_block); }
 
 void launch_copy_fp(const CopyFpArgs& a, hipStream_t s) { if (a.m) hipLaunchKernelGGL(k_copy_fp, dim3(copy_grid(a.m, COPY_WAVES)), dim3(64 * COPY_WAVES), 0, s, a); }
@@ -55,5 +65,9 @@ void launch_copy_leaders(const CopyTableArgs& a, hipStream_t s) {
 void launch_copy_equal(const CopyEqualArgs& a, hipStream_t s) { if (a.m) hipLaunchKernelGGL(k_copy_equal, dim3(copy_grid(a.m, COPY_WAVES)), dim3(64 * COPY_WAVES), 0, s, a); }
 void launch_copy_mark(const CopyMarkArgs& a, hipStream_t s) { if (a.m) hipLaunchKernelGGL(k_copy_mark, dim3(copy_grid(a.m, 256)), dim3(256), 0, s, a); }
 void launch_copy_resolve(const CopyResolveArgs& a, hipStream_t s) { if (a.n) hipLaunchKernelGGL(k_copy_resolve, dim3(copy_grid(a.n, 256)), dim3(256), 0, s, a); }
+void launch_copy_serve(const CopyServeArgs& a, hipStream_t s) {
+  const uint32_t pieces = admit_pieces(a.out_b);
+  if (a.n && pieces) hipLaunchKernelGGL(k_copy_serve, dim3(copy_grid((uint64_t)a.n * pieces, 256)), dim3(256), 0, s, a, pieces);
+}
 
 }  // namespace act

@@ -880,6 +880,49 @@ int act_redeem_cbor_admit_replay_batch(act_ctx *ctx, act_nullifier_set *set, act
                                        const uint8_t *charge /* nullable */, const uint8_t nonce_key[32], uint8_t *out_refund_cbor, uint8_t *status,
                                        uint8_t *out_key, uint8_t *out_replayed /* nullable */, uint64_t *out_counts /* nullable, host */);
 
+/* ======== admission for the replayable redemption, unique forms: copies in one batch are verified and signed once ========
+ * A client whose response was lost resends the same SpendProof, and resends it several times while the server is slow -- which is when
+ * batches are largest.  Byte-identical copies of one proof inside one batch are the normal load behind the two calls above, and they
+ * answer them the expensive way: every copy passes the screen (fresh, or a retry candidate), is verified in full and is signed again
+ * with the derived nonces, for the same bytes n times.  The admission unique forms cannot stand in: they answer the copy of an accepted
+ * leader ACT_STATUS_DOUBLE_SPEND.  These two calls run the admit-replay loop above with one more step between step 3 and step 4, which
+ * is step 3a of the admission unique forms unchanged:
+ *       3c. lane i has passed steps 1-3, as a fresh lane or as a retry candidate, and an earlier lane j < i that has also passed them
+ *           has the same input bytes -> lane i is a COPY and is not verified.  Its leader is the smallest such j; a leader is never
+ *           itself a copy.  Records form: the whole act_spend_proof_bytes record.  Wire form: the bytes [offsets[i], offsets[i + 1]),
+ *           the same length and the same content -- two different spellings of one proof, or one message with and without a trailing
+ *           byte, are NOT copies of each other (both are verified, as above).
+ * After the call's single replay tail a copy is answered from its leader's FINAL answer:
+ *       leader 0, fresh or replayed                                   -> status 0, out_replayed[i] = 1, out_key[i] = out_key[j] and the
+ *                                                                        leader's output record byte for byte (128 bytes; wire form:
+ *                                                                        the framed Refund message)
+ *       leader 255 / 6 / 7, ACT_STATUS_DOUBLE_SPEND,
+ *       ACT_STATUS_NULLIFIER_UNDETERMINED, ACT_STATUS_RECORDED_UNSIGNED -> the same status, out_key[i] = out_key[j], an all-zero record,
+ *                                                                        out_replayed[i] = 0
+ * What stays the same: every status, every out_key, every output byte, every out_replayed byte and the keys and epochs both sets hold
+ * afterwards are byte for byte those of act_redeem_(cbor_)admit_replay_batch on the same batch and identical sets.  Why: there a later
+ * copy of a fresh leader finds k spent by an earlier lane of the batch and its own tag in `receipts`, so it is a replay; nonce_i depends
+ * only on nonce_key, the signing key, k and enc(K'), so it is signed into the same refund.  A copy of a rejected lane has the same
+ * verdict by definition; a copy of a lane that lost k to another proof has the same tag and loses too.  (Not promised where lanes end
+ * ACT_STATUS_NULLIFIER_UNDETERMINED: a set too small for the batch.)
+ * What differs: only out_counts.  ACT_ADMIT_REPLAY_UNIQUE_COUNTS values: the eleven above, then copies, then copies_served (the copies
+ * whose leader ended 0).  verified = lanes - wire_rejected - wrong_charge - foreign_spend - copies; rejected_by_verification, fresh,
+ * replayed, double_spend_after and unanswered count VERIFIED lanes only.
+ * Equality is decided on the bytes themselves, as in the admission unique forms.  Whole-call refusals, locks, failure semantics (a copy
+ * of an ACT_STATUS_RECORDED_UNSIGNED leader says the same and is repaired by the same retry) and the hygiene contract are those of the
+ * two calls above; nothing staged by the new step is secret (refunds are output).  Output rows may start at any byte address.  A batch
+ * without copies in which nothing is shed still goes straight to the replay implementation with the caller's pointers; a batch in
+ * which nothing survives still launches no verification kernel. */
+#define ACT_ADMIT_REPLAY_UNIQUE_COUNTS 13
+int act_redeem_admit_replay_unique_batch(act_ctx *ctx, act_nullifier_set *set, act_nullifier_set *receipts, size_t n, int mem, const uint8_t *keys, int nkeys,
+                                         const uint32_t *key_epochs /* nullable */, int sign_key, const uint8_t *proof, const uint8_t *charge /* nullable */,
+                                         const uint8_t nonce_key[32], uint8_t *out_refund, uint8_t *status, uint8_t *out_key,
+                                         uint8_t *out_replayed /* nullable */, uint64_t *out_counts /* nullable, host */);
+int act_redeem_cbor_admit_replay_unique_batch(act_ctx *ctx, act_nullifier_set *set, act_nullifier_set *receipts, size_t n, int mem, const uint8_t *keys, int nkeys,
+                                              const uint32_t *key_epochs /* nullable */, int sign_key, const uint8_t *cbor, const uint64_t *offsets,
+                                              const uint8_t *charge /* nullable */, const uint8_t nonce_key[32], uint8_t *out_refund_cbor, uint8_t *status,
+                                              uint8_t *out_key, uint8_t *out_replayed /* nullable */, uint64_t *out_counts /* nullable, host */);
+
 /* ======== row d and test infrastructure: debug hooks, measurement knobs, kernel timing, roofline probes (nothing here is on the product's path) ==== */
 /* Debug / test hook: the exact "spend" transcript pre-images of the last act_verify_spend_batch /
  * act_refund_batch chunk (n_last * act_spend_transcript_bytes, copied to host memory). */

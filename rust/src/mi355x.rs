@@ -154,6 +154,13 @@ extern "C" {
                                           nkeys: c_int, key_epochs: *const u32, sign_key: c_int, cbor: *const u8, offsets: *const u64, charge: *const u8,
                                           nonce_key: *const u8, out_refund_cbor: *mut u8, status: *mut u8, out_key: *mut u8, out_replayed: *mut u8,
                                           out_counts: *mut u64) -> c_int;
+    fn act_redeem_admit_replay_unique_batch(ctx: *mut ActCtx, set: *mut ActNullifierSet, receipts: *mut ActNullifierSet, n: usize, mem: c_int, keys: *const u8,
+                                            nkeys: c_int, key_epochs: *const u32, sign_key: c_int, proof: *const u8, charge: *const u8, nonce_key: *const u8,
+                                            out_refund: *mut u8, status: *mut u8, out_key: *mut u8, out_replayed: *mut u8, out_counts: *mut u64) -> c_int;
+    fn act_redeem_cbor_admit_replay_unique_batch(ctx: *mut ActCtx, set: *mut ActNullifierSet, receipts: *mut ActNullifierSet, n: usize, mem: c_int, keys: *const u8,
+                                                 nkeys: c_int, key_epochs: *const u32, sign_key: c_int, cbor: *const u8, offsets: *const u64, charge: *const u8,
+                                                 nonce_key: *const u8, out_refund_cbor: *mut u8, status: *mut u8, out_key: *mut u8, out_replayed: *mut u8,
+                                                 out_counts: *mut u64) -> c_int;
     fn act_node_device_stats(node: *mut ActNode, k: c_int, weight: *mut f64, last_lanes: *mut u64, last_seconds: *mut f64, last_calls: *mut u64) -> c_int;
 }
 
@@ -1218,6 +1225,8 @@ pub const ACT_REPLAY_COUNTS: usize = 6;
 /// lanes / wire_rejected / wrong_charge / foreign_spend / retry_candidates / verified / rejected_by_verification / fresh / replayed /
 /// double_spend_after / unanswered (`GpuReplay::admit(true)`)
 pub const ACT_ADMIT_REPLAY_COUNTS: usize = 11;
+/// the eleven above, then copies / copies_served (`GpuReplay::unique(true)`)
+pub const ACT_ADMIT_REPLAY_UNIQUE_COUNTS: usize = 13;
 /// statuses, outputs (128-byte Refund records or `REFUND_CBOR_BYTES` messages, all zero where not signed), matched ring keys, the
 /// replay marks, and lanes / rejected_by_verification / fresh / replayed / double_spend / unanswered
 pub struct Replayed {
@@ -1230,8 +1239,15 @@ pub struct Replayed {
     /// all zero unless the call went through the admission screen (`GpuReplay::admit(true)`); then `counts` is its tail's view:
     /// lanes, rejected_by_verification, fresh, replayed, double_spend_after, unanswered
     pub admit_counts: [u64; ACT_ADMIT_REPLAY_COUNTS],
+    /// all zero unless the call ran the unique form (`GpuReplay::unique(true)`): copies (lanes with the bytes of an earlier lane, not
+    /// verified) and copies_served (those whose leader ended 0); `admit_counts` then counts verified lanes only
+    pub copy_counts: [u64; 2],
 }
 impl Replayed {
+    fn take_unique_counts(&mut self, u: &[u64; ACT_ADMIT_REPLAY_UNIQUE_COUNTS]) {
+        self.admit_counts.copy_from_slice(&u[..ACT_ADMIT_REPLAY_COUNTS]);
+        self.copy_counts = [u[ACT_ADMIT_REPLAY_COUNTS], u[ACT_ADMIT_REPLAY_COUNTS + 1]];
+    }
     fn take_admit_counts(&mut self) {
         let a = self.admit_counts;
         self.counts = [a[0], a[6], a[7], a[8], a[9], a[10]];
@@ -1248,17 +1264,22 @@ pub struct GpuReplay {
     receipts: *mut ActNullifierSet,
     nonce_key: [u8; 32],
     admit: bool,
+    unique: bool,
     charges: Option<Vec<u8>>,
 }
 impl GpuReplay {
     /// # Safety
     /// `ctx`, `set` and `receipts` are live handles on one device, `set != receipts`, and all three outlive `self`.
     pub unsafe fn from_raw(ctx: *mut ActCtx, set: *mut ActNullifierSet, receipts: *mut ActNullifierSet, nonce_key: [u8; 32]) -> Self {
-        GpuReplay { ctx, set, receipts, nonce_key, admit: false, charges: None }
+        GpuReplay { ctx, set, receipts, nonce_key, admit: false, unique: false, charges: None }
     }
     /// `true`: the calls go through the admission screen (include/act_mi355x.h "admission for the replayable redemption") -- a spent
     /// nullifier whose receipt is not this proof's is `DoubleSpendError` without being verified; a retry is verified and served.
     pub fn admit(mut self, on: bool) -> Self { self.admit = on; self }
+    /// `true` (with `admit(true)`; nothing without it): the unique forms (include/act_mi355x.h "admission for the replayable redemption,
+    /// unique forms") -- a lane with the bytes of an earlier lane of the batch is not verified and gets that lane's answer, its `Refund`
+    /// included.  Statuses, outputs and both sets end as without it; `Replayed::copy_counts` says how many lanes were spared.
+    pub fn unique(mut self, on: bool) -> Self { self.unique = on; self }
     /// What each request of the next calls costs: n scalars of 32 bytes, compared with `SpendProof.s` by the screen (implies nothing
     /// without `admit(true)`); `None`: no comparison.
     pub fn charges(mut self, charges: Option<Vec<u8>>) -> Self { self.charges = charges; self }
@@ -1270,8 +1291,13 @@ impl GpuReplay {
         let (n, nkeys) = (proofs.len() / PROOF_BYTES, keys.len() / 64);
         assert!(proofs.len() == n * PROOF_BYTES && key_epochs.map_or(true, |e| e.len() == nkeys));
         let mut r = Replayed { rc: 0, status: vec![0u8; n + 1], out: vec![0u8; 128 * n + 1], out_key: vec![ACT_KEY_NONE; n + 1], replayed: vec![0u8; n + 1], counts: [0; ACT_REPLAY_COUNTS],
-                               admit_counts: [0; ACT_ADMIT_REPLAY_COUNTS] };
-        r.rc = if self.admit { unsafe {
+                               admit_counts: [0; ACT_ADMIT_REPLAY_COUNTS], copy_counts: [0; 2] };
+        let mut u = [0u64; ACT_ADMIT_REPLAY_UNIQUE_COUNTS];
+        r.rc = if self.admit && self.unique { unsafe {
+            act_redeem_admit_replay_unique_batch(self.ctx, self.set, self.receipts, n, 0, keys.as_ptr(), nkeys as c_int, key_epochs.map_or(std::ptr::null(), |e| e.as_ptr()),
+                                                 sign_with.map_or(ACT_SIGN_MATCHED, |i| i as c_int), proofs.as_ptr(), self.charge_ptr(n), self.nonce_key.as_ptr(),
+                                                 r.out.as_mut_ptr(), r.status.as_mut_ptr(), r.out_key.as_mut_ptr(), r.replayed.as_mut_ptr(), u.as_mut_ptr())
+        } } else if self.admit { unsafe {
             act_redeem_admit_replay_batch(self.ctx, self.set, self.receipts, n, 0, keys.as_ptr(), nkeys as c_int, key_epochs.map_or(std::ptr::null(), |e| e.as_ptr()),
                                           sign_with.map_or(ACT_SIGN_MATCHED, |i| i as c_int), proofs.as_ptr(), self.charge_ptr(n), self.nonce_key.as_ptr(),
                                           r.out.as_mut_ptr(), r.status.as_mut_ptr(), r.out_key.as_mut_ptr(), r.replayed.as_mut_ptr(), r.admit_counts.as_mut_ptr())
@@ -1280,6 +1306,7 @@ impl GpuReplay {
                                     sign_with.map_or(ACT_SIGN_MATCHED, |i| i as c_int), proofs.as_ptr(), self.nonce_key.as_ptr(), r.out.as_mut_ptr(),
                                     r.status.as_mut_ptr(), r.out_key.as_mut_ptr(), r.replayed.as_mut_ptr(), r.counts.as_mut_ptr())
         } };
+        if self.admit && self.unique { r.take_unique_counts(&u); }
         if self.admit { r.take_admit_counts(); }
         r.status.truncate(n); r.out.truncate(128 * n); r.out_key.truncate(n); r.replayed.truncate(n);
         r
@@ -1290,8 +1317,14 @@ impl GpuReplay {
         let (n, nkeys) = (msgs.len(), keys.len() / 64);
         assert!(key_epochs.map_or(true, |e| e.len() == nkeys));
         let mut r = Replayed { rc: 0, status: vec![0u8; n + 1], out: vec![0u8; REFUND_CBOR_BYTES * n + 1], out_key: vec![ACT_KEY_NONE; n + 1], replayed: vec![0u8; n + 1],
-                               counts: [0; ACT_REPLAY_COUNTS], admit_counts: [0; ACT_ADMIT_REPLAY_COUNTS] };
-        r.rc = if self.admit { unsafe {
+                               counts: [0; ACT_REPLAY_COUNTS], admit_counts: [0; ACT_ADMIT_REPLAY_COUNTS], copy_counts: [0; 2] };
+        let mut u = [0u64; ACT_ADMIT_REPLAY_UNIQUE_COUNTS];
+        r.rc = if self.admit && self.unique { unsafe {
+            act_redeem_cbor_admit_replay_unique_batch(self.ctx, self.set, self.receipts, n, 0, keys.as_ptr(), nkeys as c_int, key_epochs.map_or(std::ptr::null(), |e| e.as_ptr()),
+                                                      sign_with.map_or(ACT_SIGN_MATCHED, |i| i as c_int), blob.as_ptr(), offsets.as_ptr(), self.charge_ptr(n),
+                                                      self.nonce_key.as_ptr(), r.out.as_mut_ptr(), r.status.as_mut_ptr(), r.out_key.as_mut_ptr(), r.replayed.as_mut_ptr(),
+                                                      u.as_mut_ptr())
+        } } else if self.admit { unsafe {
             act_redeem_cbor_admit_replay_batch(self.ctx, self.set, self.receipts, n, 0, keys.as_ptr(), nkeys as c_int, key_epochs.map_or(std::ptr::null(), |e| e.as_ptr()),
                                                sign_with.map_or(ACT_SIGN_MATCHED, |i| i as c_int), blob.as_ptr(), offsets.as_ptr(), self.charge_ptr(n),
                                                self.nonce_key.as_ptr(), r.out.as_mut_ptr(), r.status.as_mut_ptr(), r.out_key.as_mut_ptr(), r.replayed.as_mut_ptr(),
@@ -1301,6 +1334,7 @@ impl GpuReplay {
                                          sign_with.map_or(ACT_SIGN_MATCHED, |i| i as c_int), blob.as_ptr(), offsets.as_ptr(), self.nonce_key.as_ptr(),
                                          r.out.as_mut_ptr(), r.status.as_mut_ptr(), r.out_key.as_mut_ptr(), r.replayed.as_mut_ptr(), r.counts.as_mut_ptr())
         } };
+        if self.admit && self.unique { r.take_unique_counts(&u); }
         if self.admit { r.take_admit_counts(); }
         r.status.truncate(n); r.out.truncate(REFUND_CBOR_BYTES * n); r.out_key.truncate(n); r.replayed.truncate(n);
         r
