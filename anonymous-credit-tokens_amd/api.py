@@ -29,7 +29,7 @@ class Error(Exception):
     NAMES = {1: "InvalidIssuanceRequestProof", 2: "InvalidIssuanceResponseProof", 3: "DoubleSpendError",
              4: "InvalidRefundProof", 5: "InvalidRefundResponseProof", 6: "IdentityPointError",
              7: "InvalidClientSpendProof", 8: "AmountTooBigError", 9: "ScalarOutOfRangeError", 255: "UndecodablePoint",
-             250: "WrongCharge"}      # 250: the admission calls only (not a variant of the crate's enum)
+             250: "WrongCharge", 249: "ReturnTooBig"}      # 250: the admission calls only; 249: the return calls only (not variants of the crate's enum)
 
     def __init__(self, code: int):
         super().__init__(self.NAMES.get(code, f"status {code}"))
@@ -276,6 +276,33 @@ class PrivateKey(_Cbor):
         res, _ = Keyring([self]).redeem_admit_cbor_batch(params, db, msgs, rng, nbits, charges=charges, unique=unique)
         return res
 
+    # ---- partial refunds: the issuer returns t <= s unused credits with the Refund --------------------------
+    def refund_return(self, params: Params, spend_proof: "SpendProof", t, rng) -> "RefundReturn":
+        """refund, returning t of the s credits the proof spends: the client's next token holds c - s + t.  Error 249 (ReturnTooBig)
+        when t > s -- checked HERE, against the proof's own s, because the sign-only call underneath does not see s; like every
+        rejection it leaves the generator untouched."""
+        e = params.engine(spend_proof.nbits)
+        tt = scalar(t)
+
+        def check():
+            st, kp = e.verify_spend(self.record, spend_proof.record, True)
+            if st[0] == 0 and int.from_bytes(tt, "little") > int.from_bytes(scalar(int.from_bytes(spend_proof.charge(), "little")), "little"):
+                st = bytes([capi.STATUS_RETURN_TOO_BIG])
+            return st, kp
+        st, out = _check_then_sign(rng, check, lambda kp, st, rb: e.refund_sign_return_keyring([self.record], bytes(1), kp, st, rb, tt, capi.RNG_SEQUENTIAL))
+        if st[0]:
+            raise Error(st[0])
+        return RefundReturn(out)
+
+    def redeem_return_batch(self, params: Params, db: "NullifierDb", proofs: Sequence["SpendProof"], rng, returned: Sequence = None, charges: Sequence = None) -> List["RefundReturn"]:
+        """redeem_admit_batch with the amounts the issuer returns (Keyring.redeem_return_batch): entry i is a RefundReturn or an Error"""
+        res, _ = Keyring([self]).redeem_return_batch(params, db, proofs, rng, returned=returned, charges=charges)
+        return res
+
+    def redeem_return_cbor_batch(self, params: Params, db: "NullifierDb", msgs: Sequence[bytes], rng, nbits: int = L, returned: Sequence = None, charges: Sequence = None) -> list:
+        res, _ = Keyring([self]).redeem_return_cbor_batch(params, db, msgs, rng, nbits, returned=returned, charges=charges)
+        return res
+
     # ---- replayable redemption: a retried SpendProof gets its Refund again (INTEGRATION.md section 10) ----------------------------------
     def redeem_replay_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", proofs: Sequence["SpendProof"], nonce_key: bytes,
                             admit: bool = False, charges: Sequence = None, unique: bool = False) -> Tuple[list, list]:
@@ -381,6 +408,31 @@ class Keyring:
         cc = b"".join(scalar(c) for c in charges) if charges is not None else None
         st, out, ok, self.last_admit_counts = _draw_signed(rng, len(msgs), lambda src, mode: e.redeem_cbor_admit(
             db.set, self._records(), list(msgs), src, mode, self._sign_key(sign_with), charges=cc, key_epochs=self.epochs, unique=unique))
+        return [out[i] if st[i] == 0 else _wire_error(st[i]) for i in range(len(msgs))], self._indices(st, ok)
+
+    def redeem_return_batch(self, params: Params, db: "NullifierDb", proofs: Sequence["SpendProof"], rng, returned: Sequence = None, charges: Sequence = None,
+                            sign_with=None) -> Tuple[list, list]:
+        """The reserve-then-return server step (act_redeem_return_batch): redeem_admit_batch, and every accepted proof is refunded
+        with returned[i] of the s_i credits it spends -- entry i is a RefundReturn whose client ends with c - s_i + returned[i].
+        returned[i] > s_i is Error 249: not looked up, not verified, not recorded, not signed.  `self.last_admit_counts`: the call's
+        counts (capi.REDEEM_RETURN_COUNTS).  There is no replay form of this call on purpose (include/act_mi355x.h)."""
+        nbits = proofs[0].nbits if proofs else L
+        e = params.engine(nbits)
+        pb = b"".join(p.record for p in proofs)
+        cc = b"".join(scalar(c) for c in charges) if charges is not None else None
+        tt = b"".join(scalar(t) for t in returned) if returned is not None else None
+        st, out, ok, self.last_admit_counts = _draw_signed(rng, len(proofs), lambda src, mode: e.redeem_return(
+            db.set, self._records(), pb, src, mode, self._sign_key(sign_with), charges=cc, returned=tt, key_epochs=self.epochs))
+        return [RefundReturn(out[160 * i:160 * i + 160]) if st[i] == 0 else Error(st[i]) for i in range(len(proofs))], self._indices(st, ok)
+
+    def redeem_return_cbor_batch(self, params: Params, db: "NullifierDb", msgs: Sequence[bytes], rng, nbits: int = L, returned: Sequence = None,
+                                 charges: Sequence = None, sign_with=None) -> Tuple[list, list]:
+        """the same on wire bytes (act_redeem_cbor_return_batch): entry i is a CBOR RefundReturn message, a CborError or an Error"""
+        e = params.engine(nbits)
+        cc = b"".join(scalar(c) for c in charges) if charges is not None else None
+        tt = b"".join(scalar(t) for t in returned) if returned is not None else None
+        st, out, ok, self.last_admit_counts = _draw_signed(rng, len(msgs), lambda src, mode: e.redeem_cbor_return(
+            db.set, self._records(), list(msgs), src, mode, self._sign_key(sign_with), charges=cc, returned=tt, key_epochs=self.epochs))
         return [out[i] if st[i] == 0 else _wire_error(st[i]) for i in range(len(msgs))], self._indices(st, ok)
 
     def redeem_replay_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", proofs: Sequence["SpendProof"], nonce_key: bytes, sign_with=None,
@@ -526,6 +578,14 @@ class PreRefund(_Cbor):
             raise Error(st[0])
         return CreditToken(out)
 
+    def to_credit_token_return(self, params: Params, spend_proof: SpendProof, refund_return: "RefundReturn", public_key: PublicKey) -> CreditToken:
+        """to_credit_token over a RefundReturn: the proof is checked over X_A = g + K' + t h1 and the token holds m + t.  Error 4 when
+        the proof fails (also when t was altered on the way), Error 8 (AmountTooBigError) for a validly signed t > s."""
+        st, out = params.engine(spend_proof.nbits).refund_to_credit_token_return(self.record, spend_proof.record, refund_return.record, public_key.w)
+        if st[0]:
+            raise Error(st[0])
+        return CreditToken(out)
+
     def to_credit_token_ring(self, params: Params, spend_proof: SpendProof, refund: "Refund", publics: Sequence[PublicKey]) -> Tuple[CreditToken, int]:
         """to_credit_token against the issuer's published keys: a Refund names no key, and Keyring.refund_batch(sign_with=i) moves a
         client onto key i without telling it.  -> (token, index of the first ring key the refund verifies under)."""
@@ -541,6 +601,21 @@ class Refund(_Cbor):
     def __init__(self, record: bytes):
         assert len(record) == 128
         self.record = bytes(record)   # A* | e | gamma | z
+
+    def __eq__(self, other):
+        return self.record == other.record
+
+
+class RefundReturn(_Cbor):
+    """A Refund that returns t of the spent credits (include/act_mi355x.h, "partial refunds"): signed over X_A = g + K' + t h1."""
+    CBOR_TYPE = "RefundReturn"
+
+    def __init__(self, record: bytes):
+        assert len(record) == 160
+        self.record = bytes(record)   # A* | e | gamma | z | t
+
+    def returned(self) -> bytes:
+        return self.record[128:160]
 
     def __eq__(self, other):
         return self.record == other.record

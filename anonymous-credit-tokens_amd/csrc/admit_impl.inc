@@ -129,19 +129,20 @@ struct AdmitGather {
   }
 };
 
-void admit_counts_of(uint64_t* out_counts, size_t n, const uint8_t* pre, size_t m, const uint8_t* cst) {
+// ret (the return calls): a ninth value, the lanes whose returned amount exceeded their charge (ACT_REDEEM_RETURN_COUNTS)
+void admit_counts_of(uint64_t* out_counts, size_t n, const uint8_t* pre, size_t m, const uint8_t* cst, bool ret = false) {
   if (!out_counts) return;
-  uint64_t k[ACT_ADMIT_COUNTS] = {n, 0, 0, 0, m, 0, 0, 0};
+  uint64_t k[ACT_REDEEM_RETURN_COUNTS] = {n, 0, 0, 0, m, 0, 0, 0, 0};
   for (size_t i = 0; i < n; i++) {
     const uint8_t p = pre[i];
-    if (p == ACT_STATUS_WRONG_CHARGE) k[2]++; else if (p == ACT_STATUS_DOUBLE_SPEND) k[3]++; else if (p) k[1]++;
+    if (p == ACT_STATUS_WRONG_CHARGE) k[2]++; else if (p == ACT_STATUS_DOUBLE_SPEND) k[3]++; else if (ret && p == ACT_STATUS_RETURN_TOO_BIG) k[8]++; else if (p) k[1]++;
   }
   for (size_t j = 0; j < m; j++) {
     const uint8_t s = cst[j];
     if (s == 0) k[7]++; else if (s == ACT_STATUS_DOUBLE_SPEND) k[6]++;
     else if (s != ACT_STATUS_NULLIFIER_UNDETERMINED && s != ACT_STATUS_RECORDED_UNSIGNED) k[5]++;
   }
-  memcpy(out_counts, k, sizeof(k));
+  memcpy(out_counts, k, sizeof(uint64_t) * (ret ? ACT_REDEEM_RETURN_COUNTS : ACT_ADMIT_COUNTS));
 }
 
 // the copy stage of the unique forms (copies_impl.inc): what it leaves for the rest of the call.  copies == 0: nothing below is used
@@ -183,9 +184,10 @@ static int redeem_replay_locked(act_ctx* c, act_nullifier_set* set, act_nullifie
 // form's own counts are rp->out_counts
 static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int mem, const uint8_t* keys, int nkeys, const uint32_t* key_epochs, int sign_key,
                              const uint8_t* proof, const uint8_t* cbor, const uint64_t* offsets, const uint8_t* charge, const uint8_t* rng, int rng_mode,
-                             uint8_t* out, uint8_t* status, uint8_t* out_key, uint64_t* out_counts, bool unique = false, AdmitReplay* rp = nullptr) {
+                             uint8_t* out, uint8_t* status, uint8_t* out_key, uint64_t* out_counts, bool unique = false, AdmitReplay* rp = nullptr,
+                             const RedeemReturn* ret = nullptr) {      // ret (the return calls, DESIGN 4.10): never with unique or rp
   const bool wire = cbor != nullptr, dev = mem == ACT_MEM_DEVICE;
-  if (out_counts) memset(out_counts, 0, sizeof(uint64_t) * (unique ? ACT_ADMIT_UNIQUE_COUNTS : ACT_ADMIT_COUNTS));
+  if (out_counts) memset(out_counts, 0, sizeof(uint64_t) * (ret ? ACT_REDEEM_RETURN_COUNTS : unique ? ACT_ADMIT_UNIQUE_COUNTS : ACT_ADMIT_COUNTS));
   if (rp && rp->out_counts) memset(rp->out_counts, 0, sizeof(uint64_t) * (unique ? ACT_ADMIT_REPLAY_UNIQUE_COUNTS : ACT_ADMIT_REPLAY_COUNTS));
   if (!c || (mem != ACT_MEM_HOST && mem != ACT_MEM_DEVICE) || n > ((size_t)1 << 30)) return ACT_ERR_ARG;
   if (n && ((!proof && !cbor) || !out || !status || !out_key)) return ACT_ERR_ARG;
@@ -196,12 +198,13 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
   int rc = redeem_keyring_refused(c, set, 0, keys, nkeys, key_epochs, sign_key, nullptr, nullptr, rng, rng_mode, nullptr, nullptr, nullptr);
   if (rc) return rc;
   if (rp && (rc = replay_refused(c, set, rp->receipts, rp->nonce_key, n, key_epochs, nkeys))) return rc;
+  if (ret && (unique || rp)) return ACT_ERR_ARG;
   if (n == 0) return redeem_keyring_impl(c, set, 0, mem, keys, nkeys, key_epochs, sign_key, nullptr, nullptr, nullptr, rng, rng_mode, nullptr, nullptr, nullptr);
   // one admission call at a time per context: the gathered rng slices live in the context's own buffer (d_admit_rng)
   std::lock_guard<std::mutex> admission(c->admit_mu);
   std::unique_lock<std::mutex> replay;      // the replay form: the staged secrets and the derived nonces of its tail (d_replay)
   if (rp) replay = std::unique_lock<std::mutex>(c->replay_mu);
-  const size_t pb = act_spend_proof_bytes(c), out_b = wire ? act_cbor_size(c, ACT_CBOR_REFUND) : 128;
+  const size_t pb = act_spend_proof_bytes(c), out_b = redeem_out_bytes(c, wire, ret);
   const CborType* T = cbor_type(ACT_CBOR_SPEND_PROOF);
   CborLayout lay; if (wire) lay = cbor_layout(*T, c->L);
   const size_t ml = lay.tmpl.size(), nf = lay.pay_off.size();
@@ -215,6 +218,8 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
   const size_t o_pre = take(n), o_kred = take(n * 32), o_idx = take(n * 4), o_pos = take(n * 4), o_blk = take(nb * 4), o_total = take(4);
   const bool own_ks = wire || !dev;
   const size_t o_ks = own_ks ? take(n * 64) : 0, o_charge = (charge && !dev) ? take(n * 32) : 0;
+  const uint8_t* const t_in = ret ? ret->t : nullptr;      // the returned amounts, n scalars in the caller's kind of memory (null: all zero)
+  const size_t o_ret = (t_in && !dev) ? take(n * 32) : 0;
   const size_t o_code = wire ? take(n) : 0, o_flags = (wire && dev) ? take(fcap) : 0, o_off = (wire && dev && offsets) ? take((n + 1) * 8) : 0;
   const size_t o_tmpl = (wire && dev) ? take(ml) : 0, o_pay = (wire && dev) ? take(nf * 4) : 0;
   const size_t o_pwhich = wire ? take(WIRE_SETTLE_WINDOW * 4) : 0, o_patch = wire ? take(WIRE_SETTLE_WINDOW * 64) : 0;
@@ -329,6 +334,10 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
     if (dev) sa.charge = charge;
     else { ADCK(c, hipMemcpyAsync(d.p + o_charge, charge, n * 32, hipMemcpyHostToDevice, stream)); sa.charge = d.p + o_charge; }
   }
+  if (t_in) {      // t <= s is the screen's rule, in the pass that compares the charge
+    if (dev) sa.returned = t_in;
+    else { ADCK(c, hipMemcpyAsync(d.p + o_ret, t_in, n * 32, hipMemcpyHostToDevice, stream)); sa.returned = d.p + o_ret; }
+  }
 
   // ---- steps 1 and 2: the screen (the set's lock is held while its table is read) and the compaction ----------------------------------
   uint32_t m32 = 0;
@@ -384,12 +393,12 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
     return rc;
   }
   if (mv == n) {
-    rc = redeem_keyring_impl(c, set, n, mem, keys, nkeys, key_epochs, sign_key, proof, cbor, offsets, rng, rng_mode, out, status, out_key);
+    rc = redeem_keyring_impl(c, set, n, mem, keys, nkeys, key_epochs, sign_key, proof, cbor, offsets, rng, rng_mode, out, status, out_key, ret);
     if (out_counts && (rc == ACT_OK || rc == ACT_ERR_ARG)) {      // (ACT_ERR_ARG: the nullifier step refused lanes; status[] is complete)
       std::vector<uint8_t> hs;
       const uint8_t* s = status;
       if (dev) { hs.resize(n); if (hipMemcpy(hs.data(), status, n, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return rc; } s = hs.data(); }
-      admit_counts_of(out_counts, n, h_pre.data(), n, s);      // (copies: 0)
+      admit_counts_of(out_counts, n, h_pre.data(), n, s, ret != nullptr);      // (copies: 0)
     }
     return rc;
   }
@@ -403,7 +412,7 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
       if (rp && rp->out_replayed) ADCK(c, hipMemsetAsync(rp->out_replayed, 0, n, stream));
       ADCK(c, hipStreamSynchronize(stream));
     } else { memcpy(status, h_pre.data(), n); memset(out_key, ACT_KEY_NONE, n); memset(out, 0, n * out_b); if (rp && rp->out_replayed) memset(rp->out_replayed, 0, n); }
-    admit_counts_of(out_counts, n, h_pre.data(), 0, nullptr);
+    admit_counts_of(out_counts, n, h_pre.data(), 0, nullptr, ret != nullptr);
     if (rp && rp->out_counts) admit_replay_counts_of(rp->out_counts, n, h_pre.data(), 0, 0, nullptr);
     return ACT_OK;
   }
@@ -415,7 +424,7 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
   if (!dev) { h_pos.resize(n); ADCK(c, hipMemcpy(h_pos.data(), v_pos, n * 4, hipMemcpyDeviceToHost)); }
   // compact arrays in the caller's kind of memory: K' | nullifiers | verdicts | look-up answers | key indices | matched keys | statuses
   AdmitArr arr(c), cout(c);
-  if ((rc = arr.alloc(mem, mv * (rp ? 70 : 69)))) { c->err = "admission: compact arrays"; return rc; }
+  if ((rc = arr.alloc(mem, mv * (rp ? 70 : 69) + (t_in ? mv * 32 + 32 : 0)))) { c->err = "admission: compact arrays"; return rc; }
   if ((rc = cout.alloc(mem, mv * out_b))) { c->err = "admission: compact output"; return rc; }
   uint8_t *kp = arr.p, *knul = kp + mv * 32, *st = knul + mv * 32, *sp = st + mv, *kidx = sp + mv, *okey = kidx + mv, *cst = okey + mv,
           *crepl = cst + mv;      // (the replay form: the survivors' replay marks)
@@ -448,6 +457,18 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
       c_rng = rng_host.data();
     }
   }
+  // the returned amounts follow their lanes too (public; the compact copy lies behind the other compact arrays, 32-byte aligned)
+  RedeemReturn cret{nullptr};
+  if (t_in) {
+    uint8_t* ct = arr.p + ((mv * 69 + 31) & ~(size_t)31);
+    if (dev) {
+      AdmitRowsArgs ra{ct, t_in, v_idx, (uint32_t)mv, 32};
+      launch_admit_rows(ra, stream);
+      ADCK(c, hipGetLastError());
+      ADCK(c, hipStreamSynchronize(stream));
+    } else for (size_t j = 0; j < mv; j++) memcpy(ct + j * 32, t_in + (size_t)h_idx[j] * 32, 32);
+    cret.t = ct;
+  }
   const size_t W = std::max<size_t>(1, ADMIT_WINDOW_BATCHES * c->max_batch);
   AdmitGather gather(c, stream, dev, wire ? cbor : proof, wire ? ml : pb, (wire && offsets) ? &ext : nullptr);
   for (size_t w0 = 0; w0 < mv; w0 += W) {
@@ -463,7 +484,7 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
   uint64_t tc[ACT_REPLAY_COUNTS] = {0, 0, 0, 0, 0, 0};
   bool began = false;
   const int rc_tail = rp ? replay_tail(c, set, rp->receipts, mv, mem, keys, nkeys, key_epochs, sign_key, wire, knul, 32, kp, st, rp->nonce_key, cout.p, cst, okey, crepl, tc, &began)
-                         : redeem_tail_ring(c, set, mv, mem, keys, nkeys, key_epochs, sign_key, wire, knul, 32, kp, st, sp, kidx, c_rng, rng_mode, cout.p, cst, okey);
+                         : redeem_tail_ring(c, set, mv, mem, keys, nkeys, key_epochs, sign_key, wire, knul, 32, kp, st, sp, kidx, c_rng, rng_mode, cout.p, cst, okey, ret ? &cret : nullptr);
 
   if (rp && rc_tail && !began) return rc_tail;      // staging its buffers failed: as a failed verification -- nothing recorded, status untouched
   // ---- step 5: the answers back to their lanes (also behind a failure of step 4: status[] is complete on return) ----------------------------
@@ -497,7 +518,7 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
     if (cp.copies && !rp) { CopyResolveArgs ra{h_lead.data(), (uint32_t)n, status, out_key}; for (size_t i = 0; i < n; i++) copy_resolve_lane(ra, (uint32_t)i); }
     if (cp.copies && rp) { CopyServeArgs va{h_lead.data(), (uint32_t)n, out_b, status, out_key, out, rp->out_replayed}; for (size_t i = 0; i < n; i++) copy_serve_lane(va, (uint32_t)i); }
   }
-  admit_counts_of(out_counts, n, h_pre.data(), mv, dev ? h_cst.data() : cst);
+  admit_counts_of(out_counts, n, h_pre.data(), mv, dev ? h_cst.data() : cst, ret != nullptr);
   if (rp && rp->out_counts && tc[0] == mv) admit_replay_counts_of(rp->out_counts, n, h_pre.data(), rp->candidates, mv, tc);
   if (out_counts && unique) out_counts[ACT_ADMIT_COUNTS] = cp.copies;
   if (rp && rp->out_counts && unique && cp.copies && tc[0] == mv) {      // copies, then the copies whose leader ended 0
@@ -537,4 +558,28 @@ extern "C" int act_redeem_cbor_admit_unique_batch(act_ctx* c, act_nullifier_set*
   static const uint8_t none = 0;
   return redeem_admit_impl(c, set, n, mem, keys, nkeys, key_epochs, sign_key, nullptr, cbor ? cbor : &none, offsets, charge, rng, rng_mode, out_refund_cbor, status,
                            out_key, out_counts, true);
+}
+
+// ---- partial refunds (DESIGN 4.10): the admission calls with the amounts t the issuer returns ---------------------------------------------
+// The admission loop with one more rule in the screen (t_i > s_i -> ACT_STATUS_RETURN_TOO_BIG, behind the charge and in front of the
+// look-up) and a signing step over X_A = g + K' + t h1; 160-byte RefundReturn records or ACT_CBOR_REFUND_RETURN messages.  Drawn nonces
+// only: the replay forms derive e from (nonce_key, key, k, enc(K')) and two signatures with one e over X_A that differ by a multiple
+// of h1 give h1 (e + x)^-1 away -- they take no returned amounts (include/act_mi355x.h).
+extern "C" int act_redeem_return_batch(act_ctx* c, act_nullifier_set* set, size_t n, int mem, const uint8_t* keys, int nkeys, const uint32_t* key_epochs, int sign_key,
+                                       const uint8_t* proof, const uint8_t* charge, const uint8_t* returned, const uint8_t* rng, int rng_mode,
+                                       uint8_t* out_refund_return, uint8_t* status, uint8_t* out_key, uint64_t* out_counts) {
+  if (n && !proof) { if (out_counts) memset(out_counts, 0, sizeof(uint64_t) * ACT_REDEEM_RETURN_COUNTS); return ACT_ERR_ARG; }
+  const RedeemReturn ret{returned};
+  return redeem_admit_impl(c, set, n, mem, keys, nkeys, key_epochs, sign_key, proof, nullptr, nullptr, charge, rng, rng_mode, out_refund_return, status, out_key,
+                           out_counts, false, nullptr, &ret);
+}
+extern "C" int act_redeem_cbor_return_batch(act_ctx* c, act_nullifier_set* set, size_t n, int mem, const uint8_t* keys, int nkeys, const uint32_t* key_epochs,
+                                            int sign_key, const uint8_t* cbor, const uint64_t* offsets, const uint8_t* charge, const uint8_t* returned,
+                                            const uint8_t* rng, int rng_mode, uint8_t* out_refund_return_cbor, uint8_t* status, uint8_t* out_key,
+                                            uint64_t* out_counts) {
+  if (n && !cbor) { if (out_counts) memset(out_counts, 0, sizeof(uint64_t) * ACT_REDEEM_RETURN_COUNTS); return ACT_ERR_ARG; }
+  static const uint8_t none = 0;
+  const RedeemReturn ret{returned};
+  return redeem_admit_impl(c, set, n, mem, keys, nkeys, key_epochs, sign_key, nullptr, cbor ? cbor : &none, offsets, charge, rng, rng_mode, out_refund_return_cbor,
+                           status, out_key, out_counts, false, nullptr, &ret);
 }

@@ -12,23 +12,32 @@
 #pragma once
 #include "kernels.h"
 #include "null_probe.h"
+#include "return_lanes.h"
 
 namespace act {
 
 constexpr uint8_t ADMIT_WRONG_CHARGE = 250;     // ACT_STATUS_WRONG_CHARGE
 constexpr uint8_t ADMIT_DOUBLE_SPEND = 3;       // ACT_STATUS_DOUBLE_SPEND
+constexpr uint8_t ADMIT_RETURN_TOO_BIG = RETURN_TOO_BIG;      // ACT_STATUS_RETURN_TOO_BIG (return_lanes.h)
 constexpr uint32_t ADMIT_SHED = 0xFFFFFFFFu;    // pos[] of a lane that is not verified
 constexpr uint32_t ADMIT_BLOCK = 256;           // lanes per workgroup of the compaction kernels (four waves)
 
 // ---- the decision, in the order of the issue's loop ---------------------------------------------------------------------------------
 // wire_code: what the wire reader said about the message (0 = well-shaped); charge_given / charge_equal: step 2; the probe is only
 // made (found() is only called) for a lane that has passed steps 1 and 2 -- a lane with the wrong charge is not looked up.
+// return_given / return_fits (act_redeem_(cbor_)return_batch): the returned amount t against the lane's own s, in the same
+// pass and behind the charge -- a lane that fails both rules has the wrong charge, the earlier rule
 template <class Probe>
-ACT_HD uint8_t admit_decide(uint8_t wire_code, bool charge_given, bool charge_equal, Probe&& found) {
+ACT_HD uint8_t admit_decide_return(uint8_t wire_code, bool charge_given, bool charge_equal, bool return_given, bool return_fits, Probe&& found) {
   if (wire_code) return wire_code;
   if (charge_given && !charge_equal) return ADMIT_WRONG_CHARGE;
+  if (return_given && !return_fits) return ADMIT_RETURN_TOO_BIG;
   if (found()) return ADMIT_DOUBLE_SPEND;
   return 0;
+}
+template <class Probe>
+ACT_HD uint8_t admit_decide(uint8_t wire_code, bool charge_given, bool charge_equal, Probe&& found) {
+  return admit_decide_return(wire_code, charge_given, charge_equal, false, true, found);
 }
 
 struct AdmitScreenArgs {
@@ -39,18 +48,21 @@ struct AdmitScreenArgs {
   const uint32_t* tab_keys; const uint32_t* tab_state; uint32_t tab_cap; NullSalt salt;      // the set's persistent table (read only)
   uint8_t* pre;                       // n: 0 = goes on to verification, else the lane's final status
   uint8_t* kred;                      // n * 32: k reduced mod l (the set's key), all zero for a lane the wire reader rejected
+  const uint8_t* returned;            // nullable: n scalars like s, the amounts t the issuer returns (t > s, both reduced: ADMIT_RETURN_TOO_BIG)
 };
 
 ACT_HD void admit_screen_lane(const AdmitScreenArgs& a, uint32_t i) {
   if (i >= a.n) return;
   const uint8_t code = a.wire_code ? a.wire_code[i] : (uint8_t)0;
   uint32_t k[8] = {0, 0, 0, 0, 0, 0, 0, 0}, s[8], want[8];
-  bool eq = true;
+  bool eq = true, fits = true;
   if (!code) {
     null_load_key(k, a.ks + (size_t)i * a.stride);
-    if (a.charge) { null_load_key(s, a.ks + (size_t)i * a.stride + 32); null_load_key(want, a.charge + (size_t)i * 32); eq = null_eq(s, want); }
+    if (a.charge || a.returned) null_load_key(s, a.ks + (size_t)i * a.stride + 32);
+    if (a.charge) { null_load_key(want, a.charge + (size_t)i * 32); eq = null_eq(s, want); }
+    if (a.returned) { null_load_key(want, a.returned + (size_t)i * 32); fits = !return_exceeds(want, s); }
   }
-  a.pre[i] = admit_decide(code, a.charge != nullptr, eq, [&]() { return null_probe_contains(k, a.tab_keys, a.tab_state, a.tab_cap, a.salt.w); });
+  a.pre[i] = admit_decide_return(code, a.charge != nullptr, eq, a.returned != nullptr, fits, [&]() { return null_probe_contains(k, a.tab_keys, a.tab_state, a.tab_cap, a.salt.w); });
   uint32_t* dst = reinterpret_cast<uint32_t*>(a.kred + (size_t)i * 32);      // kred is the engine's own allocation: 4-byte aligned
   for (int j = 0; j < 8; j++) dst[j] = k[j];
 }

@@ -16,7 +16,7 @@ struct CborEntry { int key; int kind; int shape; };   // shape: 0 single, 1 arra
 struct CborType { int n_entries; CborEntry e[17]; bool bare; };
 
 inline const CborType* cbor_type(int t) {
-  static const CborType T[10] = {
+  static const CborType T[11] = {
     {0, {}, false},
     /* 1 IssuanceRequest  */ {4, {{1, CBOR_P, 0}, {2, CBOR_S, 0}, {3, CBOR_S, 0}, {4, CBOR_S, 0}}, false},
     /* 2 IssuanceResponse */ {5, {{1, CBOR_P, 0}, {2, CBOR_S, 0}, {3, CBOR_S, 0}, {4, CBOR_S, 0}, {5, CBOR_S, 0}}, false},
@@ -29,8 +29,10 @@ inline const CborType* cbor_type(int t) {
     /* 7 PreIssuance      */ {2, {{1, CBOR_S, 0}, {2, CBOR_S, 0}}, false},
     /* 8 CreditToken      */ {5, {{1, CBOR_P, 0}, {2, CBOR_S, 0}, {3, CBOR_S, 0}, {4, CBOR_S, 0}, {5, CBOR_S, 0}}, false},
     /* 9 PreRefund        */ {3, {{1, CBOR_S, 0}, {2, CBOR_S, 0}, {3, CBOR_S, 0}}, false},
+    /* 10 RefundReturn: Refund's map with a fifth entry, key 5 -> the returned amount t (not a type of src/cbor.rs) */
+                             {5, {{1, CBOR_P, 0}, {2, CBOR_S, 0}, {3, CBOR_S, 0}, {4, CBOR_S, 0}, {5, CBOR_S, 0}}, false},
   };
-  return (t >= 1 && t <= 9) ? &T[t] : nullptr;
+  return (t >= 1 && t <= 10) ? &T[t] : nullptr;
 }
 
 // ---- general RFC 8949 reader (host) ----------------------------------------------------------------------

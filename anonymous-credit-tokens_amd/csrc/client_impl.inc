@@ -110,12 +110,12 @@ static int copy_chain_record(act_ctx* c, Slot& sl, bool out) {
 }
 
 static int client_batch(act_ctx* c, size_t n, int mem, int label, const uint8_t* pre, const uint8_t w[32], const uint8_t* req,
-                        const uint8_t* resp, const uint8_t* proofs, uint8_t* out_token, uint8_t* status) {
+                        const uint8_t* resp, const uint8_t* proofs, uint8_t* out_token, uint8_t* status, bool with_t = false) {
   Call call(c, n);
   HIPCK(c, hipSetDevice(c->device));
   int rc = set_pubkey(c, w); if (rc) return rc;
   const bool issuance = label == LABEL_RESPOND;
-  const size_t pre_b = issuance ? 64 : 96, resp_b = issuance ? 160 : 128, pb = ProofLayout{c->L}.bytes();
+  const size_t pre_b = issuance ? 64 : 96, resp_b = (issuance || with_t) ? 160 : 128, pb = ProofLayout{c->L}.bytes();
   // Host-memory callers: the refund check reads every proof (16.8 KB per lane over PCIe against ~0.2 us of kernels), so the call is
   // cut into quarters that alternate between the two slots -- a chunk's kernels and copy out run under the next chunk's copy in.
   // Device-memory callers: one slot, full-size chunks.
@@ -132,7 +132,7 @@ static int client_batch(act_ctx* c, size_t n, int mem, int label, const uint8_t*
     uint32_t m = (uint32_t)std::min(chunk, n - off);
     sl.d_trs_dirty = std::max(sl.d_trs_dirty, (size_t)m);
     ClientArgs a{}; a.P = c->P; a.w = c->w_pub; a.n = m; a.label = label; a.coords = sl.d_coords; a.trs = sl.d_trs; a.flags = sl.d_flags; a.pbk = sl.d_buckets;
-    a.xof = sl.d_xof; a.status = sl.d_status;
+    a.xof = sl.d_xof; a.status = sl.d_status; a.with_t = with_t ? 1 : 0;
     if (two_slots && (rc = copy_chain_wait(c, sl, false))) return rc;
     if ((rc = dev_in(c, sl, 0, mem, pre + off * pre_b, (size_t)m * pre_b, &a.pre))) return rc;
     if ((rc = dev_in(c, sl, 1, mem, resp + off * resp_b, (size_t)m * resp_b, &a.resp))) return rc;
@@ -168,4 +168,12 @@ int act_refund_to_credit_token_batch(act_ctx* c, size_t n, int mem, const uint8_
                                      const uint8_t w[32], uint8_t* out_token, uint8_t* status) {
   if (!c || !w || (n && (!prerefund || !proof || !refund || !out_token || !status))) return ACT_ERR_ARG;
   return client_batch(c, n, mem, LABEL_REFUND, prerefund, w, nullptr, refund, proof, out_token, status);
+}
+// PreRefund::to_credit_token over RefundReturn records (DESIGN 4.10): the proof is checked over X_A = g + K' + t h1 and the token holds
+// (m + t) mod l; a validly signed t > s (s: field 1 of the lane's proof) is ACT_STATUS_AMOUNT_TOO_BIG.  The same chunking, kernels and
+// roads by n as the call above -- the kernels take the record's fifth field into X_A and the finish (return_lanes.h)
+int act_refund_to_credit_token_return_batch(act_ctx* c, size_t n, int mem, const uint8_t* prerefund, const uint8_t* proof, const uint8_t* refund_return,
+                                            const uint8_t w[32], uint8_t* out_token, uint8_t* status) {
+  if (!c || !w || (n && (!prerefund || !proof || !refund_return || !out_token || !status))) return ACT_ERR_ARG;
+  return client_batch(c, n, mem, LABEL_REFUND, prerefund, w, nullptr, refund_return, proof, out_token, status, true);
 }

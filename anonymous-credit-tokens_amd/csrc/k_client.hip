@@ -4,6 +4,7 @@
 //   X_g = e g + w;  Y_A = z A - gamma X_A;  Y_g = z g - gamma X_g = (z - gamma e) g - gamma w
 // with X_A = g + c h1 + K (issuance) or g + K', K' = sum 2^j Com_j (refund).
 #include "kernels.h"
+#include "return_lanes.h"
 
 namespace act {
 
@@ -25,7 +26,7 @@ __global__ void __launch_bounds__(64, 2) k_client_a(ClientArgs a) {
   if (p >= a.n) return;
   const int L = a.P.L;
   const bool issuance = a.label == LABEL_RESPOND;
-  const uint8_t* resp = a.resp + (size_t)p * (issuance ? 160 : 128);
+  const uint8_t* resp = a.resp + (size_t)p * ((issuance || a.with_t) ? 160 : 128);
   uint32_t flags = issuance ? 0u : a.flags[p];
   uint32_t wa[8]; load8(wa, resp);
   ge A; if (!ristretto_decode(A, wa)) flags |= FLAG_UNDECODABLE;
@@ -40,6 +41,7 @@ __global__ void __launch_bounds__(64, 2) k_client_a(ClientArgs a) {
     ge kp = ge_identity();                                                                 // :1224-1230 by Horner
     for (int j = L - 1; j >= 0; j--) { kp = ge_double(kp); kp = ge_madd(kp, niels_load(a.coords + ((size_t)p * L + j) * NIELS_WORDS)); }
     xa = ge_add(kp, ge_basepoint());
+        if (a.with_t) xa = return_xa(a.P, xa, load_sc(resp + 128));      // RefundReturn: + t h1 (return_lanes.h)
   }
   sc ng = sc_neg(gamma);
   ge xg = ge_add(fixed_base_acc(ge_identity(), a.P.tab[BASE_G], e), a.w);                  // :537 / :1232
@@ -89,7 +91,7 @@ __global__ void __launch_bounds__(64) k_client_a_wide(ClientArgs a) {
   const bool live = p < a.n;
   const int L = a.P.L;
   const bool issuance = a.label == LABEL_RESPOND;
-  const uint8_t* resp = a.resp + (size_t)(live ? p : 0) * (issuance ? 160 : 128);
+  const uint8_t* resp = a.resp + (size_t)(live ? p : 0) * ((issuance || a.with_t) ? 160 : 128);
   uint8_t* tr = a.trs + (size_t)(live ? p : 0) * SMALL_TR_STRIDE;
   uint8_t* el = tr + a.P.prefix_len[a.label] + (issuance ? 40 : 0);
   // after [c] | e: A (slot 1) | X_A (2) | X_g (3) | Y_A (4) | Y_g (5)
@@ -123,6 +125,7 @@ __global__ void __launch_bounds__(64) k_client_a_wide(ClientArgs a) {
         ge kp = ge_identity();                                                                 // :1224-1230 by Horner
         for (int j = L - 1; j >= 0; j--) { kp = ge_double(kp); kp = ge_madd(kp, niels_load(a.coords + ((size_t)p * L + j) * NIELS_WORDS)); }
         xa = ge_add(kp, ge_basepoint());
+        if (a.with_t) xa = return_xa(a.P, xa, load_sc(resp + 128));      // RefundReturn: + t h1 (return_lanes.h)
       }
       if (role == 3) {
         ristretto_encode(enc, xa); tr_put_bytes(el + 40 * 2, enc);
@@ -142,6 +145,11 @@ __global__ void __launch_bounds__(64) k_client_a_wide(ClientArgs a) {
   // ---- tiny calls: the transcript's hash and k_client_b's part, here --------------------------------------------------------------
   uint32_t w[16];
   b3_hash_xof64(w, reinterpret_cast<const uint32_t*>(tr), a.P.prefix_len[a.label] + 40u * (issuance ? 7u : 6u));
+  if (a.with_t) {      // (the flags word was OR-ed by other blocks of this launch; their writes are visible behind the group's counter)
+    a.flags[p] = __atomic_load_n(a.flags + p, __ATOMIC_RELAXED);
+    return_client_finish(a, p, w);
+    return;
+  }
   const sc gamma = load_sc(resp + 64);
   const uint32_t flags = __atomic_load_n(a.flags + p, __ATOMIC_RELAXED);
   uint8_t stt = 0;
@@ -163,9 +171,10 @@ __global__ void __launch_bounds__(256) k_client_b(ClientArgs a) {
   uint32_t p = blockIdx.x * 256 + threadIdx.x;
   if (p >= a.n) return;
   const bool issuance = a.label == LABEL_RESPOND;
-  const uint8_t* resp = a.resp + (size_t)p * (issuance ? 160 : 128);
+  const uint8_t* resp = a.resp + (size_t)p * ((issuance || a.with_t) ? 160 : 128);
   uint32_t w[16];
   for (int i = 0; i < 16; i++) w[i] = a.xof[(size_t)p * 16 + i];
+  if (a.with_t) { return_client_finish(a, p, w); return; }
   sc gamma = load_sc(resp + 64);
   uint8_t stt = 0;
   if (a.flags[p] & FLAG_UNDECODABLE) stt = 255;

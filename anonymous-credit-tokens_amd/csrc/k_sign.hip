@@ -5,6 +5,7 @@
 #include "kernels.h"
 #include "keyring.h"
 #include "issue_wire_lanes.h"
+#include "return_lanes.h"
 
 namespace act {
 
@@ -56,7 +57,7 @@ template <bool RING>
 __device__ __forceinline__ void sign_b_lane(const SignArgs& a, const DevKey* ring, const uint8_t* key_index) {
   uint32_t p = blockIdx.x * 256 + threadIdx.x;
   if (p >= a.n) return;
-  const int rec = a.label == LABEL_RESPOND ? 160 : 128;
+  const int rec = (a.label == LABEL_RESPOND || a.with_t) ? 160 : 128;
   uint8_t* out = a.out + (size_t)p * rec;
   if (a.status[p] != 0) { for (int i = 0; i < rec; i += 32) zero8(out + i); return; }
   const uint32_t* stt = a.state + (size_t)p * 24;
@@ -68,12 +69,13 @@ __device__ __forceinline__ void sign_b_lane(const SignArgs& a, const DevKey* rin
   sc z = sc_muladd(gamma, sc_add(x, e), alpha);                   // :660 / :861
   store8(out, enc_a); store_sc(out + 32, e); store_sc(out + 64, gamma); store_sc(out + 96, z);
   if (a.label == LABEL_RESPOND) store_sc(out + 128, load_sc(a.c_amount + (size_t)p * 32));
+  else if (a.with_t) store_sc(out + 128, a.t_amount ? load_sc(a.t_amount + (size_t)p * 32) : sc_zero());      // RefundReturn: t, reduced
 }
 __global__ void __launch_bounds__(256) k_sign_b(SignArgs a) { sign_b_lane<false>(a, nullptr, nullptr); }
 __global__ void __launch_bounds__(256) k_sign_b_ring(SignRingArgs r) { sign_b_lane<true>(r.s, r.ring, r.key_index); }
-// the ring forms are always the one-lane-per-signature kernels (no wide / fused / framed variant)
+// the ring forms are always the one-lane-per-signature kernels (no wide / fused variant; phase B frames for the return calls only)
 void launch_sign_a_ring(const SignRingArgs& a, hipStream_t s) { if (a.s.n) hipLaunchKernelGGL(k_sign_a_ring, dim3((a.s.n + 63) / 64), dim3(64), 0, s, a); }
-void launch_sign_b_ring(const SignRingArgs& a, hipStream_t s) { if (a.s.n) hipLaunchKernelGGL(k_sign_b_ring, dim3((a.s.n + 255) / 256), dim3(256), 0, s, a); }
+void launch_sign_b_ring(const SignRingArgs& a, hipStream_t s);      // (behind k_sign_b_frame_ring, below)
 // The same phase for SHORT launches, four WAVEFRONTS per 64 signatures.  One lane per signature is ~6 200 dependent field operations
 // (2.2 ms) however few signatures there are -- the issuer's single-item calls (one `issue`, one `refund`) are exactly that.  The
 // five points of the transcript do not depend on each other, so they are spread over the wavefronts of a block (wavefront = role,
@@ -139,7 +141,10 @@ void launch_sign_a(const SignArgs& a, hipStream_t s) {
 // Framed output of phase B (act_issue_sign_cbor_batch / act_issue_cbor_batch): IssuanceResponse::to_cbor (src/cbor.rs:162-175) written by the
 // lane that signed -- the template's framing bytes, then A | e | gamma | z | c at their offsets, byte-aligned 16-byte stores.  Issuance
 // runs at ~25 M/s: framed on the host that would be ~4.4 GB/s of host writes (the refund wire path frames on host workers at 0.5 M/s).
-__global__ void __launch_bounds__(256) k_sign_b_frame(SignArgs a) {
+// RING (k_sign_b_frame_ring: the return calls' wire form): lane p signs with ring[key_index[p]] and the fifth payload is the
+// returned amount t (RefundReturn, ACT_CBOR_REFUND_RETURN) where issuance has c
+template <bool RING>
+__device__ __forceinline__ void sign_b_frame_lane(const SignArgs& a, const DevKey* ring, const uint8_t* key_index) {
   uint32_t p = blockIdx.x * 256 + threadIdx.x;
   if (p >= a.n) return;
   uint8_t* out = a.out + (size_t)p * a.frame_len;
@@ -153,14 +158,17 @@ __global__ void __launch_bounds__(256) k_sign_b_frame(SignArgs a) {
   for (int i = 0; i < 8; i++) { e.v[i] = stt[i]; alpha.v[i] = stt[8 + i]; enc_a[i] = stt[16 + i]; }
   for (int i = 0; i < 16; i++) w[i] = a.xof[(size_t)p * 16 + i];
   const sc gamma = sc_from_wide_words(w);
-  const sc z = sc_muladd(gamma, sc_add(a.K.x, e), alpha);         // :660
-  const sc c = load_sc(a.c_amount + (size_t)p * 32);
+  const sc& x = RING ? ring[key_index[p]].x : a.K.x;
+  const sc z = sc_muladd(gamma, sc_add(x, e), alpha);             // :660 / :861
+  const sc c = a.label == LABEL_RESPOND ? load_sc(a.c_amount + (size_t)p * 32) : a.t_amount ? load_sc(a.t_amount + (size_t)p * 32) : sc_zero();
   const uint32_t* pay[5] = {enc_a, e.v, gamma.v, z.v, c.v};
   for (uint32_t f = 0, prev = 0; f < 5; prev = a.frame_off[f] + 32, f++) {
     for (uint32_t i = prev; i < a.frame_off[f]; i++) out[i] = a.frame[i];
     store32_bytes(out + a.frame_off[f], pay[f]);
   }
 }
+__global__ void __launch_bounds__(256) k_sign_b_frame(SignArgs a) { sign_b_frame_lane<false>(a, nullptr, nullptr); }
+__global__ void __launch_bounds__(256) k_sign_b_frame_ring(SignRingArgs r) { sign_b_frame_lane<true>(r.s, r.ring, r.key_index); }
 void launch_sign_b(const SignArgs& a, hipStream_t s) {
   if (!a.n) return;
   if (a.frame) hipLaunchKernelGGL(k_sign_b_frame, dim3((a.n + 255) / 256), dim3(256), 0, s, a);
@@ -247,6 +255,7 @@ __global__ void __launch_bounds__(64, 2) k_sign_xa(SignXaArgs a) {
   ge K;
   if (!ristretto_decode(K, w)) { a.status[p] = 255; return; }
   ge xa = a.c_amount ? ge_add(fixed_base_acc(ge_basepoint(), a.P.tab[BASE_H1], load_sc(a.c_amount + (size_t)p * 32)), K) : ge_add(K, ge_basepoint());
+  if (a.t_amount) xa = return_xa(a.P, xa, load_sc(a.t_amount + (size_t)p * 32));      // RefundReturn: g + K' + t h1 (return_lanes.h)
   ge_store(a.xa + (size_t)p * GE_WORDS, xa);
 }
 void launch_sign_xa(const SignXaArgs& a, hipStream_t s) { if (a.n) hipLaunchKernelGGL(k_sign_xa, dim3((a.n + 63) / 64), dim3(64), 0, s, a); }
@@ -545,5 +554,11 @@ __global__ void __launch_bounds__(256) k_request_fused(RequestArgs a) {
 void launch_request_fused(const RequestArgs& a, hipStream_t s) { if (a.n) hipLaunchKernelGGL(k_request_fused, dim3((a.n + 63) / 64), dim3(256), 0, s, a); }
 void launch_request_a(const RequestArgs& a, hipStream_t s) { if (a.n) hipLaunchKernelGGL(k_request_a, dim3((a.n + 63) / 64), dim3(64), 0, s, a); }
 void launch_request_b(const RequestArgs& a, hipStream_t s) { if (a.n) hipLaunchKernelGGL(k_request_b, dim3((a.n + 255) / 256), dim3(256), 0, s, a); }
+
+void launch_sign_b_ring(const SignRingArgs& a, hipStream_t s) {
+  if (!a.s.n) return;
+  if (a.s.frame) hipLaunchKernelGGL(k_sign_b_frame_ring, dim3((a.s.n + 255) / 256), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(k_sign_b_ring, dim3((a.s.n + 255) / 256), dim3(256), 0, s, a);
+}
 
 }  // namespace act

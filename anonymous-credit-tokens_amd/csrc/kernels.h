@@ -139,6 +139,9 @@ struct SignArgs {
   // framed output (issue only; k_sign_b_frame): `out` takes n IssuanceResponse messages of frame_len bytes -- the canonical template
   // `frame` with A | e | gamma | z | c at frame_off[0..4] -- instead of records; an unsigned lane gets an all-zero slot
   const uint8_t* frame; const uint32_t* frame_off; uint32_t frame_len;
+  // RefundReturn (label REFUND only): 160-byte records A | e | gamma | z | t.  X_A already holds t h1 (k_sign_xa); phase B
+  // only writes t behind the signature.  t_amount: n * 32 or null (every t = 0)
+  int with_t; const uint8_t* t_amount;
 };
 
 // k_sign_fused (k_sign.hip): the whole signature -- and, with `check`, the request's PoK check beside it -- in one kernel, for tiny calls
@@ -173,6 +176,7 @@ struct SignXaArgs {
   const uint8_t* c_amount;   // n * 32 (issue) or null (refund)
   uint32_t* xa;              // n * GE_WORDS
   uint8_t* status;           // n: in = verdict of the check phase; a lane whose point does not decode becomes 255
+  const uint8_t* t_amount;   // n * 32 or null (refund with a return): X_A gains t h1
 };
 
 struct IssueArgs {
@@ -248,6 +252,7 @@ struct ClientArgs {
   uint32_t* pbk;             // n * PREP_BUCKET_SETS * BUCKET_WORDS (msm.h chain_b); the wide kernel also parks two partial points there
   uint32_t* group_counter;   // wide kernel: one word per group of 64 items, zero between launches (which role block arrives last)
   int fused;                 // wide kernel, tiny calls: the last block also hashes the transcript and does k_client_b's part
+  int with_t;                // refund only: resp = n * 160 RefundReturn records; X_A = g + K' + t h1, the token holds m + t (return_lanes.h)
 };
 
 struct HashArgs { const uint8_t* msg; uint32_t stride; uint32_t len; uint32_t n; uint32_t* xof; const uint32_t* len_per_lane; };

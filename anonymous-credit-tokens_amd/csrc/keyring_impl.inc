@@ -166,8 +166,15 @@ int act_verify_spend_keyring_batch(act_ctx* c, size_t n, int mem, const uint8_t*
 
 // act_refund_sign_batch with the key chosen per lane: a lane whose status_in is 0 and whose key_index is not below nkeys is not signed
 // (status 255, zero record, no rng slice) -- the array may live in device memory, so that is the lane's verdict, not the call's.
-int act_refund_sign_keyring_batch(act_ctx* c, size_t n, int mem, const uint8_t* keys, int nkeys, const uint8_t* key_index, const uint8_t* kprime,
-                                  const uint8_t* status_in, const uint8_t* rng, int rng_mode, uint8_t* out_refund, uint8_t* status) {
+// with_t (act_refund_sign_return_keyring_batch, DESIGN 4.10): X_A = g + K' + t h1 and 160-byte RefundReturn records; returned = n
+// scalars in `mem` memory, or null (every t = 0: no product on h1 at all).  frame (with_t only; the wire form of the return calls):
+// out_refund takes n ACT_CBOR_REFUND_RETURN messages framed by phase B (k_sign_b_frame_ring), all zero where not signed, instead of records
+static int refund_return_frame_prepare(act_ctx* c, FrameOut* fo);      // keyring_redeem_impl.inc, behind the codec
+static int refund_sign_keyring_impl(act_ctx* c, size_t n, int mem, const uint8_t* keys, int nkeys, const uint8_t* key_index, const uint8_t* kprime,
+                                    const uint8_t* status_in, const uint8_t* rng, int rng_mode, uint8_t* out_refund, uint8_t* status, bool with_t,
+                                    const uint8_t* returned, bool frame = false) {
+  size_t rec = with_t ? 160 : 128;
+  if (frame && !with_t) return ACT_ERR_ARG;
   if (!c || !keys || nkeys < 1 || nkeys > ACT_KEYRING_MAX || (n && (!key_index || !kprime || !status_in || !rng || !out_refund || !status))) return ACT_ERR_ARG;
   if (rng_mode != ACT_RNG_PER_LANE && rng_mode != ACT_RNG_SEQUENTIAL) return ACT_ERR_ARG;
   Call call(c, n);
@@ -175,6 +182,8 @@ int act_refund_sign_keyring_batch(act_ctx* c, size_t n, int mem, const uint8_t* 
   const DevKey* d_ring = nullptr;
   int rc = ring_set(c, keys, nkeys, &d_ring); if (rc) return rc;
   RingWs* w = c->ring_ws;
+  FrameOut fo{nullptr, nullptr, 0};
+  if (frame) { if ((rc = refund_return_frame_prepare(c, &fo))) return rc; rec = fo.len; }
   const hipMemcpyKind in_kind = mem == ACT_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   size_t cursor = 0, chunk = 0;
   for (size_t off = 0; off < n; off += c->max_batch, chunk++) {
@@ -184,10 +193,11 @@ int act_refund_sign_keyring_batch(act_ctx* c, size_t n, int mem, const uint8_t* 
     const uint32_t m = (uint32_t)std::min(c->max_batch, n - off);
     SignXaArgs x{}; x.P = c->P; x.n = m; x.point_stride = 32; x.xa = sl.d_xa; x.status = sl.d_status;
     if ((rc = dev_in(c, sl, 0, mem, kprime + off * 32, (size_t)m * 32, &x.point))) return rc;
+    if (returned && (rc = dev_in(c, sl, 1, mem, returned + off * 32, (size_t)m * 32, &x.t_amount))) return rc;
     HIPCK(c, hipMemcpyAsync(sl.d_status, status_in + off, m, in_kind, sl.stream));
     HIPCK(c, hipMemcpyAsync(w->d_kidx[s], key_index + off, m, in_kind, sl.stream));
     uint8_t* d_out;
-    if ((rc = dev_out_begin(c, sl, 2, mem, out_refund + off * 128, (size_t)m * 128, &d_out))) return rc;
+    if ((rc = dev_out_begin(c, sl, 2, mem, out_refund + off * rec, (size_t)m * rec, &d_out))) return rc;
     launch_ring_index_check(sl.d_status, w->d_kidx[s], (uint32_t)nkeys, m, sl.stream);
     launch_sign_xa(x, sl.stream);
     const uint8_t* d_rng;
@@ -196,11 +206,23 @@ int act_refund_sign_keyring_batch(act_ctx* c, size_t n, int mem, const uint8_t* 
     SignRingArgs g{}; g.ring = d_ring; g.key_index = w->d_kidx[s]; g.nkeys = (uint32_t)nkeys;
     SignArgs& a = g.s; a.P = c->P; a.n = m; a.label = LABEL_REFUND; a.xa = sl.d_xa; a.status = sl.d_status; a.rng_slot = sl.d_slot;
     a.rng = d_rng; a.trs = sl.d_trs; a.state = sl.d_state; a.xof = sl.d_xof; a.out = d_out; a.pbk = sl.d_buckets;
+    a.with_t = with_t ? 1 : 0; a.t_amount = x.t_amount;
+    if (frame) { a.frame = fo.tmpl; a.frame_off = fo.off; a.frame_len = fo.len; }
     if ((rc = prof_launch(c, sl, PK_SIGN_A, m, [&] { launch_sign_a_ring(g, sl.stream); }))) return rc;
     if ((rc = hash_step(c, sl, PK_HASH_SMALL, sl.d_trs, SMALL_TR_STRIDE, c->P.prefix_len[LABEL_REFUND] + 40u * 6u, m))) return rc;
-    if ((rc = prof_launch(c, sl, PK_SIGN_B, m, [&] { launch_sign_b_ring(g, sl.stream); }))) return rc;
-    if ((rc = dev_out_end(c, sl, mem, out_refund + off * 128, d_out, (size_t)m * 128))) return rc;
+    if ((rc = prof_launch(c, sl, frame ? PK_SIGN_B_FRAME : PK_SIGN_B, m, [&] { launch_sign_b_ring(g, sl.stream); }))) return rc;
+    if ((rc = dev_out_end(c, sl, mem, out_refund + off * rec, d_out, (size_t)m * rec))) return rc;
     if ((rc = copy_status_out(c, sl, mem, status + off, m))) return rc;
   }
   return call.finish();
+}
+int act_refund_sign_keyring_batch(act_ctx* c, size_t n, int mem, const uint8_t* keys, int nkeys, const uint8_t* key_index, const uint8_t* kprime,
+                                  const uint8_t* status_in, const uint8_t* rng, int rng_mode, uint8_t* out_refund, uint8_t* status) {
+  return refund_sign_keyring_impl(c, n, mem, keys, nkeys, key_index, kprime, status_in, rng, rng_mode, out_refund, status, false, nullptr);
+}
+// the same signature over X_A = g + K' + t h1 (DESIGN 4.10).  This call does not see s: the bound t <= s is the caller's
+int act_refund_sign_return_keyring_batch(act_ctx* c, size_t n, int mem, const uint8_t* keys, int nkeys, const uint8_t* key_index, const uint8_t* kprime,
+                                         const uint8_t* status_in, const uint8_t* rng, int rng_mode, const uint8_t* returned, uint8_t* out_refund_return,
+                                         uint8_t* status) {
+  return refund_sign_keyring_impl(c, n, mem, keys, nkeys, key_index, kprime, status_in, rng, rng_mode, out_refund_return, status, true, returned);
 }

@@ -6,8 +6,27 @@
 // Arrays of n lanes in `mem` memory: st = the verdicts, out_key = the matched ring indices, kp = enc(K'), the nullifiers at
 // nul + i * nul_stride; sp and kidx are scratch of n bytes each.  The admission calls (admit_impl.inc) hand it the survivors' compact arrays.
 // the signatures of a ring redemption, each lane with ring key kidx[i], framed as Refund messages for the wire form (redeem_tail's sign_step)
+// The return calls (act_redeem_(cbor_)return_batch, DESIGN 4.10): the amounts t the signing step adds to X_A as t h1.  t: n scalars in
+// the call's kind of memory, lane for lane with the tail's arrays, or null (every t = 0).  The outputs are RefundReturn records (160
+// bytes) or messages (ACT_CBOR_REFUND_RETURN).  A null RedeemReturn* everywhere below: the Refund forms, as they were.
+struct RedeemReturn { const uint8_t* t; };
+static size_t redeem_out_bytes(const act_ctx* c, bool wire, const RedeemReturn* ret) {
+  return wire ? act_cbor_size(c, ret ? ACT_CBOR_REFUND_RETURN : ACT_CBOR_REFUND) : (ret ? (size_t)160 : (size_t)128);
+}
+// the RefundReturn layout on the device for phase B's framing (refund_sign_keyring_impl, keyring_impl.inc; the caller holds the context):
+// slot 1's layout area, as the issuance wire calls keep their response layout
+extern "C" {
+static int refund_return_frame_prepare(act_ctx* c, FrameOut* fo) {
+  CborDev d;
+  if (int rc = cbor_dev_prepare(c, c->slots[1], ACT_CBOR_REFUND_RETURN, &d)) return rc;
+  *fo = FrameOut{d.tmpl, d.pay_off, (uint32_t)d.lay.tmpl.size()};
+  return ACT_OK;
+}
+}
 static int ring_sign_step(act_ctx* c, size_t n, int mem, const uint8_t* keys, int nkeys, bool wire, const uint8_t* kidx, const uint8_t* kp, const uint8_t* verdict,
-                          const uint8_t* r, int r_mode, uint8_t* o, uint8_t* o_st) {
+                          const uint8_t* r, int r_mode, uint8_t* o, uint8_t* o_st, const RedeemReturn* ret = nullptr) {
+  // the return calls: records, or (wire) messages framed on the device by the lane that signed, as issuance frames its responses
+  if (ret) return refund_sign_keyring_impl(c, n, mem, keys, nkeys, kidx, kp, verdict, r, r_mode, o, o_st, true, ret->t, wire);
   if (!wire) return act_refund_sign_keyring_batch(c, n, mem, keys, nkeys, kidx, kp, verdict, r, r_mode, o, o_st);
   int rc_sign;
   if (mem == ACT_MEM_HOST) {      // framed as act_refund_sign_cbor_batch frames: on the host workers, where the signatures landed
@@ -36,15 +55,15 @@ static void ring_sign_index(int mem, uint8_t* kidx, const uint8_t* out_key, int 
 }
 static int redeem_tail_ring(act_ctx* c, act_nullifier_set* set, size_t n, int mem, const uint8_t* keys, int nkeys, const uint32_t* key_epochs, int sign_key, bool wire,
                             const uint8_t* nul, size_t nul_stride, const uint8_t* kp, uint8_t* st, uint8_t* sp, uint8_t* kidx, const uint8_t* rng, int rng_mode,
-                            uint8_t* out, uint8_t* status, uint8_t* out_key) {
-  return redeem_tail(c, set, n, mem, wire, st, sp, rng, rng_mode, out, status,
+                            uint8_t* out, uint8_t* status, uint8_t* out_key, const RedeemReturn* ret = nullptr) {
+  return redeem_tail_sized(c, set, n, mem, redeem_out_bytes(c, wire, ret), st, sp, rng, rng_mode, out, status,
     [&](const uint8_t* mask, uint8_t* spent) {
       return key_epochs ? act_nullifier_check_and_insert_epoch_batch(set, n, mem, nul, nul_stride, mask, out_key, key_epochs, nkeys, spent)
                         : act_nullifier_check_and_insert_batch(set, n, mem, nul, nul_stride, mask, spent);
     },
     [&] { ring_sign_index(mem, kidx, out_key, sign_key, n); },
     [&](const uint8_t* verdict, const uint8_t* r, int r_mode, uint8_t* o, uint8_t* o_st) {
-      return ring_sign_step(c, n, mem, keys, nkeys, wire, kidx, kp, verdict, r, r_mode, o, o_st);
+      return ring_sign_step(c, n, mem, keys, nkeys, wire, kidx, kp, verdict, r, r_mode, o, o_st, ret);
     });
 }
 
@@ -64,7 +83,8 @@ static int redeem_keyring_refused(act_ctx* c, act_nullifier_set* set, size_t n, 
 }
 
 static int redeem_keyring_impl(act_ctx* c, act_nullifier_set* set, size_t n, int mem, const uint8_t* keys, int nkeys, const uint32_t* key_epochs, int sign_key, const uint8_t* proof,
-                               const uint8_t* cbor, const uint64_t* offsets, const uint8_t* rng, int rng_mode, uint8_t* out, uint8_t* status, uint8_t* out_key) {
+                               const uint8_t* cbor, const uint64_t* offsets, const uint8_t* rng, int rng_mode, uint8_t* out, uint8_t* status, uint8_t* out_key,
+                               const RedeemReturn* ret = nullptr) {
   const bool wire = cbor != nullptr;
   if (int bad = redeem_keyring_refused(c, set, n, keys, nkeys, key_epochs, sign_key, proof, cbor, rng, rng_mode, out, status, out_key)) return bad;
   if (n == 0) {      // a bad ring fails the call whatever n
@@ -85,7 +105,7 @@ static int redeem_keyring_impl(act_ctx* c, act_nullifier_set* set, size_t n, int
   if (wire) { RingSel sel{keys, nkeys, out_key}; rc = verify_spend_cbor_impl(c, n, mem, nullptr, cbor, offsets, st, kp, nul, &sel); }
   else rc = act_verify_spend_keyring_batch(c, n, mem, keys, nkeys, proof, st, out_key, kp);
   if (rc) return rc;
-  return redeem_tail_ring(c, set, n, mem, keys, nkeys, key_epochs, sign_key, wire, wire ? nul : proof, wire ? 32 : pb, kp, st, sp, kidx, rng, rng_mode, out, status, out_key);
+  return redeem_tail_ring(c, set, n, mem, keys, nkeys, key_epochs, sign_key, wire, wire ? nul : proof, wire ? 32 : pb, kp, st, sp, kidx, rng, rng_mode, out, status, out_key, ret);
 }
 
 extern "C" int act_redeem_keyring_batch(act_ctx* c, act_nullifier_set* set, size_t n, int mem, const uint8_t* keys, int nkeys, int sign_key, const uint8_t* proof,

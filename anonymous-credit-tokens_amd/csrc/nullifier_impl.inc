@@ -559,10 +559,10 @@ __global__ void __launch_bounds__(256) k_mark_undetermined_status(uint8_t* statu
 //   beside_merge()                                      the caller's share of the merge's pass: in device memory it runs under c->mu and
 //                                                       may launch on the null stream, in front of the merge's synchronisation
 //   sign_step(st, rng, rng_mode, out, status) -> rc     the signatures, rng already resolved, framed or not as the call's output is
+// out_b: the bytes of one output slot (a Refund record or message; a RefundReturn's for the return calls, DESIGN 4.10)
 template <class NullStep, class BesideMerge, class SignStep>
-static int redeem_tail(act_ctx* c, act_nullifier_set* set, size_t n, int mem, bool wire, uint8_t* st, uint8_t* sp, const uint8_t* rng, int rng_mode,
-                       uint8_t* out, uint8_t* status, NullStep null_step, BesideMerge beside_merge, SignStep sign_step) {
-  const size_t out_b = wire ? act_cbor_size(c, ACT_CBOR_REFUND) : 128;
+static int redeem_tail_sized(act_ctx* c, act_nullifier_set* set, size_t n, int mem, size_t out_b, uint8_t* st, uint8_t* sp, const uint8_t* rng, int rng_mode,
+                             uint8_t* out, uint8_t* status, NullStep null_step, BesideMerge beside_merge, SignStep sign_step) {
   const int rc_null = null_step(st, sp);
   // a step failed as a whole: every lane that verified says `what`, the others their verdict, and there is no output.  (Device memory:
   // best effort on a device that may just have failed a call -- the header promises a status for every lane.)
@@ -604,6 +604,12 @@ static int redeem_tail(act_ctx* c, act_nullifier_set* set, size_t n, int mem, bo
   if (rc_sign) { give_up(ACT_STATUS_RECORDED_UNSIGNED, k_mark_recorded_unsigned); return rc_sign; }      // the nullifiers ARE recorded: the refunds are owed
   if (rc_null) c->err = null_err;
   return rc_null;
+}
+
+template <class NullStep, class BesideMerge, class SignStep>
+static int redeem_tail(act_ctx* c, act_nullifier_set* set, size_t n, int mem, bool wire, uint8_t* st, uint8_t* sp, const uint8_t* rng, int rng_mode,
+                       uint8_t* out, uint8_t* status, NullStep null_step, BesideMerge beside_merge, SignStep sign_step) {
+  return redeem_tail_sized(c, set, n, mem, wire ? act_cbor_size(c, ACT_CBOR_REFUND) : (size_t)128, st, sp, rng, rng_mode, out, status, null_step, beside_merge, sign_step);
 }
 
 static int redeem_impl(act_ctx* c, act_nullifier_set* set, size_t n, int mem, const uint8_t sk[64], const uint8_t* proof, const uint8_t* cbor,

@@ -356,6 +356,7 @@ int act_node_refund_to_credit_token_batch(act_node *node, size_t n, const uint8_
 #define ACT_CBOR_PRE_ISSUANCE 7
 #define ACT_CBOR_CREDIT_TOKEN 8
 #define ACT_CBOR_PRE_REFUND 9
+#define ACT_CBOR_REFUND_RETURN 10   /* the Refund map with one more entry, key 5 -> t (partial refunds, below); record A | e | gamma | z | t, 160 bytes */
 size_t act_cbor_size(const act_ctx *ctx, int type);
 size_t act_cbor_record_bytes(const act_ctx *ctx, int type);
 int act_cbor_encode_batch(act_ctx *ctx, int type, size_t n, int mem, const uint8_t *records, uint8_t *out_cbor);
@@ -982,6 +983,59 @@ int act_ubench_random_read(int device, size_t gib, int waves_per_simd, int in_fl
 /* The same probe over the context's own fixed-base table of base 0..3 (g, h1, h2, h3; the largest power-of-two prefix of it): the
  * product's look-ups in the product's memory with nothing else running. */
 int act_ubench_table_read(act_ctx *ctx, int base, int waves_per_simd, int in_flight, double *gbytes_per_s, double *ms);
+
+/* ======== partial refunds: the issuer returns t <= s unused credits with the Refund ========
+ * Every redeem call above charges a token exactly s credits: refund signs X_A = g + K', and K' = sum 2^j Com_j commits to c - s.  A
+ * metered service reserves s, does the work, and the work costs s - t.  These calls sign X_A = g + K' + t h1 instead; the client, who
+ * reads t from the response, checks the same proof (label "refund", the same six transcript items: t is bound through X_A) over that
+ * X_A and holds a token for c - s + t.  Both parties know t; like the amount c of an issuance it may address a table.
+ *
+ * RefundReturn record, 160 bytes: A | e | gamma | z | t.  The first 128 bytes are laid out as a Refund, t is a reduced scalar; a
+ * rejected lane's record is all zero.  On the wire it is ACT_CBOR_REFUND_RETURN: the Refund map with a fifth entry, key 5 -> t.
+ * returned: nullable (NULL = every t is 0); n scalars of 32 bytes in `mem` memory, laid out like SpendProof.s; reduced mod l on reading.
+ *
+ * act_refund_sign_return_keyring_batch is act_refund_sign_keyring_batch over X_A = g + K' + t h1 for the lanes with status_in == 0,
+ * writing 160-byte records (nkeys == 1 is the one-key call).  IT DOES NOT SEE s: whoever calls it bounds t_i <= s_i, or signs a balance
+ * the client never had.  (The client call below refuses such a record, but an issuer must not rely on its clients for its own books.)
+ *
+ * act_redeem_return_batch / act_redeem_cbor_return_batch are act_redeem_(cbor_)admit_batch with `returned`: the admission loop with one
+ * more rule in step 2, checked in the screen's pass behind the charge and before any look-up:
+ *       2b. t_i > s_i (both reduced mod l, compared as integers)  -> ACT_STATUS_RETURN_TOO_BIG: not looked up, not verified, not
+ *           recorded, not signed; a zero record, ACT_KEY_NONE, no rng slice.  A lane that also has the wrong charge reports
+ *           ACT_STATUS_WRONG_CHARGE, the earlier rule.
+ * Every other lane goes through the redemption tail of the admission calls, whose signing step adds t h1, and gets a RefundReturn
+ * record (wire form: an ACT_CBOR_REFUND_RETURN message of act_cbor_size bytes, all zero where not signed).
+ * out_counts: nullable, host, ACT_REDEEM_RETURN_COUNTS values: the eight of ACT_ADMIT_COUNTS, then return_too_big; verified excludes
+ * those lanes too.
+ * With returned all zero (or NULL): statuses, out_key, the recorded nullifiers with their epochs, out_counts[0..8) and what is drawn
+ * from the generator are byte for byte those of act_redeem_(cbor_)admit_batch on an identical set; the first 128 bytes of every record
+ * equal that call's and bytes 128..160 are zero.
+ *
+ * act_refund_to_credit_token_return_batch is act_refund_to_credit_token_batch over n * 160 RefundReturn records: the proof over
+ * X_A = g + K' + t h1 (ACT_STATUS_INVALID_REFUND_PROOF when it fails -- a record whose t was altered after signing fails it), then
+ * t > s, s from the lane's proof record -> ACT_STATUS_AMOUNT_TOO_BIG (a balance above what the client had can never be proven in
+ * range: better to learn it now), else the token A | e | k | r | (m + t) mod l.
+ *
+ * NOT OFFERED, on purpose: the replay forms (act_redeem_*replay*) take no `returned`.  They derive e and alpha from
+ * (nonce_key, key, k, enc(K')), so a retry with another t would be signed with the SAME e over an X_A that differs by (t1 - t2) h1:
+ * the two A values differ by (t1 - t2) (e + x)^-1 h1, which hands out h1 (e + x)^-1 -- and with it anyone raises the balance of a
+ * token signed under that e.  Before a replay form may take t, t must be bound into BOTH the receipt tag and the nonce derivation.
+ * The calls here use drawn nonces only.  Also not offered here: the node-handle forms, the client ring verifier and the unique forms. */
+#define ACT_STATUS_RETURN_TOO_BIG 249   /* t > s: not looked up, not verified, not recorded, not signed */
+#define ACT_REDEEM_RETURN_COUNTS 9
+int act_refund_sign_return_keyring_batch(act_ctx *ctx, size_t n, int mem, const uint8_t *keys, int nkeys, const uint8_t *key_index,
+                                         const uint8_t *kprime, const uint8_t *status_in, const uint8_t *rng, int rng_mode,
+                                         const uint8_t *returned /* nullable */, uint8_t *out_refund_return, uint8_t *status);
+int act_redeem_return_batch(act_ctx *ctx, act_nullifier_set *set, size_t n, int mem, const uint8_t *keys, int nkeys,
+                            const uint32_t *key_epochs /* nullable */, int sign_key, const uint8_t *proof, const uint8_t *charge /* nullable */,
+                            const uint8_t *returned /* nullable */, const uint8_t *rng, int rng_mode, uint8_t *out_refund_return,
+                            uint8_t *status, uint8_t *out_key, uint64_t *out_counts /* nullable, host */);
+int act_redeem_cbor_return_batch(act_ctx *ctx, act_nullifier_set *set, size_t n, int mem, const uint8_t *keys, int nkeys,
+                                 const uint32_t *key_epochs /* nullable */, int sign_key, const uint8_t *cbor, const uint64_t *offsets,
+                                 const uint8_t *charge /* nullable */, const uint8_t *returned /* nullable */, const uint8_t *rng, int rng_mode,
+                                 uint8_t *out_refund_return_cbor, uint8_t *status, uint8_t *out_key, uint64_t *out_counts /* nullable, host */);
+int act_refund_to_credit_token_return_batch(act_ctx *ctx, size_t n, int mem, const uint8_t *prerefund, const uint8_t *proof,
+                                            const uint8_t *refund_return, const uint8_t w[32], uint8_t *out_token, uint8_t *status);
 
 #ifdef __cplusplus
 }

@@ -162,6 +162,17 @@ extern "C" {
                                                  nonce_key: *const u8, out_refund_cbor: *mut u8, status: *mut u8, out_key: *mut u8, out_replayed: *mut u8,
                                                  out_counts: *mut u64) -> c_int;
     fn act_node_device_stats(node: *mut ActNode, k: c_int, weight: *mut f64, last_lanes: *mut u64, last_seconds: *mut f64, last_calls: *mut u64) -> c_int;
+    fn act_refund_sign_return_keyring_batch(ctx: *mut ActCtx, n: usize, mem: c_int, keys: *const u8, nkeys: c_int, key_index: *const u8, kprime: *const u8,
+                                            status_in: *const u8, rng: *const u8, rng_mode: c_int, returned: *const u8, out_refund_return: *mut u8,
+                                            status: *mut u8) -> c_int;
+    fn act_redeem_return_batch(ctx: *mut ActCtx, set: *mut ActNullifierSet, n: usize, mem: c_int, keys: *const u8, nkeys: c_int, key_epochs: *const u32,
+                               sign_key: c_int, proof: *const u8, charge: *const u8, returned: *const u8, rng: *const u8, rng_mode: c_int,
+                               out_refund_return: *mut u8, status: *mut u8, out_key: *mut u8, out_counts: *mut u64) -> c_int;
+    fn act_redeem_cbor_return_batch(ctx: *mut ActCtx, set: *mut ActNullifierSet, n: usize, mem: c_int, keys: *const u8, nkeys: c_int, key_epochs: *const u32,
+                                    sign_key: c_int, cbor: *const u8, offsets: *const u64, charge: *const u8, returned: *const u8, rng: *const u8,
+                                    rng_mode: c_int, out_refund_return_cbor: *mut u8, status: *mut u8, out_key: *mut u8, out_counts: *mut u64) -> c_int;
+    fn act_refund_to_credit_token_return_batch(ctx: *mut ActCtx, n: usize, mem: c_int, prerefund: *const u8, proof: *const u8, refund_return: *const u8,
+                                               w: *const u8, out_token: *mut u8, status: *mut u8) -> c_int;
 }
 
 /// ACT_MI355X_DEVICES = "0,1,2,3,4,5,6,7" (default: device 0)
@@ -1164,6 +1175,104 @@ impl GpuAdmission {
         r.counts.copy_from_slice(&counts[..ACT_ADMIT_COUNTS]); r.copies = counts[ACT_ADMIT_COUNTS];
         r.status.truncate(n); r.out.truncate(REFUND_CBOR_BYTES * n); r.out_key.truncate(n);
         r
+    }
+}
+
+/// `ACT_STATUS_RETURN_TOO_BIG`: the return calls only -- the returned amount `t` exceeds the charge `s`; not looked up, not verified,
+/// not recorded, not signed.
+pub const ACT_STATUS_RETURN_TOO_BIG: u8 = 249;
+pub const ACT_REDEEM_RETURN_COUNTS: usize = 9;
+/// a RefundReturn on the wire (`ACT_CBOR_REFUND_RETURN`): the Refund map with a fifth entry, key 5 -> t
+pub const REFUND_RETURN_CBOR_BYTES: usize = REFUND_CBOR_BYTES + 35;
+/// statuses, outputs (160-byte RefundReturn records `A | e | gamma | z | t` or `REFUND_RETURN_CBOR_BYTES` messages, all zero where not
+/// signed), matched ring keys, the eight admission counts and `return_too_big`
+pub struct Returned {
+    pub rc: c_int,
+    pub status: Vec<u8>,
+    pub out: Vec<u8>,
+    pub out_key: Vec<u8>,
+    pub counts: [u64; ACT_ADMIT_COUNTS],
+    pub return_too_big: u64,
+}
+/// Partial refunds on ONE GPU (include/act_mi355x.h "partial refunds"): the admission calls with the amounts `t <= s` the issuer gives
+/// back -- every accepted lane is signed over `X_A = g + K' + t h1`, so the client's next token holds `c - s + t`.  A lane with
+/// `t > s` is answered `ACT_STATUS_RETURN_TOO_BIG` without being looked up or verified.  A sibling of `GpuAdmission`, not a mode of
+/// the replay types: with derived nonces two returns for one proof would share `e` and give `h1 (e + x)^-1` away (the header says why).
+pub struct GpuReturn {
+    ctx: *mut ActCtx,
+    set: *mut ActNullifierSet,
+}
+impl GpuReturn {
+    /// # Safety
+    /// `ctx` and `set` are live handles on one device and outlive `self`.
+    pub unsafe fn from_raw(ctx: *mut ActCtx, set: *mut ActNullifierSet) -> Self {
+        GpuReturn { ctx, set }
+    }
+    /// `returned`: n scalars of 32 bytes (None: every t is 0); the other arguments as `GpuAdmission::redeem_admit_batch`.
+    pub fn redeem_return_batch(&self, keys: &[u8], key_epochs: Option<&[u32]>, sign_with: Option<usize>, proofs: &[u8], charges: Option<&[u8]>,
+                               returned: Option<&[u8]>, mut rng: impl CryptoRngCore) -> Returned {
+        let (n, nkeys) = (proofs.len() / PROOF_BYTES, keys.len() / 64);
+        assert!(proofs.len() == n * PROOF_BYTES && charges.map_or(true, |c| c.len() == 32 * n) && returned.map_or(true, |t| t.len() == 32 * n) &&
+                key_epochs.map_or(true, |e| e.len() == nkeys));
+        let src = rng_source(&mut rng);
+        let mut r = Returned { rc: 0, status: vec![0u8; n + 1], out: vec![0u8; 160 * n + 1], out_key: vec![ACT_KEY_NONE; n + 1], counts: [0; ACT_ADMIT_COUNTS], return_too_big: 0 };
+        let mut counts = [0u64; ACT_REDEEM_RETURN_COUNTS];
+        r.rc = unsafe {
+            act_redeem_return_batch(self.ctx, self.set, n, 0, keys.as_ptr(), nkeys as c_int, key_epochs.map_or(std::ptr::null(), |e| e.as_ptr()),
+                                    sign_with.map_or(ACT_SIGN_MATCHED, |i| i as c_int), proofs.as_ptr(), charges.map_or(std::ptr::null(), |c| c.as_ptr()),
+                                    returned.map_or(std::ptr::null(), |t| t.as_ptr()), &src as *const ActRngSource as *const u8, ACT_RNG_CALLBACK,
+                                    r.out.as_mut_ptr(), r.status.as_mut_ptr(), r.out_key.as_mut_ptr(), counts.as_mut_ptr())
+        };
+        r.counts.copy_from_slice(&counts[..ACT_ADMIT_COUNTS]); r.return_too_big = counts[ACT_ADMIT_COUNTS];
+        r.status.truncate(n); r.out.truncate(160 * n); r.out_key.truncate(n);
+        r
+    }
+    /// The same on wire bytes: CBOR SpendProof messages in, CBOR RefundReturn messages out.
+    pub fn redeem_cbor_return_batch(&self, keys: &[u8], key_epochs: Option<&[u32]>, sign_with: Option<usize>, msgs: &[&[u8]], charges: Option<&[u8]>,
+                                    returned: Option<&[u8]>, mut rng: impl CryptoRngCore) -> Returned {
+        let (blob, offsets) = gather(msgs);
+        let (n, nkeys) = (msgs.len(), keys.len() / 64);
+        assert!(charges.map_or(true, |c| c.len() == 32 * n) && returned.map_or(true, |t| t.len() == 32 * n) && key_epochs.map_or(true, |e| e.len() == nkeys));
+        let src = rng_source(&mut rng);
+        let mut r = Returned { rc: 0, status: vec![0u8; n + 1], out: vec![0u8; REFUND_RETURN_CBOR_BYTES * n + 1], out_key: vec![ACT_KEY_NONE; n + 1], counts: [0; ACT_ADMIT_COUNTS], return_too_big: 0 };
+        let mut counts = [0u64; ACT_REDEEM_RETURN_COUNTS];
+        r.rc = unsafe {
+            act_redeem_cbor_return_batch(self.ctx, self.set, n, 0, keys.as_ptr(), nkeys as c_int, key_epochs.map_or(std::ptr::null(), |e| e.as_ptr()),
+                                         sign_with.map_or(ACT_SIGN_MATCHED, |i| i as c_int), blob.as_ptr(), offsets.as_ptr(),
+                                         charges.map_or(std::ptr::null(), |c| c.as_ptr()), returned.map_or(std::ptr::null(), |t| t.as_ptr()),
+                                         &src as *const ActRngSource as *const u8, ACT_RNG_CALLBACK, r.out.as_mut_ptr(), r.status.as_mut_ptr(),
+                                         r.out_key.as_mut_ptr(), counts.as_mut_ptr())
+        };
+        r.counts.copy_from_slice(&counts[..ACT_ADMIT_COUNTS]); r.return_too_big = counts[ACT_ADMIT_COUNTS];
+        r.status.truncate(n); r.out.truncate(REFUND_RETURN_CBOR_BYTES * n); r.out_key.truncate(n);
+        r
+    }
+    /// The sign-only call: `kprime` and `status_in` as `act_verify_spend_keyring_batch` left them.  It does not see `s`: the CALLER
+    /// bounds `returned[i] <= s_i`.  -> (rc, statuses, 160-byte records)
+    pub fn refund_sign_return(&self, keys: &[u8], key_index: &[u8], kprime: &[u8], status_in: &[u8], returned: Option<&[u8]>, rng_slices: &[u8]) -> (c_int, Vec<u8>, Vec<u8>) {
+        let n = status_in.len();
+        assert!(key_index.len() == n && kprime.len() == 32 * n && returned.map_or(true, |t| t.len() == 32 * n));
+        let (mut status, mut out) = (vec![0u8; n + 1], vec![0u8; 160 * n + 1]);
+        let rc = unsafe {
+            act_refund_sign_return_keyring_batch(self.ctx, n, 0, keys.as_ptr(), (keys.len() / 64) as c_int, key_index.as_ptr(), kprime.as_ptr(), status_in.as_ptr(),
+                                                 rng_slices.as_ptr(), ACT_RNG_SEQUENTIAL, returned.map_or(std::ptr::null(), |t| t.as_ptr()), out.as_mut_ptr(),
+                                                 status.as_mut_ptr())
+        };
+        status.truncate(n); out.truncate(160 * n);
+        (rc, status, out)
+    }
+    /// The client's side: `PreRefund::to_credit_token` over RefundReturn records.  -> (rc, statuses, 160-byte CreditToken records whose
+    /// balance is `m + t`); 4 = the proof over `g + K' + t h1` fails, 8 = a validly signed `t > s`.
+    pub fn refund_to_credit_token_return(&self, prerefund: &[u8], proofs: &[u8], refund_return: &[u8], w: &[u8; 32]) -> (c_int, Vec<u8>, Vec<u8>) {
+        let n = prerefund.len() / 96;
+        assert!(prerefund.len() == 96 * n && proofs.len() == PROOF_BYTES * n && refund_return.len() == 160 * n);
+        let (mut status, mut tokens) = (vec![0u8; n + 1], vec![0u8; 160 * n + 1]);
+        let rc = unsafe {
+            act_refund_to_credit_token_return_batch(self.ctx, n, 0, prerefund.as_ptr(), proofs.as_ptr(), refund_return.as_ptr(), w.as_ptr(), tokens.as_mut_ptr(),
+                                                    status.as_mut_ptr())
+        };
+        status.truncate(n); tokens.truncate(160 * n);
+        (rc, status, tokens)
     }
 }
 
