@@ -294,13 +294,15 @@ class PrivateKey(_Cbor):
             raise Error(st[0])
         return RefundReturn(out)
 
-    def redeem_return_batch(self, params: Params, db: "NullifierDb", proofs: Sequence["SpendProof"], rng, returned: Sequence = None, charges: Sequence = None) -> List["RefundReturn"]:
+    def redeem_return_batch(self, params: Params, db: "NullifierDb", proofs: Sequence["SpendProof"], rng, returned: Sequence = None, charges: Sequence = None,
+                            unique: bool = False) -> List["RefundReturn"]:
         """redeem_admit_batch with the amounts the issuer returns (Keyring.redeem_return_batch): entry i is a RefundReturn or an Error"""
-        res, _ = Keyring([self]).redeem_return_batch(params, db, proofs, rng, returned=returned, charges=charges)
+        res, _ = Keyring([self]).redeem_return_batch(params, db, proofs, rng, returned=returned, charges=charges, unique=unique)
         return res
 
-    def redeem_return_cbor_batch(self, params: Params, db: "NullifierDb", msgs: Sequence[bytes], rng, nbits: int = L, returned: Sequence = None, charges: Sequence = None) -> list:
-        res, _ = Keyring([self]).redeem_return_cbor_batch(params, db, msgs, rng, nbits, returned=returned, charges=charges)
+    def redeem_return_cbor_batch(self, params: Params, db: "NullifierDb", msgs: Sequence[bytes], rng, nbits: int = L, returned: Sequence = None, charges: Sequence = None,
+                                 unique: bool = False) -> list:
+        res, _ = Keyring([self]).redeem_return_cbor_batch(params, db, msgs, rng, nbits, returned=returned, charges=charges, unique=unique)
         return res
 
     # ---- replayable redemption: a retried SpendProof gets its Refund again (INTEGRATION.md section 10) ----------------------------------
@@ -411,28 +413,35 @@ class Keyring:
         return [out[i] if st[i] == 0 else _wire_error(st[i]) for i in range(len(msgs))], self._indices(st, ok)
 
     def redeem_return_batch(self, params: Params, db: "NullifierDb", proofs: Sequence["SpendProof"], rng, returned: Sequence = None, charges: Sequence = None,
-                            sign_with=None) -> Tuple[list, list]:
+                            sign_with=None, unique: bool = False) -> Tuple[list, list]:
         """The reserve-then-return server step (act_redeem_return_batch): redeem_admit_batch, and every accepted proof is refunded
         with returned[i] of the s_i credits it spends -- entry i is a RefundReturn whose client ends with c - s_i + returned[i].
         returned[i] > s_i is Error 249: not looked up, not verified, not recorded, not signed.  `self.last_admit_counts`: the call's
-        counts (capi.REDEEM_RETURN_COUNTS).  There is no replay form of this call on purpose (include/act_mi355x.h)."""
+        counts (capi.REDEEM_RETURN_COUNTS), also kept as `self.last_return_counts`.  unique=True (act_redeem_return_unique_batch): a
+        proof with the bytes of an earlier proof of the batch is not verified, WHATEVER its returned amount -- the first one is the one
+        that is signed, over its own amount, and the others are DoubleSpendError as they are without unique; the results are the same
+        and the counts gain "copies" (capi.REDEEM_RETURN_UNIQUE_COUNTS, ten names).  There is no replay form of this call on purpose
+        (include/act_mi355x.h)."""
         nbits = proofs[0].nbits if proofs else L
         e = params.engine(nbits)
         pb = b"".join(p.record for p in proofs)
         cc = b"".join(scalar(c) for c in charges) if charges is not None else None
         tt = b"".join(scalar(t) for t in returned) if returned is not None else None
         st, out, ok, self.last_admit_counts = _draw_signed(rng, len(proofs), lambda src, mode: e.redeem_return(
-            db.set, self._records(), pb, src, mode, self._sign_key(sign_with), charges=cc, returned=tt, key_epochs=self.epochs))
+            db.set, self._records(), pb, src, mode, self._sign_key(sign_with), charges=cc, returned=tt, key_epochs=self.epochs, unique=unique))
+        self.last_return_counts = self.last_admit_counts
         return [RefundReturn(out[160 * i:160 * i + 160]) if st[i] == 0 else Error(st[i]) for i in range(len(proofs))], self._indices(st, ok)
 
     def redeem_return_cbor_batch(self, params: Params, db: "NullifierDb", msgs: Sequence[bytes], rng, nbits: int = L, returned: Sequence = None,
-                                 charges: Sequence = None, sign_with=None) -> Tuple[list, list]:
-        """the same on wire bytes (act_redeem_cbor_return_batch): entry i is a CBOR RefundReturn message, a CborError or an Error"""
+                                 charges: Sequence = None, sign_with=None, unique: bool = False) -> Tuple[list, list]:
+        """the same on wire bytes (act_redeem_cbor_return_batch; unique=True: act_redeem_cbor_return_unique_batch, a copy has the same
+        length and the same bytes as an earlier message): entry i is a CBOR RefundReturn message, a CborError or an Error"""
         e = params.engine(nbits)
         cc = b"".join(scalar(c) for c in charges) if charges is not None else None
         tt = b"".join(scalar(t) for t in returned) if returned is not None else None
         st, out, ok, self.last_admit_counts = _draw_signed(rng, len(msgs), lambda src, mode: e.redeem_cbor_return(
-            db.set, self._records(), list(msgs), src, mode, self._sign_key(sign_with), charges=cc, returned=tt, key_epochs=self.epochs))
+            db.set, self._records(), list(msgs), src, mode, self._sign_key(sign_with), charges=cc, returned=tt, key_epochs=self.epochs, unique=unique))
+        self.last_return_counts = self.last_admit_counts
         return [out[i] if st[i] == 0 else _wire_error(st[i]) for i in range(len(msgs))], self._indices(st, ok)
 
     def redeem_replay_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", proofs: Sequence["SpendProof"], nonce_key: bytes, sign_with=None,
@@ -585,6 +594,15 @@ class PreRefund(_Cbor):
         if st[0]:
             raise Error(st[0])
         return CreditToken(out)
+
+    def to_credit_token_return_ring(self, params: Params, spend_proof: SpendProof, refund_return: "RefundReturn", publics: Sequence[PublicKey]) -> Tuple[CreditToken, int]:
+        """to_credit_token_return against the issuer's published keys (act_refund_to_credit_token_return_keyring_batch): a RefundReturn
+        names no key either, and Keyring.redeem_return_batch(sign_with=i) signs with any ring key.  -> (token holding m + t, index of the
+        first ring key the record verifies under); Error 4 when no ring key does, Error 8 for a t > s that a ring key validly signed."""
+        st, out, ok = params.engine(spend_proof.nbits).refund_to_credit_token_return_ring(self.record, spend_proof.record, refund_return.record, [p.w for p in publics])
+        if st[0]:
+            raise Error(st[0])
+        return CreditToken(out), ok[0]
 
     def to_credit_token_ring(self, params: Params, spend_proof: SpendProof, refund: "Refund", publics: Sequence[PublicKey]) -> Tuple[CreditToken, int]:
         """to_credit_token against the issuer's published keys: a Refund names no key, and Keyring.refund_batch(sign_with=i) moves a

@@ -21,6 +21,7 @@ STATUS_WRONG_CHARGE = 250                             # act_redeem_*admit_batch:
 ADMIT_COUNTS = ("lanes", "wire_rejected", "wrong_charge", "spent_before", "verified", "rejected_by_verification", "double_spend_after", "accepted")
 STATUS_RETURN_TOO_BIG = 249                           # act_redeem_*return_batch: the returned amount t exceeds the charge s
 REDEEM_RETURN_COUNTS = ADMIT_COUNTS + ("return_too_big",)      # act_redeem_*return_batch
+REDEEM_RETURN_UNIQUE_COUNTS = REDEEM_RETURN_COUNTS + ("copies",)      # act_redeem_*return_unique_batch
 ADMIT_UNIQUE_COUNTS = ADMIT_COUNTS + ("copies",)      # act_redeem_*admit_unique_batch: lanes with the bytes of an earlier lane, not verified
 REPLAY_COUNTS = ("lanes", "rejected_by_verification", "fresh", "replayed", "double_spend", "unanswered")      # act_redeem_*replay_batch
 ADMIT_REPLAY_COUNTS = ("lanes", "wire_rejected", "wrong_charge", "foreign_spend", "retry_candidates", "verified", "rejected_by_verification", "fresh", "replayed",
@@ -62,6 +63,7 @@ EXPORTS = [
     "act_issue_check_cbor_batch", "act_issue_sign_cbor_batch", "act_issue_cbor_batch",
     "act_node_issue_check_cbor_batch", "act_node_issue_sign_cbor_batch", "act_node_issue_cbor_batch",
     "act_refund_sign_return_keyring_batch", "act_redeem_return_batch", "act_redeem_cbor_return_batch", "act_refund_to_credit_token_return_batch",
+    "act_refund_to_credit_token_return_keyring_batch", "act_redeem_return_unique_batch", "act_redeem_cbor_return_unique_batch",
     "act_ctx_host_hash_stats", "act_ctx_set_tiny_calls", "act_node_set_balance", "act_node_device_stats", "act_node_balance_state", "act_debug_set_slowdown", "act_debug_fail_next_signs",
 ]
 CBOR_TYPES = {"IssuanceRequest": 1, "IssuanceResponse": 2, "SpendProof": 3, "Refund": 4, "PrivateKey": 5, "PublicKey": 6,
@@ -266,6 +268,10 @@ def load() -> C.CDLL:
     lib.act_redeem_return_batch.argtypes = [vp, vp, sz, i32, u8p, i32, u32p, i32, u8p, u8p, u8p, u8p, i32, u8p, u8p, u8p, u64p]
     lib.act_redeem_cbor_return_batch.argtypes = [vp, vp, sz, i32, u8p, i32, u32p, i32, u8p, vp, u8p, u8p, u8p, i32, u8p, u8p, u8p, u64p]
     lib.act_refund_to_credit_token_return_batch.argtypes = [vp, sz, i32, u8p, u8p, u8p, u8p, u8p, u8p]
+    # ... against a ring of public keys, and the return calls' unique forms (out_counts: ACT_REDEEM_RETURN_UNIQUE_COUNTS values)
+    lib.act_refund_to_credit_token_return_keyring_batch.argtypes = lib.act_refund_to_credit_token_keyring_batch.argtypes
+    lib.act_redeem_return_unique_batch.argtypes = lib.act_redeem_return_batch.argtypes
+    lib.act_redeem_cbor_return_unique_batch.argtypes = lib.act_redeem_cbor_return_batch.argtypes
     lib.act_issue_check_cbor_batch.argtypes = [vp, sz, i32, u8p, vp, u8p, u8p]
     lib.act_issue_sign_cbor_batch.argtypes = [vp, sz, i32, u8p, u8p, u8p, u8p, u8p, i32, u8p, u8p]
     lib.act_issue_cbor_batch.argtypes = [vp, sz, i32, u8p, u8p, vp, u8p, u8p, i32, u8p, u8p]
@@ -791,9 +797,12 @@ class Engine:
         return st.tobytes(), out.tobytes(), ok.tobytes()
 
     def client_ring_ptr(self, fn: str, publics, n: int, mem: int, **p):
-        """the same on raw pointers of either kind (device-memory callers): fn = issuance / refund; the ring itself is host bytes"""
+        """the same on raw pointers of either kind (device-memory callers): fn = issuance / refund / refund_return (p["refund"]: the
+        160-byte RefundReturn records); the ring itself is host bytes"""
         pw, kw = _in(b"".join(publics)); nk = len(publics)
-        if fn == "issuance":
+        if fn == "refund_return":
+            self._ck(self.lib.act_refund_to_credit_token_return_keyring_batch(self.ctx, n, mem, p["pre"], p["proofs"], p["refund"], pw, nk, p["out"], p["status"], p["out_key"]))
+        elif fn == "issuance":
             self._ck(self.lib.act_issuance_to_credit_token_keyring_batch(self.ctx, n, mem, p["pre"], pw, nk, p["req"], p["resp"], p["out"], p["status"], p["out_key"]))
         else:
             self._ck(self.lib.act_refund_to_credit_token_keyring_batch(self.ctx, n, mem, p["pre"], p["proofs"], p["refund"], pw, nk, p["out"], p["status"], p["out_key"]))
@@ -898,36 +907,42 @@ class Engine:
         return st.tobytes(), out.tobytes()
 
     def redeem_return(self, nullifier_set, keys, proofs: bytes, rng, rng_mode: int = RNG_PER_LANE, sign_key: int = SIGN_MATCHED, charges: bytes = None,
-                      returned: bytes = None, key_epochs=None, raw: bool = False):
+                      returned: bytes = None, key_epochs=None, raw: bool = False, unique: bool = False):
         """redeem_admit with the amounts the issuer returns: a lane with t > s is STATUS_RETURN_TOO_BIG (not looked up, not verified,
         not recorded, not signed); the others are signed over X_A = g + K' + t h1.  -> (statuses, 160-byte RefundReturn records,
-        out_key, counts dict); raw=True: (rc, ...), no exception"""
+        out_key, counts dict); raw=True: (rc, ...), no exception.  unique=True: act_redeem_return_unique_batch -- a lane with the proof
+        bytes of an earlier lane (whatever its t) is not verified; the same answers, and counts gains "copies"."""
         n = len(proofs) // self.proof_bytes; out = np.full(160 * n, 7 if raw else 0, np.uint8); st = np.zeros(n, np.uint8); ok = np.zeros(n, np.uint8)
         pk, kk = _in(b"".join(keys)); p0, k0 = _in(proofs, self.proof_bytes * n); p1, k1 = _rng_arg(rng)
         pc, kc = _in(charges, 32 * n) if charges is not None else (None, None)
         pt, kt = _in(returned, 32 * n) if returned is not None else (None, None)
         ke = _epoch_table(key_epochs, len(keys)) if key_epochs is not None else None
-        cnt = (C.c_uint64 * len(REDEEM_RETURN_COUNTS))()
-        rc = self.lib.act_redeem_return_batch(self.ctx, nullifier_set.h, n, MEM_HOST, pk, len(keys), ke.ctypes.data if ke is not None else None, sign_key, p0, pc, pt,
-                                              p1, rng_mode, out.ctypes.data, st.ctypes.data, ok.ctypes.data, cnt)
-        counts = dict(zip(REDEEM_RETURN_COUNTS, (int(v) for v in cnt)))
+        names = REDEEM_RETURN_UNIQUE_COUNTS if unique else REDEEM_RETURN_COUNTS
+        cnt = (C.c_uint64 * len(names))()
+        fn = self.lib.act_redeem_return_unique_batch if unique else self.lib.act_redeem_return_batch
+        rc = fn(self.ctx, nullifier_set.h, n, MEM_HOST, pk, len(keys), ke.ctypes.data if ke is not None else None, sign_key, p0, pc, pt,
+                p1, rng_mode, out.ctypes.data, st.ctypes.data, ok.ctypes.data, cnt)
+        counts = dict(zip(names, (int(v) for v in cnt)))
         if raw:
             return rc, st.tobytes(), out.tobytes(), ok.tobytes(), counts
         self._ck(rc)
         return st.tobytes(), out.tobytes(), ok.tobytes(), counts
 
     def redeem_cbor_return(self, nullifier_set, keys, messages: list, rng, rng_mode: int = RNG_SEQUENTIAL, sign_key: int = SIGN_MATCHED, charges: bytes = None,
-                           returned: bytes = None, key_epochs=None, raw: bool = False):
-        """wire bytes in, wire bytes out -> (statuses, list of CBOR RefundReturn messages (b"" where not signed), out_key, counts dict)"""
+                           returned: bytes = None, key_epochs=None, raw: bool = False, unique: bool = False):
+        """wire bytes in, wire bytes out -> (statuses, list of CBOR RefundReturn messages (b"" where not signed), out_key, counts dict);
+        unique=True: act_redeem_cbor_return_unique_batch (a copy has the same length and the same bytes as an earlier message)"""
         n = len(messages); p0, k0, offs = _msgs(messages); ml = self.cbor_size("RefundReturn")
         st = np.zeros(n, np.uint8); ok = np.zeros(n, np.uint8); out = np.zeros(ml * n, np.uint8); pk, kk = _in(b"".join(keys)); pr, kr = _rng_arg(rng)
         pc, kc = _in(charges, 32 * n) if charges is not None else (None, None)
         pt, kt = _in(returned, 32 * n) if returned is not None else (None, None)
         ke = _epoch_table(key_epochs, len(keys)) if key_epochs is not None else None
-        cnt = (C.c_uint64 * len(REDEEM_RETURN_COUNTS))()
-        rc = self.lib.act_redeem_cbor_return_batch(self.ctx, nullifier_set.h, n, MEM_HOST, pk, len(keys), ke.ctypes.data if ke is not None else None, sign_key, p0,
-                                                   offs.ctypes.data, pc, pt, pr, rng_mode, out.ctypes.data, st.ctypes.data, ok.ctypes.data, cnt)
-        counts = dict(zip(REDEEM_RETURN_COUNTS, (int(v) for v in cnt)))
+        names = REDEEM_RETURN_UNIQUE_COUNTS if unique else REDEEM_RETURN_COUNTS
+        cnt = (C.c_uint64 * len(names))()
+        fn = self.lib.act_redeem_cbor_return_unique_batch if unique else self.lib.act_redeem_cbor_return_batch
+        rc = fn(self.ctx, nullifier_set.h, n, MEM_HOST, pk, len(keys), ke.ctypes.data if ke is not None else None, sign_key, p0,
+                offs.ctypes.data, pc, pt, pr, rng_mode, out.ctypes.data, st.ctypes.data, ok.ctypes.data, cnt)
+        counts = dict(zip(names, (int(v) for v in cnt)))
         b = out.tobytes()
         msgs = [b[i * ml:(i + 1) * ml] if st[i] == 0 else b"" for i in range(n)]
         if raw:
@@ -937,19 +952,24 @@ class Engine:
         return st.tobytes(), msgs, ok.tobytes(), counts
 
     def return_ptr(self, fn: str, keys, n: int, mem: int, **p):
-        """the return calls on raw pointers of either kind: fn = redeem / redeem_cbor; p as admit_ptr's plus returned.  -> counts dict"""
+        """the return calls on raw pointers of either kind: fn = redeem / redeem_cbor; p as admit_ptr's plus returned (unique: the
+        act_redeem_*return_unique_batch forms).  -> counts dict"""
         pk, kk = _in(b"".join(keys)); nk = len(keys)
         ke = _epoch_table(p["key_epochs"], nk) if p.get("key_epochs") is not None else None
         kep = ke.ctypes.data if ke is not None else None
-        cnt = (C.c_uint64 * len(REDEEM_RETURN_COUNTS))()
+        unique = bool(p.get("unique"))
+        names = REDEEM_RETURN_UNIQUE_COUNTS if unique else REDEEM_RETURN_COUNTS
+        cnt = (C.c_uint64 * len(names))()
         if fn == "redeem":
-            rc = self.lib.act_redeem_return_batch(self.ctx, p["set"].h, n, mem, pk, nk, kep, p.get("sign_key", SIGN_MATCHED), p["proofs"], p.get("charges") or None,
-                                                  p.get("returned") or None, p["rng"], p["rng_mode"], p["out"], p["status"], p["out_key"], cnt)
+            call = self.lib.act_redeem_return_unique_batch if unique else self.lib.act_redeem_return_batch
+            rc = call(self.ctx, p["set"].h, n, mem, pk, nk, kep, p.get("sign_key", SIGN_MATCHED), p["proofs"], p.get("charges") or None,
+                      p.get("returned") or None, p["rng"], p["rng_mode"], p["out"], p["status"], p["out_key"], cnt)
         else:
-            rc = self.lib.act_redeem_cbor_return_batch(self.ctx, p["set"].h, n, mem, pk, nk, kep, p.get("sign_key", SIGN_MATCHED), p["cbor"], p.get("offsets") or None,
-                                                       p.get("charges") or None, p.get("returned") or None, p["rng"], p["rng_mode"], p["out"], p["status"], p["out_key"], cnt)
+            call = self.lib.act_redeem_cbor_return_unique_batch if unique else self.lib.act_redeem_cbor_return_batch
+            rc = call(self.ctx, p["set"].h, n, mem, pk, nk, kep, p.get("sign_key", SIGN_MATCHED), p["cbor"], p.get("offsets") or None,
+                      p.get("charges") or None, p.get("returned") or None, p["rng"], p["rng_mode"], p["out"], p["status"], p["out_key"], cnt)
         self._ck(rc)
-        return dict(zip(REDEEM_RETURN_COUNTS, (int(v) for v in cnt)))
+        return dict(zip(names, (int(v) for v in cnt)))
 
     def refund_to_credit_token_return(self, prerefund: bytes, proofs: bytes, refund_return: bytes, w: bytes):
         """refund_to_credit_token over 160-byte RefundReturn records -> (statuses, tokens with balance m + t); t > s is status 8"""
@@ -957,6 +977,17 @@ class Engine:
         p0, k0 = _in(prerefund, 96 * n); p1, k1 = _in(proofs, self.proof_bytes * n); p2, k2 = _in(refund_return, 160 * n); pw, kw = _in(w, 32)
         self._ck(self.lib.act_refund_to_credit_token_return_batch(self.ctx, n, MEM_HOST, p0, p1, p2, pw, out.ctypes.data, st.ctypes.data))
         return st.tobytes(), out.tobytes()
+
+    def refund_to_credit_token_return_ring(self, prerefund: bytes, proofs: bytes, refund_return: bytes, publics, raw: bool = False):
+        """refund_to_credit_token_return against a ring of issuer public keys -> (statuses, tokens, out_key bytes: the smallest ring
+        index every accepted lane verifies under, KEY_NONE elsewhere).  raw=True: (rc, statuses, tokens, out_key), no exception."""
+        n = len(prerefund) // 96; out = np.zeros(160 * n, np.uint8); st = np.zeros(n, np.uint8); ok = np.zeros(n, np.uint8)
+        p0, k0 = _in(prerefund, 96 * n); p1, k1 = _in(proofs, self.proof_bytes * n); p2, k2 = _in(refund_return, 160 * n); pw, kw = _in(b"".join(publics))
+        rc = self.lib.act_refund_to_credit_token_return_keyring_batch(self.ctx, n, MEM_HOST, p0, p1, p2, pw, len(publics), out.ctypes.data, st.ctypes.data, ok.ctypes.data)
+        if raw:
+            return rc, st.tobytes(), out.tobytes(), ok.tobytes()
+        self._ck(rc)
+        return st.tobytes(), out.tobytes(), ok.tobytes()
 
     # ---- replayable redemption (act_redeem_replay_batch / act_redeem_cbor_replay_batch / act_replay_derive_batch) -------------------
     def redeem_replay(self, nullifier_set, receipts, keys, proofs: bytes, nonce_key: bytes, sign_key: int = SIGN_MATCHED, key_epochs=None, raw: bool = False):

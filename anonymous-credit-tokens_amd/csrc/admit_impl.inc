@@ -129,7 +129,8 @@ struct AdmitGather {
   }
 };
 
-// ret (the return calls): a ninth value, the lanes whose returned amount exceeded their charge (ACT_REDEEM_RETURN_COUNTS)
+// ret (the return calls): a ninth value, the lanes whose returned amount exceeded their charge (ACT_REDEEM_RETURN_COUNTS); their
+// unique forms keep a tenth, the copies, which the caller fills in (ACT_REDEEM_RETURN_UNIQUE_COUNTS)
 void admit_counts_of(uint64_t* out_counts, size_t n, const uint8_t* pre, size_t m, const uint8_t* cst, bool ret = false) {
   if (!out_counts) return;
   uint64_t k[ACT_REDEEM_RETURN_COUNTS] = {n, 0, 0, 0, m, 0, 0, 0, 0};
@@ -185,9 +186,9 @@ static int redeem_replay_locked(act_ctx* c, act_nullifier_set* set, act_nullifie
 static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int mem, const uint8_t* keys, int nkeys, const uint32_t* key_epochs, int sign_key,
                              const uint8_t* proof, const uint8_t* cbor, const uint64_t* offsets, const uint8_t* charge, const uint8_t* rng, int rng_mode,
                              uint8_t* out, uint8_t* status, uint8_t* out_key, uint64_t* out_counts, bool unique = false, AdmitReplay* rp = nullptr,
-                             const RedeemReturn* ret = nullptr) {      // ret (the return calls, DESIGN 4.10): never with unique or rp
+                             const RedeemReturn* ret = nullptr) {      // ret (the return calls, DESIGN 4.10): never with rp
   const bool wire = cbor != nullptr, dev = mem == ACT_MEM_DEVICE;
-  if (out_counts) memset(out_counts, 0, sizeof(uint64_t) * (ret ? ACT_REDEEM_RETURN_COUNTS : unique ? ACT_ADMIT_UNIQUE_COUNTS : ACT_ADMIT_COUNTS));
+  if (out_counts) memset(out_counts, 0, sizeof(uint64_t) * (ret ? (unique ? ACT_REDEEM_RETURN_UNIQUE_COUNTS : ACT_REDEEM_RETURN_COUNTS) : unique ? ACT_ADMIT_UNIQUE_COUNTS : ACT_ADMIT_COUNTS));
   if (rp && rp->out_counts) memset(rp->out_counts, 0, sizeof(uint64_t) * (unique ? ACT_ADMIT_REPLAY_UNIQUE_COUNTS : ACT_ADMIT_REPLAY_COUNTS));
   if (!c || (mem != ACT_MEM_HOST && mem != ACT_MEM_DEVICE) || n > ((size_t)1 << 30)) return ACT_ERR_ARG;
   if (n && ((!proof && !cbor) || !out || !status || !out_key)) return ACT_ERR_ARG;
@@ -198,7 +199,7 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
   int rc = redeem_keyring_refused(c, set, 0, keys, nkeys, key_epochs, sign_key, nullptr, nullptr, rng, rng_mode, nullptr, nullptr, nullptr);
   if (rc) return rc;
   if (rp && (rc = replay_refused(c, set, rp->receipts, rp->nonce_key, n, key_epochs, nkeys))) return rc;
-  if (ret && (unique || rp)) return ACT_ERR_ARG;
+  if (ret && rp) return ACT_ERR_ARG;
   if (n == 0) return redeem_keyring_impl(c, set, 0, mem, keys, nkeys, key_epochs, sign_key, nullptr, nullptr, nullptr, rng, rng_mode, nullptr, nullptr, nullptr);
   // one admission call at a time per context: the gathered rng slices live in the context's own buffer (d_admit_rng)
   std::lock_guard<std::mutex> admission(c->admit_mu);
@@ -457,7 +458,8 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
       c_rng = rng_host.data();
     }
   }
-  // the returned amounts follow their lanes too (public; the compact copy lies behind the other compact arrays, 32-byte aligned)
+  // the returned amounts follow their lanes too (public; the compact copy lies behind the other compact arrays, 32-byte aligned).  Like
+  // the rng slices they are gathered by v_idx: in the unique forms the amounts of the lanes that are verified -- a copy's t is never read
   RedeemReturn cret{nullptr};
   if (t_in) {
     uint8_t* ct = arr.p + ((mv * 69 + 31) & ~(size_t)31);
@@ -520,7 +522,7 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
   }
   admit_counts_of(out_counts, n, h_pre.data(), mv, dev ? h_cst.data() : cst, ret != nullptr);
   if (rp && rp->out_counts && tc[0] == mv) admit_replay_counts_of(rp->out_counts, n, h_pre.data(), rp->candidates, mv, tc);
-  if (out_counts && unique) out_counts[ACT_ADMIT_COUNTS] = cp.copies;
+  if (out_counts && unique) out_counts[ret ? ACT_REDEEM_RETURN_COUNTS : ACT_ADMIT_COUNTS] = cp.copies;
   if (rp && rp->out_counts && unique && cp.copies && tc[0] == mv) {      // copies, then the copies whose leader ended 0
     const uint8_t* fin = dev ? h_fin.data() : status;
     uint64_t served = 0;
@@ -582,4 +584,28 @@ extern "C" int act_redeem_cbor_return_batch(act_ctx* c, act_nullifier_set* set, 
   const RedeemReturn ret{returned};
   return redeem_admit_impl(c, set, n, mem, keys, nkeys, key_epochs, sign_key, nullptr, cbor ? cbor : &none, offsets, charge, rng, rng_mode, out_refund_return_cbor,
                            status, out_key, out_counts, false, nullptr, &ret);
+}
+
+// The return calls with the copy stage of the unique forms in its usual place, behind the screen and in front of verification.  Equality
+// is decided on the proof bytes alone: t takes no part in it, because what a lane that passed the screen is answered depends on t only if
+// it is the lane that is signed, and that lane is the leader -- in act_redeem_(cbor_)return_batch lanes that share a fresh nullifier are
+// all verified and the first valid one in lane order wins, whatever the others' t.  A lane the screen sheds (t > s among the reasons) is
+// neither a leader nor a copy.  out_counts: ACT_REDEEM_RETURN_UNIQUE_COUNTS values.
+extern "C" int act_redeem_return_unique_batch(act_ctx* c, act_nullifier_set* set, size_t n, int mem, const uint8_t* keys, int nkeys, const uint32_t* key_epochs,
+                                              int sign_key, const uint8_t* proof, const uint8_t* charge, const uint8_t* returned, const uint8_t* rng, int rng_mode,
+                                              uint8_t* out_refund_return, uint8_t* status, uint8_t* out_key, uint64_t* out_counts) {
+  if (n && !proof) { if (out_counts) memset(out_counts, 0, sizeof(uint64_t) * ACT_REDEEM_RETURN_UNIQUE_COUNTS); return ACT_ERR_ARG; }
+  const RedeemReturn ret{returned};
+  return redeem_admit_impl(c, set, n, mem, keys, nkeys, key_epochs, sign_key, proof, nullptr, nullptr, charge, rng, rng_mode, out_refund_return, status, out_key,
+                           out_counts, true, nullptr, &ret);
+}
+extern "C" int act_redeem_cbor_return_unique_batch(act_ctx* c, act_nullifier_set* set, size_t n, int mem, const uint8_t* keys, int nkeys, const uint32_t* key_epochs,
+                                                   int sign_key, const uint8_t* cbor, const uint64_t* offsets, const uint8_t* charge, const uint8_t* returned,
+                                                   const uint8_t* rng, int rng_mode, uint8_t* out_refund_return_cbor, uint8_t* status, uint8_t* out_key,
+                                                   uint64_t* out_counts) {
+  if (n && !cbor) { if (out_counts) memset(out_counts, 0, sizeof(uint64_t) * ACT_REDEEM_RETURN_UNIQUE_COUNTS); return ACT_ERR_ARG; }
+  static const uint8_t none = 0;
+  const RedeemReturn ret{returned};
+  return redeem_admit_impl(c, set, n, mem, keys, nkeys, key_epochs, sign_key, nullptr, cbor ? cbor : &none, offsets, charge, rng, rng_mode, out_refund_return_cbor,
+                           status, out_key, out_counts, true, nullptr, &ret);
 }

@@ -1,6 +1,8 @@
 // client_ring_impl.inc — included by engine.hip inside its extern "C" block, behind client_impl.inc: the client's side of key rotation.
 //   act_issuance_to_credit_token_keyring_batch    PreIssuance::to_credit_token against a ring of issuer public keys
 //   act_refund_to_credit_token_keyring_batch      PreRefund::to_credit_token against the same
+//   act_refund_to_credit_token_return_keyring_batch   the same over RefundReturn records (DESIGN 4.10): phase A with t h1 in X_A, the
+//                                                 candidates and hashes at the 160-byte stride, k_client_ring_return_finish behind them
 // Neither message names the key it was signed with, and w enters the check only through X_g and Y_g (client_ring_lanes.h).  A ring
 // call is therefore client_batch's schedule -- same chunks, same staging and wiping of the secret `pre` records, same host / device
 // memory handling -- with phase A run ONCE under ring key 0 (fused = 0) and per chunk: the candidates X_g,k / Y_g,k of the other keys
@@ -72,14 +74,14 @@ static int client_ring_set(act_ctx* c, const uint8_t* ring_w, uint32_t nkeys) {
 }
 
 static int client_ring_batch(act_ctx* c, size_t n, int mem, int label, const uint8_t* pre, const uint8_t* ring_w, uint32_t nkeys, const uint8_t* req,
-                             const uint8_t* resp, const uint8_t* proofs, uint8_t* out_token, uint8_t* status, uint8_t* out_key) {
+                             const uint8_t* resp, const uint8_t* proofs, uint8_t* out_token, uint8_t* status, uint8_t* out_key, bool with_t = false) {
   Call call(c, n);
   HIPCK(c, hipSetDevice(c->device));
   int rc = client_ring_set(c, ring_w, nkeys); if (rc) return rc;
   ClientRingWs* ws = c->client_ring_ws;
   const bool issuance = label == LABEL_RESPOND;
   const uint32_t extra = nkeys - 1u;
-  const size_t pre_b = issuance ? 64 : 96, resp_b = issuance ? 160 : 128, pb = ProofLayout{c->L}.bytes();
+  const size_t pre_b = issuance ? 64 : 96, resp_b = client_ring_resp_stride(label, with_t), pb = ProofLayout{c->L}.bytes();
   // client_batch's chunk schedule: host-memory refund calls in quarters that alternate between the two slots, everything else on one slot
   size_t chunk = std::min(c->max_batch, std::max<size_t>(16384, (n / 4 + 1023) / 1024 * 1024));
   const bool taper_off = tune(T_NO_TAPER) != 0;
@@ -97,7 +99,7 @@ static int client_ring_batch(act_ctx* c, size_t n, int mem, int label, const uin
     ClientRingArgs r{}; r.tabw = ws->d_tabw; r.nkeys = nkeys; r.cand = ws->d_cand[s]; r.xofs = ws->d_xofs[s]; r.out_key = ws->d_okey[s];
     ClientArgs& a = r.c;
     a.P = c->P; a.w = c->w_pub; a.n = m; a.label = label; a.coords = sl.d_coords; a.trs = sl.d_trs; a.flags = sl.d_flags; a.pbk = sl.d_buckets;
-    a.xof = sl.d_xof; a.status = sl.d_status;
+    a.xof = sl.d_xof; a.status = sl.d_status; a.with_t = with_t ? 1 : 0;
     if (two_slots && (rc = copy_chain_wait(c, sl, false))) return rc;
     if ((rc = dev_in(c, sl, 0, mem, pre + off * pre_b, (size_t)m * pre_b, &a.pre))) return rc;
     if ((rc = dev_in(c, sl, 1, mem, resp + off * resp_b, (size_t)m * resp_b, &a.resp))) return rc;
@@ -119,7 +121,7 @@ static int client_ring_batch(act_ctx* c, size_t n, int mem, int label, const uin
       if ((rc = prof_launch(c, sl, PK_CLIENT, (uint64_t)m * extra, [&] { launch_client_ring_hash(r, sl.stream); }))) return rc;
     }
     if ((rc = hash_end(c, sl, SMALL_TR_STRIDE, len, m))) return rc;
-    if ((rc = prof_launch(c, sl, PK_CLIENT, m, [&] { launch_client_ring_finish(r, sl.stream); }))) return rc;
+    if ((rc = prof_launch(c, sl, PK_CLIENT, m, [&] { if (with_t) launch_client_ring_return_finish(r, sl.stream); else launch_client_ring_finish(r, sl.stream); }))) return rc;
     if ((rc = dev_out_end(c, sl, mem, out_token + off * 160, a.out_token, (size_t)m * 160))) return rc;
     HIPCK(c, hipMemcpyAsync(out_key + off, ws->d_okey[s], m, mem == ACT_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, sl.stream));
     if ((rc = copy_status_out(c, sl, mem, status + off, m))) return rc;
@@ -136,4 +138,11 @@ int act_refund_to_credit_token_keyring_batch(act_ctx* c, size_t n, int mem, cons
                                              const uint8_t* ring_w, uint32_t nkeys, uint8_t* out_token, uint8_t* status, uint8_t* out_key) {
   if (!c || !ring_w || nkeys < 1 || nkeys > ACT_KEYRING_MAX || (n && (!prerefund || !proof || !refund || !out_token || !status || !out_key))) return ACT_ERR_ARG;
   return client_ring_batch(c, n, mem, LABEL_REFUND, prerefund, ring_w, nkeys, nullptr, refund, proof, out_token, status, out_key);
+}
+// PreRefund::to_credit_token over RefundReturn records against a ring (client_ring_return_lanes.h): X_A = g + K' + t h1 does not depend
+// on the key, so the per-extra-key work is that of the call above; status 8 only for a t > s that some ring key validly signed
+int act_refund_to_credit_token_return_keyring_batch(act_ctx* c, size_t n, int mem, const uint8_t* prerefund, const uint8_t* proof, const uint8_t* refund_return,
+                                                    const uint8_t* ring_w, uint32_t nkeys, uint8_t* out_token, uint8_t* status, uint8_t* out_key) {
+  if (!c || !ring_w || nkeys < 1 || nkeys > ACT_KEYRING_MAX || (n && (!prerefund || !proof || !refund_return || !out_token || !status || !out_key))) return ACT_ERR_ARG;
+  return client_ring_batch(c, n, mem, LABEL_REFUND, prerefund, ring_w, nkeys, nullptr, refund_return, proof, out_token, status, out_key, true);
 }

@@ -10,6 +10,7 @@
 //   client_ring_hash_lane    lane = (k, item)   the challenge hash of the item's transcript with the X_g and Y_g payloads replaced
 //                                               (one BLAKE3 chunk: the transcripts are under 512 bytes)
 //   client_ring_finish_lane  lane = item        nkeys challenges against gamma, the smallest index wins -> status, out_key, token
+// (RefundReturn records, ClientArgs::with_t: the same two per-key lanes at the 160-byte stride and the finish of client_ring_return_lanes.h)
 // Direct, not as a difference to key 0: X_g,0 and Y_g,0 exist only as encodings in the transcript, and decoding the two costs more
 // (two square roots, ~530 field operations) than the two products on g that the direct form adds (32 mixed additions, 224).  It
 // also makes the candidates independent of phase A.  gamma and w are public, so gamma w_k is an ADDRESSED fixed-base product like
@@ -45,6 +46,9 @@ ACT_HD uint32_t client_ring_xg_offset(const DevParams& P, int label) {
   return P.prefix_len[label] + (label == LABEL_RESPOND ? 40u : 0u) + 40u * 3u + 8u;
 }
 ACT_HD uint32_t client_ring_tr_len(const DevParams& P, int label) { return P.prefix_len[label] + 40u * (label == LABEL_RESPOND ? 7u : 6u); }
+// bytes per answer record: IssuanceResponse 160, Refund 128, RefundReturn (with_t: A | e | gamma | z | t) 160.  The one place the ring
+// lanes take their stride from; e, gamma and z lie at 32, 64 and 96 in all three.
+ACT_HD uint32_t client_ring_resp_stride(int label, int with_t) { return (label == LABEL_RESPOND || with_t) ? 160u : 128u; }
 
 // X_g,k = e g + w_k and Y_g,k = (z - gamma e) g - gamma w_k (src/lib.rs:537, :541 / :1232, :1234), encoded.  w_k itself is entry 1 of
 // window 0 of its table.  An item whose A or Com_j does not decode is rejected by its flags whatever lands here.
@@ -53,7 +57,7 @@ ACT_HD void client_ring_cand_lane(const ClientRingArgs& r, uint32_t gid) {
   if (gid >= r.c.n * extra) return;
   const uint32_t p = gid % r.c.n, k = gid / r.c.n + 1u;      // key-major: the lanes of a wavefront walk ONE ring table
   const ClientArgs& a = r.c;
-  const uint8_t* resp = a.resp + (size_t)p * (a.label == LABEL_RESPOND ? 160 : 128);
+  const uint8_t* resp = a.resp + (size_t)p * client_ring_resp_stride(a.label, a.with_t);
   const sc e = load_sc(resp + 32), gamma = load_sc(resp + 64), z = load_sc(resp + 96);
   const FbTab tw = client_ring_table(r, k);
   const ge xg = ge_madd(fixed_base_acc(ge_identity(), a.P.tab[BASE_G], e), niels_load(tw.p + NIELS_WORDS));
@@ -119,21 +123,26 @@ ACT_HD void client_ring_hash_lane(const ClientRingArgs& r, uint32_t gid) {
   for (int i = 0; i < 16; i++) q[i] = o[i];
 }
 
-// k_client_b over a ring: the smallest k whose challenge equals gamma (counting down, so that the smallest index is kept).  The
-// token (:554-560 / :1246-1252) does not depend on the key.
-ACT_HD void client_ring_finish_lane(const ClientRingArgs& r, uint32_t p) {
-  const ClientArgs& a = r.c;
-  const bool issuance = a.label == LABEL_RESPOND;
+// the smallest ring index whose challenge for item p equals gamma (counting down, so that the smallest index is kept), or KEY_NONE
+ACT_HD uint32_t client_ring_match(const ClientRingArgs& r, uint32_t p, const sc& gamma) {
   const uint32_t extra = r.nkeys - 1u;
-  const uint8_t* resp = a.resp + (size_t)p * (issuance ? 160 : 128);
-  const sc gamma = load_sc(resp + 64);
   uint32_t match = KEY_NONE;
   for (uint32_t k = r.nkeys; k-- > 0;) {
-    const uint32_t* q = k ? r.xofs + ((size_t)p * extra + (k - 1u)) * 16 : a.xof + (size_t)p * 16;
+    const uint32_t* q = k ? r.xofs + ((size_t)p * extra + (k - 1u)) * 16 : r.c.xof + (size_t)p * 16;
     uint32_t w[16];
     for (int i = 0; i < 16; i++) w[i] = q[i];
     if (sc_equal(sc_from_wide_words(w), gamma)) match = k;
   }
+  return match;
+}
+
+// k_client_b over a ring: the smallest k whose challenge equals gamma.  The token (:554-560 / :1246-1252) does not depend on the key.
+ACT_HD void client_ring_finish_lane(const ClientRingArgs& r, uint32_t p) {
+  const ClientArgs& a = r.c;
+  const bool issuance = a.label == LABEL_RESPOND;
+  const uint8_t* resp = a.resp + (size_t)p * client_ring_resp_stride(a.label, a.with_t);
+  const sc gamma = load_sc(resp + 64);
+  const uint32_t match = client_ring_match(r, p, gamma);
   uint8_t stt = 0;
   if (a.flags[p] & FLAG_UNDECODABLE) stt = 255;
   else if (match == KEY_NONE) stt = issuance ? 2 : 4;       // InvalidIssuanceResponseProof / InvalidRefundProof under every ring key

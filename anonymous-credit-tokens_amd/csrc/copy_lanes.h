@@ -21,7 +21,8 @@
 namespace act {
 
 constexpr uint32_t COPY_NONE = 0xFFFFFFFFu;       // copy_of[] / lead[] of a lane that is not a copy; lane word of an unclaimed slot
-constexpr uint8_t COPY_MARK = 249;                // a copy in the side array the second compaction reads; never a status
+constexpr uint8_t COPY_MARK = 249;                // a copy in the side array the second compaction reads: any non-zero byte would do.  (The
+                                                  // return calls' RETURN_TOO_BIG has this value: a copy is told from a shed lane by lead[] alone.)
 constexpr uint8_t COPY_RECORDED_UNSIGNED = 251;   // ACT_STATUS_RECORDED_UNSIGNED
 
 // ---- where a survivor's input bytes are ---------------------------------------------------------------------------------------------

@@ -19,7 +19,7 @@
 #include <vector>
 #include "kernels.h"
 #include "keyring.h"
-#include "client_ring_lanes.h"
+#include "client_ring_return_lanes.h"
 #include "admit.h"
 #include "replay_lanes.h"
 #include "admit_replay_lanes.h"

@@ -1020,9 +1020,34 @@ int act_ubench_table_read(act_ctx *ctx, int base, int waves_per_simd, int in_fli
  * (nonce_key, key, k, enc(K')), so a retry with another t would be signed with the SAME e over an X_A that differs by (t1 - t2) h1:
  * the two A values differ by (t1 - t2) (e + x)^-1 h1, which hands out h1 (e + x)^-1 -- and with it anyone raises the balance of a
  * token signed under that e.  Before a replay form may take t, t must be bound into BOTH the receipt tag and the nonce derivation.
- * The calls here use drawn nonces only.  Also not offered here: the node-handle forms, the client ring verifier and the unique forms. */
+ * The calls here use drawn nonces only.  Also not offered here: the node-handle forms.
+ *
+ * act_refund_to_credit_token_return_keyring_batch is act_refund_to_credit_token_keyring_batch over n * 160 RefundReturn records: a
+ * RefundReturn names no key either.  The same chunk schedule, staging and wiping of `pre`, ring checks (an entry that is not a canonical
+ * encoding: ACT_ERR_ARG, nothing written), table cache and out_key contract -- the smallest ring index the item verifies under,
+ * ACT_KEY_NONE where status != 0.  t h1 does not depend on the key: X_A = g + K' + t h1 is computed once, under ring key 0, and an extra
+ * key costs what it costs a plain Refund.  The refusals in order: an undecodable point -> 255; no ring key's challenge equals gamma ->
+ * ACT_STATUS_INVALID_REFUND_PROOF; a t > s that a ring key validly signed -> ACT_STATUS_AMOUNT_TOO_BIG; otherwise the token
+ * A | e | k | r | (m + t) mod l.  A rejected lane's token is all zero.  No tiny or fused road, like every ring call.
+ * With nkeys == 1: status and token bytes are those of act_refund_to_credit_token_return_batch, out_key is 0 where accepted.
+ * With t == 0 in every record: status, token and out_key are those of act_refund_to_credit_token_keyring_batch on the first 128 bytes
+ * of each record.
+ *
+ * act_redeem_return_unique_batch / act_redeem_cbor_return_unique_batch are the two return calls with step 3a of the admission unique
+ * forms in its usual place, behind the screen and in front of verification.  The screen does not change (wire code, wrong charge,
+ * t > s, spent before), and a lane shed by any of its rules is never a leader and never a copy.  Equality is decided on the proof bytes
+ * alone (record or message): t takes no part in it.  What a lane that passed the screen is answered depends on its t only if it is the
+ * lane that is signed, and that lane is the leader: in act_redeem_(cbor_)return_batch lanes that share a fresh nullifier are all
+ * verified and the first valid one in lane order wins, whatever the others' t.  So a copy takes the answer of the admission unique
+ * forms from its leader's final status -- ACT_STATUS_DOUBLE_SPEND behind a leader that ended 0 or ACT_STATUS_RECORDED_UNSIGNED, the
+ * leader's own status otherwise -- a zero record and the leader's out_key, and draws no rng.
+ * Statuses, out_key, output bytes, the recorded nullifiers with their epochs and the bytes drawn under all three rng conventions are
+ * those of act_redeem_(cbor_)return_batch on an identical set, batches whose copies carry different t included; only the counts differ.
+ * out_counts: nullable, host, ACT_REDEEM_RETURN_UNIQUE_COUNTS values: the eight of ACT_ADMIT_COUNTS, then return_too_big, then copies;
+ * verified = lanes - wire_rejected - wrong_charge - return_too_big - spent_before - copies. */
 #define ACT_STATUS_RETURN_TOO_BIG 249   /* t > s: not looked up, not verified, not recorded, not signed */
 #define ACT_REDEEM_RETURN_COUNTS 9
+#define ACT_REDEEM_RETURN_UNIQUE_COUNTS 10
 int act_refund_sign_return_keyring_batch(act_ctx *ctx, size_t n, int mem, const uint8_t *keys, int nkeys, const uint8_t *key_index,
                                          const uint8_t *kprime, const uint8_t *status_in, const uint8_t *rng, int rng_mode,
                                          const uint8_t *returned /* nullable */, uint8_t *out_refund_return, uint8_t *status);
@@ -1036,6 +1061,17 @@ int act_redeem_cbor_return_batch(act_ctx *ctx, act_nullifier_set *set, size_t n,
                                  uint8_t *out_refund_return_cbor, uint8_t *status, uint8_t *out_key, uint64_t *out_counts /* nullable, host */);
 int act_refund_to_credit_token_return_batch(act_ctx *ctx, size_t n, int mem, const uint8_t *prerefund, const uint8_t *proof,
                                             const uint8_t *refund_return, const uint8_t w[32], uint8_t *out_token, uint8_t *status);
+int act_refund_to_credit_token_return_keyring_batch(act_ctx *ctx, size_t n, int mem, const uint8_t *prerefund, const uint8_t *proof,
+                                                    const uint8_t *refund_return, const uint8_t *ring_w, uint32_t nkeys, uint8_t *out_token,
+                                                    uint8_t *status, uint8_t *out_key);
+int act_redeem_return_unique_batch(act_ctx *ctx, act_nullifier_set *set, size_t n, int mem, const uint8_t *keys, int nkeys,
+                                   const uint32_t *key_epochs /* nullable */, int sign_key, const uint8_t *proof, const uint8_t *charge /* nullable */,
+                                   const uint8_t *returned /* nullable */, const uint8_t *rng, int rng_mode, uint8_t *out_refund_return,
+                                   uint8_t *status, uint8_t *out_key, uint64_t *out_counts /* nullable, host */);
+int act_redeem_cbor_return_unique_batch(act_ctx *ctx, act_nullifier_set *set, size_t n, int mem, const uint8_t *keys, int nkeys,
+                                        const uint32_t *key_epochs /* nullable */, int sign_key, const uint8_t *cbor, const uint64_t *offsets,
+                                        const uint8_t *charge /* nullable */, const uint8_t *returned /* nullable */, const uint8_t *rng, int rng_mode,
+                                        uint8_t *out_refund_return_cbor, uint8_t *status, uint8_t *out_key, uint64_t *out_counts /* nullable, host */);
 
 #ifdef __cplusplus
 }

@@ -173,6 +173,15 @@ extern "C" {
                                     rng_mode: c_int, out_refund_return_cbor: *mut u8, status: *mut u8, out_key: *mut u8, out_counts: *mut u64) -> c_int;
     fn act_refund_to_credit_token_return_batch(ctx: *mut ActCtx, n: usize, mem: c_int, prerefund: *const u8, proof: *const u8, refund_return: *const u8,
                                                w: *const u8, out_token: *mut u8, status: *mut u8) -> c_int;
+    // ... against a ring of issuer public keys, and the return calls with byte-identical proofs of one batch verified once
+    fn act_refund_to_credit_token_return_keyring_batch(ctx: *mut ActCtx, n: usize, mem: c_int, prerefund: *const u8, proof: *const u8, refund_return: *const u8,
+                                                       ring_w: *const u8, nkeys: u32, out_token: *mut u8, status: *mut u8, out_key: *mut u8) -> c_int;
+    fn act_redeem_return_unique_batch(ctx: *mut ActCtx, set: *mut ActNullifierSet, n: usize, mem: c_int, keys: *const u8, nkeys: c_int, key_epochs: *const u32,
+                                      sign_key: c_int, proof: *const u8, charge: *const u8, returned: *const u8, rng: *const u8, rng_mode: c_int,
+                                      out_refund_return: *mut u8, status: *mut u8, out_key: *mut u8, out_counts: *mut u64) -> c_int;
+    fn act_redeem_cbor_return_unique_batch(ctx: *mut ActCtx, set: *mut ActNullifierSet, n: usize, mem: c_int, keys: *const u8, nkeys: c_int, key_epochs: *const u32,
+                                           sign_key: c_int, cbor: *const u8, offsets: *const u64, charge: *const u8, returned: *const u8, rng: *const u8,
+                                           rng_mode: c_int, out_refund_return_cbor: *mut u8, status: *mut u8, out_key: *mut u8, out_counts: *mut u64) -> c_int;
 }
 
 /// ACT_MI355X_DEVICES = "0,1,2,3,4,5,6,7" (default: device 0)
@@ -1182,10 +1191,12 @@ impl GpuAdmission {
 /// not recorded, not signed.
 pub const ACT_STATUS_RETURN_TOO_BIG: u8 = 249;
 pub const ACT_REDEEM_RETURN_COUNTS: usize = 9;
+/// the nine above, then copies (`GpuReturn::unique(true)`)
+pub const ACT_REDEEM_RETURN_UNIQUE_COUNTS: usize = 10;
 /// a RefundReturn on the wire (`ACT_CBOR_REFUND_RETURN`): the Refund map with a fifth entry, key 5 -> t
 pub const REFUND_RETURN_CBOR_BYTES: usize = REFUND_CBOR_BYTES + 35;
 /// statuses, outputs (160-byte RefundReturn records `A | e | gamma | z | t` or `REFUND_RETURN_CBOR_BYTES` messages, all zero where not
-/// signed), matched ring keys, the eight admission counts and `return_too_big`
+/// signed), matched ring keys, the eight admission counts, `return_too_big` and (`GpuReturn::unique(true)`; 0 otherwise) `copies`
 pub struct Returned {
     pub rc: c_int,
     pub status: Vec<u8>,
@@ -1193,6 +1204,7 @@ pub struct Returned {
     pub out_key: Vec<u8>,
     pub counts: [u64; ACT_ADMIT_COUNTS],
     pub return_too_big: u64,
+    pub copies: u64,
 }
 /// Partial refunds on ONE GPU (include/act_mi355x.h "partial refunds"): the admission calls with the amounts `t <= s` the issuer gives
 /// back -- every accepted lane is signed over `X_A = g + K' + t h1`, so the client's next token holds `c - s + t`.  A lane with
@@ -1201,12 +1213,20 @@ pub struct Returned {
 pub struct GpuReturn {
     ctx: *mut ActCtx,
     set: *mut ActNullifierSet,
+    unique: bool,
 }
 impl GpuReturn {
     /// # Safety
     /// `ctx` and `set` are live handles on one device and outlive `self`.
     pub unsafe fn from_raw(ctx: *mut ActCtx, set: *mut ActNullifierSet) -> Self {
-        GpuReturn { ctx, set }
+        GpuReturn { ctx, set, unique: false }
+    }
+    /// `true`: the calls go to `act_redeem_return_unique_batch` / `act_redeem_cbor_return_unique_batch` -- a proof with the bytes of an
+    /// earlier proof of the batch is not verified, whatever its `t`: the first one is signed over its own `t` and the others are double
+    /// spends, as they are without this.  The same statuses, outputs and recorded nullifiers; `Returned::copies` counts them.
+    pub fn unique(mut self, enabled: bool) -> Self {
+        self.unique = enabled;
+        self
     }
     /// `returned`: n scalars of 32 bytes (None: every t is 0); the other arguments as `GpuAdmission::redeem_admit_batch`.
     pub fn redeem_return_batch(&self, keys: &[u8], key_epochs: Option<&[u32]>, sign_with: Option<usize>, proofs: &[u8], charges: Option<&[u8]>,
@@ -1215,15 +1235,16 @@ impl GpuReturn {
         assert!(proofs.len() == n * PROOF_BYTES && charges.map_or(true, |c| c.len() == 32 * n) && returned.map_or(true, |t| t.len() == 32 * n) &&
                 key_epochs.map_or(true, |e| e.len() == nkeys));
         let src = rng_source(&mut rng);
-        let mut r = Returned { rc: 0, status: vec![0u8; n + 1], out: vec![0u8; 160 * n + 1], out_key: vec![ACT_KEY_NONE; n + 1], counts: [0; ACT_ADMIT_COUNTS], return_too_big: 0 };
-        let mut counts = [0u64; ACT_REDEEM_RETURN_COUNTS];
+        let mut r = Returned { rc: 0, status: vec![0u8; n + 1], out: vec![0u8; 160 * n + 1], out_key: vec![ACT_KEY_NONE; n + 1], counts: [0; ACT_ADMIT_COUNTS], return_too_big: 0, copies: 0 };
+        let mut counts = [0u64; ACT_REDEEM_RETURN_UNIQUE_COUNTS];
+        let call = if self.unique { act_redeem_return_unique_batch } else { act_redeem_return_batch };
         r.rc = unsafe {
-            act_redeem_return_batch(self.ctx, self.set, n, 0, keys.as_ptr(), nkeys as c_int, key_epochs.map_or(std::ptr::null(), |e| e.as_ptr()),
-                                    sign_with.map_or(ACT_SIGN_MATCHED, |i| i as c_int), proofs.as_ptr(), charges.map_or(std::ptr::null(), |c| c.as_ptr()),
-                                    returned.map_or(std::ptr::null(), |t| t.as_ptr()), &src as *const ActRngSource as *const u8, ACT_RNG_CALLBACK,
-                                    r.out.as_mut_ptr(), r.status.as_mut_ptr(), r.out_key.as_mut_ptr(), counts.as_mut_ptr())
+            call(self.ctx, self.set, n, 0, keys.as_ptr(), nkeys as c_int, key_epochs.map_or(std::ptr::null(), |e| e.as_ptr()),
+                 sign_with.map_or(ACT_SIGN_MATCHED, |i| i as c_int), proofs.as_ptr(), charges.map_or(std::ptr::null(), |c| c.as_ptr()),
+                 returned.map_or(std::ptr::null(), |t| t.as_ptr()), &src as *const ActRngSource as *const u8, ACT_RNG_CALLBACK,
+                 r.out.as_mut_ptr(), r.status.as_mut_ptr(), r.out_key.as_mut_ptr(), counts.as_mut_ptr())
         };
-        r.counts.copy_from_slice(&counts[..ACT_ADMIT_COUNTS]); r.return_too_big = counts[ACT_ADMIT_COUNTS];
+        r.counts.copy_from_slice(&counts[..ACT_ADMIT_COUNTS]); r.return_too_big = counts[ACT_ADMIT_COUNTS]; r.copies = counts[ACT_REDEEM_RETURN_COUNTS];
         r.status.truncate(n); r.out.truncate(160 * n); r.out_key.truncate(n);
         r
     }
@@ -1234,16 +1255,17 @@ impl GpuReturn {
         let (n, nkeys) = (msgs.len(), keys.len() / 64);
         assert!(charges.map_or(true, |c| c.len() == 32 * n) && returned.map_or(true, |t| t.len() == 32 * n) && key_epochs.map_or(true, |e| e.len() == nkeys));
         let src = rng_source(&mut rng);
-        let mut r = Returned { rc: 0, status: vec![0u8; n + 1], out: vec![0u8; REFUND_RETURN_CBOR_BYTES * n + 1], out_key: vec![ACT_KEY_NONE; n + 1], counts: [0; ACT_ADMIT_COUNTS], return_too_big: 0 };
-        let mut counts = [0u64; ACT_REDEEM_RETURN_COUNTS];
+        let mut r = Returned { rc: 0, status: vec![0u8; n + 1], out: vec![0u8; REFUND_RETURN_CBOR_BYTES * n + 1], out_key: vec![ACT_KEY_NONE; n + 1], counts: [0; ACT_ADMIT_COUNTS], return_too_big: 0, copies: 0 };
+        let mut counts = [0u64; ACT_REDEEM_RETURN_UNIQUE_COUNTS];
+        let call = if self.unique { act_redeem_cbor_return_unique_batch } else { act_redeem_cbor_return_batch };
         r.rc = unsafe {
-            act_redeem_cbor_return_batch(self.ctx, self.set, n, 0, keys.as_ptr(), nkeys as c_int, key_epochs.map_or(std::ptr::null(), |e| e.as_ptr()),
-                                         sign_with.map_or(ACT_SIGN_MATCHED, |i| i as c_int), blob.as_ptr(), offsets.as_ptr(),
-                                         charges.map_or(std::ptr::null(), |c| c.as_ptr()), returned.map_or(std::ptr::null(), |t| t.as_ptr()),
-                                         &src as *const ActRngSource as *const u8, ACT_RNG_CALLBACK, r.out.as_mut_ptr(), r.status.as_mut_ptr(),
-                                         r.out_key.as_mut_ptr(), counts.as_mut_ptr())
+            call(self.ctx, self.set, n, 0, keys.as_ptr(), nkeys as c_int, key_epochs.map_or(std::ptr::null(), |e| e.as_ptr()),
+                 sign_with.map_or(ACT_SIGN_MATCHED, |i| i as c_int), blob.as_ptr(), offsets.as_ptr(),
+                 charges.map_or(std::ptr::null(), |c| c.as_ptr()), returned.map_or(std::ptr::null(), |t| t.as_ptr()),
+                 &src as *const ActRngSource as *const u8, ACT_RNG_CALLBACK, r.out.as_mut_ptr(), r.status.as_mut_ptr(),
+                 r.out_key.as_mut_ptr(), counts.as_mut_ptr())
         };
-        r.counts.copy_from_slice(&counts[..ACT_ADMIT_COUNTS]); r.return_too_big = counts[ACT_ADMIT_COUNTS];
+        r.counts.copy_from_slice(&counts[..ACT_ADMIT_COUNTS]); r.return_too_big = counts[ACT_ADMIT_COUNTS]; r.copies = counts[ACT_REDEEM_RETURN_COUNTS];
         r.status.truncate(n); r.out.truncate(REFUND_RETURN_CBOR_BYTES * n); r.out_key.truncate(n);
         r
     }
@@ -1325,6 +1347,18 @@ impl PublicRing {
         r.rc = unsafe {
             act_refund_to_credit_token_keyring_batch(self.ctx, n, 0, prerefund.as_ptr(), proofs.as_ptr(), refunds.as_ptr(), self.ring_w.as_ptr(),
                                                      (self.ring_w.len() / 32) as u32, r.tokens.as_mut_ptr(), r.status.as_mut_ptr(), r.out_key.as_mut_ptr())
+        };
+        r
+    }
+    /// The same over RefundReturn records (160 bytes, `A | e | gamma | z | t`): the tokens hold `m + t`; status 4 where no ring key's
+    /// proof over `g + K' + t h1` holds, 8 for a `t > s` that a ring key validly signed.
+    pub fn refund_return_to_credit_token(&self, prerefund: &[u8], proofs: &[u8], refund_returns: &[u8]) -> RingTokens {
+        let n = prerefund.len() / 96;
+        assert!(prerefund.len() == 96 * n && proofs.len() == PROOF_BYTES * n && refund_returns.len() == 160 * n);
+        let mut r = Self::empty(n);
+        r.rc = unsafe {
+            act_refund_to_credit_token_return_keyring_batch(self.ctx, n, 0, prerefund.as_ptr(), proofs.as_ptr(), refund_returns.as_ptr(), self.ring_w.as_ptr(),
+                                                            (self.ring_w.len() / 32) as u32, r.tokens.as_mut_ptr(), r.status.as_mut_ptr(), r.out_key.as_mut_ptr())
         };
         r
     }
