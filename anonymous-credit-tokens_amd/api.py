@@ -307,16 +307,17 @@ class PrivateKey(_Cbor):
 
     # ---- replayable redemption: a retried SpendProof gets its Refund again ----------------------------------
     def redeem_replay_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", proofs: Sequence["SpendProof"], nonce_key: bytes,
-                            admit: bool = False, charges: Sequence = None, unique: bool = False) -> Tuple[list, list]:
+                            admit: bool = False, charges: Sequence = None, unique: bool = False, returned: Sequence = None) -> Tuple[list, list]:
         """redeem_batch without a generator: the nonces are derived from `nonce_key` (32 secret bytes the issuer keeps), this key, the
         nullifier and K', and `receipts` (a second NullifierDb) remembers which K' a nullifier was spent for -- a proof that is sent
-        again gets the same Refund, byte for byte, instead of DoubleSpendError.  admit / charges / unique: Keyring.redeem_replay_batch.  -> (results, replayed flags)"""
-        res, _, replayed = Keyring([self]).redeem_replay_batch(params, db, receipts, proofs, nonce_key, admit=admit, charges=charges, unique=unique)
+        again gets the same Refund, byte for byte, instead of DoubleSpendError.  admit / charges / unique / returned: Keyring.redeem_replay_batch.  -> (results, replayed flags)"""
+        res, _, replayed = Keyring([self]).redeem_replay_batch(params, db, receipts, proofs, nonce_key, admit=admit, charges=charges, unique=unique, returned=returned)
         return res, replayed
 
     def redeem_replay_cbor_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", msgs: Sequence[bytes], nonce_key: bytes, nbits: int = L,
-                                 admit: bool = False, charges: Sequence = None, unique: bool = False) -> Tuple[list, list]:
-        res, _, replayed = Keyring([self]).redeem_replay_cbor_batch(params, db, receipts, msgs, nonce_key, nbits, admit=admit, charges=charges, unique=unique)
+                                 admit: bool = False, charges: Sequence = None, unique: bool = False, returned: Sequence = None) -> Tuple[list, list]:
+        res, _, replayed = Keyring([self]).redeem_replay_cbor_batch(params, db, receipts, msgs, nonce_key, nbits, admit=admit, charges=charges, unique=unique,
+                                                                    returned=returned)
         return res, replayed
 
     def verify_spend_batch(self, params: Params, proofs: Sequence["SpendProof"]) -> bytes:
@@ -420,8 +421,7 @@ class Keyring:
         counts (capi.REDEEM_RETURN_COUNTS), also kept as `self.last_return_counts`.  unique=True (act_redeem_return_unique_batch): a
         proof with the bytes of an earlier proof of the batch is not verified, WHATEVER its returned amount -- the first one is the one
         that is signed, over its own amount, and the others are DoubleSpendError as they are without unique; the results are the same
-        and the counts gain "copies" (capi.REDEEM_RETURN_UNIQUE_COUNTS, ten names).  There is no replay form of this call on purpose
-        (include/act_mi355x.h)."""
+        and the counts gain "copies" (capi.REDEEM_RETURN_UNIQUE_COUNTS, ten names).  The retry-safe form of this call is redeem_replay_batch(..., returned=)."""
         nbits = proofs[0].nbits if proofs else L
         e = params.engine(nbits)
         pb = b"".join(p.record for p in proofs)
@@ -445,7 +445,7 @@ class Keyring:
         return [out[i] if st[i] == 0 else _wire_error(st[i]) for i in range(len(msgs))], self._indices(st, ok)
 
     def redeem_replay_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", proofs: Sequence["SpendProof"], nonce_key: bytes, sign_with=None,
-                            admit: bool = False, charges: Sequence = None, unique: bool = False) -> Tuple[list, list, list]:
+                            admit: bool = False, charges: Sequence = None, unique: bool = False, returned: Sequence = None) -> Tuple[list, list, list]:
         """redeem_batch made retry-safe (act_redeem_replay_batch): no generator -- the nonces are derived from `nonce_key`, the key a
         lane is signed with, the nullifier and K' -- and `receipts`, a second NullifierDb, records for which K' every nullifier was
         spent.  A proof that is sent again (same ring key to sign with, same nonce_key) gets the same Refund, byte for byte; another
@@ -456,13 +456,26 @@ class Keyring:
         without it; the counts are capi.ADMIT_REPLAY_COUNTS.
         unique=True (with admit=True; act_redeem_admit_replay_unique_batch): byte-identical proofs of the batch are verified and signed
         once and the copies get the same Refund; the results are the same and the counts gain "copies" and "copies_served".
+        returned (one amount per proof; act_redeem_return_replay_batch; implies admit=True): the reserve-then-return step made
+        retry-safe -- entry i is a RefundReturn over returned[i]; returned[i] > s_i is Error 249.  The receipt PINS the amount: a proof
+        sent again with the same amount gets the same RefundReturn, with another amount DoubleSpendError -- derive the amount from the
+        request, or remember it.  The counts are capi.RETURN_REPLAY_COUNTS.  Not with unique=True (ValueError).
         -> (results, matched ring indices, replayed flags); `self.last_replay_counts`: the call's counts."""
         nbits = proofs[0].nbits if proofs else L
+        if returned is not None and unique:
+            raise ValueError("a copy may name another amount than its leader: no unique form with returned amounts")
+        admit = admit or returned is not None
         if charges is not None and not admit:
             raise ValueError("charges are compared by the admission screen: admit=True")
         if unique and not admit:
             raise ValueError("copies are found behind the admission screen: admit=True")
         e, pb = params.engine(nbits), b"".join(p.record for p in proofs)
+        if returned is not None:
+            cc = b"".join(scalar(c) for c in charges) if charges is not None else None
+            tt = b"".join(scalar(t) for t in returned)
+            st, out, ok, rep, self.last_replay_counts = e.redeem_return_replay(
+                db.set, receipts.set, self._records(), pb, nonce_key, self._sign_key(sign_with), key_epochs=self.epochs, charges=cc, returned=tt)
+            return [RefundReturn(out[160 * i:160 * i + 160]) if st[i] == 0 else Error(st[i]) for i in range(len(proofs))], self._indices(st, ok), [bool(r) for r in rep]
         if admit:
             cc = b"".join(scalar(c) for c in charges) if charges is not None else None
             st, out, ok, rep, self.last_replay_counts = e.redeem_admit_replay(
@@ -472,16 +485,25 @@ class Keyring:
         return [Refund(out[128 * i:128 * i + 128]) if st[i] == 0 else Error(st[i]) for i in range(len(proofs))], self._indices(st, ok), [bool(r) for r in rep]
 
     def redeem_replay_cbor_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", msgs: Sequence[bytes], nonce_key: bytes, nbits: int = L,
-                                 sign_with=None, admit: bool = False, charges: Sequence = None, unique: bool = False) -> Tuple[list, list, list]:
+                                 sign_with=None, admit: bool = False, charges: Sequence = None, unique: bool = False, returned: Sequence = None) -> Tuple[list, list, list]:
         """the same on wire bytes (act_redeem_cbor_replay_batch; admit=True: act_redeem_cbor_admit_replay_batch): a retry may be another
         CBOR spelling of the same proof.  unique=True (with admit=True): act_redeem_cbor_admit_replay_unique_batch -- a copy is a message
-        of the same length and the same bytes; another spelling is verified on its own"""
+        of the same length and the same bytes; another spelling is verified on its own.  returned: act_redeem_cbor_return_replay_batch --
+        entry i is a CBOR RefundReturn message (implies admit=True, not with unique=True)"""
+        if returned is not None and unique:
+            raise ValueError("a copy may name another amount than its leader: no unique form with returned amounts")
+        admit = admit or returned is not None
         if charges is not None and not admit:
             raise ValueError("charges are compared by the admission screen: admit=True")
         if unique and not admit:
             raise ValueError("copies are found behind the admission screen: admit=True")
         e = params.engine(nbits)
-        if admit:
+        if returned is not None:
+            cc = b"".join(scalar(c) for c in charges) if charges is not None else None
+            tt = b"".join(scalar(t) for t in returned)
+            st, out, ok, rep, self.last_replay_counts = e.redeem_cbor_return_replay(
+                db.set, receipts.set, self._records(), list(msgs), nonce_key, self._sign_key(sign_with), key_epochs=self.epochs, charges=cc, returned=tt)
+        elif admit:
             cc = b"".join(scalar(c) for c in charges) if charges is not None else None
             st, out, ok, rep, self.last_replay_counts = e.redeem_cbor_admit_replay(
                 db.set, receipts.set, self._records(), list(msgs), nonce_key, self._sign_key(sign_with), key_epochs=self.epochs, charges=cc, unique=unique)

@@ -16,6 +16,8 @@
 // survivor whose input bytes are those of an earlier survivor is not verified and takes its answer from that lane      [k_copies.hip]
 // act_redeem_(cbor_)admit_replay_batch (admit_replay_impl.inc, included behind replay_impl.inc; DESIGN 4.9) add a stage between steps 1
 // and 2 -- a spent lane whose receipt is this proof's own is a retry candidate and survives -- and end in the replay tail, not the ring's
+// act_redeem_(cbor_)return_replay_batch are that form with the returned amounts of the return calls (ret && rp, DESIGN 4.10): t <= s is the
+// screen's rule, a candidate's tag and every tag and nonce of the tail take the lane's t, and the outputs are RefundReturns.  No unique form.
 // act_redeem_(cbor_)admit_replay_unique_batch are both at once (unique && rp): the copy stage runs over fresh lanes and retry candidates
 // alike, and behind the scatters a copy is SERVED -- it takes its leader's refund -- where the unique forms above resolve it  [k_copy_serve]
 namespace {
@@ -167,29 +169,30 @@ struct AdmitReplay {
 struct AdmitReplayStage {
   hipStream_t stream; size_t n; bool dev, wire, dev_reader; const uint8_t* proof; const uint8_t* cbor; const WireExtent* ext; bool offsets;
   uint8_t* d_pre; const uint8_t* d_kred; uint32_t *d_blk, *d_idx, *d_pos, *d_total;
+  const uint8_t* d_t;                 // the return form: the n returned amounts in device memory, as the screen read them (null: every t = 0)
 };
 
 }  // namespace
 
 static int admit_replay_stage(act_ctx* c, AdmitReplay& rp, const AdmitReplayStage& g);
-static void admit_replay_counts_of(uint64_t* out_counts, size_t n, const uint8_t* pre, size_t candidates, size_t m, const uint64_t* tail_counts);
+static void admit_replay_counts_of(uint64_t* out_counts, size_t n, const uint8_t* pre, size_t candidates, size_t m, const uint64_t* tail_counts, bool ret = false);
 static int replay_refused(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, const uint8_t* nonce_key, size_t n, const uint32_t* key_epochs, int nkeys);
 static int replay_tail(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys, int nkeys, const uint32_t* key_epochs,
                        int sign_key, bool wire, const uint8_t* k_at, size_t k_stride, const uint8_t* kp, uint8_t* st, const uint8_t* nonce_key, uint8_t* out,
-                       uint8_t* status, uint8_t* out_key, uint8_t* out_replayed, uint64_t* out_counts, bool* began = nullptr);
+                       uint8_t* status, uint8_t* out_key, uint8_t* out_replayed, uint64_t* out_counts, bool* began = nullptr, const RedeemReturn* ret = nullptr);
 static int redeem_replay_locked(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys, int nkeys,
                                 const uint32_t* key_epochs, int sign_key, const uint8_t* proof, const uint8_t* cbor, const uint64_t* offsets, const uint8_t* nonce_key,
-                                uint8_t* out, uint8_t* status, uint8_t* out_key, uint8_t* out_replayed, uint64_t* out_counts);
+                                uint8_t* out, uint8_t* status, uint8_t* out_key, uint8_t* out_replayed, uint64_t* out_counts, const RedeemReturn* ret = nullptr);
 
 // rp (the replay form): rng / rng_mode are the derived nonces' stand-in (one byte, ACT_RNG_PER_LANE) and out_counts is null -- the
 // form's own counts are rp->out_counts
 static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int mem, const uint8_t* keys, int nkeys, const uint32_t* key_epochs, int sign_key,
                              const uint8_t* proof, const uint8_t* cbor, const uint64_t* offsets, const uint8_t* charge, const uint8_t* rng, int rng_mode,
                              uint8_t* out, uint8_t* status, uint8_t* out_key, uint64_t* out_counts, bool unique = false, AdmitReplay* rp = nullptr,
-                             const RedeemReturn* ret = nullptr) {      // ret (the return calls, DESIGN 4.10): never with rp
+                             const RedeemReturn* ret = nullptr) {      // ret (the return calls, DESIGN 4.10); ret && rp: the return replay form, never unique
   const bool wire = cbor != nullptr, dev = mem == ACT_MEM_DEVICE;
   if (out_counts) memset(out_counts, 0, sizeof(uint64_t) * (ret ? (unique ? ACT_REDEEM_RETURN_UNIQUE_COUNTS : ACT_REDEEM_RETURN_COUNTS) : unique ? ACT_ADMIT_UNIQUE_COUNTS : ACT_ADMIT_COUNTS));
-  if (rp && rp->out_counts) memset(rp->out_counts, 0, sizeof(uint64_t) * (unique ? ACT_ADMIT_REPLAY_UNIQUE_COUNTS : ACT_ADMIT_REPLAY_COUNTS));
+  if (rp && rp->out_counts) memset(rp->out_counts, 0, sizeof(uint64_t) * (ret ? ACT_RETURN_REPLAY_COUNTS : unique ? ACT_ADMIT_REPLAY_UNIQUE_COUNTS : ACT_ADMIT_REPLAY_COUNTS));
   if (!c || (mem != ACT_MEM_HOST && mem != ACT_MEM_DEVICE) || n > ((size_t)1 << 30)) return ACT_ERR_ARG;
   if (n && ((!proof && !cbor) || !out || !status || !out_key)) return ACT_ERR_ARG;
   if (wire && offsets) for (size_t i = 0; i < n; i++) if (offsets[i + 1] < offsets[i]) return ACT_ERR_ARG;
@@ -199,7 +202,8 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
   int rc = redeem_keyring_refused(c, set, 0, keys, nkeys, key_epochs, sign_key, nullptr, nullptr, rng, rng_mode, nullptr, nullptr, nullptr);
   if (rc) return rc;
   if (rp && (rc = replay_refused(c, set, rp->receipts, rp->nonce_key, n, key_epochs, nkeys))) return rc;
-  if (ret && rp) return ACT_ERR_ARG;
+  // a copy that names another t than its leader must not be served the leader's row: the unique forms take no returned amounts with rp
+  if (ret && rp && unique) { c->err = "act_redeem_return_replay_batch: the unique forms take no returned amounts (a copy's t may differ from its leader's)"; return ACT_ERR_ARG; }
   if (n == 0) return redeem_keyring_impl(c, set, 0, mem, keys, nkeys, key_epochs, sign_key, nullptr, nullptr, nullptr, rng, rng_mode, nullptr, nullptr, nullptr);
   // one admission call at a time per context: the gathered rng slices live in the context's own buffer (d_admit_rng)
   std::lock_guard<std::mutex> admission(c->admit_mu);
@@ -356,7 +360,7 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
     ADCK(c, hipStreamSynchronize(stream));
   }
   if (rp) {      // the spent lanes: retry candidates go on, the others stay double spends; then the compaction over what that leaves
-    const AdmitReplayStage g{stream, n, dev, wire, dev_reader, proof, cbor, &ext, offsets != nullptr, d_pre, d_kred, d_blk, d_idx, d_pos, d_total};
+    const AdmitReplayStage g{stream, n, dev, wire, dev_reader, proof, cbor, &ext, offsets != nullptr, d_pre, d_kred, d_blk, d_idx, d_pos, d_total, sa.returned};
     if ((rc = admit_replay_stage(c, *rp, g))) return rc;
     launch_admit_compact(d_pre, (uint32_t)n, d_blk, d_idx, d_pos, d_total, stream);
     ADCK(c, hipGetLastError());
@@ -389,8 +393,8 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
   if (mv == n && rp) {
     uint64_t tc[ACT_REPLAY_COUNTS] = {0, 0, 0, 0, 0, 0};
     rc = redeem_replay_locked(c, set, rp->receipts, n, mem, keys, nkeys, key_epochs, sign_key, proof, cbor, offsets, rp->nonce_key, out, status, out_key, rp->out_replayed,
-                              rp->out_counts ? tc : nullptr);
-    if (rp->out_counts && tc[0] == n) admit_replay_counts_of(rp->out_counts, n, h_pre.data(), rp->candidates, n, tc);      // (tc[0] == 0: the call ended before its tail)
+                              rp->out_counts ? tc : nullptr, ret);      // (the caller's `returned`, lane for lane)
+    if (rp->out_counts && tc[0] == n) admit_replay_counts_of(rp->out_counts, n, h_pre.data(), rp->candidates, n, tc, ret != nullptr);      // (tc[0] == 0: the call ended before its tail)
     return rc;
   }
   if (mv == n) {
@@ -414,7 +418,7 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
       ADCK(c, hipStreamSynchronize(stream));
     } else { memcpy(status, h_pre.data(), n); memset(out_key, ACT_KEY_NONE, n); memset(out, 0, n * out_b); if (rp && rp->out_replayed) memset(rp->out_replayed, 0, n); }
     admit_counts_of(out_counts, n, h_pre.data(), 0, nullptr, ret != nullptr);
-    if (rp && rp->out_counts) admit_replay_counts_of(rp->out_counts, n, h_pre.data(), 0, 0, nullptr);
+    if (rp && rp->out_counts) admit_replay_counts_of(rp->out_counts, n, h_pre.data(), 0, 0, nullptr, ret != nullptr);
     return ACT_OK;
   }
 
@@ -425,7 +429,8 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
   if (!dev) { h_pos.resize(n); ADCK(c, hipMemcpy(h_pos.data(), v_pos, n * 4, hipMemcpyDeviceToHost)); }
   // compact arrays in the caller's kind of memory: K' | nullifiers | verdicts | look-up answers | key indices | matched keys | statuses
   AdmitArr arr(c), cout(c);
-  if ((rc = arr.alloc(mem, mv * (rp ? 70 : 69) + (t_in ? mv * 32 + 32 : 0)))) { c->err = "admission: compact arrays"; return rc; }
+  const size_t arr_lane = rp ? 70 : 69;
+  if ((rc = arr.alloc(mem, mv * arr_lane + (t_in ? mv * 32 + 32 : 0)))) { c->err = "admission: compact arrays"; return rc; }
   if ((rc = cout.alloc(mem, mv * out_b))) { c->err = "admission: compact output"; return rc; }
   uint8_t *kp = arr.p, *knul = kp + mv * 32, *st = knul + mv * 32, *sp = st + mv, *kidx = sp + mv, *okey = kidx + mv, *cst = okey + mv,
           *crepl = cst + mv;      // (the replay form: the survivors' replay marks)
@@ -462,7 +467,7 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
   // the rng slices they are gathered by v_idx: in the unique forms the amounts of the lanes that are verified -- a copy's t is never read
   RedeemReturn cret{nullptr};
   if (t_in) {
-    uint8_t* ct = arr.p + ((mv * 69 + 31) & ~(size_t)31);
+    uint8_t* ct = arr.p + ((mv * arr_lane + 31) & ~(size_t)31);
     if (dev) {
       AdmitRowsArgs ra{ct, t_in, v_idx, (uint32_t)mv, 32};
       launch_admit_rows(ra, stream);
@@ -485,7 +490,7 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
   // ---- step 4: once per call, over the compact arrays ---------------------------------------------------------------------------------------
   uint64_t tc[ACT_REPLAY_COUNTS] = {0, 0, 0, 0, 0, 0};
   bool began = false;
-  const int rc_tail = rp ? replay_tail(c, set, rp->receipts, mv, mem, keys, nkeys, key_epochs, sign_key, wire, knul, 32, kp, st, rp->nonce_key, cout.p, cst, okey, crepl, tc, &began)
+  const int rc_tail = rp ? replay_tail(c, set, rp->receipts, mv, mem, keys, nkeys, key_epochs, sign_key, wire, knul, 32, kp, st, rp->nonce_key, cout.p, cst, okey, crepl, tc, &began, ret ? &cret : nullptr)
                          : redeem_tail_ring(c, set, mv, mem, keys, nkeys, key_epochs, sign_key, wire, knul, 32, kp, st, sp, kidx, c_rng, rng_mode, cout.p, cst, okey, ret ? &cret : nullptr);
 
   if (rp && rc_tail && !began) return rc_tail;      // staging its buffers failed: as a failed verification -- nothing recorded, status untouched
@@ -521,7 +526,7 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
     if (cp.copies && rp) { CopyServeArgs va{h_lead.data(), (uint32_t)n, out_b, status, out_key, out, rp->out_replayed}; for (size_t i = 0; i < n; i++) copy_serve_lane(va, (uint32_t)i); }
   }
   admit_counts_of(out_counts, n, h_pre.data(), mv, dev ? h_cst.data() : cst, ret != nullptr);
-  if (rp && rp->out_counts && tc[0] == mv) admit_replay_counts_of(rp->out_counts, n, h_pre.data(), rp->candidates, mv, tc);
+  if (rp && rp->out_counts && tc[0] == mv) admit_replay_counts_of(rp->out_counts, n, h_pre.data(), rp->candidates, mv, tc, ret != nullptr);
   if (out_counts && unique) out_counts[ret ? ACT_REDEEM_RETURN_COUNTS : ACT_ADMIT_COUNTS] = cp.copies;
   if (rp && rp->out_counts && unique && cp.copies && tc[0] == mv) {      // copies, then the copies whose leader ended 0
     const uint8_t* fin = dev ? h_fin.data() : status;
@@ -565,8 +570,9 @@ extern "C" int act_redeem_cbor_admit_unique_batch(act_ctx* c, act_nullifier_set*
 // ---- partial refunds (DESIGN 4.10): the admission calls with the amounts t the issuer returns ---------------------------------------------
 // The admission loop with one more rule in the screen (t_i > s_i -> ACT_STATUS_RETURN_TOO_BIG, behind the charge and in front of the
 // look-up) and a signing step over X_A = g + K' + t h1; 160-byte RefundReturn records or ACT_CBOR_REFUND_RETURN messages.  Drawn nonces
-// only: the replay forms derive e from (nonce_key, key, k, enc(K')) and two signatures with one e over X_A that differ by a multiple
-// of h1 give h1 (e + x)^-1 away -- they take no returned amounts (include/act_mi355x.h).
+// here; the replay form with amounts is act_redeem_(cbor_)return_replay_batch (admit_replay_impl.inc), where t enters the receipt's tag
+// and the nonce derivation -- with e derived from (nonce_key, key, k, enc(K')) alone, two signatures with one e over X_A that differ by
+// a multiple of h1 would give h1 (e + x)^-1 away.
 extern "C" int act_redeem_return_batch(act_ctx* c, act_nullifier_set* set, size_t n, int mem, const uint8_t* keys, int nkeys, const uint32_t* key_epochs, int sign_key,
                                        const uint8_t* proof, const uint8_t* charge, const uint8_t* returned, const uint8_t* rng, int rng_mode,
                                        uint8_t* out_refund_return, uint8_t* status, uint8_t* out_key, uint64_t* out_counts) {

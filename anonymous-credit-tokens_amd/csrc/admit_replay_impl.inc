@@ -18,14 +18,15 @@ struct AdmitComJob { uint8_t* dst; const uint8_t* src; const uint32_t* idx; size
 }  // namespace
 
 // pre: the final pre-statuses; tc: the replay tail's ACT_REPLAY_COUNTS over the m verified lanes (null: none was verified)
-static void admit_replay_counts_of(uint64_t* out_counts, size_t n, const uint8_t* pre, size_t candidates, size_t m, const uint64_t* tc) {
-  uint64_t k[ACT_ADMIT_REPLAY_COUNTS] = {n, 0, 0, 0, candidates, m, 0, 0, 0, 0, 0};
+// ret (the return replay form): a twelfth value, the lanes whose returned amount exceeded their charge (ACT_RETURN_REPLAY_COUNTS)
+static void admit_replay_counts_of(uint64_t* out_counts, size_t n, const uint8_t* pre, size_t candidates, size_t m, const uint64_t* tc, bool ret) {
+  uint64_t k[ACT_RETURN_REPLAY_COUNTS] = {n, 0, 0, 0, candidates, m, 0, 0, 0, 0, 0, 0};
   for (size_t i = 0; i < n; i++) {
     const uint8_t p = pre[i];
-    if (p == ACT_STATUS_WRONG_CHARGE) k[2]++; else if (p == ACT_STATUS_DOUBLE_SPEND) k[3]++; else if (p) k[1]++;
+    if (p == ACT_STATUS_WRONG_CHARGE) k[2]++; else if (p == ACT_STATUS_DOUBLE_SPEND) k[3]++; else if (ret && p == ACT_STATUS_RETURN_TOO_BIG) k[11]++; else if (p) k[1]++;
   }
   if (tc) for (int j = 0; j < 5; j++) k[6 + j] = tc[1 + j];      // rejected_by_verification, fresh, replayed, double_spend_after, unanswered
-  memcpy(out_counts, k, sizeof(k));
+  memcpy(out_counts, k, sizeof(uint64_t) * (ret ? ACT_RETURN_REPLAY_COUNTS : ACT_ADMIT_REPLAY_COUNTS));
 }
 
 static int admit_replay_stage(act_ctx* c, AdmitReplay& rp, const AdmitReplayStage& g) {
@@ -138,9 +139,9 @@ static int admit_replay_stage(act_ctx* c, AdmitReplay& rp, const AdmitReplayStag
     ADCK(c, hipMemsetAsync(d_flags, 0, w * 4, stream));
     KprimeArgs ka{};
     ka.s.P.L = L; ka.s.proofs = d_rec.p; ka.s.n = (uint32_t)w; ka.s.coords = d_coords; ka.s.flags = d_flags;
-    ka.kred = g.d_kred; ka.idx = g.d_idx + w0; ka.kp = d_kp + w0 * 32; ka.tag = d_tag + w0 * 32; ka.mark = d_mark + w0;
+    ka.kred = g.d_kred; ka.idx = g.d_idx + w0; ka.kp = d_kp + w0 * 32; ka.tag = d_tag + w0 * 32; ka.mark = d_mark + w0; ka.t = g.d_t;
     launch_kprime_decode(ka, stream);
-    launch_kprime_tag(ka, stream);
+    if (ka.t) launch_kprime_tag_return(ka, stream); else launch_kprime_tag(ka, stream);      // (the candidate's t, by the same idx as its nullifier)
     ADCK(c, hipGetLastError());
     ADCK(c, hipStreamSynchronize(stream));      // the window's buffers are reused
   }
@@ -164,11 +165,11 @@ static int admit_replay_stage(act_ctx* c, AdmitReplay& rp, const AdmitReplayStag
 static int redeem_admit_replay_impl(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys, int nkeys,
                                     const uint32_t* key_epochs, int sign_key, const uint8_t* proof, const uint8_t* cbor, const uint64_t* offsets, const uint8_t* charge,
                                     const uint8_t* nonce_key, uint8_t* out, uint8_t* status, uint8_t* out_key, uint8_t* out_replayed, uint64_t* out_counts,
-                                    bool unique = false) {
+                                    bool unique = false, const RedeemReturn* ret = nullptr) {
   static const uint8_t derived = 0;      // the nonces stand where the admission calls' rng stands
   AdmitReplay rp{receipts, nonce_key, out_replayed, out_counts};
   return redeem_admit_impl(c, set, n, mem, keys, nkeys, key_epochs, sign_key, proof, cbor, offsets, charge, &derived, ACT_RNG_PER_LANE, out, status, out_key, nullptr,
-                           unique, &rp);
+                           unique, &rp, ret);
 }
 
 extern "C" int act_redeem_admit_replay_batch(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys, int nkeys,
@@ -205,4 +206,28 @@ extern "C" int act_redeem_cbor_admit_replay_unique_batch(act_ctx* c, act_nullifi
   static const uint8_t none = 0;
   return redeem_admit_replay_impl(c, set, receipts, n, mem, keys, nkeys, key_epochs, sign_key, nullptr, cbor ? cbor : &none, offsets, charge, nonce_key, out_refund_cbor,
                                   status, out_key, out_replayed, out_counts, true);
+}
+
+// ---- replayable partial refunds (DESIGN 4.10): the admission replay calls with the amounts t the issuer returns ----------------------------
+// The screen's rule t <= s (ACT_STATUS_RETURN_TOO_BIG) behind the charge and in front of both look-ups; the receipt's tag and the derived
+// nonces take t^ = t mod l (return_replay_lanes.h: t^ = 0 is the v1 hash, so `returned` null or all zero is act_redeem_(cbor_)admit_
+// replay_batch with RefundReturn outputs); the signing step is the return calls'.  out_counts: ACT_RETURN_REPLAY_COUNTS values.
+extern "C" int act_redeem_return_replay_batch(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys, int nkeys,
+                                              const uint32_t* key_epochs, int sign_key, const uint8_t* proof, const uint8_t* charge, const uint8_t* returned,
+                                              const uint8_t nonce_key[32], uint8_t* out_refund_return, uint8_t* status, uint8_t* out_key, uint8_t* out_replayed,
+                                              uint64_t* out_counts) {
+  if (n && !proof) { if (out_counts) memset(out_counts, 0, sizeof(uint64_t) * ACT_RETURN_REPLAY_COUNTS); return ACT_ERR_ARG; }
+  const RedeemReturn ret{returned};
+  return redeem_admit_replay_impl(c, set, receipts, n, mem, keys, nkeys, key_epochs, sign_key, proof, nullptr, nullptr, charge, nonce_key, out_refund_return, status,
+                                  out_key, out_replayed, out_counts, false, &ret);
+}
+extern "C" int act_redeem_cbor_return_replay_batch(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys, int nkeys,
+                                                   const uint32_t* key_epochs, int sign_key, const uint8_t* cbor, const uint64_t* offsets, const uint8_t* charge,
+                                                   const uint8_t* returned, const uint8_t nonce_key[32], uint8_t* out_refund_return_cbor, uint8_t* status,
+                                                   uint8_t* out_key, uint8_t* out_replayed, uint64_t* out_counts) {
+  if (n && !cbor) { if (out_counts) memset(out_counts, 0, sizeof(uint64_t) * ACT_RETURN_REPLAY_COUNTS); return ACT_ERR_ARG; }
+  static const uint8_t none = 0;
+  const RedeemReturn ret{returned};
+  return redeem_admit_replay_impl(c, set, receipts, n, mem, keys, nkeys, key_epochs, sign_key, nullptr, cbor ? cbor : &none, offsets, charge, nonce_key,
+                                  out_refund_return_cbor, status, out_key, out_replayed, out_counts, false, &ret);
 }

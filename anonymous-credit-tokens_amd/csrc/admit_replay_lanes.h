@@ -52,6 +52,7 @@ struct KprimeArgs {
   SpendArgs s;
   const uint8_t* kred; const uint32_t* idx;      // candidate c's reduced nullifier at kred + idx[c] * 32 (idx null: kred + c * 32)
   uint8_t* kp; uint8_t* tag; uint8_t* mark;      // n * 32, n * 32, n: enc(K'), the tag, 1 where a Com_j did not decode (then both are zero)
+  const uint8_t* t;                              // the return form (return_replay_lanes.h) only: candidate c's returned amount at t + idx[c] * 32, nullable
 };
 ACT_HD void kprime_decode_lane(const KprimeArgs& a, uint32_t gid) { spend_coords_lane(a.s, gid); }
 ACT_HD void kprime_tag_lane(const KprimeArgs& a, uint32_t c) {

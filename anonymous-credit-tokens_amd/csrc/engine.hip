@@ -23,6 +23,7 @@
 #include "admit.h"
 #include "replay_lanes.h"
 #include "admit_replay_lanes.h"
+#include "return_replay_lanes.h"
 #include "cbor_lanes.h"
 #include "issue_wire_lanes.h"
 #include "rng_source.h"

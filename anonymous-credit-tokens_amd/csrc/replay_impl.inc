@@ -40,7 +40,15 @@ struct ReplayDeriveJob { ReplayDeriveArgs a; };
 // the lane bodies on the host workers (host-memory callers)
 void replay_derive_host(const ReplayDeriveArgs& a, bool nonce) {
   ReplayDeriveJob job{a};
-  if (nonce) act_host_parallel_for(a.n, 256, 0, [](void* p, size_t i0, size_t i1) {
+  if (a.t && nonce) act_host_parallel_for(a.n, 256, 0, [](void* p, size_t i0, size_t i1) {      // the return forms: the lane's t in both hashes
+    const ReplayDeriveArgs& a = static_cast<ReplayDeriveJob*>(p)->a;
+    for (size_t i = i0; i < i1; i++) return_replay_nonce_lane(a, (uint32_t)i);
+  }, &job);
+  else if (a.t) act_host_parallel_for(a.n, 256, 0, [](void* p, size_t i0, size_t i1) {
+    const ReplayDeriveArgs& a = static_cast<ReplayDeriveJob*>(p)->a;
+    for (size_t i = i0; i < i1; i++) return_replay_tag_lane(a, (uint32_t)i);
+  }, &job);
+  else if (nonce) act_host_parallel_for(a.n, 256, 0, [](void* p, size_t i0, size_t i1) {
     const ReplayDeriveArgs& a = static_cast<ReplayDeriveJob*>(p)->a;
     for (size_t i = i0; i < i1; i++) replay_nonce_lane(a, (uint32_t)i);
   }, &job);
@@ -48,6 +56,11 @@ void replay_derive_host(const ReplayDeriveArgs& a, bool nonce) {
     const ReplayDeriveArgs& a = static_cast<ReplayDeriveJob*>(p)->a;
     for (size_t i = i0; i < i1; i++) replay_tag_lane(a, (uint32_t)i);
   }, &job);
+}
+// the kernels of k_replay.hip, or with amounts (a.t) those of k_return_replay.hip
+void replay_derive_dev(const ReplayDeriveArgs& a, bool nonce, hipStream_t s) {
+  if (a.t) { if (nonce) launch_return_replay_nonce(a, s); else launch_return_replay_tag(a, s); }
+  else if (nonce) launch_replay_nonce(a, s); else launch_replay_tag(a, s);
 }
 // The same buffer for host-memory callers: nonce_key | ring records where the host lane body reads them (4-byte aligned: the
 // allocation's own), then the nonces.  Not zero-filled (the lane body writes all 128 bytes of every lane) and wiped with
@@ -99,11 +112,14 @@ static int replay_refused(act_ctx* c, act_nullifier_set* set, act_nullifier_set*
 // kp, the verdicts st (merged in place), the matched keys out_key.  Tags, both set steps, resolve, derived nonces, the sign step and the
 // counts (ACT_REPLAY_COUNTS values, nullable).  The replay calls end in it over the caller's lanes, the admission form over its
 // survivors.  The caller holds replay_mu.  began (nullable): set once nothing in front of the tail proper can fail any more -- a return
-// with it unset has recorded nothing and written no status.
+// with it unset has recorded nothing and written no status.  ret (act_redeem_(cbor_)return_replay_batch, DESIGN 4.10): the returned amounts
+// lane for lane with the tail's arrays (ret->t null: every t = 0) -- they enter the tags, the nonces and the signing step, and the
+// outputs are RefundReturn records or messages.
 static int replay_tail(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys, int nkeys, const uint32_t* key_epochs,
                        int sign_key, bool wire, const uint8_t* k_at, size_t k_stride, const uint8_t* kp, uint8_t* st, const uint8_t* nonce_key, uint8_t* out,
-                       uint8_t* status, uint8_t* out_key, uint8_t* out_replayed, uint64_t* out_counts, bool* began) {
+                       uint8_t* status, uint8_t* out_key, uint8_t* out_replayed, uint64_t* out_counts, bool* began, const RedeemReturn* ret) {
   const bool dev = mem == ACT_MEM_DEVICE;
+  const uint8_t* const t = ret ? ret->t : nullptr;
   // tags; merged answers, key indices, the two sets' answers, the receipts mask and its answers, the replay marks
   const size_t per_lane = 32 + 7;
   std::vector<uint8_t> h; DevTmp d(c);
@@ -122,13 +138,13 @@ static int replay_tail(act_ctx* c, act_nullifier_set* set, act_nullifier_set* re
   hipStream_t stream = set->stream;
   int rc_receipts = ACT_OK; std::string receipts_err;
   if (began) *began = true;      // from here on status[] is complete on return, whatever fails
-  const int rc_tail = redeem_tail(c, set, n, mem, wire, st, sp, nonces, ACT_RNG_PER_LANE, out, status,
+  const int rc_tail = redeem_tail_sized(c, set, n, mem, redeem_out_bytes(c, wire, ret), st, sp, nonces, ACT_RNG_PER_LANE, out, status,
     [&](const uint8_t* mask, uint8_t* sp_out) -> int {
       // the tags first: they depend on the verification alone, and behind the insert of k nothing but the receipts may fail
-      ReplayDeriveArgs ta{}; ta.n = (uint32_t)n; ta.stride = (uint32_t)k_stride; ta.nul = k_at; ta.kp = kp; ta.st = mask; ta.out = tag;
+      ReplayDeriveArgs ta{}; ta.n = (uint32_t)n; ta.stride = (uint32_t)k_stride; ta.nul = k_at; ta.kp = kp; ta.st = mask; ta.out = tag; ta.t = t;
       if (dev) {
         RPCK(c, hipSetDevice(c->device));
-        launch_replay_tag(ta, stream);
+        replay_derive_dev(ta, false, stream);
         RPCK(c, hipGetLastError());
         RPCK(c, hipMemsetAsync(found, 0, n, stream)); RPCK(c, hipMemsetAsync(repl, 0, n, stream));
         RPCK(c, hipStreamSynchronize(stream));
@@ -154,11 +170,11 @@ static int replay_tail(act_ctx* c, act_nullifier_set* set, act_nullifier_set* re
     [&] {      // st is merged by now: the nonces of exactly the lanes that are signed, under the key each is signed with
       ring_sign_index(mem, kidx, out_key, sign_key, n);
       ReplayDeriveArgs na{}; na.n = (uint32_t)n; na.stride = (uint32_t)k_stride; na.nkeys = (uint32_t)nkeys; na.nul = k_at; na.kp = kp; na.st = st; na.kidx = kidx;
-      na.secrets = secrets; na.out = nonces;
-      if (dev) launch_replay_nonce(na, nullptr); else replay_derive_host(na, true);
+      na.secrets = secrets; na.out = nonces; na.t = t;
+      if (dev) replay_derive_dev(na, true, nullptr); else replay_derive_host(na, true);
     },
     [&](const uint8_t* verdict, const uint8_t* r, int r_mode, uint8_t* o, uint8_t* o_st) {
-      return ring_sign_step(c, n, mem, keys, nkeys, wire, kidx, kp, verdict, r, r_mode, o, o_st);
+      return ring_sign_step(c, n, mem, keys, nkeys, wire, kidx, kp, verdict, r, r_mode, o, o_st, ret);
     });
   if (out_counts) {      // status[] is complete behind the tail, whatever it returned
     std::vector<uint8_t> hs;
@@ -182,7 +198,7 @@ static int replay_tail(act_ctx* c, act_nullifier_set* set, act_nullifier_set* re
 // the verification and the tail over the caller's lanes; the caller has made the whole-call refusals and holds replay_mu
 static int redeem_replay_locked(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys, int nkeys,
                                 const uint32_t* key_epochs, int sign_key, const uint8_t* proof, const uint8_t* cbor, const uint64_t* offsets, const uint8_t* nonce_key,
-                                uint8_t* out, uint8_t* status, uint8_t* out_key, uint8_t* out_replayed, uint64_t* out_counts) {
+                                uint8_t* out, uint8_t* status, uint8_t* out_key, uint8_t* out_replayed, uint64_t* out_counts, const RedeemReturn* ret) {
   const bool wire = cbor != nullptr, dev = mem == ACT_MEM_DEVICE;
   const size_t pb = act_spend_proof_bytes(c);
   // K', the verdicts and (wire form) the nullifiers
@@ -196,7 +212,7 @@ static int redeem_replay_locked(act_ctx* c, act_nullifier_set* set, act_nullifie
   else rc = act_verify_spend_keyring_batch(c, n, mem, keys, nkeys, proof, st, out_key, kp);
   if (rc) return rc;
   return replay_tail(c, set, receipts, n, mem, keys, nkeys, key_epochs, sign_key, wire, wire ? nul : proof, wire ? 32 : pb, kp, st, nonce_key, out, status, out_key,
-                     out_replayed, out_counts);
+                     out_replayed, out_counts, nullptr, ret);
 }
 
 static int redeem_replay_impl(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys, int nkeys,
@@ -211,7 +227,8 @@ static int redeem_replay_impl(act_ctx* c, act_nullifier_set* set, act_nullifier_
   if (n == 0) return redeem_keyring_impl(c, set, 0, mem, keys, nkeys, key_epochs, sign_key, nullptr, nullptr, nullptr, &derived, ACT_RNG_PER_LANE, nullptr, nullptr, nullptr);
   // one replay call at a time per context: the staged secrets and the derived nonces live in the context's own buffer (d_replay)
   std::lock_guard<std::mutex> replay(c->replay_mu);
-  return redeem_replay_locked(c, set, receipts, n, mem, keys, nkeys, key_epochs, sign_key, proof, cbor, offsets, nonce_key, out, status, out_key, out_replayed, out_counts);
+  return redeem_replay_locked(c, set, receipts, n, mem, keys, nkeys, key_epochs, sign_key, proof, cbor, offsets, nonce_key, out, status, out_key, out_replayed, out_counts,
+                              nullptr);
 }
 
 extern "C" int act_redeem_replay_batch(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys, int nkeys,
@@ -230,14 +247,16 @@ extern "C" int act_redeem_cbor_replay_batch(act_ctx* c, act_nullifier_set* set, 
                             out_key, out_replayed, out_counts);
 }
 
-extern "C" int act_replay_derive_batch(act_ctx* c, size_t n, int mem, const uint8_t* keys, int nkeys, const uint8_t* key_index, const uint8_t nonce_key[32],
-                                       const uint8_t* nullifiers, size_t stride, const uint8_t* kprime, const uint8_t* status_in, uint8_t* out_tags,
-                                       uint8_t* out_nonces) {
+// the building block of both derive calls; returned (act_replay_derive_return_batch): n amounts in `mem` memory, null: act_replay_derive_batch
+static int replay_derive_impl(act_ctx* c, size_t n, int mem, const uint8_t* keys, int nkeys, const uint8_t* key_index, const uint8_t* nonce_key,
+                              const uint8_t* nullifiers, size_t stride, const uint8_t* kprime, const uint8_t* status_in, const uint8_t* returned, uint8_t* out_tags,
+                              uint8_t* out_nonces) {
   if (!c || !keys || !nonce_key || nkeys < 1 || nkeys > ACT_KEYRING_MAX || (mem != ACT_MEM_HOST && mem != ACT_MEM_DEVICE)) return ACT_ERR_ARG;
   if (n > ((size_t)1 << 30) || stride < 32 || stride > 0xFFFFFFFFu || (n && (!key_index || !nullifiers || !kprime || !status_in))) return ACT_ERR_ARG;
   if (n == 0 || (!out_tags && !out_nonces)) return ACT_OK;
   std::lock_guard<std::mutex> replay(c->replay_mu);
   ReplayDeriveArgs a{}; a.n = (uint32_t)n; a.stride = (uint32_t)stride; a.nkeys = (uint32_t)nkeys; a.nul = nullifiers; a.kp = kprime; a.st = status_in; a.kidx = key_index;
+  a.t = returned;
   if (mem == ACT_MEM_HOST) {
     ReplaySecretsHost sec;
     sec.stage(0, nonce_key, keys, nkeys);
@@ -252,9 +271,19 @@ extern "C" int act_replay_derive_batch(act_ctx* c, size_t n, int mem, const uint
   std::lock_guard<std::mutex> lk(c->mu);
   RPCK(c, hipSetDevice(c->device));
   hipStream_t stream = c->slots[0].stream;
-  if (out_tags) { a.out = out_tags; launch_replay_tag(a, stream); }
-  if (out_nonces) { a.out = out_nonces; launch_replay_nonce(a, stream); }
+  if (out_tags) { a.out = out_tags; replay_derive_dev(a, false, stream); }
+  if (out_nonces) { a.out = out_nonces; replay_derive_dev(a, true, stream); }
   RPCK(c, hipGetLastError());
   RPCK(c, hipStreamSynchronize(stream));
   return ACT_OK;
+}
+extern "C" int act_replay_derive_batch(act_ctx* c, size_t n, int mem, const uint8_t* keys, int nkeys, const uint8_t* key_index, const uint8_t nonce_key[32],
+                                       const uint8_t* nullifiers, size_t stride, const uint8_t* kprime, const uint8_t* status_in, uint8_t* out_tags,
+                                       uint8_t* out_nonces) {
+  return replay_derive_impl(c, n, mem, keys, nkeys, key_index, nonce_key, nullifiers, stride, kprime, status_in, nullptr, out_tags, out_nonces);
+}
+extern "C" int act_replay_derive_return_batch(act_ctx* c, size_t n, int mem, const uint8_t* keys, int nkeys, const uint8_t* key_index, const uint8_t nonce_key[32],
+                                              const uint8_t* nullifiers, size_t stride, const uint8_t* kprime, const uint8_t* status_in, const uint8_t* returned,
+                                              uint8_t* out_tags, uint8_t* out_nonces) {
+  return replay_derive_impl(c, n, mem, keys, nkeys, key_index, nonce_key, nullifiers, stride, kprime, status_in, returned, out_tags, out_nonces);
 }

@@ -63,6 +63,7 @@ struct ReplayDeriveArgs {
   const uint8_t* kidx;                // n key indices: nullable for the tag (it does not depend on the key), required for the nonce
   const uint8_t* secrets;             // the nonce: REPLAY_SECRET_BYTES, 4-byte aligned -- nonce_key | nkeys records of 64 bytes
   uint8_t* out;                       // n * 32 tags or n * 128 nonces, any alignment
+  const uint8_t* t;                   // the return forms (return_replay_lanes.h) only: nullable, n returned amounts of 32 bytes at any alignment
 };
 ACT_HD bool replay_lane_live(const ReplayDeriveArgs& a, uint32_t i) { return a.st[i] == 0 && (!a.kidx || a.kidx[i] < a.nkeys); }
 

@@ -1016,11 +1016,12 @@ int act_ubench_table_read(act_ctx *ctx, int base, int waves_per_simd, int in_fli
  * t > s, s from the lane's proof record -> ACT_STATUS_AMOUNT_TOO_BIG (a balance above what the client had can never be proven in
  * range: better to learn it now), else the token A | e | k | r | (m + t) mod l.
  *
- * NOT OFFERED, on purpose: the replay forms (act_redeem_*replay*) take no `returned`.  They derive e and alpha from
- * (nonce_key, key, k, enc(K')), so a retry with another t would be signed with the SAME e over an X_A that differs by (t1 - t2) h1:
- * the two A values differ by (t1 - t2) (e + x)^-1 h1, which hands out h1 (e + x)^-1 -- and with it anyone raises the balance of a
- * token signed under that e.  Before a replay form may take t, t must be bound into BOTH the receipt tag and the nonce derivation.
- * The calls here use drawn nonces only.  Also not offered here: the node-handle forms.
+ * NOT OFFERED, on purpose: the replay forms of the sections above (act_redeem_(cbor_)replay_batch, act_redeem_(cbor_)admit_replay_batch
+ * and their unique forms) take no `returned`.  They derive e and alpha from (nonce_key, key, k, enc(K')) alone, so a retry with another
+ * t would be signed with the SAME e over an X_A that differs by (t1 - t2) h1: the two A values differ by (t1 - t2) (e + x)^-1 h1, which
+ * hands out h1 (e + x)^-1 -- and with it anyone raises the balance of a token signed under that e.  The calls here use drawn nonces.
+ * The replay form WITH amounts is a pair of calls of its own, act_redeem_(cbor_)return_replay_batch below ("replayable partial
+ * refunds"), where t is bound into BOTH the receipt tag and the nonce derivation.  Also not offered here: the node-handle forms.
  *
  * act_refund_to_credit_token_return_keyring_batch is act_refund_to_credit_token_keyring_batch over n * 160 RefundReturn records: a
  * RefundReturn names no key either.  The same chunk schedule, staging and wiping of `pre`, ring checks (an entry that is not a canonical
@@ -1072,6 +1073,67 @@ int act_redeem_cbor_return_unique_batch(act_ctx *ctx, act_nullifier_set *set, si
                                         const uint32_t *key_epochs /* nullable */, int sign_key, const uint8_t *cbor, const uint64_t *offsets,
                                         const uint8_t *charge /* nullable */, const uint8_t *returned /* nullable */, const uint8_t *rng, int rng_mode,
                                         uint8_t *out_refund_return_cbor, uint8_t *status, uint8_t *out_key, uint64_t *out_counts /* nullable, host */);
+
+/* ======== replayable partial refunds: the receipt pins t, the nonces take it ========
+ * act_redeem_return_replay_batch / act_redeem_cbor_return_replay_batch are act_redeem_(cbor_)admit_replay_batch with `returned` (the
+ * `amounts` argument of the prototypes below: n scalars in `mem` memory behind `charge`, nullable: all zero): a metered service that reserves s and gives t <= s back stays
+ * retry-safe.  Write t^ = t mod l.  The outputs are RefundReturn records of 160 bytes (wire form: ACT_CBOR_REFUND_RETURN messages of
+ * act_cbor_size bytes) ALWAYS, all zero where not signed.
+ *
+ * The two hashes of the replayable redemption with an amount:
+ *       t^ == 0   the tag and the nonces are the v1 hashes above ("act-mi355x/receipt/v1", "act-mi355x/refund-nonce/v1"), bit for bit
+ *       t^ != 0   tag   = BLAKE3("act-mi355x/receipt-t/v1" padded to 32 | k | enc(K') | t^)[0:32], top nibble cleared      (128 bytes)
+ *                 nonce = BLAKE3-XOF("act-mi355x/refund-nonce-t/v1" padded to 32 | nonce_key | key | k | enc(K') | t^, 128)  (224 bytes)
+ * t is public (it travels in the record), so which hash a lane takes is public too.  Under any history of the two sets, rollbacks from
+ * snapshots included, two different t^ for one (key, k, K') never share an e.
+ *
+ * Per lane, in this order:
+ *   1. the wire reader's code (wire form), 2. the charge (ACT_STATUS_WRONG_CHARGE) -- as act_redeem_(cbor_)admit_replay_batch.
+ *   2b. t^ > s^ (both reduced mod l, compared as integers) -> ACT_STATUS_RETURN_TOO_BIG: behind the charge rule and in front of BOTH
+ *       look-ups; not verified, not recorded, not signed, a zero record, ACT_KEY_NONE.  A lane that also has the wrong charge reports
+ *       ACT_STATUS_WRONG_CHARGE.  A shed lane leaves no trace in either set.
+ *   3. k is looked up.  A spent lane is a retry candidate only if `receipts` holds the tag of (k, enc(K'), t^): THE RECEIPT PINS THE
+ *      AMOUNT.  A retry that names the t^ the spend was recorded with is verified and signed again, and its RefundReturn is byte for
+ *      byte the one handed out before (out_replayed = 1).  A retry that names ANOTHER amount is ACT_STATUS_DOUBLE_SPEND, shed
+ *      unverified (counted as foreign_spend, not in verified; zero record, ACT_KEY_NONE), and both sets stay as they were.
+ *   4. verification, then the replay tail over the lanes that are left: check-and-insert of k; a receipt (k, enc(K'), t^) ONLY where
+ *      k was fresh; the others are looked up -- found: replayed, else ACT_STATUS_DOUBLE_SPEND (so inside one batch [P t1, P t1, P t2]
+ *      ends 0 / 0 replayed / 3); the nonces of (nonce_key, key, k, enc(K'), t^); the signature over X_A = g + K' + t h1.
+ * This is on purpose: a SpendProof is not bound to a request.  The pinned t^ is what keeps a client from replaying an expensive spend
+ * beside a cheap request and collecting a larger refund.  THE CALLER'S CONTRACT: a service must derive t deterministically from the
+ * request, or remember it -- a retry answered with another t is refused, not re-priced.
+ *
+ * With returned all zero (or NULL): statuses, out_key, out_replayed, both sets with their epochs, out_counts[0..11) and the first 128
+ * bytes of every record are those of act_redeem_(cbor_)admit_replay_batch on identical sets, and bytes 128..160 are zero (wire form:
+ * the type 10 framing of the same fields).  A spend recorded by act_redeem_(cbor_)(admit_)replay_batch is served here with t = 0, and
+ * retried here with t != 0 it is a double spend; a spend recorded here with t != 0 is a double spend for the calls without amounts.
+ *
+ * out_counts: nullable, host, ACT_RETURN_REPLAY_COUNTS values: the eleven of ACT_ADMIT_REPLAY_COUNTS in their order, then
+ * return_too_big; verified = lanes - wire_rejected - wrong_charge - return_too_big - foreign_spend.
+ * Refused as a whole (nothing written, nothing recorded): everything act_redeem_(cbor_)admit_replay_batch refuses -- receipts == set,
+ * a receipts set without room for n more keys, epoch tables that do not fit both sets, a bad ring.  The failure contract is that
+ * call's: after ACT_STATUS_RECORDED_UNSIGNED a later retry with the same t is served.
+ * NOT OFFERED, on purpose: unique forms with returned amounts (a copy that names another t than its leader must not be served the
+ * leader's row; the engine refuses the combination with ACT_ERR_ARG); node-handle forms; tiny or fused roads; a `returned` argument
+ * on the screenless act_redeem_(cbor_)replay_batch -- the bound t <= s lives in the screen.
+ *
+ * act_replay_derive_return_batch is act_replay_derive_batch plus `returned` (nullable: that call): the tags and nonces above for
+ * callers that compose the feature over the node-level calls with act_refund_sign_return_keyring_batch -- which is how it reaches
+ * several GPUs.  A lane that does not take part (status_in != 0, key_index >= nkeys) gets zeros and its amount is not read. */
+#define ACT_RETURN_REPLAY_COUNTS 12
+int act_redeem_return_replay_batch(act_ctx *ctx, act_nullifier_set *set, act_nullifier_set *receipts, size_t n, int mem, const uint8_t *keys, int nkeys,
+                                   const uint32_t *key_epochs /* nullable */, int sign_key, const uint8_t *proof, const uint8_t *charge /* nullable */,
+                                   const uint8_t *amounts /* t; nullable: all zero */, const uint8_t nonce_key[32], uint8_t *out_refund_return,
+                                   uint8_t *status, uint8_t *out_key, uint8_t *out_replayed /* nullable */, uint64_t *out_counts /* nullable, host */);
+int act_redeem_cbor_return_replay_batch(act_ctx *ctx, act_nullifier_set *set, act_nullifier_set *receipts, size_t n, int mem, const uint8_t *keys, int nkeys,
+                                        const uint32_t *key_epochs /* nullable */, int sign_key, const uint8_t *cbor, const uint64_t *offsets,
+                                        const uint8_t *charge /* nullable */, const uint8_t *amounts /* t; nullable: all zero */, const uint8_t nonce_key[32],
+                                        uint8_t *out_refund_return_cbor, uint8_t *status, uint8_t *out_key, uint8_t *out_replayed /* nullable */,
+                                        uint64_t *out_counts /* nullable, host */);
+int act_replay_derive_return_batch(act_ctx *ctx, size_t n, int mem, const uint8_t *keys, int nkeys, const uint8_t *key_index,
+                                   const uint8_t nonce_key[32], const uint8_t *nullifiers, size_t stride, const uint8_t *kprime,
+                                   const uint8_t *status_in, const uint8_t *amounts /* t; nullable */, uint8_t *out_tags /* nullable */,
+                                   uint8_t *out_nonces /* nullable */);
 
 #ifdef __cplusplus
 }

@@ -182,6 +182,16 @@ extern "C" {
     fn act_redeem_cbor_return_unique_batch(ctx: *mut ActCtx, set: *mut ActNullifierSet, n: usize, mem: c_int, keys: *const u8, nkeys: c_int, key_epochs: *const u32,
                                            sign_key: c_int, cbor: *const u8, offsets: *const u64, charge: *const u8, returned: *const u8, rng: *const u8,
                                            rng_mode: c_int, out_refund_return_cbor: *mut u8, status: *mut u8, out_key: *mut u8, out_counts: *mut u64) -> c_int;
+    fn act_redeem_return_replay_batch(ctx: *mut ActCtx, set: *mut ActNullifierSet, receipts: *mut ActNullifierSet, n: usize, mem: c_int, keys: *const u8, nkeys: c_int,
+                                      key_epochs: *const u32, sign_key: c_int, proof: *const u8, charge: *const u8, amounts: *const u8, nonce_key: *const u8,
+                                      out_refund_return: *mut u8, status: *mut u8, out_key: *mut u8, out_replayed: *mut u8, out_counts: *mut u64) -> c_int;
+    fn act_redeem_cbor_return_replay_batch(ctx: *mut ActCtx, set: *mut ActNullifierSet, receipts: *mut ActNullifierSet, n: usize, mem: c_int, keys: *const u8,
+                                           nkeys: c_int, key_epochs: *const u32, sign_key: c_int, cbor: *const u8, offsets: *const u64, charge: *const u8,
+                                           amounts: *const u8, nonce_key: *const u8, out_refund_return_cbor: *mut u8, status: *mut u8, out_key: *mut u8,
+                                           out_replayed: *mut u8, out_counts: *mut u64) -> c_int;
+    fn act_replay_derive_return_batch(ctx: *mut ActCtx, n: usize, mem: c_int, keys: *const u8, nkeys: c_int, key_index: *const u8, nonce_key: *const u8,
+                                      nullifiers: *const u8, stride: usize, kprime: *const u8, status_in: *const u8, amounts: *const u8, out_tags: *mut u8,
+                                      out_nonces: *mut u8) -> c_int;
 }
 
 /// ACT_MI355X_DEVICES = "0,1,2,3,4,5,6,7" (default: device 0)
@@ -1209,7 +1219,7 @@ pub struct Returned {
 /// Partial refunds on ONE GPU (include/act_mi355x.h "partial refunds"): the admission calls with the amounts `t <= s` the issuer gives
 /// back -- every accepted lane is signed over `X_A = g + K' + t h1`, so the client's next token holds `c - s + t`.  A lane with
 /// `t > s` is answered `ACT_STATUS_RETURN_TOO_BIG` without being looked up or verified.  A sibling of `GpuAdmission`, not a mode of
-/// the replay types: with derived nonces two returns for one proof would share `e` and give `h1 (e + x)^-1` away (the header says why).
+/// the replay types: drawn nonces here.  The retry-safe form is `GpuReplay::returned`, where `t` enters the receipt tag and the nonces.
 pub struct GpuReturn {
     ctx: *mut ActCtx,
     set: *mut ActNullifierSet,
@@ -1370,6 +1380,8 @@ pub const ACT_REPLAY_COUNTS: usize = 6;
 pub const ACT_ADMIT_REPLAY_COUNTS: usize = 11;
 /// the eleven above, then copies / copies_served (`GpuReplay::unique(true)`)
 pub const ACT_ADMIT_REPLAY_UNIQUE_COUNTS: usize = 13;
+/// the eleven of `ACT_ADMIT_REPLAY_COUNTS`, then return_too_big (`GpuReplay::returned(Some(..))`)
+pub const ACT_RETURN_REPLAY_COUNTS: usize = 12;
 /// statuses, outputs (128-byte Refund records or `REFUND_CBOR_BYTES` messages, all zero where not signed), matched ring keys, the
 /// replay marks, and lanes / rejected_by_verification / fresh / replayed / double_spend / unanswered
 pub struct Replayed {
@@ -1385,8 +1397,15 @@ pub struct Replayed {
     /// all zero unless the call ran the unique form (`GpuReplay::unique(true)`): copies (lanes with the bytes of an earlier lane, not
     /// verified) and copies_served (those whose leader ended 0); `admit_counts` then counts verified lanes only
     pub copy_counts: [u64; 2],
+    /// 0 unless the call took returned amounts (`GpuReplay::returned`): the lanes whose amount exceeded their charge.  `out` then holds
+    /// 160-byte RefundReturn records or `REFUND_RETURN_CBOR_BYTES` messages
+    pub return_too_big: u64,
 }
 impl Replayed {
+    fn take_return_counts(&mut self, t: &[u64; ACT_RETURN_REPLAY_COUNTS]) {
+        self.admit_counts.copy_from_slice(&t[..ACT_ADMIT_REPLAY_COUNTS]);
+        self.return_too_big = t[ACT_ADMIT_REPLAY_COUNTS];
+    }
     fn take_unique_counts(&mut self, u: &[u64; ACT_ADMIT_REPLAY_UNIQUE_COUNTS]) {
         self.admit_counts.copy_from_slice(&u[..ACT_ADMIT_REPLAY_COUNTS]);
         self.copy_counts = [u[ACT_ADMIT_REPLAY_COUNTS], u[ACT_ADMIT_REPLAY_COUNTS + 1]];
@@ -1409,12 +1428,13 @@ pub struct GpuReplay {
     admit: bool,
     unique: bool,
     charges: Option<Vec<u8>>,
+    returned: Option<Vec<u8>>,
 }
 impl GpuReplay {
     /// # Safety
     /// `ctx`, `set` and `receipts` are live handles on one device, `set != receipts`, and all three outlive `self`.
     pub unsafe fn from_raw(ctx: *mut ActCtx, set: *mut ActNullifierSet, receipts: *mut ActNullifierSet, nonce_key: [u8; 32]) -> Self {
-        GpuReplay { ctx, set, receipts, nonce_key, admit: false, unique: false, charges: None }
+        GpuReplay { ctx, set, receipts, nonce_key, admit: false, unique: false, charges: None, returned: None }
     }
     /// `true`: the calls go through the admission screen (include/act_mi355x.h "admission for the replayable redemption") -- a spent
     /// nullifier whose receipt is not this proof's is `DoubleSpendError` without being verified; a retry is verified and served.
@@ -1426,6 +1446,15 @@ impl GpuReplay {
     /// What each request of the next calls costs: n scalars of 32 bytes, compared with `SpendProof.s` by the screen (implies nothing
     /// without `admit(true)`); `None`: no comparison.
     pub fn charges(mut self, charges: Option<Vec<u8>>) -> Self { self.charges = charges; self }
+    /// The amounts the issuer gives back with the next calls (include/act_mi355x.h "replayable partial refunds"): n scalars of 32 bytes,
+    /// `t <= s` per lane (`ACT_STATUS_RETURN_TOO_BIG` otherwise).  `Some`: the calls go to `act_redeem_(cbor_)return_replay_batch` -- the
+    /// admission screen is implied, the outputs are RefundReturns, and the receipt PINS the amount: a retry with the same amount gets
+    /// the same bytes, with another amount `DoubleSpendError`.  Derive the amount from the request, or remember it.  Together with
+    /// `unique(true)` the calls return `ACT_ERR_ARG` and write nothing.  `None`: the calls without amounts.
+    pub fn returned(mut self, returned: Option<Vec<u8>>) -> Self { self.returned = returned; self }
+    fn returned_ptr(&self, n: usize) -> *const u8 {
+        self.returned.as_ref().map_or(std::ptr::null(), |t| { assert!(t.len() == 32 * n); t.as_ptr() })
+    }
     fn charge_ptr(&self, n: usize) -> *const u8 {
         self.charges.as_ref().map_or(std::ptr::null(), |c| { assert!(c.len() == 32 * n); c.as_ptr() })
     }
@@ -1433,10 +1462,16 @@ impl GpuReplay {
     pub fn redeem_replay_batch(&self, keys: &[u8], key_epochs: Option<&[u32]>, sign_with: Option<usize>, proofs: &[u8]) -> Replayed {
         let (n, nkeys) = (proofs.len() / PROOF_BYTES, keys.len() / 64);
         assert!(proofs.len() == n * PROOF_BYTES && key_epochs.map_or(true, |e| e.len() == nkeys));
-        let mut r = Replayed { rc: 0, status: vec![0u8; n + 1], out: vec![0u8; 128 * n + 1], out_key: vec![ACT_KEY_NONE; n + 1], replayed: vec![0u8; n + 1], counts: [0; ACT_REPLAY_COUNTS],
-                               admit_counts: [0; ACT_ADMIT_REPLAY_COUNTS], copy_counts: [0; 2] };
+        let rec = if self.returned.is_some() { 160 } else { 128 };
+        let mut r = Replayed { rc: 0, status: vec![0u8; n + 1], out: vec![0u8; rec * n + 1], out_key: vec![ACT_KEY_NONE; n + 1], replayed: vec![0u8; n + 1], counts: [0; ACT_REPLAY_COUNTS],
+                               admit_counts: [0; ACT_ADMIT_REPLAY_COUNTS], copy_counts: [0; 2], return_too_big: 0 };
         let mut u = [0u64; ACT_ADMIT_REPLAY_UNIQUE_COUNTS];
-        r.rc = if self.admit && self.unique { unsafe {
+        let mut t = [0u64; ACT_RETURN_REPLAY_COUNTS];
+        r.rc = if self.returned.is_some() && self.unique { 1 /* ACT_ERR_ARG: no unique form with amounts */ } else if self.returned.is_some() { unsafe {
+            act_redeem_return_replay_batch(self.ctx, self.set, self.receipts, n, 0, keys.as_ptr(), nkeys as c_int, key_epochs.map_or(std::ptr::null(), |e| e.as_ptr()),
+                                           sign_with.map_or(ACT_SIGN_MATCHED, |i| i as c_int), proofs.as_ptr(), self.charge_ptr(n), self.returned_ptr(n),
+                                           self.nonce_key.as_ptr(), r.out.as_mut_ptr(), r.status.as_mut_ptr(), r.out_key.as_mut_ptr(), r.replayed.as_mut_ptr(), t.as_mut_ptr())
+        } } else if self.admit && self.unique { unsafe {
             act_redeem_admit_replay_unique_batch(self.ctx, self.set, self.receipts, n, 0, keys.as_ptr(), nkeys as c_int, key_epochs.map_or(std::ptr::null(), |e| e.as_ptr()),
                                                  sign_with.map_or(ACT_SIGN_MATCHED, |i| i as c_int), proofs.as_ptr(), self.charge_ptr(n), self.nonce_key.as_ptr(),
                                                  r.out.as_mut_ptr(), r.status.as_mut_ptr(), r.out_key.as_mut_ptr(), r.replayed.as_mut_ptr(), u.as_mut_ptr())
@@ -1449,9 +1484,10 @@ impl GpuReplay {
                                     sign_with.map_or(ACT_SIGN_MATCHED, |i| i as c_int), proofs.as_ptr(), self.nonce_key.as_ptr(), r.out.as_mut_ptr(),
                                     r.status.as_mut_ptr(), r.out_key.as_mut_ptr(), r.replayed.as_mut_ptr(), r.counts.as_mut_ptr())
         } };
-        if self.admit && self.unique { r.take_unique_counts(&u); }
-        if self.admit { r.take_admit_counts(); }
-        r.status.truncate(n); r.out.truncate(128 * n); r.out_key.truncate(n); r.replayed.truncate(n);
+        if self.returned.is_some() { r.take_return_counts(&t); }
+        else if self.admit && self.unique { r.take_unique_counts(&u); }
+        if self.admit || self.returned.is_some() { r.take_admit_counts(); }
+        r.status.truncate(n); r.out.truncate(rec * n); r.out_key.truncate(n); r.replayed.truncate(n);
         r
     }
     /// The same on wire bytes: CBOR SpendProof messages in (a retry may be another spelling of the same proof), CBOR Refund messages out.
@@ -1459,10 +1495,17 @@ impl GpuReplay {
         let (blob, offsets) = gather(msgs);
         let (n, nkeys) = (msgs.len(), keys.len() / 64);
         assert!(key_epochs.map_or(true, |e| e.len() == nkeys));
-        let mut r = Replayed { rc: 0, status: vec![0u8; n + 1], out: vec![0u8; REFUND_CBOR_BYTES * n + 1], out_key: vec![ACT_KEY_NONE; n + 1], replayed: vec![0u8; n + 1],
-                               counts: [0; ACT_REPLAY_COUNTS], admit_counts: [0; ACT_ADMIT_REPLAY_COUNTS], copy_counts: [0; 2] };
+        let rec = if self.returned.is_some() { REFUND_RETURN_CBOR_BYTES } else { REFUND_CBOR_BYTES };
+        let mut r = Replayed { rc: 0, status: vec![0u8; n + 1], out: vec![0u8; rec * n + 1], out_key: vec![ACT_KEY_NONE; n + 1], replayed: vec![0u8; n + 1],
+                               counts: [0; ACT_REPLAY_COUNTS], admit_counts: [0; ACT_ADMIT_REPLAY_COUNTS], copy_counts: [0; 2], return_too_big: 0 };
         let mut u = [0u64; ACT_ADMIT_REPLAY_UNIQUE_COUNTS];
-        r.rc = if self.admit && self.unique { unsafe {
+        let mut t = [0u64; ACT_RETURN_REPLAY_COUNTS];
+        r.rc = if self.returned.is_some() && self.unique { 1 /* ACT_ERR_ARG: no unique form with amounts */ } else if self.returned.is_some() { unsafe {
+            act_redeem_cbor_return_replay_batch(self.ctx, self.set, self.receipts, n, 0, keys.as_ptr(), nkeys as c_int, key_epochs.map_or(std::ptr::null(), |e| e.as_ptr()),
+                                                sign_with.map_or(ACT_SIGN_MATCHED, |i| i as c_int), blob.as_ptr(), offsets.as_ptr(), self.charge_ptr(n), self.returned_ptr(n),
+                                                self.nonce_key.as_ptr(), r.out.as_mut_ptr(), r.status.as_mut_ptr(), r.out_key.as_mut_ptr(), r.replayed.as_mut_ptr(),
+                                                t.as_mut_ptr())
+        } } else if self.admit && self.unique { unsafe {
             act_redeem_cbor_admit_replay_unique_batch(self.ctx, self.set, self.receipts, n, 0, keys.as_ptr(), nkeys as c_int, key_epochs.map_or(std::ptr::null(), |e| e.as_ptr()),
                                                       sign_with.map_or(ACT_SIGN_MATCHED, |i| i as c_int), blob.as_ptr(), offsets.as_ptr(), self.charge_ptr(n),
                                                       self.nonce_key.as_ptr(), r.out.as_mut_ptr(), r.status.as_mut_ptr(), r.out_key.as_mut_ptr(), r.replayed.as_mut_ptr(),
@@ -1477,9 +1520,10 @@ impl GpuReplay {
                                          sign_with.map_or(ACT_SIGN_MATCHED, |i| i as c_int), blob.as_ptr(), offsets.as_ptr(), self.nonce_key.as_ptr(),
                                          r.out.as_mut_ptr(), r.status.as_mut_ptr(), r.out_key.as_mut_ptr(), r.replayed.as_mut_ptr(), r.counts.as_mut_ptr())
         } };
-        if self.admit && self.unique { r.take_unique_counts(&u); }
-        if self.admit { r.take_admit_counts(); }
-        r.status.truncate(n); r.out.truncate(REFUND_CBOR_BYTES * n); r.out_key.truncate(n); r.replayed.truncate(n);
+        if self.returned.is_some() { r.take_return_counts(&t); }
+        else if self.admit && self.unique { r.take_unique_counts(&u); }
+        if self.admit || self.returned.is_some() { r.take_admit_counts(); }
+        r.status.truncate(n); r.out.truncate(rec * n); r.out_key.truncate(n); r.replayed.truncate(n);
         r
     }
     /// The building block: per lane with `status_in[i] == 0` and `key_index[i] < nkeys` the 32-byte receipt tag and the 128 nonce
@@ -1488,10 +1532,13 @@ impl GpuReplay {
         let n = status_in.len();
         assert!(key_index.len() == n && nullifiers.len() == 32 * n && kprime.len() == 32 * n);
         let (mut tags, mut nonces) = (vec![0u8; 32 * n + 1], vec![0u8; 128 * n + 1]);
-        let rc = unsafe {
+        let rc = if self.returned.is_some() { unsafe {      // the hashes take the lanes' amounts
+            act_replay_derive_return_batch(self.ctx, n, 0, keys.as_ptr(), (keys.len() / 64) as c_int, key_index.as_ptr(), self.nonce_key.as_ptr(), nullifiers.as_ptr(), 32,
+                                           kprime.as_ptr(), status_in.as_ptr(), self.returned_ptr(n), tags.as_mut_ptr(), nonces.as_mut_ptr())
+        } } else { unsafe {
             act_replay_derive_batch(self.ctx, n, 0, keys.as_ptr(), (keys.len() / 64) as c_int, key_index.as_ptr(), self.nonce_key.as_ptr(), nullifiers.as_ptr(), 32,
                                     kprime.as_ptr(), status_in.as_ptr(), tags.as_mut_ptr(), nonces.as_mut_ptr())
-        };
+        } };
         tags.truncate(32 * n); nonces.truncate(128 * n);
         (rc, tags, nonces)
     }
