@@ -320,6 +320,17 @@ class PrivateKey(_Cbor):
                                                                     returned=returned)
         return res, replayed
 
+    def redeem_return_replay_unique_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", proofs: Sequence["SpendProof"], nonce_key: bytes,
+                                          returned: Sequence = None, charges: Sequence = None) -> Tuple[list, list]:
+        """Keyring.redeem_return_replay_unique_batch with this key alone.  -> (results, replayed flags)"""
+        res, _, replayed = Keyring([self]).redeem_return_replay_unique_batch(params, db, receipts, proofs, nonce_key, returned=returned, charges=charges)
+        return res, replayed
+
+    def redeem_return_replay_unique_cbor_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", msgs: Sequence[bytes], nonce_key: bytes, nbits: int = L,
+                                               returned: Sequence = None, charges: Sequence = None) -> Tuple[list, list]:
+        res, _, replayed = Keyring([self]).redeem_return_replay_unique_cbor_batch(params, db, receipts, msgs, nonce_key, nbits, returned=returned, charges=charges)
+        return res, replayed
+
     def verify_spend_batch(self, params: Params, proofs: Sequence["SpendProof"]) -> bytes:
         nbits = proofs[0].nbits if proofs else L
         return params.engine(nbits).verify_spend(self.record, b"".join(p.record for p in proofs))
@@ -459,11 +470,12 @@ class Keyring:
         returned (one amount per proof; act_redeem_return_replay_batch; implies admit=True): the reserve-then-return step made
         retry-safe -- entry i is a RefundReturn over returned[i]; returned[i] > s_i is Error 249.  The receipt PINS the amount: a proof
         sent again with the same amount gets the same RefundReturn, with another amount DoubleSpendError -- derive the amount from the
-        request, or remember it.  The counts are capi.RETURN_REPLAY_COUNTS.  Not with unique=True (ValueError).
+        request, or remember it.  The counts are capi.RETURN_REPLAY_COUNTS.  Not with unique=True (ValueError): that form is a method
+        of its own, redeem_return_replay_unique_batch.
         -> (results, matched ring indices, replayed flags); `self.last_replay_counts`: the call's counts."""
         nbits = proofs[0].nbits if proofs else L
         if returned is not None and unique:
-            raise ValueError("a copy may name another amount than its leader: no unique form with returned amounts")
+            raise ValueError("a copy may name another amount than its leader: the unique form with returned amounts is redeem_return_replay_unique_batch")
         admit = admit or returned is not None
         if charges is not None and not admit:
             raise ValueError("charges are compared by the admission screen: admit=True")
@@ -489,9 +501,9 @@ class Keyring:
         """the same on wire bytes (act_redeem_cbor_replay_batch; admit=True: act_redeem_cbor_admit_replay_batch): a retry may be another
         CBOR spelling of the same proof.  unique=True (with admit=True): act_redeem_cbor_admit_replay_unique_batch -- a copy is a message
         of the same length and the same bytes; another spelling is verified on its own.  returned: act_redeem_cbor_return_replay_batch --
-        entry i is a CBOR RefundReturn message (implies admit=True, not with unique=True)"""
+        entry i is a CBOR RefundReturn message (implies admit=True; not with unique=True: redeem_return_replay_unique_cbor_batch)"""
         if returned is not None and unique:
-            raise ValueError("a copy may name another amount than its leader: no unique form with returned amounts")
+            raise ValueError("a copy may name another amount than its leader: the unique form with returned amounts is redeem_return_replay_unique_cbor_batch")
         admit = admit or returned is not None
         if charges is not None and not admit:
             raise ValueError("charges are compared by the admission screen: admit=True")
@@ -509,6 +521,35 @@ class Keyring:
                 db.set, receipts.set, self._records(), list(msgs), nonce_key, self._sign_key(sign_with), key_epochs=self.epochs, charges=cc, unique=unique)
         else:
             st, out, ok, rep, self.last_replay_counts = e.redeem_cbor_replay(db.set, receipts.set, self._records(), list(msgs), nonce_key, self._sign_key(sign_with), key_epochs=self.epochs)
+        return [out[i] if st[i] == 0 else _wire_error(st[i]) for i in range(len(msgs))], self._indices(st, ok), [bool(r) for r in rep]
+
+    def redeem_return_replay_unique_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", proofs: Sequence["SpendProof"], nonce_key: bytes,
+                                          returned: Sequence = None, sign_with=None, charges: Sequence = None) -> Tuple[list, list, list]:
+        """redeem_replay_batch(..., returned=) with byte-identical proofs of the batch verified and signed once
+        (act_redeem_return_replay_unique_batch).  A proof with the bytes of an earlier proof that passed the screen is a copy WHATEVER
+        amount it names; behind the call it is answered from its leader: the leader's RefundReturn, byte for byte, if it names the
+        leader's amount and the leader was accepted; DoubleSpendError if it names another amount (the receipt pins the leader's); the
+        leader's error otherwise.  Results, matched keys, replayed flags and both databases are those of redeem_replay_batch(...,
+        returned=) on the same batch; the counts are capi.RETURN_REPLAY_UNIQUE_COUNTS (fifteen names: "copies", "copies_served",
+        "copies_other_amount" behind the twelve).  returned=None: every amount is 0.
+        -> (results, matched ring indices, replayed flags); `self.last_replay_counts`: the call's counts."""
+        nbits = proofs[0].nbits if proofs else L
+        e, pb = params.engine(nbits), b"".join(p.record for p in proofs)
+        cc = b"".join(scalar(c) for c in charges) if charges is not None else None
+        tt = b"".join(scalar(t) for t in returned) if returned is not None else None
+        st, out, ok, rep, self.last_replay_counts = e.redeem_return_replay(
+            db.set, receipts.set, self._records(), pb, nonce_key, self._sign_key(sign_with), key_epochs=self.epochs, charges=cc, returned=tt, unique=True)
+        return [RefundReturn(out[160 * i:160 * i + 160]) if st[i] == 0 else Error(st[i]) for i in range(len(proofs))], self._indices(st, ok), [bool(r) for r in rep]
+
+    def redeem_return_replay_unique_cbor_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", msgs: Sequence[bytes], nonce_key: bytes, nbits: int = L,
+                                               returned: Sequence = None, sign_with=None, charges: Sequence = None) -> Tuple[list, list, list]:
+        """the same on wire bytes (act_redeem_cbor_return_replay_unique_batch): a copy is a message of the same length and the same
+        bytes; another spelling is verified on its own.  Entry i is a CBOR RefundReturn message or an Error."""
+        e = params.engine(nbits)
+        cc = b"".join(scalar(c) for c in charges) if charges is not None else None
+        tt = b"".join(scalar(t) for t in returned) if returned is not None else None
+        st, out, ok, rep, self.last_replay_counts = e.redeem_cbor_return_replay(
+            db.set, receipts.set, self._records(), list(msgs), nonce_key, self._sign_key(sign_with), key_epochs=self.epochs, charges=cc, returned=tt, unique=True)
         return [out[i] if st[i] == 0 else _wire_error(st[i]) for i in range(len(msgs))], self._indices(st, ok), [bool(r) for r in rep]
 
 

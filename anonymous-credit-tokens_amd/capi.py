@@ -28,6 +28,8 @@ ADMIT_REPLAY_COUNTS = ("lanes", "wire_rejected", "wrong_charge", "foreign_spend"
                        "double_spend_after", "unanswered")      # act_redeem_*admit_replay_batch
 ADMIT_REPLAY_UNIQUE_COUNTS = ADMIT_REPLAY_COUNTS + ("copies", "copies_served")      # act_redeem_*admit_replay_unique_batch: copies, and those whose leader ended 0
 RETURN_REPLAY_COUNTS = ADMIT_REPLAY_COUNTS + ("return_too_big",)      # act_redeem_*return_replay_batch
+# act_redeem_*return_replay_unique_batch: copies, those answered 0, and those that name another amount than their leader
+RETURN_REPLAY_UNIQUE_COUNTS = RETURN_REPLAY_COUNTS + ("copies", "copies_served", "copies_other_amount")
 _ERRS = {1: "ACT_ERR_ARG", 2: "ACT_ERR_HIP", 3: "ACT_ERR_PARAMS", 4: "ACT_ERR_NO_DEVICE", 5: "ACT_ERR_RNG"}
 
 EXPORTS = [
@@ -66,6 +68,7 @@ EXPORTS = [
     "act_refund_sign_return_keyring_batch", "act_redeem_return_batch", "act_redeem_cbor_return_batch", "act_refund_to_credit_token_return_batch",
     "act_refund_to_credit_token_return_keyring_batch", "act_redeem_return_unique_batch", "act_redeem_cbor_return_unique_batch",
     "act_redeem_return_replay_batch", "act_redeem_cbor_return_replay_batch", "act_replay_derive_return_batch",
+    "act_redeem_return_replay_unique_batch", "act_redeem_cbor_return_replay_unique_batch",
     "act_ctx_host_hash_stats", "act_ctx_set_tiny_calls", "act_node_set_balance", "act_node_device_stats", "act_node_balance_state", "act_debug_set_slowdown", "act_debug_fail_next_signs",
 ]
 CBOR_TYPES = {"IssuanceRequest": 1, "IssuanceResponse": 2, "SpendProof": 3, "Refund": 4, "PrivateKey": 5, "PublicKey": 6,
@@ -277,6 +280,9 @@ def load() -> C.CDLL:
     # replayable partial refunds: the admission replay calls with `returned` behind `charge` (out_counts: ACT_RETURN_REPLAY_COUNTS values)
     lib.act_redeem_return_replay_batch.argtypes = [vp, vp, vp, sz, i32, u8p, i32, u32p, i32, u8p, u8p, u8p, u8p, u8p, u8p, u8p, u8p, u64p]
     lib.act_redeem_cbor_return_replay_batch.argtypes = [vp, vp, vp, sz, i32, u8p, i32, u32p, i32, u8p, vp, u8p, u8p, u8p, u8p, u8p, u8p, u8p, u64p]
+    # their unique forms: a copy is served only if it names its leader's amount (out_counts: ACT_RETURN_REPLAY_UNIQUE_COUNTS values)
+    lib.act_redeem_return_replay_unique_batch.argtypes = lib.act_redeem_return_replay_batch.argtypes
+    lib.act_redeem_cbor_return_replay_unique_batch.argtypes = lib.act_redeem_cbor_return_replay_batch.argtypes
     lib.act_replay_derive_return_batch.argtypes = [vp, sz, i32, u8p, i32, u8p, u8p, u8p, sz, u8p, u8p, u8p, u8p, u8p]
     lib.act_issue_check_cbor_batch.argtypes = [vp, sz, i32, u8p, vp, u8p, u8p]
     lib.act_issue_sign_cbor_batch.argtypes = [vp, sz, i32, u8p, u8p, u8p, u8p, u8p, i32, u8p, u8p]
@@ -1120,38 +1126,45 @@ class Engine:
 
     # ---- replayable partial refunds (act_redeem_return_replay_batch / act_redeem_cbor_return_replay_batch / act_replay_derive_return_batch)
     def redeem_return_replay(self, nullifier_set, receipts, keys, proofs: bytes, nonce_key: bytes, sign_key: int = SIGN_MATCHED, key_epochs=None, charges: bytes = None,
-                             returned: bytes = None, raw: bool = False):
+                             returned: bytes = None, raw: bool = False, unique: bool = False):
         """redeem_admit_replay with the amounts the issuer returns: t > s is STATUS_RETURN_TOO_BIG in the screen; the receipt pins t, so
         a retry with the same t is served byte for byte and one with another t is STATUS_DOUBLE_SPEND.
-        -> (statuses, 160-byte RefundReturn records, out_key, replayed, counts dict); raw=True: (rc, ...), no exception"""
+        -> (statuses, 160-byte RefundReturn records, out_key, replayed, counts dict); raw=True: (rc, ...), no exception
+        unique=True: act_redeem_return_replay_unique_batch -- a lane with the bytes of an earlier lane is not verified; it takes that
+        lane's answer if it names that lane's amount and is STATUS_DOUBLE_SPEND behind an accepted leader if it names another"""
+        names = RETURN_REPLAY_UNIQUE_COUNTS if unique else RETURN_REPLAY_COUNTS
+        fn = self.lib.act_redeem_return_replay_unique_batch if unique else self.lib.act_redeem_return_replay_batch
         n = len(proofs) // self.proof_bytes; out = np.full(160 * n, 7 if raw else 0, np.uint8)
         st = np.full(n, 99 if raw else 0, np.uint8); ok = np.zeros(n, np.uint8); rp = np.zeros(n, np.uint8)
         pk, kk = _in(b"".join(keys)); p0, k0 = _in(proofs, self.proof_bytes * n); pn, kn = _in(nonce_key, 32)
         pc, kc = _in(charges, 32 * n) if charges is not None else (None, None)
         pt, kt = _in(returned, 32 * n) if returned is not None else (None, None)
         ke = _epoch_table(key_epochs, len(keys)) if key_epochs is not None else None
-        cnt = (C.c_uint64 * len(RETURN_REPLAY_COUNTS))()
-        rc = self.lib.act_redeem_return_replay_batch(self.ctx, nullifier_set.h, receipts.h, n, MEM_HOST, pk, len(keys), ke.ctypes.data if ke is not None else None, sign_key,
-                                                     p0, pc, pt, pn, out.ctypes.data, st.ctypes.data, ok.ctypes.data, rp.ctypes.data, cnt)
-        counts = dict(zip(RETURN_REPLAY_COUNTS, (int(v) for v in cnt)))
+        cnt = (C.c_uint64 * len(names))()
+        rc = fn(self.ctx, nullifier_set.h, receipts.h, n, MEM_HOST, pk, len(keys), ke.ctypes.data if ke is not None else None, sign_key,
+                p0, pc, pt, pn, out.ctypes.data, st.ctypes.data, ok.ctypes.data, rp.ctypes.data, cnt)
+        counts = dict(zip(names, (int(v) for v in cnt)))
         if raw:
             return rc, st.tobytes(), out.tobytes(), ok.tobytes(), rp.tobytes(), counts
         self._ck(rc)
         return st.tobytes(), out.tobytes(), ok.tobytes(), rp.tobytes(), counts
 
     def redeem_cbor_return_replay(self, nullifier_set, receipts, keys, messages: list, nonce_key: bytes, sign_key: int = SIGN_MATCHED, key_epochs=None,
-                                  charges: bytes = None, returned: bytes = None, raw: bool = False):
-        """wire bytes in, wire bytes out -> (statuses, list of CBOR RefundReturn messages (b"" where not signed), out_key, replayed, counts dict)"""
+                                  charges: bytes = None, returned: bytes = None, raw: bool = False, unique: bool = False):
+        """wire bytes in, wire bytes out -> (statuses, list of CBOR RefundReturn messages (b"" where not signed), out_key, replayed, counts dict)
+        unique=True: act_redeem_cbor_return_replay_unique_batch (a copy has the same length and the same bytes as an earlier message)"""
+        names = RETURN_REPLAY_UNIQUE_COUNTS if unique else RETURN_REPLAY_COUNTS
+        fn = self.lib.act_redeem_cbor_return_replay_unique_batch if unique else self.lib.act_redeem_cbor_return_replay_batch
         n = len(messages); p0, k0, offs = _msgs(messages); ml = self.cbor_size("RefundReturn")
         st = np.full(n, 99 if raw else 0, np.uint8); ok = np.zeros(n, np.uint8); rp = np.zeros(n, np.uint8); out = np.zeros(ml * n, np.uint8)
         pk, kk = _in(b"".join(keys)); pn, kn = _in(nonce_key, 32)
         pc, kc = _in(charges, 32 * n) if charges is not None else (None, None)
         pt, kt = _in(returned, 32 * n) if returned is not None else (None, None)
         ke = _epoch_table(key_epochs, len(keys)) if key_epochs is not None else None
-        cnt = (C.c_uint64 * len(RETURN_REPLAY_COUNTS))()
-        rc = self.lib.act_redeem_cbor_return_replay_batch(self.ctx, nullifier_set.h, receipts.h, n, MEM_HOST, pk, len(keys), ke.ctypes.data if ke is not None else None,
-                                                          sign_key, p0, offs.ctypes.data, pc, pt, pn, out.ctypes.data, st.ctypes.data, ok.ctypes.data, rp.ctypes.data, cnt)
-        counts = dict(zip(RETURN_REPLAY_COUNTS, (int(v) for v in cnt)))
+        cnt = (C.c_uint64 * len(names))()
+        rc = fn(self.ctx, nullifier_set.h, receipts.h, n, MEM_HOST, pk, len(keys), ke.ctypes.data if ke is not None else None,
+                sign_key, p0, offs.ctypes.data, pc, pt, pn, out.ctypes.data, st.ctypes.data, ok.ctypes.data, rp.ctypes.data, cnt)
+        counts = dict(zip(names, (int(v) for v in cnt)))
         b = out.tobytes()
         msgs = [b[i * ml:(i + 1) * ml] if st[i] == 0 else b"" for i in range(n)]
         if raw:
@@ -1161,23 +1174,26 @@ class Engine:
         return st.tobytes(), msgs, ok.tobytes(), rp.tobytes(), counts
 
     def return_replay_ptr(self, fn: str, keys, n: int, mem: int, **p):
-        """the two calls on raw pointers of either kind: fn = redeem / redeem_cbor; p as admit_replay_ptr's (no unique) plus returned.
-        -> counts dict, or (rc, counts) with raw"""
+        """the two calls on raw pointers of either kind: fn = redeem / redeem_cbor; p as admit_replay_ptr's plus returned (unique: the
+        act_redeem_*return_replay_unique_batch forms).  -> counts dict, or (rc, counts) with raw"""
+        unique = bool(p.get("unique"))
+        names = RETURN_REPLAY_UNIQUE_COUNTS if unique else RETURN_REPLAY_COUNTS
         pk, kk = _in(b"".join(keys)); nk = len(keys); pn, kn = _in(p["nonce_key"], 32)
         ke = _epoch_table(p["key_epochs"], nk) if p.get("key_epochs") is not None else None
         kep = ke.ctypes.data if ke is not None else None
-        cnt = (C.c_uint64 * len(RETURN_REPLAY_COUNTS))()
+        cnt = (C.c_uint64 * len(names))()
         if fn == "redeem":
-            rc = self.lib.act_redeem_return_replay_batch(self.ctx, p["set"].h, p["receipts"].h, n, mem, pk, nk, kep, p.get("sign_key", SIGN_MATCHED), p["proofs"],
-                                                         p.get("charges") or None, p.get("returned") or None, pn, p["out"], p["status"], p["out_key"],
-                                                         p.get("replayed") or None, cnt)
+            call = self.lib.act_redeem_return_replay_unique_batch if unique else self.lib.act_redeem_return_replay_batch
+            rc = call(self.ctx, p["set"].h, p["receipts"].h, n, mem, pk, nk, kep, p.get("sign_key", SIGN_MATCHED), p["proofs"],
+                      p.get("charges") or None, p.get("returned") or None, pn, p["out"], p["status"], p["out_key"], p.get("replayed") or None, cnt)
         else:
-            rc = self.lib.act_redeem_cbor_return_replay_batch(self.ctx, p["set"].h, p["receipts"].h, n, mem, pk, nk, kep, p.get("sign_key", SIGN_MATCHED), p["cbor"],
-                                                              p.get("offsets") or None, p.get("charges") or None, p.get("returned") or None, pn, p["out"], p["status"],
-                                                              p["out_key"], p.get("replayed") or None, cnt)
+            call = self.lib.act_redeem_cbor_return_replay_unique_batch if unique else self.lib.act_redeem_cbor_return_replay_batch
+            rc = call(self.ctx, p["set"].h, p["receipts"].h, n, mem, pk, nk, kep, p.get("sign_key", SIGN_MATCHED), p["cbor"],
+                      p.get("offsets") or None, p.get("charges") or None, p.get("returned") or None, pn, p["out"], p["status"],
+                      p["out_key"], p.get("replayed") or None, cnt)
         if not p.get("raw"):
             self._ck(rc)
-        counts = dict(zip(RETURN_REPLAY_COUNTS, (int(v) for v in cnt)))
+        counts = dict(zip(names, (int(v) for v in cnt)))
         return (rc, counts) if p.get("raw") else counts
 
     def replay_derive(self, keys, key_index: bytes, nonce_key: bytes, nullifiers: bytes, kprime: bytes, status_in: bytes, stride: int = 32, returned: bytes = None):

@@ -22,6 +22,7 @@ void launch_copy_equal(const CopyEqualArgs& a, hipStream_t s);          // copy_
 void launch_copy_mark(const CopyMarkArgs& a, hipStream_t s);            // pre2 = a copy of pre and lead all-ones before
 void launch_copy_resolve(const CopyResolveArgs& a, hipStream_t s);      // behind launch_admit_scatter on the same stream
 void launch_copy_serve(const CopyServeArgs& a, hipStream_t s);          // the replay unique forms: behind BOTH scatters (rows and replay marks)
+void launch_copy_serve_return(const CopyServeReturnArgs& a, hipStream_t s);      // the return replay unique forms: the same place, with the amounts
 #endif
 
 }  // namespace act

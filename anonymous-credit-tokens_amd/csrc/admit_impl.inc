@@ -17,9 +17,11 @@
 // act_redeem_(cbor_)admit_replay_batch (admit_replay_impl.inc, included behind replay_impl.inc; DESIGN 4.9) add a stage between steps 1
 // and 2 -- a spent lane whose receipt is this proof's own is a retry candidate and survives -- and end in the replay tail, not the ring's
 // act_redeem_(cbor_)return_replay_batch are that form with the returned amounts of the return calls (ret && rp, DESIGN 4.10): t <= s is the
-// screen's rule, a candidate's tag and every tag and nonce of the tail take the lane's t, and the outputs are RefundReturns.  No unique form.
+// screen's rule, a candidate's tag and every tag and nonce of the tail take the lane's t, and the outputs are RefundReturns.
 // act_redeem_(cbor_)admit_replay_unique_batch are both at once (unique && rp): the copy stage runs over fresh lanes and retry candidates
 // alike, and behind the scatters a copy is SERVED -- it takes its leader's refund -- where the unique forms above resolve it  [k_copy_serve]
+// act_redeem_(cbor_)return_replay_unique_batch are all three (ret && rp && unique): equality is decided on the proof bytes alone, the amounts
+// of the verified lanes are gathered by v_idx, and a copy is served only if it names its leader's amount                 [k_copy_serve_return]
 namespace {
 
 constexpr size_t ADMIT_WINDOW_BATCHES = 4;       // survivors gathered and verified at a time, in units of max_batch
@@ -189,10 +191,10 @@ static int redeem_replay_locked(act_ctx* c, act_nullifier_set* set, act_nullifie
 static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int mem, const uint8_t* keys, int nkeys, const uint32_t* key_epochs, int sign_key,
                              const uint8_t* proof, const uint8_t* cbor, const uint64_t* offsets, const uint8_t* charge, const uint8_t* rng, int rng_mode,
                              uint8_t* out, uint8_t* status, uint8_t* out_key, uint64_t* out_counts, bool unique = false, AdmitReplay* rp = nullptr,
-                             const RedeemReturn* ret = nullptr) {      // ret (the return calls, DESIGN 4.10); ret && rp: the return replay form, never unique
+                             const RedeemReturn* ret = nullptr) {      // ret (the return calls, DESIGN 4.10); ret && rp: the return replay forms
   const bool wire = cbor != nullptr, dev = mem == ACT_MEM_DEVICE;
   if (out_counts) memset(out_counts, 0, sizeof(uint64_t) * (ret ? (unique ? ACT_REDEEM_RETURN_UNIQUE_COUNTS : ACT_REDEEM_RETURN_COUNTS) : unique ? ACT_ADMIT_UNIQUE_COUNTS : ACT_ADMIT_COUNTS));
-  if (rp && rp->out_counts) memset(rp->out_counts, 0, sizeof(uint64_t) * (ret ? ACT_RETURN_REPLAY_COUNTS : unique ? ACT_ADMIT_REPLAY_UNIQUE_COUNTS : ACT_ADMIT_REPLAY_COUNTS));
+  if (rp && rp->out_counts) memset(rp->out_counts, 0, sizeof(uint64_t) * (ret ? (unique ? ACT_RETURN_REPLAY_UNIQUE_COUNTS : ACT_RETURN_REPLAY_COUNTS) : unique ? ACT_ADMIT_REPLAY_UNIQUE_COUNTS : ACT_ADMIT_REPLAY_COUNTS));
   if (!c || (mem != ACT_MEM_HOST && mem != ACT_MEM_DEVICE) || n > ((size_t)1 << 30)) return ACT_ERR_ARG;
   if (n && ((!proof && !cbor) || !out || !status || !out_key)) return ACT_ERR_ARG;
   if (wire && offsets) for (size_t i = 0; i < n; i++) if (offsets[i + 1] < offsets[i]) return ACT_ERR_ARG;
@@ -202,8 +204,6 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
   int rc = redeem_keyring_refused(c, set, 0, keys, nkeys, key_epochs, sign_key, nullptr, nullptr, rng, rng_mode, nullptr, nullptr, nullptr);
   if (rc) return rc;
   if (rp && (rc = replay_refused(c, set, rp->receipts, rp->nonce_key, n, key_epochs, nkeys))) return rc;
-  // a copy that names another t than its leader must not be served the leader's row: the unique forms take no returned amounts with rp
-  if (ret && rp && unique) { c->err = "act_redeem_return_replay_batch: the unique forms take no returned amounts (a copy's t may differ from its leader's)"; return ACT_ERR_ARG; }
   if (n == 0) return redeem_keyring_impl(c, set, 0, mem, keys, nkeys, key_epochs, sign_key, nullptr, nullptr, nullptr, rng, rng_mode, nullptr, nullptr, nullptr);
   // one admission call at a time per context: the gathered rng slices live in the context's own buffer (d_admit_rng)
   std::lock_guard<std::mutex> admission(c->admit_mu);
@@ -495,7 +495,7 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
 
   if (rp && rc_tail && !began) return rc_tail;      // staging its buffers failed: as a failed verification -- nothing recorded, status untouched
   // ---- step 5: the answers back to their lanes (also behind a failure of step 4: status[] is complete on return) ----------------------------
-  std::vector<uint8_t> h_cst, h_fin;      // h_fin: the final statuses of a device-memory caller (the replay unique forms' copies_served)
+  std::vector<uint8_t> h_cst, h_fin, h_t;      // h_fin, h_t: the final statuses and the amounts of a device-memory caller (the replay unique forms' copy counts)
   if (dev) {
     AdmitScatterArgs sc{}; sc.n = (uint32_t)n; sc.out_bytes = out_b; sc.pos = v_pos; sc.pre = v_pre; sc.c_status = cst; sc.c_key = okey; sc.c_out = cout.p;
     sc.status = status; sc.out_key = out_key; sc.out = out;
@@ -506,13 +506,18 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
       launch_admit_scatter(sr, stream);
     }
     // the replay unique forms: behind both scatters the rows of leaders are final; a copy takes its leader's whole answer
-    if (cp.copies && rp) { CopyServeArgs va{cp.d_lead, (uint32_t)n, out_b, status, out_key, out, rp->out_replayed}; launch_copy_serve(va, stream); }
+    // (with amounts: only if it names its leader's -- a copy's t is read here and nowhere else)
+    if (cp.copies && rp) {
+      const CopyServeArgs va{cp.d_lead, (uint32_t)n, out_b, status, out_key, out, rp->out_replayed};
+      if (ret) { CopyServeReturnArgs vr{va, t_in}; launch_copy_serve_return(vr, stream); } else launch_copy_serve(va, stream);
+    }
     ADCK(c, hipGetLastError());
     if (out_counts) { h_cst.resize(mv); ADCK(c, hipMemcpyAsync(h_cst.data(), cst, mv, hipMemcpyDeviceToHost, stream)); }
     if (cp.copies && rp && rp->out_counts) {      // copies_served is counted on the final statuses
       h_lead.resize(n); h_fin.resize(n);
       ADCK(c, hipMemcpyAsync(h_lead.data(), cp.d_lead, n * 4, hipMemcpyDeviceToHost, stream));
       ADCK(c, hipMemcpyAsync(h_fin.data(), status, n, hipMemcpyDeviceToHost, stream));
+      if (t_in) { h_t.resize(n * 32); ADCK(c, hipMemcpyAsync(h_t.data(), t_in, n * 32, hipMemcpyDeviceToHost, stream)); }
     }
     ADCK(c, hipStreamSynchronize(stream));
   } else {
@@ -523,16 +528,23 @@ static int redeem_admit_impl(act_ctx* c, act_nullifier_set* set, size_t n, int m
       if (rp && rp->out_replayed) rp->out_replayed[i] = j == ADMIT_SHED ? 0 : crepl[j];
     }
     if (cp.copies && !rp) { CopyResolveArgs ra{h_lead.data(), (uint32_t)n, status, out_key}; for (size_t i = 0; i < n; i++) copy_resolve_lane(ra, (uint32_t)i); }
-    if (cp.copies && rp) { CopyServeArgs va{h_lead.data(), (uint32_t)n, out_b, status, out_key, out, rp->out_replayed}; for (size_t i = 0; i < n; i++) copy_serve_lane(va, (uint32_t)i); }
+    if (cp.copies && rp && ret) { CopyServeReturnArgs vr{{h_lead.data(), (uint32_t)n, out_b, status, out_key, out, rp->out_replayed}, t_in}; for (size_t i = 0; i < n; i++) copy_serve_return_lane(vr, (uint32_t)i); }
+    else if (cp.copies && rp) { CopyServeArgs va{h_lead.data(), (uint32_t)n, out_b, status, out_key, out, rp->out_replayed}; for (size_t i = 0; i < n; i++) copy_serve_lane(va, (uint32_t)i); }
   }
   admit_counts_of(out_counts, n, h_pre.data(), mv, dev ? h_cst.data() : cst, ret != nullptr);
   if (rp && rp->out_counts && tc[0] == mv) admit_replay_counts_of(rp->out_counts, n, h_pre.data(), rp->candidates, mv, tc, ret != nullptr);
   if (out_counts && unique) out_counts[ret ? ACT_REDEEM_RETURN_COUNTS : ACT_ADMIT_COUNTS] = cp.copies;
   if (rp && rp->out_counts && unique && cp.copies && tc[0] == mv) {      // copies, then the copies whose leader ended 0
     const uint8_t* fin = dev ? h_fin.data() : status;
-    uint64_t served = 0;
+    uint64_t served = 0, other = 0;
     for (size_t i = 0; i < n; i++) served += h_lead[i] != COPY_NONE && fin[i] == 0;
-    rp->out_counts[ACT_ADMIT_REPLAY_COUNTS] = cp.copies; rp->out_counts[ACT_ADMIT_REPLAY_COUNTS + 1] = served;
+    uint64_t* const at = rp->out_counts + (ret ? ACT_RETURN_REPLAY_COUNTS : ACT_ADMIT_REPLAY_COUNTS);
+    at[0] = cp.copies; at[1] = served;
+    if (ret) {      // the return form: then the copies that name another amount than their leader (no amounts: none does)
+      const uint8_t* t = dev ? h_t.data() : t_in;
+      if (t_in) for (size_t i = 0; i < n; i++) other += h_lead[i] != COPY_NONE && !copy_same_amount(t + i * 32, t + (size_t)h_lead[i] * 32);
+      at[2] = other;
+    }
   }
   return rc_tail;
 }

@@ -231,3 +231,27 @@ extern "C" int act_redeem_cbor_return_replay_batch(act_ctx* c, act_nullifier_set
   return redeem_admit_replay_impl(c, set, receipts, n, mem, keys, nkeys, key_epochs, sign_key, nullptr, cbor ? cbor : &none, offsets, charge, nonce_key,
                                   out_refund_return_cbor, status, out_key, out_replayed, out_counts, false, &ret);
 }
+
+// The unique forms of the two calls above: the copy stage of the admit-replay unique forms behind this screen, equality decided on the
+// proof bytes ALONE (t takes no part, as in act_redeem_(cbor_)return_unique_batch), the amounts of the verified lanes gathered by v_idx --
+// a copy's t never reaches a tag, a nonce or a signature -- and behind the tail a copy answered from its leader's final status and from
+// whether it names its leader's amount (copy_serve_return_lane).  out_counts: ACT_RETURN_REPLAY_UNIQUE_COUNTS values.
+extern "C" int act_redeem_return_replay_unique_batch(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys, int nkeys,
+                                                     const uint32_t* key_epochs, int sign_key, const uint8_t* proof, const uint8_t* charge, const uint8_t* returned,
+                                                     const uint8_t nonce_key[32], uint8_t* out_refund_return, uint8_t* status, uint8_t* out_key, uint8_t* out_replayed,
+                                                     uint64_t* out_counts) {
+  if (n && !proof) { if (out_counts) memset(out_counts, 0, sizeof(uint64_t) * ACT_RETURN_REPLAY_UNIQUE_COUNTS); return ACT_ERR_ARG; }
+  const RedeemReturn ret{returned};
+  return redeem_admit_replay_impl(c, set, receipts, n, mem, keys, nkeys, key_epochs, sign_key, proof, nullptr, nullptr, charge, nonce_key, out_refund_return, status,
+                                  out_key, out_replayed, out_counts, true, &ret);
+}
+extern "C" int act_redeem_cbor_return_replay_unique_batch(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys,
+                                                          int nkeys, const uint32_t* key_epochs, int sign_key, const uint8_t* cbor, const uint64_t* offsets,
+                                                          const uint8_t* charge, const uint8_t* returned, const uint8_t nonce_key[32], uint8_t* out_refund_return_cbor,
+                                                          uint8_t* status, uint8_t* out_key, uint8_t* out_replayed, uint64_t* out_counts) {
+  if (n && !cbor) { if (out_counts) memset(out_counts, 0, sizeof(uint64_t) * ACT_RETURN_REPLAY_UNIQUE_COUNTS); return ACT_ERR_ARG; }
+  static const uint8_t none = 0;
+  const RedeemReturn ret{returned};
+  return redeem_admit_replay_impl(c, set, receipts, n, mem, keys, nkeys, key_epochs, sign_key, nullptr, cbor ? cbor : &none, offsets, charge, nonce_key,
+                                  out_refund_return_cbor, status, out_key, out_replayed, out_counts, true, &ret);
+}

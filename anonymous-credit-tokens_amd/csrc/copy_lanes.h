@@ -14,7 +14,9 @@
 //   copy_resolve_lane  lane = item                     a copy's status and out_key from its leader's final ones
 //   copy_serve_lane    lane = item                     the replay unique forms: a copy's status, out_key, replay mark and output row
 //                                                      from its leader's final ones (copy_serve_piece: one 16-byte piece of the row)
-// Nothing here is secret: proofs, fingerprints and lane numbers are public.
+//   copy_serve_return_lane  lane = item                the return replay unique forms: the same from the leader's final status AND
+//                                                      whether the copy names the leader's amount (copy_serve_return_piece)
+// Nothing here is secret: proofs, fingerprints, lane numbers, amounts, statuses and refunds are public.
 #pragma once
 #include "admit_lanes.h"
 
@@ -206,6 +208,50 @@ ACT_HD void copy_serve_piece(const CopyServeArgs& a, uint32_t i, uint32_t q) {
 ACT_HD void copy_serve_lane(const CopyServeArgs& a, uint32_t i) {
   const uint32_t pieces = admit_pieces(a.out_b);
   for (uint32_t q = 0; q < pieces; q++) copy_serve_piece(a, i, q);
+}
+
+// ---- a copy's answer when lanes name returned amounts (act_redeem_(cbor_)return_replay_unique_batch) ---------------------------
+// Equality is decided on the proof bytes alone, so a copy may name another amount than its leader -- and the receipt pins the LEADER's.
+// The table of the header, from the leader's final status s and same = (t^_i == t^_l), both reduced mod l as return_exceeds_bytes
+// reduces them (t and t + l are one amount):
+//   s == 0, same            status 0, replay mark 1, the leader's RefundReturn byte for byte
+//   s == 0 or 251, other    ACT_STATUS_DOUBLE_SPEND, a zero record, mark 0
+//   s == 251, same          251, a zero record, mark 1: k is spent and the leader's receipt is this lane's own, which is what
+//                           act_redeem_(cbor_)return_replay_batch's tail marks before its signing step fails
+//   anything else           s, a zero record, mark 0
+// out_key is the leader's in every row (the key the shared bytes verified under; ACT_KEY_NONE where they did not verify).
+struct CopyServed { uint8_t status, replayed; bool row; };
+ACT_HD CopyServed copy_serve_return_verdict(uint8_t s, bool same) {
+  if (s == 0) return same ? CopyServed{0, 1, true} : CopyServed{ADMIT_DOUBLE_SPEND, 0, false};
+  if (s == COPY_RECORDED_UNSIGNED) return same ? CopyServed{COPY_RECORDED_UNSIGNED, 1, false} : CopyServed{ADMIT_DOUBLE_SPEND, 0, false};
+  return CopyServed{s, 0, false};
+}
+// two amounts as they lie in memory name one t^ (32 little-endian bytes each at any address, any value below 2^256; the screen's
+// load, whose reduction is return_exceeds_bytes')
+ACT_HD bool copy_same_amount(const uint8_t* x, const uint8_t* y) {
+  uint32_t a[8], b[8];
+  null_load_key(a, x); null_load_key(b, y);
+  return null_eq(a, b);
+}
+// amounts: n scalars in the memory the arrays of `v` lie in; null: every t^ is 0, so every copy names its leader's amount
+struct CopyServeReturnArgs { CopyServeArgs v; const uint8_t* amounts; };
+// piece q of lane i's row.  Every thread of a row reads the same leader status and the same two amounts, so all reach one verdict;
+// piece 0 also writes the lane's three bytes.  Reads rows, statuses and keys of leaders only, writes those of copies only.
+ACT_HD void copy_serve_return_piece(const CopyServeReturnArgs& r, uint32_t i, uint32_t q) {
+  const CopyServeArgs& a = r.v;
+  if (i >= a.n) return;
+  const uint32_t l = a.lead[i];
+  if (l == COPY_NONE) return;
+  const CopyServed c = copy_serve_return_verdict(a.status[l], !r.amounts || copy_same_amount(r.amounts + (uint64_t)i * 32, r.amounts + (uint64_t)l * 32));
+  if (q == 0) { a.status[i] = c.status; a.out_key[i] = a.out_key[l]; if (a.out_replayed) a.out_replayed[i] = c.replayed; }
+  const uint32_t bytes = admit_piece_bytes(a.out_b, q);
+  uint64_t w[2] = {0, 0};
+  if (c.row) copy_load16(w, a.out + (uint64_t)l * a.out_b + (uint64_t)q * 16, bytes);
+  copy_store16(a.out + (uint64_t)i * a.out_b + (uint64_t)q * 16, w, bytes);
+}
+ACT_HD void copy_serve_return_lane(const CopyServeReturnArgs& r, uint32_t i) {
+  const uint32_t pieces = admit_pieces(r.v.out_b);
+  for (uint32_t q = 0; q < pieces; q++) copy_serve_return_piece(r, i, q);
 }
 
 }  // namespace act

@@ -1,6 +1,7 @@
 // k_copies.hip — the copy stage of admission: byte-identical proofs of one batch are verified once (act_redeem_admit_unique_batch /
 // act_redeem_cbor_admit_unique_batch; lane bodies in copy_lanes.h, which says what they compute; engine side in copies_impl.inc), and
-// the serve pass of act_redeem_(cbor_)admit_replay_unique_batch, where a copy gets its leader's refund.
+// the serve pass of act_redeem_(cbor_)admit_replay_unique_batch, where a copy gets its leader's refund, and that of
+// act_redeem_(cbor_)return_replay_unique_batch, where it gets it only if it names its leader's amount.
 // Nothing here is on the verification path.
 #include "copy_lanes.h"
 #include "admit.h"
@@ -54,6 +55,15 @@ __global__ void __launch_bounds__(256) k_copy_serve(CopyServeArgs a, uint32_t pi
   if (i < a.n) copy_serve_piece(a, (uint32_t)i, (uint32_t)(p % pieces));
 }
 
+// The return replay unique forms: k_copy_serve's shape and mapping, and per thread two 32-byte amounts more -- the copy's and its
+// leader's, in the caller's array.  The threads of a row load the same 64 bytes (the copy's amount is one line, the leader's another:
+// broadcasts within the row's threads) and reach the same verdict, so a row is written whole or zeroed whole.
+__global__ void __launch_bounds__(256) k_copy_serve_return(CopyServeReturnArgs a, uint32_t pieces) {
+  const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  const uint64_t i = p / pieces;
+  if (i < a.v.n) copy_serve_return_piece(a, (uint32_t)i, (uint32_t)(p % pieces));
+}
+
 static unsigned copy_grid(uint64_t lanes, uint32_t per_block) { return (unsigned)((lanes + per_block - 1) / per_block); }
 
 void launch_copy_fp(const CopyFpArgs& a, hipStream_t s) { if (a.m) hipLaunchKernelGGL(k_copy_fp, dim3(copy_grid(a.m, COPY_WAVES)), dim3(64 * COPY_WAVES), 0, s, a); }
@@ -68,6 +78,10 @@ void launch_copy_resolve(const CopyResolveArgs& a, hipStream_t s) { if (a.n) hip
 void launch_copy_serve(const CopyServeArgs& a, hipStream_t s) {
   const uint32_t pieces = admit_pieces(a.out_b);
   if (a.n && pieces) hipLaunchKernelGGL(k_copy_serve, dim3(copy_grid((uint64_t)a.n * pieces, 256)), dim3(256), 0, s, a, pieces);
+}
+void launch_copy_serve_return(const CopyServeReturnArgs& a, hipStream_t s) {
+  const uint32_t pieces = admit_pieces(a.v.out_b);
+  if (a.v.n && pieces) hipLaunchKernelGGL(k_copy_serve_return, dim3(copy_grid((uint64_t)a.v.n * pieces, 256)), dim3(256), 0, s, a, pieces);
 }
 
 }  // namespace act

@@ -1113,9 +1113,9 @@ int act_redeem_cbor_return_unique_batch(act_ctx *ctx, act_nullifier_set *set, si
  * Refused as a whole (nothing written, nothing recorded): everything act_redeem_(cbor_)admit_replay_batch refuses -- receipts == set,
  * a receipts set without room for n more keys, epoch tables that do not fit both sets, a bad ring.  The failure contract is that
  * call's: after ACT_STATUS_RECORDED_UNSIGNED a later retry with the same t is served.
- * NOT OFFERED, on purpose: unique forms with returned amounts (a copy that names another t than its leader must not be served the
- * leader's row; the engine refuses the combination with ACT_ERR_ARG); node-handle forms; tiny or fused roads; a `returned` argument
- * on the screenless act_redeem_(cbor_)replay_batch -- the bound t <= s lives in the screen.
+ * The unique forms are act_redeem_(cbor_)return_replay_unique_batch below ("replayable partial refunds, unique forms"): a copy that
+ * names another t than its leader is not served the leader's row, it is refused.  Still not offered: node-handle forms; tiny or fused
+ * roads; a `returned` argument on the screenless act_redeem_(cbor_)replay_batch -- the bound t <= s lives in the screen.
  *
  * act_replay_derive_return_batch is act_replay_derive_batch plus `returned` (nullable: that call): the tags and nonces above for
  * callers that compose the feature over the node-level calls with act_refund_sign_return_keyring_batch -- which is how it reaches
@@ -1134,6 +1134,61 @@ int act_replay_derive_return_batch(act_ctx *ctx, size_t n, int mem, const uint8_
                                    const uint8_t nonce_key[32], const uint8_t *nullifiers, size_t stride, const uint8_t *kprime,
                                    const uint8_t *status_in, const uint8_t *amounts /* t; nullable */, uint8_t *out_tags /* nullable */,
                                    uint8_t *out_nonces /* nullable */);
+
+/* ======== replayable partial refunds, unique forms: a copy answers to its own t ========
+ * act_redeem_return_replay_unique_batch / act_redeem_cbor_return_replay_unique_batch are the two return replay calls above with step
+ * 3c of the admit-replay unique forms unchanged, behind the screen (wire code, charge, t^ > s^ -> 249, both look-ups with the tag of
+ * (k, enc(K'), t^)) and in front of verification.  Equality is decided on the proof bytes ALONE, as in act_redeem_(cbor_)return_
+ * unique_batch: a lane that repeats the bytes of an earlier lane that passed the screen is a copy and is not verified, whatever amount
+ * it names.  A lane the screen sheds (t^ > s^ and a spent k whose receipt names another amount among the reasons) is neither a leader
+ * nor a copy.  The amounts of the VERIFIED lanes follow their lanes into the tail; a copy's t never reaches a tag, a nonce or a
+ * signature.  Behind the call's single replay tail a copy i with leader j is answered from the leader's FINAL status and from whether
+ * t^_i == t^_j (both reduced mod l, so t and t + l are one amount):
+ *       leader's final status                     t^_i == t^_j   the copy's answer
+ *       0 (fresh or replayed)                     yes            status 0, out_replayed[i] = 1, the leader's RefundReturn byte for byte
+ *                                                                (160 bytes; wire form: the framed ACT_CBOR_REFUND_RETURN message)
+ *       0 or ACT_STATUS_RECORDED_UNSIGNED         no             ACT_STATUS_DOUBLE_SPEND, a zero record, out_replayed[i] = 0: the receipt
+ *                                                                pins the leader's amount
+ *       ACT_STATUS_RECORDED_UNSIGNED              yes            ACT_STATUS_RECORDED_UNSIGNED, a zero record, out_replayed[i] = 1 (k is
+ *                                                                spent and the receipt is this lane's own: what the tail of the calls
+ *                                                                above marks before its signing step fails); repaired by the same retry
+ *       anything else (255 / 6 / 7, DOUBLE_SPEND,
+ *       ACT_STATUS_NULLIFIER_UNDETERMINED)        either         the leader's status, a zero record, out_replayed[i] = 0
+ * out_key[i] = out_key[j] in every row: the key the shared bytes verified under, ACT_KEY_NONE where they did not verify -- which is
+ * what the calls above report for a verified lane that their tail refuses.
+ * THE PROMISE: on any batch and identical pairs of sets every status, every out_key, every output byte, every out_replayed byte and the
+ * keys and epochs both sets hold afterwards are byte for byte those of act_redeem_(cbor_)return_replay_batch; only the counts differ.
+ * Why: there a later copy with the leader's t^ finds k spent and its own tag in `receipts` and is signed with the same derived nonces;
+ * a later copy with another t^ finds k spent and no tag for its amount ([P t1, P t1, P t2] -> 0 / 0 replayed / 3 in both).
+ * Not promised:
+ *   - lanes that end ACT_STATUS_NULLIFIER_UNDETERMINED (a set too small for the batch), as in the other unique forms;
+ *   - a `receipts` set that holds tags for TWO amounts of one (k, enc(K')) -- only rolling `set` back from a snapshot while keeping
+ *     `receipts` produces that.  There the calls above serve a copy that names the second amount and these refuse it
+ *     (ACT_STATUS_DOUBLE_SPEND): the conservative direction;
+ *   - wire form only: a copy of a leader that ended ACT_STATUS_DOUBLE_SPEND BECAUSE OF ITS AMOUNT -- the leader is another spelling of
+ *     a message an earlier lane of the batch was served for with t1, names t2 and loses; its byte-identical copy that names t1 takes
+ *     the leader's status here and is replayed by the calls above.  Again the conservative direction; sent alone it is served.
+ * With amounts NULL or all zero: the first 128 bytes of every record, statuses, out_key, both sets, out_counts[0..11), copies and
+ * copies_served are those of act_redeem_(cbor_)admit_replay_unique_batch, and return_too_big and copies_other_amount are 0;
+ * out_replayed differs in one place, the copy of an ACT_STATUS_RECORDED_UNSIGNED leader (1 here, as in the calls above; 0 there).
+ * out_counts: nullable, host, ACT_RETURN_REPLAY_UNIQUE_COUNTS values: the twelve of ACT_RETURN_REPLAY_COUNTS in their order, then
+ * copies, copies_served (the copies answered 0) and copies_other_amount (the copies whose t^ differs from their leader's, whatever they
+ * were answered).  verified = lanes - wire_rejected - wrong_charge - return_too_big - foreign_spend - copies; the tail's five counts
+ * are over VERIFIED lanes only.
+ * Whole-call refusals, locks, failure semantics and the hygiene contract are those of the calls above; nothing the serve step reads is
+ * secret (amounts, statuses and refunds are public).  Output rows may start at any byte address.  A batch without copies in which
+ * nothing is shed still goes straight to the replay implementation with the caller's pointers.  Still not offered: node-handle forms,
+ * tiny or fused roads. */
+#define ACT_RETURN_REPLAY_UNIQUE_COUNTS 15
+int act_redeem_return_replay_unique_batch(act_ctx *ctx, act_nullifier_set *set, act_nullifier_set *receipts, size_t n, int mem, const uint8_t *keys, int nkeys,
+                                          const uint32_t *key_epochs /* nullable */, int sign_key, const uint8_t *proof, const uint8_t *charge /* nullable */,
+                                          const uint8_t *amounts /* t; nullable: all zero */, const uint8_t nonce_key[32], uint8_t *out_refund_return,
+                                          uint8_t *status, uint8_t *out_key, uint8_t *out_replayed /* nullable */, uint64_t *out_counts /* nullable, host */);
+int act_redeem_cbor_return_replay_unique_batch(act_ctx *ctx, act_nullifier_set *set, act_nullifier_set *receipts, size_t n, int mem, const uint8_t *keys, int nkeys,
+                                               const uint32_t *key_epochs /* nullable */, int sign_key, const uint8_t *cbor, const uint64_t *offsets,
+                                               const uint8_t *charge /* nullable */, const uint8_t *amounts /* t; nullable: all zero */, const uint8_t nonce_key[32],
+                                               uint8_t *out_refund_return_cbor, uint8_t *status, uint8_t *out_key, uint8_t *out_replayed /* nullable */,
+                                               uint64_t *out_counts /* nullable, host */);
 
 #ifdef __cplusplus
 }

@@ -192,6 +192,14 @@ extern "C" {
     fn act_replay_derive_return_batch(ctx: *mut ActCtx, n: usize, mem: c_int, keys: *const u8, nkeys: c_int, key_index: *const u8, nonce_key: *const u8,
                                       nullifiers: *const u8, stride: usize, kprime: *const u8, status_in: *const u8, amounts: *const u8, out_tags: *mut u8,
                                       out_nonces: *mut u8) -> c_int;
+    fn act_redeem_return_replay_unique_batch(ctx: *mut ActCtx, set: *mut ActNullifierSet, receipts: *mut ActNullifierSet, n: usize, mem: c_int, keys: *const u8,
+                                             nkeys: c_int, key_epochs: *const u32, sign_key: c_int, proof: *const u8, charge: *const u8, amounts: *const u8,
+                                             nonce_key: *const u8, out_refund_return: *mut u8, status: *mut u8, out_key: *mut u8, out_replayed: *mut u8,
+                                             out_counts: *mut u64) -> c_int;
+    fn act_redeem_cbor_return_replay_unique_batch(ctx: *mut ActCtx, set: *mut ActNullifierSet, receipts: *mut ActNullifierSet, n: usize, mem: c_int, keys: *const u8,
+                                                  nkeys: c_int, key_epochs: *const u32, sign_key: c_int, cbor: *const u8, offsets: *const u64, charge: *const u8,
+                                                  amounts: *const u8, nonce_key: *const u8, out_refund_return_cbor: *mut u8, status: *mut u8, out_key: *mut u8,
+                                                  out_replayed: *mut u8, out_counts: *mut u64) -> c_int;
 }
 
 /// ACT_MI355X_DEVICES = "0,1,2,3,4,5,6,7" (default: device 0)
@@ -1382,6 +1390,8 @@ pub const ACT_ADMIT_REPLAY_COUNTS: usize = 11;
 pub const ACT_ADMIT_REPLAY_UNIQUE_COUNTS: usize = 13;
 /// the eleven of `ACT_ADMIT_REPLAY_COUNTS`, then return_too_big (`GpuReplay::returned(Some(..))`)
 pub const ACT_RETURN_REPLAY_COUNTS: usize = 12;
+/// the twelve above, then copies / copies_served / copies_other_amount (`GpuReplay::returned(Some(..))` with `unique(true)`)
+pub const ACT_RETURN_REPLAY_UNIQUE_COUNTS: usize = 15;
 /// statuses, outputs (128-byte Refund records or `REFUND_CBOR_BYTES` messages, all zero where not signed), matched ring keys, the
 /// replay marks, and lanes / rejected_by_verification / fresh / replayed / double_spend / unanswered
 pub struct Replayed {
@@ -1400,11 +1410,20 @@ pub struct Replayed {
     /// 0 unless the call took returned amounts (`GpuReplay::returned`): the lanes whose amount exceeded their charge.  `out` then holds
     /// 160-byte RefundReturn records or `REFUND_RETURN_CBOR_BYTES` messages
     pub return_too_big: u64,
+    /// 0 unless the call took returned amounts AND ran the unique form: the copies that named another amount than their leader (behind
+    /// an accepted leader they are `DoubleSpendError`: the receipt pins the leader's amount)
+    pub copies_other_amount: u64,
 }
 impl Replayed {
     fn take_return_counts(&mut self, t: &[u64; ACT_RETURN_REPLAY_COUNTS]) {
         self.admit_counts.copy_from_slice(&t[..ACT_ADMIT_REPLAY_COUNTS]);
         self.return_too_big = t[ACT_ADMIT_REPLAY_COUNTS];
+    }
+    fn take_return_unique_counts(&mut self, v: &[u64; ACT_RETURN_REPLAY_UNIQUE_COUNTS]) {
+        self.admit_counts.copy_from_slice(&v[..ACT_ADMIT_REPLAY_COUNTS]);
+        self.return_too_big = v[ACT_ADMIT_REPLAY_COUNTS];
+        self.copy_counts = [v[ACT_RETURN_REPLAY_COUNTS], v[ACT_RETURN_REPLAY_COUNTS + 1]];
+        self.copies_other_amount = v[ACT_RETURN_REPLAY_COUNTS + 2];
     }
     fn take_unique_counts(&mut self, u: &[u64; ACT_ADMIT_REPLAY_UNIQUE_COUNTS]) {
         self.admit_counts.copy_from_slice(&u[..ACT_ADMIT_REPLAY_COUNTS]);
@@ -1450,7 +1469,9 @@ impl GpuReplay {
     /// `t <= s` per lane (`ACT_STATUS_RETURN_TOO_BIG` otherwise).  `Some`: the calls go to `act_redeem_(cbor_)return_replay_batch` -- the
     /// admission screen is implied, the outputs are RefundReturns, and the receipt PINS the amount: a retry with the same amount gets
     /// the same bytes, with another amount `DoubleSpendError`.  Derive the amount from the request, or remember it.  Together with
-    /// `unique(true)` the calls return `ACT_ERR_ARG` and write nothing.  `None`: the calls without amounts.
+    /// `unique(true)` the calls go to `act_redeem_(cbor_)return_replay_unique_batch` ("replayable partial refunds, unique forms"): a
+    /// lane with the bytes of an earlier lane is not verified whatever amount it names, and gets that lane's RefundReturn only if it
+    /// names that lane's amount (`Replayed::copies_other_amount` counts the others).  `None`: the calls without amounts.
     pub fn returned(mut self, returned: Option<Vec<u8>>) -> Self { self.returned = returned; self }
     fn returned_ptr(&self, n: usize) -> *const u8 {
         self.returned.as_ref().map_or(std::ptr::null(), |t| { assert!(t.len() == 32 * n); t.as_ptr() })
@@ -1464,10 +1485,16 @@ impl GpuReplay {
         assert!(proofs.len() == n * PROOF_BYTES && key_epochs.map_or(true, |e| e.len() == nkeys));
         let rec = if self.returned.is_some() { 160 } else { 128 };
         let mut r = Replayed { rc: 0, status: vec![0u8; n + 1], out: vec![0u8; rec * n + 1], out_key: vec![ACT_KEY_NONE; n + 1], replayed: vec![0u8; n + 1], counts: [0; ACT_REPLAY_COUNTS],
-                               admit_counts: [0; ACT_ADMIT_REPLAY_COUNTS], copy_counts: [0; 2], return_too_big: 0 };
+                               admit_counts: [0; ACT_ADMIT_REPLAY_COUNTS], copy_counts: [0; 2], return_too_big: 0, copies_other_amount: 0 };
         let mut u = [0u64; ACT_ADMIT_REPLAY_UNIQUE_COUNTS];
         let mut t = [0u64; ACT_RETURN_REPLAY_COUNTS];
-        r.rc = if self.returned.is_some() && self.unique { 1 /* ACT_ERR_ARG: no unique form with amounts */ } else if self.returned.is_some() { unsafe {
+        let mut v = [0u64; ACT_RETURN_REPLAY_UNIQUE_COUNTS];
+        r.rc = if self.returned.is_some() && self.unique { unsafe {
+            act_redeem_return_replay_unique_batch(self.ctx, self.set, self.receipts, n, 0, keys.as_ptr(), nkeys as c_int, key_epochs.map_or(std::ptr::null(), |e| e.as_ptr()),
+                                                  sign_with.map_or(ACT_SIGN_MATCHED, |i| i as c_int), proofs.as_ptr(), self.charge_ptr(n), self.returned_ptr(n),
+                                                  self.nonce_key.as_ptr(), r.out.as_mut_ptr(), r.status.as_mut_ptr(), r.out_key.as_mut_ptr(), r.replayed.as_mut_ptr(),
+                                                  v.as_mut_ptr())
+        } } else if self.returned.is_some() { unsafe {
             act_redeem_return_replay_batch(self.ctx, self.set, self.receipts, n, 0, keys.as_ptr(), nkeys as c_int, key_epochs.map_or(std::ptr::null(), |e| e.as_ptr()),
                                            sign_with.map_or(ACT_SIGN_MATCHED, |i| i as c_int), proofs.as_ptr(), self.charge_ptr(n), self.returned_ptr(n),
                                            self.nonce_key.as_ptr(), r.out.as_mut_ptr(), r.status.as_mut_ptr(), r.out_key.as_mut_ptr(), r.replayed.as_mut_ptr(), t.as_mut_ptr())
@@ -1484,7 +1511,8 @@ impl GpuReplay {
                                     sign_with.map_or(ACT_SIGN_MATCHED, |i| i as c_int), proofs.as_ptr(), self.nonce_key.as_ptr(), r.out.as_mut_ptr(),
                                     r.status.as_mut_ptr(), r.out_key.as_mut_ptr(), r.replayed.as_mut_ptr(), r.counts.as_mut_ptr())
         } };
-        if self.returned.is_some() { r.take_return_counts(&t); }
+        if self.returned.is_some() && self.unique { r.take_return_unique_counts(&v); }
+        else if self.returned.is_some() { r.take_return_counts(&t); }
         else if self.admit && self.unique { r.take_unique_counts(&u); }
         if self.admit || self.returned.is_some() { r.take_admit_counts(); }
         r.status.truncate(n); r.out.truncate(rec * n); r.out_key.truncate(n); r.replayed.truncate(n);
@@ -1497,10 +1525,16 @@ impl GpuReplay {
         assert!(key_epochs.map_or(true, |e| e.len() == nkeys));
         let rec = if self.returned.is_some() { REFUND_RETURN_CBOR_BYTES } else { REFUND_CBOR_BYTES };
         let mut r = Replayed { rc: 0, status: vec![0u8; n + 1], out: vec![0u8; rec * n + 1], out_key: vec![ACT_KEY_NONE; n + 1], replayed: vec![0u8; n + 1],
-                               counts: [0; ACT_REPLAY_COUNTS], admit_counts: [0; ACT_ADMIT_REPLAY_COUNTS], copy_counts: [0; 2], return_too_big: 0 };
+                               counts: [0; ACT_REPLAY_COUNTS], admit_counts: [0; ACT_ADMIT_REPLAY_COUNTS], copy_counts: [0; 2], return_too_big: 0, copies_other_amount: 0 };
         let mut u = [0u64; ACT_ADMIT_REPLAY_UNIQUE_COUNTS];
         let mut t = [0u64; ACT_RETURN_REPLAY_COUNTS];
-        r.rc = if self.returned.is_some() && self.unique { 1 /* ACT_ERR_ARG: no unique form with amounts */ } else if self.returned.is_some() { unsafe {
+        let mut v = [0u64; ACT_RETURN_REPLAY_UNIQUE_COUNTS];
+        r.rc = if self.returned.is_some() && self.unique { unsafe {
+            act_redeem_cbor_return_replay_unique_batch(self.ctx, self.set, self.receipts, n, 0, keys.as_ptr(), nkeys as c_int, key_epochs.map_or(std::ptr::null(), |e| e.as_ptr()),
+                                                       sign_with.map_or(ACT_SIGN_MATCHED, |i| i as c_int), blob.as_ptr(), offsets.as_ptr(), self.charge_ptr(n),
+                                                       self.returned_ptr(n), self.nonce_key.as_ptr(), r.out.as_mut_ptr(), r.status.as_mut_ptr(), r.out_key.as_mut_ptr(),
+                                                       r.replayed.as_mut_ptr(), v.as_mut_ptr())
+        } } else if self.returned.is_some() { unsafe {
             act_redeem_cbor_return_replay_batch(self.ctx, self.set, self.receipts, n, 0, keys.as_ptr(), nkeys as c_int, key_epochs.map_or(std::ptr::null(), |e| e.as_ptr()),
                                                 sign_with.map_or(ACT_SIGN_MATCHED, |i| i as c_int), blob.as_ptr(), offsets.as_ptr(), self.charge_ptr(n), self.returned_ptr(n),
                                                 self.nonce_key.as_ptr(), r.out.as_mut_ptr(), r.status.as_mut_ptr(), r.out_key.as_mut_ptr(), r.replayed.as_mut_ptr(),
@@ -1520,7 +1554,8 @@ impl GpuReplay {
                                          sign_with.map_or(ACT_SIGN_MATCHED, |i| i as c_int), blob.as_ptr(), offsets.as_ptr(), self.nonce_key.as_ptr(),
                                          r.out.as_mut_ptr(), r.status.as_mut_ptr(), r.out_key.as_mut_ptr(), r.replayed.as_mut_ptr(), r.counts.as_mut_ptr())
         } };
-        if self.returned.is_some() { r.take_return_counts(&t); }
+        if self.returned.is_some() && self.unique { r.take_return_unique_counts(&v); }
+        else if self.returned.is_some() { r.take_return_counts(&t); }
         else if self.admit && self.unique { r.take_unique_counts(&u); }
         if self.admit || self.returned.is_some() { r.take_admit_counts(); }
         r.status.truncate(n); r.out.truncate(rec * n); r.out_key.truncate(n); r.replayed.truncate(n);
