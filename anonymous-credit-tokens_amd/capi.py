@@ -841,6 +841,69 @@ class Engine:
             self._ck(self.lib.act_redeem_cbor_keyring_batch(self.ctx, p["set"].h, n, mem, pk, nk, p.get("sign_key", SIGN_MATCHED), p["cbor"], p.get("offsets") or None,
                                                             p["rng"], p["rng_mode"], p["out"], p["status"], p["out_key"]))
 
+    # ---- the admission family: five kinds of call, each on records and on wire bytes, plain and (but `replay`) unique -----------------
+    # kind -> (C symbol stem, count names, count names of the unique form, record row, CBOR type of the output, takes charges, takes
+    # returned, tail: receipts / nonce_key / replayed where True, rng / rng_mode where False, the _ptr form honours raw)
+    _FAMILY = {"admit": ("admit", ADMIT_COUNTS, ADMIT_UNIQUE_COUNTS, 128, "Refund", True, False, False, True),
+               "return": ("return", REDEEM_RETURN_COUNTS, REDEEM_RETURN_UNIQUE_COUNTS, 160, "RefundReturn", True, True, False, False),
+               "replay": ("replay", REPLAY_COUNTS, REPLAY_COUNTS, 128, "Refund", False, False, True, True),
+               "admit_replay": ("admit_replay", ADMIT_REPLAY_COUNTS, ADMIT_REPLAY_UNIQUE_COUNTS, 128, "Refund", True, False, True, True),
+               "return_replay": ("return_replay", RETURN_REPLAY_COUNTS, RETURN_REPLAY_UNIQUE_COUNTS, 160, "RefundReturn", True, True, True, True)}
+
+    def _family_ptr(self, kind: str, fn: str, keys, n: int, mem: int, p: dict, raw: bool = None):
+        """one call of the family on raw pointers of either kind, its arguments in the header's order.  -> counts dict, or (rc, counts)
+        with raw; raw=None: what p asks for, where the kind's _ptr method honours it"""
+        stem, names, unique_names, _, _, has_charges, has_returned, replay, honours_raw = self._FAMILY[kind]
+        raw = (honours_raw and bool(p.get("raw"))) if raw is None else raw; unique = kind != "replay" and bool(p.get("unique")); wire = fn != "redeem"
+        pk, kk = _in(b"".join(keys)); nk = len(keys)
+        ke = _epoch_table(p["key_epochs"], nk) if p.get("key_epochs") is not None else None
+        names = unique_names if unique else names
+        cnt = (C.c_uint64 * len(names))()
+        args = [self.ctx, p["set"].h] + ([p["receipts"].h] if replay else []) + [n, mem, pk, nk, ke.ctypes.data if ke is not None else None, p.get("sign_key", SIGN_MATCHED)]
+        args += [p["cbor"], p.get("offsets") or None] if wire else [p["proofs"]]
+        args += ([p.get("charges") or None] if has_charges else []) + ([p.get("returned") or None] if has_returned else [])
+        if replay:
+            pn, kn = _in(p["nonce_key"], 32)
+            args += [pn, p["out"], p["status"], p["out_key"], p.get("replayed") or None, cnt]
+        else:
+            args += [p["rng"], p["rng_mode"], p["out"], p["status"], p["out_key"], cnt]
+        rc = getattr(self.lib, "act_redeem_%s%s%s_batch" % ("cbor_" if wire else "", stem, "_unique" if unique else ""))(*args)
+        if not raw:
+            self._ck(rc)
+        counts = dict(zip(names, (int(v) for v in cnt)))
+        return (rc, counts) if raw else counts
+
+    def _family_host(self, kind: str, nullifier_set, keys, rows, tail: dict, sign_key, key_epochs, charges, returned, raw: bool, unique: bool):
+        """one call of the family from host memory; rows: records (bytes) or messages (a list).  -> (statuses, records | list of messages
+        (b"" where not signed), out_key, [replayed,] counts dict); raw=True: (rc, ...), no exception"""
+        _, _, _, row, cbor_type, _, _, replay, _ = self._FAMILY[kind]
+        wire = isinstance(rows, (list, tuple))
+        if wire:
+            n = len(rows); p0, k0, offs = _msgs(rows); ob = self.cbor_size(cbor_type)
+            p = dict(cbor=p0, offsets=offs.ctypes.data)
+        else:
+            n = len(rows) // self.proof_bytes; p0, k0 = _in(rows, self.proof_bytes * n); ob = row
+            p = dict(proofs=p0)
+        out = np.full(ob * n, 7 if raw and not wire else 0, np.uint8)      # (records under raw: a call that writes nothing leaves the 7s)
+        st = np.full(n, 99 if raw and replay else 0, np.uint8); ok = np.zeros(n, np.uint8); rp = np.zeros(n, np.uint8)
+        pc, kc = _in(charges, 32 * n) if charges is not None else (None, None)
+        pt, kt = _in(returned, 32 * n) if returned is not None else (None, None)
+        if replay:
+            p.update(receipts=tail["receipts"], nonce_key=tail["nonce_key"], replayed=rp.ctypes.data)
+        else:
+            pr, kr = _rng_arg(tail["rng"])
+            p.update(rng=pr, rng_mode=tail["rng_mode"])
+        p.update(set=nullifier_set, sign_key=sign_key, key_epochs=key_epochs, charges=pc, returned=pt, out=out.ctypes.data, status=st.ctypes.data, out_key=ok.ctypes.data,
+                 unique=unique)
+        rc, counts = self._family_ptr(kind, "redeem_cbor" if wire else "redeem", keys, n, MEM_HOST, p, raw=True)
+        b = out.tobytes()
+        res = (st.tobytes(), [b[i * ob:(i + 1) * ob] if st[i] == 0 else b"" for i in range(n)] if wire else b, ok.tobytes()) + ((rp.tobytes(),) if replay else ()) + (counts,)
+        if raw:
+            return (rc,) + res
+        self._ck(rc)
+        assert not wire or all(st[i] == 0 or not out[i * ob:(i + 1) * ob].any() for i in range(n)), "a failed lane's slot is not zero"
+        return res
+
     # ---- admission before verification (act_redeem_admit_batch / act_redeem_cbor_admit_batch) ---------------------------------------
     def redeem_admit(self, nullifier_set, keys, proofs: bytes, rng, rng_mode: int = RNG_PER_LANE, sign_key: int = SIGN_MATCHED, charges: bytes = None,
                      key_epochs=None, raw: bool = False, unique: bool = False):
@@ -848,64 +911,18 @@ class Engine:
         nullifier is already in the set (3) is answered without being verified.  -> (statuses, refunds, out_key, counts dict);
         raw=True: (rc, statuses, refunds, out_key, counts), no exception.  unique=True: act_redeem_admit_unique_batch -- a lane with
         the bytes of an earlier lane is not verified either; the same answers, and counts gains "copies"."""
-        n = len(proofs) // self.proof_bytes; out = np.full(128 * n, 7 if raw else 0, np.uint8); st = np.zeros(n, np.uint8); ok = np.zeros(n, np.uint8)
-        pk, kk = _in(b"".join(keys)); p0, k0 = _in(proofs, self.proof_bytes * n); p1, k1 = _rng_arg(rng)
-        pc, kc = _in(charges, 32 * n) if charges is not None else (None, None)
-        ke = _epoch_table(key_epochs, len(keys)) if key_epochs is not None else None
-        names = ADMIT_UNIQUE_COUNTS if unique else ADMIT_COUNTS
-        cnt = (C.c_uint64 * len(names))()
-        fn = self.lib.act_redeem_admit_unique_batch if unique else self.lib.act_redeem_admit_batch
-        rc = fn(self.ctx, nullifier_set.h, n, MEM_HOST, pk, len(keys), ke.ctypes.data if ke is not None else None, sign_key, p0, pc, p1,
-                rng_mode, out.ctypes.data, st.ctypes.data, ok.ctypes.data, cnt)
-        counts = dict(zip(names, (int(v) for v in cnt)))
-        if raw:
-            return rc, st.tobytes(), out.tobytes(), ok.tobytes(), counts
-        self._ck(rc)
-        return st.tobytes(), out.tobytes(), ok.tobytes(), counts
+        return self._family_host("admit", nullifier_set, keys, proofs, dict(rng=rng, rng_mode=rng_mode), sign_key, key_epochs, charges, None, raw, unique)
 
     def redeem_cbor_admit(self, nullifier_set, keys, messages: list, rng, rng_mode: int = RNG_SEQUENTIAL, sign_key: int = SIGN_MATCHED, charges: bytes = None,
                           key_epochs=None, raw: bool = False, unique: bool = False):
         """wire bytes in, wire bytes out -> (statuses, list of CBOR Refund messages (b"" where not signed), out_key, counts dict);
         unique=True: act_redeem_cbor_admit_unique_batch (a copy has the same length and the same bytes as an earlier message)"""
-        n = len(messages); p0, k0, offs = _msgs(messages); ml = self.cbor_size("Refund")
-        st = np.zeros(n, np.uint8); ok = np.zeros(n, np.uint8); out = np.zeros(ml * n, np.uint8); pk, kk = _in(b"".join(keys)); pr, kr = _rng_arg(rng)
-        pc, kc = _in(charges, 32 * n) if charges is not None else (None, None)
-        ke = _epoch_table(key_epochs, len(keys)) if key_epochs is not None else None
-        names = ADMIT_UNIQUE_COUNTS if unique else ADMIT_COUNTS
-        cnt = (C.c_uint64 * len(names))()
-        fn = self.lib.act_redeem_cbor_admit_unique_batch if unique else self.lib.act_redeem_cbor_admit_batch
-        rc = fn(self.ctx, nullifier_set.h, n, MEM_HOST, pk, len(keys), ke.ctypes.data if ke is not None else None, sign_key, p0,
-                offs.ctypes.data, pc, pr, rng_mode, out.ctypes.data, st.ctypes.data, ok.ctypes.data, cnt)
-        counts = dict(zip(names, (int(v) for v in cnt)))
-        b = out.tobytes()
-        msgs = [b[i * ml:(i + 1) * ml] if st[i] == 0 else b"" for i in range(n)]
-        if raw:
-            return rc, st.tobytes(), msgs, ok.tobytes(), counts
-        self._ck(rc)
-        assert all(st[i] == 0 or not out[i * ml:(i + 1) * ml].any() for i in range(n)), "a failed lane's slot is not zero"
-        return st.tobytes(), msgs, ok.tobytes(), counts
+        return self._family_host("admit", nullifier_set, keys, list(messages), dict(rng=rng, rng_mode=rng_mode), sign_key, key_epochs, charges, None, raw, unique)
 
     def admit_ptr(self, fn: str, keys, n: int, mem: int, **p):
         """the admission calls on raw pointers of either kind: fn = redeem / redeem_cbor; p: set, proofs | cbor (+ offsets), charges,
         rng, rng_mode, out, status, out_key, key_epochs, sign_key, unique (the act_redeem_*admit_unique_batch forms).  -> counts dict"""
-        pk, kk = _in(b"".join(keys)); nk = len(keys)
-        ke = _epoch_table(p["key_epochs"], nk) if p.get("key_epochs") is not None else None
-        kep = ke.ctypes.data if ke is not None else None
-        unique = bool(p.get("unique"))
-        names = ADMIT_UNIQUE_COUNTS if unique else ADMIT_COUNTS
-        cnt = (C.c_uint64 * len(names))()
-        if fn == "redeem":
-            call = self.lib.act_redeem_admit_unique_batch if unique else self.lib.act_redeem_admit_batch
-            rc = call(self.ctx, p["set"].h, n, mem, pk, nk, kep, p.get("sign_key", SIGN_MATCHED), p["proofs"], p.get("charges") or None,
-                      p["rng"], p["rng_mode"], p["out"], p["status"], p["out_key"], cnt)
-        else:
-            call = self.lib.act_redeem_cbor_admit_unique_batch if unique else self.lib.act_redeem_cbor_admit_batch
-            rc = call(self.ctx, p["set"].h, n, mem, pk, nk, kep, p.get("sign_key", SIGN_MATCHED), p["cbor"], p.get("offsets") or None,
-                      p.get("charges") or None, p["rng"], p["rng_mode"], p["out"], p["status"], p["out_key"], cnt)
-        if not p.get("raw"):
-            self._ck(rc)
-        counts = dict(zip(names, (int(v) for v in cnt)))
-        return (rc, counts) if p.get("raw") else counts
+        return self._family_ptr("admit", fn, keys, n, mem, p)
 
     # ---- partial refunds (act_redeem_return_batch / act_redeem_cbor_return_batch and the two calls around them) ---------------------
     def refund_sign_return_keyring(self, keys, key_index: bytes, kprime: bytes, status_in: bytes, rng: bytes, returned: bytes = None,
@@ -924,64 +941,18 @@ class Engine:
         not recorded, not signed); the others are signed over X_A = g + K' + t h1.  -> (statuses, 160-byte RefundReturn records,
         out_key, counts dict); raw=True: (rc, ...), no exception.  unique=True: act_redeem_return_unique_batch -- a lane with the proof
         bytes of an earlier lane (whatever its t) is not verified; the same answers, and counts gains "copies"."""
-        n = len(proofs) // self.proof_bytes; out = np.full(160 * n, 7 if raw else 0, np.uint8); st = np.zeros(n, np.uint8); ok = np.zeros(n, np.uint8)
-        pk, kk = _in(b"".join(keys)); p0, k0 = _in(proofs, self.proof_bytes * n); p1, k1 = _rng_arg(rng)
-        pc, kc = _in(charges, 32 * n) if charges is not None else (None, None)
-        pt, kt = _in(returned, 32 * n) if returned is not None else (None, None)
-        ke = _epoch_table(key_epochs, len(keys)) if key_epochs is not None else None
-        names = REDEEM_RETURN_UNIQUE_COUNTS if unique else REDEEM_RETURN_COUNTS
-        cnt = (C.c_uint64 * len(names))()
-        fn = self.lib.act_redeem_return_unique_batch if unique else self.lib.act_redeem_return_batch
-        rc = fn(self.ctx, nullifier_set.h, n, MEM_HOST, pk, len(keys), ke.ctypes.data if ke is not None else None, sign_key, p0, pc, pt,
-                p1, rng_mode, out.ctypes.data, st.ctypes.data, ok.ctypes.data, cnt)
-        counts = dict(zip(names, (int(v) for v in cnt)))
-        if raw:
-            return rc, st.tobytes(), out.tobytes(), ok.tobytes(), counts
-        self._ck(rc)
-        return st.tobytes(), out.tobytes(), ok.tobytes(), counts
+        return self._family_host("return", nullifier_set, keys, proofs, dict(rng=rng, rng_mode=rng_mode), sign_key, key_epochs, charges, returned, raw, unique)
 
     def redeem_cbor_return(self, nullifier_set, keys, messages: list, rng, rng_mode: int = RNG_SEQUENTIAL, sign_key: int = SIGN_MATCHED, charges: bytes = None,
                            returned: bytes = None, key_epochs=None, raw: bool = False, unique: bool = False):
         """wire bytes in, wire bytes out -> (statuses, list of CBOR RefundReturn messages (b"" where not signed), out_key, counts dict);
         unique=True: act_redeem_cbor_return_unique_batch (a copy has the same length and the same bytes as an earlier message)"""
-        n = len(messages); p0, k0, offs = _msgs(messages); ml = self.cbor_size("RefundReturn")
-        st = np.zeros(n, np.uint8); ok = np.zeros(n, np.uint8); out = np.zeros(ml * n, np.uint8); pk, kk = _in(b"".join(keys)); pr, kr = _rng_arg(rng)
-        pc, kc = _in(charges, 32 * n) if charges is not None else (None, None)
-        pt, kt = _in(returned, 32 * n) if returned is not None else (None, None)
-        ke = _epoch_table(key_epochs, len(keys)) if key_epochs is not None else None
-        names = REDEEM_RETURN_UNIQUE_COUNTS if unique else REDEEM_RETURN_COUNTS
-        cnt = (C.c_uint64 * len(names))()
-        fn = self.lib.act_redeem_cbor_return_unique_batch if unique else self.lib.act_redeem_cbor_return_batch
-        rc = fn(self.ctx, nullifier_set.h, n, MEM_HOST, pk, len(keys), ke.ctypes.data if ke is not None else None, sign_key, p0,
-                offs.ctypes.data, pc, pt, pr, rng_mode, out.ctypes.data, st.ctypes.data, ok.ctypes.data, cnt)
-        counts = dict(zip(names, (int(v) for v in cnt)))
-        b = out.tobytes()
-        msgs = [b[i * ml:(i + 1) * ml] if st[i] == 0 else b"" for i in range(n)]
-        if raw:
-            return rc, st.tobytes(), msgs, ok.tobytes(), counts
-        self._ck(rc)
-        assert all(st[i] == 0 or not out[i * ml:(i + 1) * ml].any() for i in range(n)), "a failed lane's slot is not zero"
-        return st.tobytes(), msgs, ok.tobytes(), counts
+        return self._family_host("return", nullifier_set, keys, list(messages), dict(rng=rng, rng_mode=rng_mode), sign_key, key_epochs, charges, returned, raw, unique)
 
     def return_ptr(self, fn: str, keys, n: int, mem: int, **p):
         """the return calls on raw pointers of either kind: fn = redeem / redeem_cbor; p as admit_ptr's plus returned (unique: the
         act_redeem_*return_unique_batch forms).  -> counts dict"""
-        pk, kk = _in(b"".join(keys)); nk = len(keys)
-        ke = _epoch_table(p["key_epochs"], nk) if p.get("key_epochs") is not None else None
-        kep = ke.ctypes.data if ke is not None else None
-        unique = bool(p.get("unique"))
-        names = REDEEM_RETURN_UNIQUE_COUNTS if unique else REDEEM_RETURN_COUNTS
-        cnt = (C.c_uint64 * len(names))()
-        if fn == "redeem":
-            call = self.lib.act_redeem_return_unique_batch if unique else self.lib.act_redeem_return_batch
-            rc = call(self.ctx, p["set"].h, n, mem, pk, nk, kep, p.get("sign_key", SIGN_MATCHED), p["proofs"], p.get("charges") or None,
-                      p.get("returned") or None, p["rng"], p["rng_mode"], p["out"], p["status"], p["out_key"], cnt)
-        else:
-            call = self.lib.act_redeem_cbor_return_unique_batch if unique else self.lib.act_redeem_cbor_return_batch
-            rc = call(self.ctx, p["set"].h, n, mem, pk, nk, kep, p.get("sign_key", SIGN_MATCHED), p["cbor"], p.get("offsets") or None,
-                      p.get("charges") or None, p.get("returned") or None, p["rng"], p["rng_mode"], p["out"], p["status"], p["out_key"], cnt)
-        self._ck(rc)
-        return dict(zip(names, (int(v) for v in cnt)))
+        return self._family_ptr("return", fn, keys, n, mem, p)
 
     def refund_to_credit_token_return(self, prerefund: bytes, proofs: bytes, refund_return: bytes, w: bytes):
         """refund_to_credit_token over 160-byte RefundReturn records -> (statuses, tokens with balance m + t); t > s is status 8"""
@@ -1005,54 +976,16 @@ class Engine:
     def redeem_replay(self, nullifier_set, receipts, keys, proofs: bytes, nonce_key: bytes, sign_key: int = SIGN_MATCHED, key_epochs=None, raw: bool = False):
         """redeem_keyring with derived nonces and a receipts set: a retried proof gets its refund again, byte for byte.
         -> (statuses, refunds, out_key, replayed, counts dict); raw=True: (rc, ...), no exception"""
-        n = len(proofs) // self.proof_bytes; out = np.full(128 * n, 7 if raw else 0, np.uint8)
-        st = np.full(n, 99 if raw else 0, np.uint8); ok = np.zeros(n, np.uint8); rp = np.zeros(n, np.uint8)
-        pk, kk = _in(b"".join(keys)); p0, k0 = _in(proofs, self.proof_bytes * n); pn, kn = _in(nonce_key, 32)
-        ke = _epoch_table(key_epochs, len(keys)) if key_epochs is not None else None
-        cnt = (C.c_uint64 * len(REPLAY_COUNTS))()
-        rc = self.lib.act_redeem_replay_batch(self.ctx, nullifier_set.h, receipts.h, n, MEM_HOST, pk, len(keys), ke.ctypes.data if ke is not None else None, sign_key, p0, pn,
-                                              out.ctypes.data, st.ctypes.data, ok.ctypes.data, rp.ctypes.data, cnt)
-        counts = dict(zip(REPLAY_COUNTS, (int(v) for v in cnt)))
-        if raw:
-            return rc, st.tobytes(), out.tobytes(), ok.tobytes(), rp.tobytes(), counts
-        self._ck(rc)
-        return st.tobytes(), out.tobytes(), ok.tobytes(), rp.tobytes(), counts
+        return self._family_host("replay", nullifier_set, keys, proofs, dict(receipts=receipts, nonce_key=nonce_key), sign_key, key_epochs, None, None, raw, False)
 
     def redeem_cbor_replay(self, nullifier_set, receipts, keys, messages: list, nonce_key: bytes, sign_key: int = SIGN_MATCHED, key_epochs=None, raw: bool = False):
         """wire bytes in, wire bytes out -> (statuses, list of CBOR Refund messages (b"" where not signed), out_key, replayed, counts dict)"""
-        n = len(messages); p0, k0, offs = _msgs(messages); ml = self.cbor_size("Refund")
-        st = np.full(n, 99 if raw else 0, np.uint8); ok = np.zeros(n, np.uint8); rp = np.zeros(n, np.uint8); out = np.zeros(ml * n, np.uint8)
-        pk, kk = _in(b"".join(keys)); pn, kn = _in(nonce_key, 32)
-        ke = _epoch_table(key_epochs, len(keys)) if key_epochs is not None else None
-        cnt = (C.c_uint64 * len(REPLAY_COUNTS))()
-        rc = self.lib.act_redeem_cbor_replay_batch(self.ctx, nullifier_set.h, receipts.h, n, MEM_HOST, pk, len(keys), ke.ctypes.data if ke is not None else None, sign_key, p0,
-                                                   offs.ctypes.data, pn, out.ctypes.data, st.ctypes.data, ok.ctypes.data, rp.ctypes.data, cnt)
-        counts = dict(zip(REPLAY_COUNTS, (int(v) for v in cnt)))
-        b = out.tobytes()
-        msgs = [b[i * ml:(i + 1) * ml] if st[i] == 0 else b"" for i in range(n)]
-        if raw:
-            return rc, st.tobytes(), msgs, ok.tobytes(), rp.tobytes(), counts
-        self._ck(rc)
-        assert all(st[i] == 0 or not out[i * ml:(i + 1) * ml].any() for i in range(n)), "a failed lane's slot is not zero"
-        return st.tobytes(), msgs, ok.tobytes(), rp.tobytes(), counts
+        return self._family_host("replay", nullifier_set, keys, list(messages), dict(receipts=receipts, nonce_key=nonce_key), sign_key, key_epochs, None, None, raw, False)
 
     def replay_ptr(self, fn: str, keys, n: int, mem: int, **p):
         """the replay calls on raw pointers of either kind: fn = redeem / redeem_cbor; p: set, receipts, proofs | cbor (+ offsets), nonce_key,
         out, status, out_key, replayed, key_epochs, sign_key, raw.  -> counts dict, or (rc, counts) with raw"""
-        pk, kk = _in(b"".join(keys)); nk = len(keys); pn, kn = _in(p["nonce_key"], 32)
-        ke = _epoch_table(p["key_epochs"], nk) if p.get("key_epochs") is not None else None
-        kep = ke.ctypes.data if ke is not None else None
-        cnt = (C.c_uint64 * len(REPLAY_COUNTS))()
-        if fn == "redeem":
-            rc = self.lib.act_redeem_replay_batch(self.ctx, p["set"].h, p["receipts"].h, n, mem, pk, nk, kep, p.get("sign_key", SIGN_MATCHED), p["proofs"], pn,
-                                                  p["out"], p["status"], p["out_key"], p.get("replayed") or None, cnt)
-        else:
-            rc = self.lib.act_redeem_cbor_replay_batch(self.ctx, p["set"].h, p["receipts"].h, n, mem, pk, nk, kep, p.get("sign_key", SIGN_MATCHED), p["cbor"],
-                                                       p.get("offsets") or None, pn, p["out"], p["status"], p["out_key"], p.get("replayed") or None, cnt)
-        if not p.get("raw"):
-            self._ck(rc)
-        counts = dict(zip(REPLAY_COUNTS, (int(v) for v in cnt)))
-        return (rc, counts) if p.get("raw") else counts
+        return self._family_ptr("replay", fn, keys, n, mem, p)
 
     # ---- admission for the replayable redemption (act_redeem_admit_replay_batch / act_redeem_cbor_admit_replay_batch) ----------------
     def redeem_admit_replay(self, nullifier_set, receipts, keys, proofs: bytes, nonce_key: bytes, sign_key: int = SIGN_MATCHED, key_epochs=None, charges: bytes = None,
@@ -1061,68 +994,19 @@ class Engine:
         not this proof's (STATUS_DOUBLE_SPEND) are answered unverified; a retry is verified and served.
         -> (statuses, refunds, out_key, replayed, counts dict); raw=True: (rc, ...), no exception.  unique=True:
         act_redeem_admit_replay_unique_batch -- a lane with the bytes of an earlier lane is not verified and takes that lane's answer"""
-        names = ADMIT_REPLAY_UNIQUE_COUNTS if unique else ADMIT_REPLAY_COUNTS
-        fn = self.lib.act_redeem_admit_replay_unique_batch if unique else self.lib.act_redeem_admit_replay_batch
-        n = len(proofs) // self.proof_bytes; out = np.full(128 * n, 7 if raw else 0, np.uint8)
-        st = np.full(n, 99 if raw else 0, np.uint8); ok = np.zeros(n, np.uint8); rp = np.zeros(n, np.uint8)
-        pk, kk = _in(b"".join(keys)); p0, k0 = _in(proofs, self.proof_bytes * n); pn, kn = _in(nonce_key, 32)
-        pc, kc = _in(charges, 32 * n) if charges is not None else (None, None)
-        ke = _epoch_table(key_epochs, len(keys)) if key_epochs is not None else None
-        cnt = (C.c_uint64 * len(names))()
-        rc = fn(self.ctx, nullifier_set.h, receipts.h, n, MEM_HOST, pk, len(keys), ke.ctypes.data if ke is not None else None, sign_key,
-                p0, pc, pn, out.ctypes.data, st.ctypes.data, ok.ctypes.data, rp.ctypes.data, cnt)
-        counts = dict(zip(names, (int(v) for v in cnt)))
-        if raw:
-            return rc, st.tobytes(), out.tobytes(), ok.tobytes(), rp.tobytes(), counts
-        self._ck(rc)
-        return st.tobytes(), out.tobytes(), ok.tobytes(), rp.tobytes(), counts
+        return self._family_host("admit_replay", nullifier_set, keys, proofs, dict(receipts=receipts, nonce_key=nonce_key), sign_key, key_epochs, charges, None, raw, unique)
 
     def redeem_cbor_admit_replay(self, nullifier_set, receipts, keys, messages: list, nonce_key: bytes, sign_key: int = SIGN_MATCHED, key_epochs=None,
                                  charges: bytes = None, raw: bool = False, unique: bool = False):
         """wire bytes in, wire bytes out -> (statuses, list of CBOR Refund messages (b"" where not signed), out_key, replayed, counts dict)
         unique=True: act_redeem_cbor_admit_replay_unique_batch (a copy has the same length and the same bytes as an earlier message)"""
-        names = ADMIT_REPLAY_UNIQUE_COUNTS if unique else ADMIT_REPLAY_COUNTS
-        fn = self.lib.act_redeem_cbor_admit_replay_unique_batch if unique else self.lib.act_redeem_cbor_admit_replay_batch
-        n = len(messages); p0, k0, offs = _msgs(messages); ml = self.cbor_size("Refund")
-        st = np.full(n, 99 if raw else 0, np.uint8); ok = np.zeros(n, np.uint8); rp = np.zeros(n, np.uint8); out = np.zeros(ml * n, np.uint8)
-        pk, kk = _in(b"".join(keys)); pn, kn = _in(nonce_key, 32)
-        pc, kc = _in(charges, 32 * n) if charges is not None else (None, None)
-        ke = _epoch_table(key_epochs, len(keys)) if key_epochs is not None else None
-        cnt = (C.c_uint64 * len(names))()
-        rc = fn(self.ctx, nullifier_set.h, receipts.h, n, MEM_HOST, pk, len(keys), ke.ctypes.data if ke is not None else None,
-                sign_key, p0, offs.ctypes.data, pc, pn, out.ctypes.data, st.ctypes.data, ok.ctypes.data, rp.ctypes.data, cnt)
-        counts = dict(zip(names, (int(v) for v in cnt)))
-        b = out.tobytes()
-        msgs = [b[i * ml:(i + 1) * ml] if st[i] == 0 else b"" for i in range(n)]
-        if raw:
-            return rc, st.tobytes(), msgs, ok.tobytes(), rp.tobytes(), counts
-        self._ck(rc)
-        assert all(st[i] == 0 or not out[i * ml:(i + 1) * ml].any() for i in range(n)), "a failed lane's slot is not zero"
-        return st.tobytes(), msgs, ok.tobytes(), rp.tobytes(), counts
+        return self._family_host("admit_replay", nullifier_set, keys, list(messages), dict(receipts=receipts, nonce_key=nonce_key), sign_key, key_epochs, charges, None, raw, unique)
 
     def admit_replay_ptr(self, fn: str, keys, n: int, mem: int, **p):
         """the two calls on raw pointers of either kind: fn = redeem / redeem_cbor; p: set, receipts, proofs | cbor (+ offsets), charges, nonce_key,
         out, status, out_key, replayed, key_epochs, sign_key, raw, unique (the act_redeem_*admit_replay_unique_batch forms).
         -> counts dict, or (rc, counts) with raw"""
-        pk, kk = _in(b"".join(keys)); nk = len(keys); pn, kn = _in(p["nonce_key"], 32)
-        ke = _epoch_table(p["key_epochs"], nk) if p.get("key_epochs") is not None else None
-        kep = ke.ctypes.data if ke is not None else None
-        unique = bool(p.get("unique", False))
-        names = ADMIT_REPLAY_UNIQUE_COUNTS if unique else ADMIT_REPLAY_COUNTS
-        cnt = (C.c_uint64 * len(names))()
-        if fn == "redeem":
-            call = self.lib.act_redeem_admit_replay_unique_batch if unique else self.lib.act_redeem_admit_replay_batch
-            rc = call(self.ctx, p["set"].h, p["receipts"].h, n, mem, pk, nk, kep, p.get("sign_key", SIGN_MATCHED), p["proofs"],
-                      p.get("charges") or None, pn, p["out"], p["status"], p["out_key"], p.get("replayed") or None, cnt)
-        else:
-            call = self.lib.act_redeem_cbor_admit_replay_unique_batch if unique else self.lib.act_redeem_cbor_admit_replay_batch
-            rc = call(self.ctx, p["set"].h, p["receipts"].h, n, mem, pk, nk, kep, p.get("sign_key", SIGN_MATCHED), p["cbor"],
-                      p.get("offsets") or None, p.get("charges") or None, pn, p["out"], p["status"], p["out_key"],
-                      p.get("replayed") or None, cnt)
-        if not p.get("raw"):
-            self._ck(rc)
-        counts = dict(zip(names, (int(v) for v in cnt)))
-        return (rc, counts) if p.get("raw") else counts
+        return self._family_ptr("admit_replay", fn, keys, n, mem, p)
 
     # ---- replayable partial refunds (act_redeem_return_replay_batch / act_redeem_cbor_return_replay_batch / act_replay_derive_return_batch)
     def redeem_return_replay(self, nullifier_set, receipts, keys, proofs: bytes, nonce_key: bytes, sign_key: int = SIGN_MATCHED, key_epochs=None, charges: bytes = None,
@@ -1132,69 +1016,18 @@ class Engine:
         -> (statuses, 160-byte RefundReturn records, out_key, replayed, counts dict); raw=True: (rc, ...), no exception
         unique=True: act_redeem_return_replay_unique_batch -- a lane with the bytes of an earlier lane is not verified; it takes that
         lane's answer if it names that lane's amount and is STATUS_DOUBLE_SPEND behind an accepted leader if it names another"""
-        names = RETURN_REPLAY_UNIQUE_COUNTS if unique else RETURN_REPLAY_COUNTS
-        fn = self.lib.act_redeem_return_replay_unique_batch if unique else self.lib.act_redeem_return_replay_batch
-        n = len(proofs) // self.proof_bytes; out = np.full(160 * n, 7 if raw else 0, np.uint8)
-        st = np.full(n, 99 if raw else 0, np.uint8); ok = np.zeros(n, np.uint8); rp = np.zeros(n, np.uint8)
-        pk, kk = _in(b"".join(keys)); p0, k0 = _in(proofs, self.proof_bytes * n); pn, kn = _in(nonce_key, 32)
-        pc, kc = _in(charges, 32 * n) if charges is not None else (None, None)
-        pt, kt = _in(returned, 32 * n) if returned is not None else (None, None)
-        ke = _epoch_table(key_epochs, len(keys)) if key_epochs is not None else None
-        cnt = (C.c_uint64 * len(names))()
-        rc = fn(self.ctx, nullifier_set.h, receipts.h, n, MEM_HOST, pk, len(keys), ke.ctypes.data if ke is not None else None, sign_key,
-                p0, pc, pt, pn, out.ctypes.data, st.ctypes.data, ok.ctypes.data, rp.ctypes.data, cnt)
-        counts = dict(zip(names, (int(v) for v in cnt)))
-        if raw:
-            return rc, st.tobytes(), out.tobytes(), ok.tobytes(), rp.tobytes(), counts
-        self._ck(rc)
-        return st.tobytes(), out.tobytes(), ok.tobytes(), rp.tobytes(), counts
+        return self._family_host("return_replay", nullifier_set, keys, proofs, dict(receipts=receipts, nonce_key=nonce_key), sign_key, key_epochs, charges, returned, raw, unique)
 
     def redeem_cbor_return_replay(self, nullifier_set, receipts, keys, messages: list, nonce_key: bytes, sign_key: int = SIGN_MATCHED, key_epochs=None,
                                   charges: bytes = None, returned: bytes = None, raw: bool = False, unique: bool = False):
         """wire bytes in, wire bytes out -> (statuses, list of CBOR RefundReturn messages (b"" where not signed), out_key, replayed, counts dict)
         unique=True: act_redeem_cbor_return_replay_unique_batch (a copy has the same length and the same bytes as an earlier message)"""
-        names = RETURN_REPLAY_UNIQUE_COUNTS if unique else RETURN_REPLAY_COUNTS
-        fn = self.lib.act_redeem_cbor_return_replay_unique_batch if unique else self.lib.act_redeem_cbor_return_replay_batch
-        n = len(messages); p0, k0, offs = _msgs(messages); ml = self.cbor_size("RefundReturn")
-        st = np.full(n, 99 if raw else 0, np.uint8); ok = np.zeros(n, np.uint8); rp = np.zeros(n, np.uint8); out = np.zeros(ml * n, np.uint8)
-        pk, kk = _in(b"".join(keys)); pn, kn = _in(nonce_key, 32)
-        pc, kc = _in(charges, 32 * n) if charges is not None else (None, None)
-        pt, kt = _in(returned, 32 * n) if returned is not None else (None, None)
-        ke = _epoch_table(key_epochs, len(keys)) if key_epochs is not None else None
-        cnt = (C.c_uint64 * len(names))()
-        rc = fn(self.ctx, nullifier_set.h, receipts.h, n, MEM_HOST, pk, len(keys), ke.ctypes.data if ke is not None else None,
-                sign_key, p0, offs.ctypes.data, pc, pt, pn, out.ctypes.data, st.ctypes.data, ok.ctypes.data, rp.ctypes.data, cnt)
-        counts = dict(zip(names, (int(v) for v in cnt)))
-        b = out.tobytes()
-        msgs = [b[i * ml:(i + 1) * ml] if st[i] == 0 else b"" for i in range(n)]
-        if raw:
-            return rc, st.tobytes(), msgs, ok.tobytes(), rp.tobytes(), counts
-        self._ck(rc)
-        assert all(st[i] == 0 or not out[i * ml:(i + 1) * ml].any() for i in range(n)), "a failed lane's slot is not zero"
-        return st.tobytes(), msgs, ok.tobytes(), rp.tobytes(), counts
+        return self._family_host("return_replay", nullifier_set, keys, list(messages), dict(receipts=receipts, nonce_key=nonce_key), sign_key, key_epochs, charges, returned, raw, unique)
 
     def return_replay_ptr(self, fn: str, keys, n: int, mem: int, **p):
         """the two calls on raw pointers of either kind: fn = redeem / redeem_cbor; p as admit_replay_ptr's plus returned (unique: the
         act_redeem_*return_replay_unique_batch forms).  -> counts dict, or (rc, counts) with raw"""
-        unique = bool(p.get("unique"))
-        names = RETURN_REPLAY_UNIQUE_COUNTS if unique else RETURN_REPLAY_COUNTS
-        pk, kk = _in(b"".join(keys)); nk = len(keys); pn, kn = _in(p["nonce_key"], 32)
-        ke = _epoch_table(p["key_epochs"], nk) if p.get("key_epochs") is not None else None
-        kep = ke.ctypes.data if ke is not None else None
-        cnt = (C.c_uint64 * len(names))()
-        if fn == "redeem":
-            call = self.lib.act_redeem_return_replay_unique_batch if unique else self.lib.act_redeem_return_replay_batch
-            rc = call(self.ctx, p["set"].h, p["receipts"].h, n, mem, pk, nk, kep, p.get("sign_key", SIGN_MATCHED), p["proofs"],
-                      p.get("charges") or None, p.get("returned") or None, pn, p["out"], p["status"], p["out_key"], p.get("replayed") or None, cnt)
-        else:
-            call = self.lib.act_redeem_cbor_return_replay_unique_batch if unique else self.lib.act_redeem_cbor_return_replay_batch
-            rc = call(self.ctx, p["set"].h, p["receipts"].h, n, mem, pk, nk, kep, p.get("sign_key", SIGN_MATCHED), p["cbor"],
-                      p.get("offsets") or None, p.get("charges") or None, p.get("returned") or None, pn, p["out"], p["status"],
-                      p["out_key"], p.get("replayed") or None, cnt)
-        if not p.get("raw"):
-            self._ck(rc)
-        counts = dict(zip(names, (int(v) for v in cnt)))
-        return (rc, counts) if p.get("raw") else counts
+        return self._family_ptr("return_replay", fn, keys, n, mem, p)
 
     def replay_derive(self, keys, key_index: bytes, nonce_key: bytes, nullifiers: bytes, kprime: bytes, status_in: bytes, stride: int = 32, returned: bytes = None):
         """-> (tags: 32 bytes a lane, nonces: 128 bytes a lane) of the lanes with status_in 0 and key_index < len(keys); zeros elsewhere.

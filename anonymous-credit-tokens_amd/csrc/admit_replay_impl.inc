@@ -1,5 +1,5 @@
 // admit_replay_impl.inc — included by engine.hip behind replay_impl.inc: admission for the replayable redemption (DESIGN 4.9; kernels in
-// k_admit_replay.hip, lane bodies in admit_replay_lanes.h).  act_redeem_(cbor_)admit_replay_batch are redeem_admit_impl (admit_impl.inc)
+// k_admit_replay.hip, lane bodies in admit_replay_lanes.h).  act_redeem_(cbor_)admit_replay_batch are redeem_admit (admit_impl.inc)
 // with one stage between its screen and its compaction, and the replay tail (replay_impl.inc) where the admission calls have the ring
 // redeem tail:
 //   a. compaction    the lanes the screen found spent, in lane order                            [k_admit_replay_key, k_admit_count / _scan / _write]
@@ -17,19 +17,7 @@ struct AdmitComJob { uint8_t* dst; const uint8_t* src; const uint32_t* idx; size
 
 }  // namespace
 
-// pre: the final pre-statuses; tc: the replay tail's ACT_REPLAY_COUNTS over the m verified lanes (null: none was verified)
-// ret (the return replay form): a twelfth value, the lanes whose returned amount exceeded their charge (ACT_RETURN_REPLAY_COUNTS)
-static void admit_replay_counts_of(uint64_t* out_counts, size_t n, const uint8_t* pre, size_t candidates, size_t m, const uint64_t* tc, bool ret) {
-  uint64_t k[ACT_RETURN_REPLAY_COUNTS] = {n, 0, 0, 0, candidates, m, 0, 0, 0, 0, 0, 0};
-  for (size_t i = 0; i < n; i++) {
-    const uint8_t p = pre[i];
-    if (p == ACT_STATUS_WRONG_CHARGE) k[2]++; else if (p == ACT_STATUS_DOUBLE_SPEND) k[3]++; else if (ret && p == ACT_STATUS_RETURN_TOO_BIG) k[11]++; else if (p) k[1]++;
-  }
-  if (tc) for (int j = 0; j < 5; j++) k[6 + j] = tc[1 + j];      // rejected_by_verification, fresh, replayed, double_spend_after, unanswered
-  memcpy(out_counts, k, sizeof(uint64_t) * (ret ? ACT_RETURN_REPLAY_COUNTS : ACT_ADMIT_REPLAY_COUNTS));
-}
-
-static int admit_replay_stage(act_ctx* c, AdmitReplay& rp, const AdmitReplayStage& g) {
+static int admit_replay_stage(act_ctx* c, act_nullifier_set* receipts, const AdmitReplayStage& g, size_t* candidates) {
   const size_t n = g.n; hipStream_t stream = g.stream; int rc;
   const int L = c->L; const ProofLayout pl{L}; const size_t pb = pl.bytes();
   ADCK(c, hipSetDevice(c->device));
@@ -147,8 +135,8 @@ static int admit_replay_stage(act_ctx* c, AdmitReplay& rp, const AdmitReplayStag
   }
 
   // ---- c. the receipts, read only, and d. the decision -------------------------------------------------------------------------------------
-  if ((rc = act_nullifier_contains_batch(rp.receipts, ns, ACT_MEM_DEVICE, d_tag, 32, d_found))) {
-    c->err = std::string("admission: receipts set: ") + act_nullifier_set_last_error(rp.receipts);
+  if ((rc = act_nullifier_contains_batch(receipts, ns, ACT_MEM_DEVICE, d_tag, 32, d_found))) {
+    c->err = std::string("admission: receipts set: ") + act_nullifier_set_last_error(receipts);
     return rc;
   }
   AdmitReplayDecideArgs da{(uint32_t)n, g.d_pos, d_mark, d_found, g.d_pre};
@@ -157,36 +145,25 @@ static int admit_replay_stage(act_ctx* c, AdmitReplay& rp, const AdmitReplayStag
   std::vector<uint8_t> mf(2 * ns);
   ADCK(c, hipMemcpyAsync(mf.data(), d_mark, 2 * ns, hipMemcpyDeviceToHost, stream));
   ADCK(c, hipStreamSynchronize(stream));
-  rp.candidates = 0;
-  for (size_t k = 0; k < ns; k++) rp.candidates += admit_replay_decide(ACT_STATUS_DOUBLE_SPEND, true, mf[k] != 0, mf[ns + k] != 0).candidate;
+  *candidates = 0;
+  for (size_t k = 0; k < ns; k++) *candidates += admit_replay_decide(ACT_STATUS_DOUBLE_SPEND, true, mf[k] != 0, mf[ns + k] != 0).candidate;
   return ACT_OK;
-}
-
-static int redeem_admit_replay_impl(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys, int nkeys,
-                                    const uint32_t* key_epochs, int sign_key, const uint8_t* proof, const uint8_t* cbor, const uint64_t* offsets, const uint8_t* charge,
-                                    const uint8_t* nonce_key, uint8_t* out, uint8_t* status, uint8_t* out_key, uint8_t* out_replayed, uint64_t* out_counts,
-                                    bool unique = false, const RedeemReturn* ret = nullptr) {
-  static const uint8_t derived = 0;      // the nonces stand where the admission calls' rng stands
-  AdmitReplay rp{receipts, nonce_key, out_replayed, out_counts};
-  return redeem_admit_impl(c, set, n, mem, keys, nkeys, key_epochs, sign_key, proof, cbor, offsets, charge, &derived, ACT_RNG_PER_LANE, out, status, out_key, nullptr,
-                           unique, &rp, ret);
 }
 
 extern "C" int act_redeem_admit_replay_batch(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys, int nkeys,
                                              const uint32_t* key_epochs, int sign_key, const uint8_t* proof, const uint8_t* charge, const uint8_t nonce_key[32],
                                              uint8_t* out_refund, uint8_t* status, uint8_t* out_key, uint8_t* out_replayed, uint64_t* out_counts) {
   if (n && !proof) return ACT_ERR_ARG;
-  return redeem_admit_replay_impl(c, set, receipts, n, mem, keys, nkeys, key_epochs, sign_key, proof, nullptr, nullptr, charge, nonce_key, out_refund, status, out_key,
-                                  out_replayed, out_counts);
+  return redeem_admit(AdmitCall(c, set, n, mem).ring(keys, nkeys, key_epochs, sign_key).records(proof).charged(charge).replays(receipts, nonce_key, out_replayed)
+                          .answers(out_refund, status, out_key, out_counts));
 }
 extern "C" int act_redeem_cbor_admit_replay_batch(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys, int nkeys,
                                                   const uint32_t* key_epochs, int sign_key, const uint8_t* cbor, const uint64_t* offsets, const uint8_t* charge,
                                                   const uint8_t nonce_key[32], uint8_t* out_refund_cbor, uint8_t* status, uint8_t* out_key, uint8_t* out_replayed,
                                                   uint64_t* out_counts) {
   if (n && !cbor) return ACT_ERR_ARG;
-  static const uint8_t none = 0;
-  return redeem_admit_replay_impl(c, set, receipts, n, mem, keys, nkeys, key_epochs, sign_key, nullptr, cbor ? cbor : &none, offsets, charge, nonce_key, out_refund_cbor,
-                                  status, out_key, out_replayed, out_counts);
+  return redeem_admit(AdmitCall(c, set, n, mem).ring(keys, nkeys, key_epochs, sign_key).messages(cbor, offsets).charged(charge).replays(receipts, nonce_key, out_replayed)
+                          .answers(out_refund_cbor, status, out_key, out_counts));
 }
 
 // the unique forms: the copy stage of the admission unique forms (copies_impl.inc) behind this screen, and copies SERVED from their
@@ -195,17 +172,16 @@ extern "C" int act_redeem_admit_replay_unique_batch(act_ctx* c, act_nullifier_se
                                                     const uint32_t* key_epochs, int sign_key, const uint8_t* proof, const uint8_t* charge, const uint8_t nonce_key[32],
                                                     uint8_t* out_refund, uint8_t* status, uint8_t* out_key, uint8_t* out_replayed, uint64_t* out_counts) {
   if (n && !proof) return ACT_ERR_ARG;
-  return redeem_admit_replay_impl(c, set, receipts, n, mem, keys, nkeys, key_epochs, sign_key, proof, nullptr, nullptr, charge, nonce_key, out_refund, status, out_key,
-                                  out_replayed, out_counts, true);
+  return redeem_admit(AdmitCall(c, set, n, mem).ring(keys, nkeys, key_epochs, sign_key).records(proof).charged(charge).replays(receipts, nonce_key, out_replayed)
+                          .uniquely().answers(out_refund, status, out_key, out_counts));
 }
 extern "C" int act_redeem_cbor_admit_replay_unique_batch(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys,
                                                          int nkeys, const uint32_t* key_epochs, int sign_key, const uint8_t* cbor, const uint64_t* offsets,
                                                          const uint8_t* charge, const uint8_t nonce_key[32], uint8_t* out_refund_cbor, uint8_t* status, uint8_t* out_key,
                                                          uint8_t* out_replayed, uint64_t* out_counts) {
   if (n && !cbor) return ACT_ERR_ARG;
-  static const uint8_t none = 0;
-  return redeem_admit_replay_impl(c, set, receipts, n, mem, keys, nkeys, key_epochs, sign_key, nullptr, cbor ? cbor : &none, offsets, charge, nonce_key, out_refund_cbor,
-                                  status, out_key, out_replayed, out_counts, true);
+  return redeem_admit(AdmitCall(c, set, n, mem).ring(keys, nkeys, key_epochs, sign_key).messages(cbor, offsets).charged(charge).replays(receipts, nonce_key, out_replayed)
+                          .uniquely().answers(out_refund_cbor, status, out_key, out_counts));
 }
 
 // ---- replayable partial refunds (DESIGN 4.10): the admission replay calls with the amounts t the issuer returns ----------------------------
@@ -216,20 +192,15 @@ extern "C" int act_redeem_return_replay_batch(act_ctx* c, act_nullifier_set* set
                                               const uint32_t* key_epochs, int sign_key, const uint8_t* proof, const uint8_t* charge, const uint8_t* returned,
                                               const uint8_t nonce_key[32], uint8_t* out_refund_return, uint8_t* status, uint8_t* out_key, uint8_t* out_replayed,
                                               uint64_t* out_counts) {
-  if (n && !proof) { if (out_counts) memset(out_counts, 0, sizeof(uint64_t) * ACT_RETURN_REPLAY_COUNTS); return ACT_ERR_ARG; }
-  const RedeemReturn ret{returned};
-  return redeem_admit_replay_impl(c, set, receipts, n, mem, keys, nkeys, key_epochs, sign_key, proof, nullptr, nullptr, charge, nonce_key, out_refund_return, status,
-                                  out_key, out_replayed, out_counts, false, &ret);
+  return redeem_admit(AdmitCall(c, set, n, mem).ring(keys, nkeys, key_epochs, sign_key).records(proof).charged(charge).returns(returned)
+                          .replays(receipts, nonce_key, out_replayed).answers(out_refund_return, status, out_key, out_counts));
 }
 extern "C" int act_redeem_cbor_return_replay_batch(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys, int nkeys,
                                                    const uint32_t* key_epochs, int sign_key, const uint8_t* cbor, const uint64_t* offsets, const uint8_t* charge,
                                                    const uint8_t* returned, const uint8_t nonce_key[32], uint8_t* out_refund_return_cbor, uint8_t* status,
                                                    uint8_t* out_key, uint8_t* out_replayed, uint64_t* out_counts) {
-  if (n && !cbor) { if (out_counts) memset(out_counts, 0, sizeof(uint64_t) * ACT_RETURN_REPLAY_COUNTS); return ACT_ERR_ARG; }
-  static const uint8_t none = 0;
-  const RedeemReturn ret{returned};
-  return redeem_admit_replay_impl(c, set, receipts, n, mem, keys, nkeys, key_epochs, sign_key, nullptr, cbor ? cbor : &none, offsets, charge, nonce_key,
-                                  out_refund_return_cbor, status, out_key, out_replayed, out_counts, false, &ret);
+  return redeem_admit(AdmitCall(c, set, n, mem).ring(keys, nkeys, key_epochs, sign_key).messages(cbor, offsets).charged(charge).returns(returned)
+                          .replays(receipts, nonce_key, out_replayed).answers(out_refund_return_cbor, status, out_key, out_counts));
 }
 
 // The unique forms of the two calls above: the copy stage of the admit-replay unique forms behind this screen, equality decided on the
@@ -240,18 +211,13 @@ extern "C" int act_redeem_return_replay_unique_batch(act_ctx* c, act_nullifier_s
                                                      const uint32_t* key_epochs, int sign_key, const uint8_t* proof, const uint8_t* charge, const uint8_t* returned,
                                                      const uint8_t nonce_key[32], uint8_t* out_refund_return, uint8_t* status, uint8_t* out_key, uint8_t* out_replayed,
                                                      uint64_t* out_counts) {
-  if (n && !proof) { if (out_counts) memset(out_counts, 0, sizeof(uint64_t) * ACT_RETURN_REPLAY_UNIQUE_COUNTS); return ACT_ERR_ARG; }
-  const RedeemReturn ret{returned};
-  return redeem_admit_replay_impl(c, set, receipts, n, mem, keys, nkeys, key_epochs, sign_key, proof, nullptr, nullptr, charge, nonce_key, out_refund_return, status,
-                                  out_key, out_replayed, out_counts, true, &ret);
+  return redeem_admit(AdmitCall(c, set, n, mem).ring(keys, nkeys, key_epochs, sign_key).records(proof).charged(charge).returns(returned)
+                          .replays(receipts, nonce_key, out_replayed).uniquely().answers(out_refund_return, status, out_key, out_counts));
 }
 extern "C" int act_redeem_cbor_return_replay_unique_batch(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys,
                                                           int nkeys, const uint32_t* key_epochs, int sign_key, const uint8_t* cbor, const uint64_t* offsets,
                                                           const uint8_t* charge, const uint8_t* returned, const uint8_t nonce_key[32], uint8_t* out_refund_return_cbor,
                                                           uint8_t* status, uint8_t* out_key, uint8_t* out_replayed, uint64_t* out_counts) {
-  if (n && !cbor) { if (out_counts) memset(out_counts, 0, sizeof(uint64_t) * ACT_RETURN_REPLAY_UNIQUE_COUNTS); return ACT_ERR_ARG; }
-  static const uint8_t none = 0;
-  const RedeemReturn ret{returned};
-  return redeem_admit_replay_impl(c, set, receipts, n, mem, keys, nkeys, key_epochs, sign_key, nullptr, cbor ? cbor : &none, offsets, charge, nonce_key,
-                                  out_refund_return_cbor, status, out_key, out_replayed, out_counts, true, &ret);
+  return redeem_admit(AdmitCall(c, set, n, mem).ring(keys, nkeys, key_epochs, sign_key).messages(cbor, offsets).charged(charge).returns(returned)
+                          .replays(receipts, nonce_key, out_replayed).uniquely().answers(out_refund_return_cbor, status, out_key, out_counts));
 }

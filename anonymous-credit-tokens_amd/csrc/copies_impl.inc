@@ -6,7 +6,7 @@
 //   c. compare       copy_of[j] = leader[j] iff every byte is equal: k_copy_equal, or the host workers (4 bytes per lane come down)
 //   d. mark          pre2 = pre with COPY_MARK on the copies, lead[lane] = a copy's leader lane       k_copy_mark
 //   e. compaction    launch_admit_compact over pre2: the lanes that are verified, in lane order
-// The caller goes on with idx2 / pos2 / pre2 in place of the screen's arrays and launches k_copy_resolve behind the scatter -- or, in
+// The caller goes on with v (idx2 / pos2 / pre2 where there are copies, else the screen's arrays as passed) and launches k_copy_resolve behind the scatter -- or, in
 // the replay unique forms (act_redeem_(cbor_)admit_replay_unique_batch), k_copy_serve behind both scatters: a copy gets its leader's refund.
 // Everything staged here is public (proof bytes never leave the caller's memory; fingerprints and lane numbers are derived from them).
 namespace {
@@ -15,8 +15,8 @@ struct CopyHostJob { CopySpan span; const uint32_t* idx; const uint32_t* leader;
 
 }  // namespace
 
-int AdmitCopies::run(hipStream_t stream, bool dev, size_t n, size_t m, const CopySpan& span, const uint8_t* d_pre, const uint32_t* d_idx,
-                     const uint32_t* h_idx, const uint32_t salt[4]) {
+int AdmitCopies::run(hipStream_t stream, bool dev, size_t n, const CopySpan& span, const uint32_t* h_idx, const uint32_t salt[4]) {
+  const uint8_t* const d_pre = v.pre; const uint32_t* const d_idx = v.idx; const size_t m = v.m;      // the screen's survivors, as passed
   copies = 0; m2 = m;
   if (m < 2) return ACT_OK;                                   // nothing to be a copy of
   uint32_t cap = 4; while (cap < 2 * m) cap <<= 1;
@@ -90,6 +90,7 @@ int AdmitCopies::run(hipStream_t stream, bool dev, size_t n, size_t m, const Cop
   ADCK(c, hipStreamSynchronize(stream));
   if (m32 == 0 || m32 > m) { c->err = "admission: the copy stage counted survivors it cannot have"; return ACT_ERR_HIP; }      // (a leader always survives)
   m2 = m32; copies = m - m2;
+  if (copies) v = {d_pre2, d_idx2, d_pos2, m2};      // the lanes that are verified: the second compaction's
   return ACT_OK;
 }
 
