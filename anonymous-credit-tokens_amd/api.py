@@ -331,6 +331,19 @@ class PrivateKey(_Cbor):
         res, _, replayed = Keyring([self]).redeem_return_replay_unique_cbor_batch(params, db, receipts, msgs, nonce_key, nbits, returned=returned, charges=charges)
         return res, replayed
 
+    # ---- reserve and settle: record a spend now, sign its partial refund later -----------------------------------
+    def reserve_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", proofs: Sequence["SpendProof"], charges: Sequence = None) -> Tuple[list, list]:
+        """Keyring.reserve_batch with this key alone.  -> (results: a Reservation or an Error per proof, replayed flags)"""
+        return Keyring([self]).reserve_batch(params, db, receipts, proofs, charges=charges)
+
+    def reserve_cbor_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", msgs: Sequence[bytes], nbits: int = L, charges: Sequence = None) -> Tuple[list, list]:
+        return Keyring([self]).reserve_cbor_batch(params, db, receipts, msgs, nbits, charges=charges)
+
+    def settle_batch(self, params: Params, receipts: "NullifierDb", reservations: Sequence["Reservation"], returned: Sequence, nonce_key: bytes, nbits: int = L,
+                     cbor: bool = False) -> Tuple[list, list]:
+        """Keyring.settle_batch with this key alone.  -> (results, settled-before flags)"""
+        return Keyring([self]).settle_batch(params, receipts, reservations, returned, nonce_key, nbits=nbits, cbor=cbor)
+
     def verify_spend_batch(self, params: Params, proofs: Sequence["SpendProof"]) -> bytes:
         nbits = proofs[0].nbits if proofs else L
         return params.engine(nbits).verify_spend(self.record, b"".join(p.record for p in proofs))
@@ -553,6 +566,50 @@ class Keyring:
         return [out[i] if st[i] == 0 else _wire_error(st[i]) for i in range(len(msgs))], self._indices(st, ok), [bool(r) for r in rep]
 
 
+    # ---- reserve and settle (include/act_mi355x.h "reserve and settle") -------------------------------------------
+    def _reservations(self, st, out, ok, rep):
+        res = [Reservation(out[96 * i:96 * i + 96], ok[i]) if st[i] == 0 else Error(st[i]) for i in range(len(st))]
+        return res, [bool(r) for r in rep]
+
+    def reserve_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", proofs: Sequence["SpendProof"], charges: Sequence = None) -> Tuple[list, list]:
+        """The first half of the metered-service step (act_redeem_reserve_batch): redeem_replay_batch(..., admit=True) WITHOUT the
+        signature.  Every proof is screened (`charges`, optional: Error 250 where s differs; a spent nullifier that is not this proof's
+        own reservation: DoubleSpendError, unverified), verified and RECORDED as spent, and entry i is a Reservation -- what the service
+        keeps beside the job until it knows what the work cost.  No nonce_key, no generator: nothing is signed.  A proof that is sent
+        again gets the same Reservation and replayed[i] = True: the job for it exists already -- never start a second one.
+        -> (results, replayed flags); `self.last_reserve_counts`: the call's counts (capi.RESERVE_COUNTS)."""
+        nbits = proofs[0].nbits if proofs else L
+        cc = b"".join(scalar(c) for c in charges) if charges is not None else None
+        st, out, ok, rep, self.last_reserve_counts = params.engine(nbits).redeem_reserve(db.set, receipts.set, self._records(), b"".join(p.record for p in proofs),
+                                                                                        key_epochs=self.epochs, charges=cc)
+        return self._reservations(st, out, ok, rep)
+
+    def reserve_cbor_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", msgs: Sequence[bytes], nbits: int = L, charges: Sequence = None) -> Tuple[list, list]:
+        """the same on CBOR SpendProof messages (act_redeem_cbor_reserve_batch): a retry may be another spelling of the same proof.  Entry i
+        is a Reservation, a CborError or an Error -- the reservation has no wire type, it never goes to a client"""
+        cc = b"".join(scalar(c) for c in charges) if charges is not None else None
+        st, out, ok, rep, self.last_reserve_counts = params.engine(nbits).redeem_cbor_reserve(db.set, receipts.set, self._records(), list(msgs), key_epochs=self.epochs, charges=cc)
+        res, replayed = self._reservations(st, out, ok, rep)
+        return [r if st[i] == 0 else _wire_error(st[i]) for i, r in enumerate(res)], replayed
+
+    def settle_batch(self, params: Params, receipts: "NullifierDb", reservations: Sequence["Reservation"], returned: Sequence, nonce_key: bytes, nbits: int = L,
+                     sign_with=None, cbor: bool = False) -> Tuple[list, list]:
+        """The second half (act_redeem_settle_batch): the work behind reservations[i] cost s_i - returned[i].  The reservation is looked
+        up in `receipts` (Error 248: not reserved -- altered, recorded by a one-phase call, or its epoch retired), the amount is bound
+        (returned[i] > s_i: Error 249) and PINNED, and entry i is the RefundReturn over returned[i], signed with nonces derived from
+        `nonce_key`.  Settling a reservation again with the same amount gives the same bytes (settled_before[i] = True); with another
+        amount Error 247.  After settlement a client that resends its SpendProof is served by redeem_replay_batch(..., returned=).
+        returned=None: every amount is 0.  cbor=True (act_redeem_cbor_settle_batch): entry i is a CBOR RefundReturn message.
+        -> (results, settled-before flags); `self.last_settle_counts`: the call's counts (capi.SETTLE_COUNTS)."""
+        tt = b"".join(scalar(t) for t in returned) if returned is not None else None
+        st, out, before, self.last_settle_counts = params.engine(nbits).redeem_settle(
+            receipts.set, self._records(), b"".join(r.record for r in reservations), bytes(r.key for r in reservations), nonce_key, tt, self._sign_key(sign_with),
+            key_epochs=self.epochs, cbor=cbor)
+        n = len(reservations)
+        res = [(out[i] if cbor else RefundReturn(out[160 * i:160 * i + 160])) if st[i] == 0 else Error(st[i]) for i in range(n)]
+        return res, [bool(b) for b in before]
+
+
 class PreIssuance(_Cbor):
     CBOR_TYPE = "PreIssuance"
 
@@ -700,6 +757,34 @@ class RefundReturn(_Cbor):
 
     def __eq__(self, other):
         return self.record == other.record
+
+
+class Reservation:
+    """What reserve hands back for an accepted proof and the service keeps until it settles (include/act_mi355x.h "reserve and settle"):
+    the 96 public bytes k^ | enc(K') | s^ and the ring index the proof matched.  It has no CBOR type: it never goes to a client.
+    to_bytes / from_bytes: 97 bytes for the service's own storage, beside the job -- and, once known, the amount."""
+
+    def __init__(self, record: bytes, key: int):
+        assert len(record) == 96 and 0 <= key < 256
+        self.record, self.key = bytes(record), int(key)
+
+    def nullifier(self) -> bytes:
+        return self.record[:32]
+
+    def charge(self) -> int:
+        return int.from_bytes(self.record[64:96], "little")
+
+    def to_bytes(self) -> bytes:
+        return self.record + bytes([self.key])
+
+    @classmethod
+    def from_bytes(cls, data: bytes) -> "Reservation":
+        if len(data) != 97:
+            raise ValueError("a stored reservation is 97 bytes")
+        return cls(data[:96], data[96])
+
+    def __eq__(self, other):
+        return (self.record, self.key) == (other.record, other.key)
 
 
 class NullifierDb:

@@ -30,6 +30,11 @@ ADMIT_REPLAY_UNIQUE_COUNTS = ADMIT_REPLAY_COUNTS + ("copies", "copies_served")  
 RETURN_REPLAY_COUNTS = ADMIT_REPLAY_COUNTS + ("return_too_big",)      # act_redeem_*return_replay_batch
 # act_redeem_*return_replay_unique_batch: copies, those answered 0, and those that name another amount than their leader
 RETURN_REPLAY_UNIQUE_COUNTS = RETURN_REPLAY_COUNTS + ("copies", "copies_served", "copies_other_amount")
+# reserve and settle (act_redeem_*reserve_batch / act_redeem_*settle_batch): record a spend now, sign its partial refund later
+STATUS_NOT_RESERVED, STATUS_SETTLED_OTHER_AMOUNT = 248, 247
+RESERVATION_BYTES = 96                                # k^ | enc(K') | s^
+RESERVE_COUNTS = ADMIT_REPLAY_COUNTS
+SETTLE_COUNTS = ("lanes", "not_reserved", "return_too_big", "settled", "settled_again", "other_amount", "unanswered")
 _ERRS = {1: "ACT_ERR_ARG", 2: "ACT_ERR_HIP", 3: "ACT_ERR_PARAMS", 4: "ACT_ERR_NO_DEVICE", 5: "ACT_ERR_RNG"}
 
 EXPORTS = [
@@ -69,6 +74,7 @@ EXPORTS = [
     "act_refund_to_credit_token_return_keyring_batch", "act_redeem_return_unique_batch", "act_redeem_cbor_return_unique_batch",
     "act_redeem_return_replay_batch", "act_redeem_cbor_return_replay_batch", "act_replay_derive_return_batch",
     "act_redeem_return_replay_unique_batch", "act_redeem_cbor_return_replay_unique_batch",
+    "act_redeem_reserve_batch", "act_redeem_cbor_reserve_batch", "act_redeem_settle_batch", "act_redeem_cbor_settle_batch",
     "act_ctx_host_hash_stats", "act_ctx_set_tiny_calls", "act_node_set_balance", "act_node_device_stats", "act_node_balance_state", "act_debug_set_slowdown", "act_debug_fail_next_signs",
 ]
 CBOR_TYPES = {"IssuanceRequest": 1, "IssuanceResponse": 2, "SpendProof": 3, "Refund": 4, "PrivateKey": 5, "PublicKey": 6,
@@ -283,6 +289,12 @@ def load() -> C.CDLL:
     # their unique forms: a copy is served only if it names its leader's amount (out_counts: ACT_RETURN_REPLAY_UNIQUE_COUNTS values)
     lib.act_redeem_return_replay_unique_batch.argtypes = lib.act_redeem_return_replay_batch.argtypes
     lib.act_redeem_cbor_return_replay_unique_batch.argtypes = lib.act_redeem_cbor_return_replay_batch.argtypes
+    # reserve and settle: the admit-replay call without sign_key / nonce_key, 96-byte reservation records out (ACT_RESERVE_COUNTS values);
+    # reservation records, key indices and amounts in, RefundReturn records or messages out (ACT_SETTLE_COUNTS values)
+    lib.act_redeem_reserve_batch.argtypes = [vp, vp, vp, sz, i32, u8p, i32, u32p, u8p, u8p, u8p, u8p, u8p, u8p, u64p]
+    lib.act_redeem_cbor_reserve_batch.argtypes = [vp, vp, vp, sz, i32, u8p, i32, u32p, u8p, vp, u8p, u8p, u8p, u8p, u8p, u64p]
+    lib.act_redeem_settle_batch.argtypes = [vp, vp, sz, i32, u8p, i32, u32p, i32, u8p, u8p, u8p, u8p, u8p, u8p, u8p, u64p]
+    lib.act_redeem_cbor_settle_batch.argtypes = lib.act_redeem_settle_batch.argtypes
     lib.act_replay_derive_return_batch.argtypes = [vp, sz, i32, u8p, i32, u8p, u8p, u8p, sz, u8p, u8p, u8p, u8p, u8p]
     lib.act_issue_check_cbor_batch.argtypes = [vp, sz, i32, u8p, vp, u8p, u8p]
     lib.act_issue_sign_cbor_batch.argtypes = [vp, sz, i32, u8p, u8p, u8p, u8p, u8p, i32, u8p, u8p]
@@ -1050,6 +1062,83 @@ class Engine:
         else:
             self._ck(self.lib.act_replay_derive_return_batch(self.ctx, n, mem, pk, len(keys), p_key_index, pn, p_nullifiers, stride, p_kprime, p_status_in, p_returned or None,
                                                              p_tags or None, p_nonces or None))
+
+    # ---- reserve and settle (act_redeem_reserve_batch / act_redeem_cbor_reserve_batch / act_redeem_settle_batch / act_redeem_cbor_settle_batch)
+    def reserve_ptr(self, fn: str, keys, n: int, mem: int, **p):
+        """the reserve calls on raw pointers of either kind: fn = redeem / redeem_cbor; p: set, receipts, proofs | cbor (+ offsets), charges,
+        out (96 bytes a lane), status, out_key, replayed, key_epochs, raw.  -> counts dict, or (rc, counts) with raw"""
+        wire = fn != "redeem"; nk = len(keys); pk, kk = _in(b"".join(keys))
+        ke = _epoch_table(p["key_epochs"], nk) if p.get("key_epochs") is not None else None
+        cnt = (C.c_uint64 * len(RESERVE_COUNTS))()
+        args = [self.ctx, p["set"].h, p["receipts"].h if p["receipts"] is not None else None, n, mem, pk, nk, ke.ctypes.data if ke is not None else None]
+        args += [p["cbor"], p.get("offsets") or None] if wire else [p["proofs"]]
+        args += [p.get("charges") or None, p["out"], p["status"], p["out_key"], p.get("replayed") or None, cnt]
+        rc = (self.lib.act_redeem_cbor_reserve_batch if wire else self.lib.act_redeem_reserve_batch)(*args)
+        counts = dict(zip(RESERVE_COUNTS, (int(v) for v in cnt)))
+        if p.get("raw"):
+            return rc, counts
+        self._ck(rc)
+        return counts
+
+    def _reserve_host(self, nullifier_set, receipts, keys, rows, key_epochs, charges, raw: bool):
+        wire = isinstance(rows, (list, tuple))
+        if wire:
+            n = len(rows); p0, k0, offs = _msgs(rows); p = dict(cbor=p0, offsets=offs.ctypes.data)
+        else:
+            n = len(rows) // self.proof_bytes; p0, k0 = _in(rows, self.proof_bytes * n); p = dict(proofs=p0)
+        out = np.full(RESERVATION_BYTES * n, 7 if raw else 0, np.uint8); st = np.full(n, 99 if raw else 0, np.uint8); ok = np.zeros(n, np.uint8); rp = np.zeros(n, np.uint8)
+        pc, kc = _in(charges, 32 * n) if charges is not None else (None, None)
+        rc, counts = self.reserve_ptr("redeem_cbor" if wire else "redeem", keys, n, MEM_HOST, set=nullifier_set, receipts=receipts, key_epochs=key_epochs, charges=pc,
+                                      out=out.ctypes.data, status=st.ctypes.data, out_key=ok.ctypes.data, replayed=rp.ctypes.data, raw=True, **p)
+        res = (st.tobytes(), out.tobytes(), ok.tobytes(), rp.tobytes(), counts)
+        if raw:
+            return (rc,) + res
+        self._ck(rc)
+        return res
+
+    def redeem_reserve(self, nullifier_set, receipts, keys, proofs: bytes, key_epochs=None, charges: bytes = None, raw: bool = False):
+        """redeem_admit_replay WITHOUT the signature: screen, verify, record k and a reservation tag.  -> (statuses, 96-byte reservation
+        records k^ | enc(K') | s^ (zero where rejected), out_key, replayed, counts dict); raw=True: (rc, ...), no exception"""
+        return self._reserve_host(nullifier_set, receipts, keys, proofs, key_epochs, charges, raw)
+
+    def redeem_cbor_reserve(self, nullifier_set, receipts, keys, messages: list, key_epochs=None, charges: bytes = None, raw: bool = False):
+        """SpendProof messages in -> what redeem_reserve returns (the reservation record has no wire type)"""
+        return self._reserve_host(nullifier_set, receipts, keys, list(messages), key_epochs, charges, raw)
+
+    def settle_ptr(self, keys, n: int, mem: int, **p):
+        """the settle calls on raw pointers of either kind; p: receipts, reservations (96 bytes a lane), key_index, amounts (0: all zero),
+        nonce_key, out, status, settled_before, key_epochs, sign_key, cbor (the wire form), raw.  -> counts dict, or (rc, counts) with raw"""
+        nk = len(keys); pk, kk = _in(b"".join(keys))
+        ke = _epoch_table(p["key_epochs"], nk) if p.get("key_epochs") is not None else None
+        pn, kn = _in(p["nonce_key"], 32) if p.get("nonce_key") is not None else (None, None)
+        cnt = (C.c_uint64 * len(SETTLE_COUNTS))()
+        fn = self.lib.act_redeem_cbor_settle_batch if p.get("cbor") else self.lib.act_redeem_settle_batch
+        rc = fn(self.ctx, p["receipts"].h if p["receipts"] is not None else None, n, mem, pk, nk, ke.ctypes.data if ke is not None else None, p.get("sign_key", SIGN_MATCHED),
+                p["reservations"], p["key_index"], p.get("amounts") or None, pn, p["out"], p["status"], p.get("settled_before") or None, cnt)
+        counts = dict(zip(SETTLE_COUNTS, (int(v) for v in cnt)))
+        if p.get("raw"):
+            return rc, counts
+        self._ck(rc)
+        return counts
+
+    def redeem_settle(self, receipts, keys, reservations: bytes, key_index: bytes, nonce_key: bytes, amounts: bytes = None, sign_key: int = SIGN_MATCHED, key_epochs=None,
+                      cbor: bool = False, raw: bool = False):
+        """reservation records and amounts t <= s in, RefundReturn out: the reservation is looked up, the amount pinned, the refund signed
+        with derived nonces -- the same reservation with the same amount again gives the same bytes.  -> (statuses, 160-byte records |
+        (cbor=True) list of RefundReturn messages (b"" where not signed), settled_before, counts dict); raw=True: (rc, ...), no exception"""
+        n = len(key_index); ob = self.cbor_size("RefundReturn") if cbor else 160
+        out = np.full(ob * n, 7 if raw and not cbor else 0, np.uint8); st = np.full(n, 99 if raw else 0, np.uint8); sb = np.zeros(n, np.uint8)
+        p0, k0 = _in(reservations, RESERVATION_BYTES * n); p1, k1 = _in(key_index, n)
+        pt, kt = _in(amounts, 32 * n) if amounts is not None else (None, None)
+        rc, counts = self.settle_ptr(keys, n, MEM_HOST, receipts=receipts, reservations=p0, key_index=p1, amounts=pt, nonce_key=nonce_key, out=out.ctypes.data,
+                                     status=st.ctypes.data, settled_before=sb.ctypes.data, key_epochs=key_epochs, sign_key=sign_key, cbor=cbor, raw=True)
+        b = out.tobytes()
+        res = (st.tobytes(), [b[i * ob:(i + 1) * ob] if st[i] == 0 else b"" for i in range(n)] if cbor else b, sb.tobytes(), counts)
+        if raw:
+            return (rc,) + res
+        self._ck(rc)
+        assert not cbor or all(st[i] == 0 or not out[i * ob:(i + 1) * ob].any() for i in range(n)), "a failed lane's slot is not zero"
+        return res
 
     def copy_leaders(self, fps):
         """act_debug_copy_leaders: the leader table of the unique admission forms over made-up fingerprints -> (leaders, milliseconds)"""

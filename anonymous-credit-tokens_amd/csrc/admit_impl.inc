@@ -4,7 +4,8 @@
 // is verified, and only the lanes that pass go through verification -> check-and-insert -> sign.
 // Every entry point of the family fills one AdmitCall -- the ring, the input, the prices, the rng or the replay part, the outputs and the
 // form (unique: the copy stage, copies_impl.inc [k_copies.hip]; replay: receipts and the replay tail, admit_replay_impl.inc, DESIGN 4.9;
-// ret: returned amounts and RefundReturn outputs, DESIGN 4.10) -- and calls redeem_admit, which runs the stages of AdmitState in order:
+// ret: returned amounts and RefundReturn outputs, DESIGN 4.10; reserve: the replay form without its signature half and with 96-byte
+// reservation records out, reserve_impl.inc, DESIGN 4.11) -- and calls redeem_admit, which runs the stages of AdmitState in order:
 //   refusals         admit_refused: everything refused as a whole, before anything is looked at; n == 0 is the empty ring call
 //   locate_ks        k and s of every lane (records: fields 0 and 1; wire, wire_ks: the payloads of a canonical message, and of any other
 //                    spelling what the wire reader's reduced form gives -- cbor_lanes.h with keep_fields = 2, as a kernel for
@@ -181,6 +182,12 @@ struct AdmitCall {
     static const uint8_t derived = 0;      // the nonces stand where the admission calls' rng stands
     form.replay = true; receipts = rs; nonce_key = key; out_replayed = marks; return draws(&derived, ACT_RNG_PER_LANE);
   }
+  // act_redeem_(cbor_)reserve_batch (DESIGN 4.11): the replay form without its signature half -- no sign_key, no nonce_key, 96-byte records out
+  bool reserve = false;
+  AdmitCall& reserves(act_nullifier_set* rs, uint8_t* marks) {
+    static const uint8_t unsigned_key[32] = {0};      // where replay_refused wants a nonce_key: never staged, never hashed
+    reserve = true; return replays(rs, unsigned_key, marks);
+  }
   AdmitCall& uniquely() { form.unique = true; return *this; }
   AdmitCall& answers(uint8_t* o, uint8_t* st, uint8_t* key, uint64_t* counts) { out = o; status = st; out_key = key; out_counts = counts; return *this; }
 
@@ -197,19 +204,28 @@ struct AdmitReplayStage {
   hipStream_t stream; size_t n; bool dev, wire, dev_reader; const uint8_t* proof; const uint8_t* cbor; const WireExtent* ext; bool offsets;
   uint8_t* d_pre; const uint8_t* d_kred; uint32_t *d_blk, *d_idx, *d_pos, *d_total;
   const uint8_t* d_t;                 // the return form: the n returned amounts in device memory, as the screen read them (null: every t = 0)
+  bool reserve;                       // the reserve form: d_t holds the n reduced charges s^ and the tag is tag_res (reserve_lanes.h)
 };
 
 }  // namespace
+
+// the reserve form of the replay tail (reserve_impl.inc): the charges lane for lane with the tail's arrays, in the call's kind of memory
+struct ReplayReserve { const uint8_t* s; };
+static void reserve_tags_host(const ReplayDeriveArgs& a);
+static int reserve_emit(act_ctx* c, hipStream_t stream, size_t n, int mem, const uint8_t* k_at, size_t k_stride, const uint8_t* kp, const uint8_t* s, const uint8_t* st,
+                        uint8_t* out, uint8_t* status);
 
 // candidates: the spent lanes whose tag the receipts hold -- verified like fresh lanes
 static int admit_replay_stage(act_ctx* c, act_nullifier_set* receipts, const AdmitReplayStage& g, size_t* candidates);
 static int replay_refused(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, const uint8_t* nonce_key, size_t n, const uint32_t* key_epochs, int nkeys);
 static int replay_tail(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys, int nkeys, const uint32_t* key_epochs,
                        int sign_key, bool wire, const uint8_t* k_at, size_t k_stride, const uint8_t* kp, uint8_t* st, const uint8_t* nonce_key, uint8_t* out,
-                       uint8_t* status, uint8_t* out_key, uint8_t* out_replayed, uint64_t* out_counts, bool* began = nullptr, const RedeemReturn* ret = nullptr);
+                       uint8_t* status, uint8_t* out_key, uint8_t* out_replayed, uint64_t* out_counts, bool* began = nullptr, const RedeemReturn* ret = nullptr,
+                       const ReplayReserve* res = nullptr);
 static int redeem_replay_locked(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys, int nkeys,
                                 const uint32_t* key_epochs, int sign_key, const uint8_t* proof, const uint8_t* cbor, const uint64_t* offsets, const uint8_t* nonce_key,
-                                uint8_t* out, uint8_t* status, uint8_t* out_key, uint8_t* out_replayed, uint64_t* out_counts, const RedeemReturn* ret = nullptr);
+                                uint8_t* out, uint8_t* status, uint8_t* out_key, uint8_t* out_replayed, uint64_t* out_counts, const RedeemReturn* ret = nullptr,
+                                const ReplayReserve* res = nullptr);
 
 namespace {
 
@@ -233,12 +249,13 @@ struct AdmitState {
   uint8_t *kp = nullptr, *knul = nullptr, *st = nullptr, *sp = nullptr, *kidx = nullptr, *okey = nullptr, *cst = nullptr, *crepl = nullptr;
   AdmitRngDev rng_dev; std::vector<uint8_t> rng_host; AdmitHostWipe rng_wipe{rng_host};      // the verified lanes' rng slices (secret): wiped on every exit
   const uint8_t* c_rng; RedeemReturn cret{nullptr};
+  uint8_t* d_sred = nullptr; std::vector<uint8_t> h_sred; ReplayReserve cres{nullptr};      // the reserve form: every lane's s^ (device; host copy), the verified lanes'
   uint64_t tc[ACT_REPLAY_COUNTS] = {0, 0, 0, 0, 0, 0};      // replay: the tail's counts
   std::vector<uint8_t> h_cst, h_fin, h_t;  // device-memory callers, for the counts: compact statuses; the replay unique forms' final statuses and amounts
 
   explicit AdmitState(const AdmitCall& a_)
       : a(a_), c(a_.c), n(a_.n), wire(a_.wire()), dev(a_.dev()), rp(a_.replay()), ret(a_.ret()), stream(a_.set->stream), pb(act_spend_proof_bytes(a_.c)),
-        out_b(redeem_out_bytes(a_.c, a_.wire(), a_.ret())), T(cbor_type(ACT_CBOR_SPEND_PROOF)), lay(a_.wire() ? cbor_layout(*T, a_.c->L) : CborLayout()),
+        out_b(a_.reserve ? (size_t)RESERVATION_BYTES : redeem_out_bytes(a_.c, a_.wire(), a_.ret())), T(cbor_type(ACT_CBOR_SPEND_PROOF)), lay(a_.wire() ? cbor_layout(*T, a_.c->L) : CborLayout()),
         ml(lay.tmpl.size()), nf(lay.pay_off.size()), ext{a_.cbor, a_.offsets, ml}, dev_reader(a_.wire() && a_.c->wire_reader.load() == ACT_WIRE_READER_DEVICE),
         d(a_.c), cp(a_.c), arr(a_.c), cout(a_.c), rng_dev(a_.c), c_rng(a_.rng) {}
 
@@ -257,9 +274,10 @@ struct AdmitState {
     o_tmpl = (wire && dev) ? take(ml) : 0; o_pay = (wire && dev) ? take(nf * 4) : 0;
     o_pwhich = wire ? take(WIRE_SETTLE_WINDOW * 4) : 0; o_patch = wire ? take(WIRE_SETTLE_WINDOW * 64) : 0;
     o_rcode = (dev_reader && dev) ? take(2 * n) : 0;      // the device reader's codes, then its infos
+    const size_t o_sred = a.reserve ? take(n * 32) : 0;
     if (int rc = d.alloc(need)) return rc;
     ADCK(c, hipSetDevice(c->device));
-    d_pre = d.p + o_pre; d_kred = d.p + o_kred; d_ks = d.p + o_ks;
+    d_pre = d.p + o_pre; d_kred = d.p + o_kred; d_ks = d.p + o_ks; d_sred = a.reserve ? d.p + o_sred : nullptr;
     d_idx = reinterpret_cast<uint32_t*>(d.p + o_idx); d_pos = reinterpret_cast<uint32_t*>(d.p + o_pos);
     d_blk = reinterpret_cast<uint32_t*>(d.p + o_blk); d_total = reinterpret_cast<uint32_t*>(d.p + o_total);
     return ACT_OK;
@@ -387,11 +405,12 @@ struct AdmitState {
     std::unique_lock<std::mutex> lk(a.set->mu);
     sa.tab_keys = a.set->tab_keys; sa.tab_state = a.set->tab_state; sa.tab_cap = a.set->tab_cap; memcpy(sa.salt.w, a.set->salt, 16);
     launch_admit_screen(sa, stream);
+    if (a.reserve) { ReserveSredArgs ra{(uint32_t)n, sa.stride, sa.ks, d_sred}; launch_reserve_sred(ra, stream); }      // s^ beside k^, for the tags and the records
     if (rp) {      // the spent lanes: retry candidates go on, the others stay double spends; the compaction is over what that leaves
       ADCK(c, hipGetLastError());
       ADCK(c, hipStreamSynchronize(stream));
       lk.unlock();
-      const AdmitReplayStage g{stream, n, dev, wire, dev_reader, a.proof, a.cbor, &ext, a.offsets != nullptr, d_pre, d_kred, d_blk, d_idx, d_pos, d_total, sa.returned};
+      const AdmitReplayStage g{stream, n, dev, wire, dev_reader, a.proof, a.cbor, &ext, a.offsets != nullptr, d_pre, d_kred, d_blk, d_idx, d_pos, d_total, a.reserve ? d_sred : sa.returned, a.reserve};
       if (int rc = admit_replay_stage(c, a.receipts, g, &candidates)) return rc;
     }
     launch_admit_compact(d_pre, (uint32_t)n, d_blk, d_idx, d_pos, d_total, stream);
@@ -421,8 +440,12 @@ struct AdmitState {
   // ---- nothing shed: the honest batch pays the screen and nothing else; replay: the replay call itself ---------------------------------------------
   int nothing_shed() {
     if (rp) {
+      if (a.reserve) {      // every lane's s^ in the caller's kind of memory, lane for lane
+        cres.s = d_sred;
+        if (!dev) { h_sred.resize(n * 32); ADCK(c, hipMemcpy(h_sred.data(), d_sred, n * 32, hipMemcpyDeviceToHost)); cres.s = h_sred.data(); }
+      }
       const int rc = redeem_replay_locked(c, a.set, a.receipts, n, a.mem, a.keys, a.nkeys, a.key_epochs, a.sign_key, a.proof, a.cbor, a.offsets, a.nonce_key, a.out, a.status,
-                                          a.out_key, a.out_replayed, a.out_counts ? tc : nullptr, ret);      // (the caller's `returned`, lane for lane)
+                                          a.out_key, a.out_replayed, a.out_counts ? tc : nullptr, ret, a.reserve ? &cres : nullptr);      // (the caller's `returned`, lane for lane)
       counts(nullptr, tc);      // (tc[0] == 0: the call ended before its tail, and the counts stay zero)
       return rc;
     }
@@ -469,7 +492,7 @@ struct AdmitState {
     ADCK(c, hipMemcpy(h_vidx.data(), cp.v.idx, mv * 4, hipMemcpyDeviceToHost));
     if (!dev) { h_pos.resize(n); ADCK(c, hipMemcpy(h_pos.data(), cp.v.pos, n * 4, hipMemcpyDeviceToHost)); }
     const size_t arr_lane = rp ? 70 : 69;
-    if ((rc = arr.alloc(a.mem, mv * arr_lane + (a.returned ? mv * 32 + 32 : 0)))) { c->err = "admission: compact arrays"; return rc; }
+    if ((rc = arr.alloc(a.mem, mv * arr_lane + ((a.returned || a.reserve) ? mv * 32 + 32 : 0)))) { c->err = "admission: compact arrays"; return rc; }
     if ((rc = cout.alloc(a.mem, mv * out_b))) { c->err = "admission: compact output"; return rc; }
     kp = arr.p; knul = kp + mv * 32; st = knul + mv * 32; sp = st + mv; kidx = sp + mv; okey = kidx + mv; cst = okey + mv;
     crepl = cst + mv;      // (the replay form: the verified lanes' replay marks)
@@ -489,6 +512,11 @@ struct AdmitState {
       uint8_t* ct = arr.p + ((mv * arr_lane + 31) & ~(size_t)31);
       if ((rc = gather_verified(ct, a.returned, dev, 32))) return rc;
       cret.t = ct;
+    }
+    if (a.reserve) {      // the reserve form: the verified lanes' s^ in the same place (it takes no amounts)
+      uint8_t* cs = arr.p + ((mv * arr_lane + 31) & ~(size_t)31);
+      if ((rc = gather_verified(cs, d_sred, true, 32))) return rc;
+      cres.s = cs;
     }
     return ACT_OK;
   }
@@ -517,7 +545,7 @@ struct AdmitState {
       return redeem_tail_ring(c, a.set, mv(), a.mem, a.keys, a.nkeys, a.key_epochs, a.sign_key, wire, knul, 32, kp, st, sp, kidx, c_rng, a.rng_mode, cout.p, cst, okey, t);
     }
     bool began = false;
-    const int rc = replay_tail(c, a.set, a.receipts, mv(), a.mem, a.keys, a.nkeys, a.key_epochs, a.sign_key, wire, knul, 32, kp, st, a.nonce_key, cout.p, cst, okey, crepl, tc, &began, t);
+    const int rc = replay_tail(c, a.set, a.receipts, mv(), a.mem, a.keys, a.nkeys, a.key_epochs, a.sign_key, wire, knul, 32, kp, st, a.nonce_key, cout.p, cst, okey, crepl, tc, &began, t, a.reserve ? &cres : nullptr);
     *answer = !rc || began;      // staging its buffers failed: as a failed verification -- nothing recorded, status untouched
     return rc;
   }

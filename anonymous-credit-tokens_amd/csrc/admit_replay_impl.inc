@@ -129,7 +129,8 @@ static int admit_replay_stage(act_ctx* c, act_nullifier_set* receipts, const Adm
     ka.s.P.L = L; ka.s.proofs = d_rec.p; ka.s.n = (uint32_t)w; ka.s.coords = d_coords; ka.s.flags = d_flags;
     ka.kred = g.d_kred; ka.idx = g.d_idx + w0; ka.kp = d_kp + w0 * 32; ka.tag = d_tag + w0 * 32; ka.mark = d_mark + w0; ka.t = g.d_t;
     launch_kprime_decode(ka, stream);
-    if (ka.t) launch_kprime_tag_return(ka, stream); else launch_kprime_tag(ka, stream);      // (the candidate's t, by the same idx as its nullifier)
+    if (g.reserve) launch_kprime_tag_reserve(ka, stream);      // (the reserve form: tag_res, the candidate's s^ where the return form has its t)
+    else if (ka.t) launch_kprime_tag_return(ka, stream); else launch_kprime_tag(ka, stream);      // (the candidate's t, by the same idx as its nullifier)
     ADCK(c, hipGetLastError());
     ADCK(c, hipStreamSynchronize(stream));      // the window's buffers are reused
   }

@@ -24,6 +24,7 @@
 #include "replay_lanes.h"
 #include "admit_replay_lanes.h"
 #include "return_replay_lanes.h"
+#include "reserve_lanes.h"
 #include "cbor_lanes.h"
 #include "issue_wire_lanes.h"
 #include "rng_source.h"
@@ -1322,3 +1323,4 @@ int act_refund_batch(act_ctx* c, size_t n, int mem, const uint8_t sk[64], const 
 #include "copies_impl.inc"         // its copy stage: act_redeem_admit_unique_batch, act_redeem_cbor_admit_unique_batch
 #include "replay_impl.inc"         // replayable redemption: act_redeem_replay_batch, act_redeem_cbor_replay_batch, act_replay_derive_batch
 #include "admit_replay_impl.inc"   // its admission form: act_redeem_admit_replay_batch, act_redeem_cbor_admit_replay_batch
+#include "reserve_impl.inc"        // reserve and settle: act_redeem_(cbor_)reserve_batch, act_redeem_(cbor_)settle_batch

@@ -562,7 +562,9 @@ __global__ void __launch_bounds__(256) k_mark_undetermined_status(uint8_t* statu
 // out_b: the bytes of one output slot (a Refund record or message; a RefundReturn's for the return calls, DESIGN 4.10)
 template <class NullStep, class BesideMerge, class SignStep>
 static int redeem_tail_sized(act_ctx* c, act_nullifier_set* set, size_t n, int mem, size_t out_b, uint8_t* st, uint8_t* sp, const uint8_t* rng, int rng_mode,
-                             uint8_t* out, uint8_t* status, NullStep null_step, BesideMerge beside_merge, SignStep sign_step) {
+                             uint8_t* out, uint8_t* status, NullStep null_step, BesideMerge beside_merge, SignStep sign_step, bool signs = true) {
+  // signs == false (act_redeem_(cbor_)reserve_batch, reserve_impl.inc): the last step signs nothing -- the test hook below is not for it,
+  // and if it fails there is no refund owed: its lanes read as not answered, and the same call again is served as a retry
   const int rc_null = null_step(st, sp);
   // a step failed as a whole: every lane that verified says `what`, the others their verdict, and there is no output.  (Device memory:
   // best effort on a device that may just have failed a call -- the header promises a status for every lane.)
@@ -596,11 +598,12 @@ static int redeem_tail_sized(act_ctx* c, act_nullifier_set* set, size_t n, int m
   // the generator is touched only now, for the lanes that are signed (the reference draws e, alpha after its checks, src/lib.rs:842-852)
   ResolvedRng rr(c);
   int rc_sign = rr.resolve(c, mem, st, n, rng, rng_mode);
-  const bool fail_sign = c->debug_fail_signs.load() > 0 && c->debug_fail_signs.fetch_sub(1) > 0;      // error-path test hook (act_debug_fail_next_signs)
+  const bool fail_sign = signs && c->debug_fail_signs.load() > 0 && c->debug_fail_signs.fetch_sub(1) > 0;      // error-path test hook (act_debug_fail_next_signs)
   if (!rc_sign) {
     if (fail_sign) { rc_sign = ACT_ERR_HIP; c->err = "act_debug_fail_next_signs: simulated failure of the signature step"; }
     else rc_sign = sign_step(st, rng, rng_mode, out, status);
   }
+  if (rc_sign && !signs) { give_up(ACT_STATUS_NULLIFIER_UNDETERMINED, k_mark_undetermined_status); return rc_sign; }
   if (rc_sign) { give_up(ACT_STATUS_RECORDED_UNSIGNED, k_mark_recorded_unsigned); return rc_sign; }      // the nullifiers ARE recorded: the refunds are owed
   if (rc_null) c->err = null_err;
   return rc_null;

@@ -114,12 +114,14 @@ static int replay_refused(act_ctx* c, act_nullifier_set* set, act_nullifier_set*
 // survivors.  The caller holds replay_mu.  began (nullable): set once nothing in front of the tail proper can fail any more -- a return
 // with it unset has recorded nothing and written no status.  ret (act_redeem_(cbor_)return_replay_batch, DESIGN 4.10): the returned amounts
 // lane for lane with the tail's arrays (ret->t null: every t = 0) -- they enter the tags, the nonces and the signing step, and the
-// outputs are RefundReturn records or messages.
+// outputs are RefundReturn records or messages.  res (act_redeem_(cbor_)reserve_batch, DESIGN 4.11): the tail without its signature half --
+// the receipt's tag is tag_res over the charges res->s (lane for lane with the tail's arrays), no secret is staged, no nonce derived, and
+// where the sign step stands the 96-byte reservation records are written (reserve_impl.inc).
 static int replay_tail(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys, int nkeys, const uint32_t* key_epochs,
                        int sign_key, bool wire, const uint8_t* k_at, size_t k_stride, const uint8_t* kp, uint8_t* st, const uint8_t* nonce_key, uint8_t* out,
-                       uint8_t* status, uint8_t* out_key, uint8_t* out_replayed, uint64_t* out_counts, bool* began, const RedeemReturn* ret) {
+                       uint8_t* status, uint8_t* out_key, uint8_t* out_replayed, uint64_t* out_counts, bool* began, const RedeemReturn* ret, const ReplayReserve* res) {
   const bool dev = mem == ACT_MEM_DEVICE;
-  const uint8_t* const t = ret ? ret->t : nullptr;
+  const uint8_t* const t = res ? res->s : ret ? ret->t : nullptr;
   // tags; merged answers, key indices, the two sets' answers, the receipts mask and its answers, the replay marks
   const size_t per_lane = 32 + 7;
   std::vector<uint8_t> h; DevTmp d(c);
@@ -130,25 +132,28 @@ static int replay_tail(act_ctx* c, act_nullifier_set* set, act_nullifier_set* re
           *repl = out_replayed ? out_replayed : r_ans + n;
 
   ReplaySecretsDev sec_dev(c); ReplaySecretsHost sec_host;
-  const uint8_t* secrets; uint8_t* nonces;
-  if (dev) { if ((rc = sec_dev.stage(n * 128, nonce_key, keys, nkeys))) return rc; secrets = c->d_replay; }
-  else { sec_host.stage(n * 128, nonce_key, keys, nkeys); secrets = sec_host.p.get(); }
-  nonces = const_cast<uint8_t*>(secrets) + REPLAY_NONCE_OFF;
+  static uint8_t unsigned_stand_in = 0;      // res: where the nonces stand (never read: nothing is signed)
+  const uint8_t* secrets = nullptr; uint8_t* nonces = &unsigned_stand_in;
+  if (!res) {
+    if (dev) { if ((rc = sec_dev.stage(n * 128, nonce_key, keys, nkeys))) return rc; secrets = c->d_replay; }
+    else { sec_host.stage(n * 128, nonce_key, keys, nkeys); secrets = sec_host.p.get(); }
+    nonces = const_cast<uint8_t*>(secrets) + REPLAY_NONCE_OFF;
+  }
 
   hipStream_t stream = set->stream;
   int rc_receipts = ACT_OK; std::string receipts_err;
   if (began) *began = true;      // from here on status[] is complete on return, whatever fails
-  const int rc_tail = redeem_tail_sized(c, set, n, mem, redeem_out_bytes(c, wire, ret), st, sp, nonces, ACT_RNG_PER_LANE, out, status,
+  const int rc_tail = redeem_tail_sized(c, set, n, mem, res ? (size_t)RESERVATION_BYTES : redeem_out_bytes(c, wire, ret), st, sp, nonces, ACT_RNG_PER_LANE, out, status,
     [&](const uint8_t* mask, uint8_t* sp_out) -> int {
       // the tags first: they depend on the verification alone, and behind the insert of k nothing but the receipts may fail
       ReplayDeriveArgs ta{}; ta.n = (uint32_t)n; ta.stride = (uint32_t)k_stride; ta.nul = k_at; ta.kp = kp; ta.st = mask; ta.out = tag; ta.t = t;
       if (dev) {
         RPCK(c, hipSetDevice(c->device));
-        replay_derive_dev(ta, false, stream);
+        if (res) launch_reserve_tag(ta, stream); else replay_derive_dev(ta, false, stream);
         RPCK(c, hipGetLastError());
         RPCK(c, hipMemsetAsync(found, 0, n, stream)); RPCK(c, hipMemsetAsync(repl, 0, n, stream));
         RPCK(c, hipStreamSynchronize(stream));
-      } else { replay_derive_host(ta, false); memset(found, 0, n); memset(repl, 0, n); }
+      } else { if (res) reserve_tags_host(ta); else replay_derive_host(ta, false); memset(found, 0, n); memset(repl, 0, n); }
       const int rc_set = key_epochs ? act_nullifier_check_and_insert_epoch_batch(set, n, mem, k_at, k_stride, mask, out_key, key_epochs, nkeys, spent)
                                     : act_nullifier_check_and_insert_batch(set, n, mem, k_at, k_stride, mask, spent);
       if (rc_set == ACT_ERR_HIP) return rc_set;      // no answer can be trusted: redeem_tail gives every verified lane up as undetermined
@@ -168,14 +173,16 @@ static int replay_tail(act_ctx* c, act_nullifier_set* set, act_nullifier_set* re
       return rc_set;
     },
     [&] {      // st is merged by now: the nonces of exactly the lanes that are signed, under the key each is signed with
+      if (res) return;
       ring_sign_index(mem, kidx, out_key, sign_key, n);
       ReplayDeriveArgs na{}; na.n = (uint32_t)n; na.stride = (uint32_t)k_stride; na.nkeys = (uint32_t)nkeys; na.nul = k_at; na.kp = kp; na.st = st; na.kidx = kidx;
       na.secrets = secrets; na.out = nonces; na.t = t;
       if (dev) replay_derive_dev(na, true, nullptr); else replay_derive_host(na, true);
     },
     [&](const uint8_t* verdict, const uint8_t* r, int r_mode, uint8_t* o, uint8_t* o_st) {
+      if (res) return reserve_emit(c, stream, n, mem, k_at, k_stride, kp, res->s, verdict, o, o_st);
       return ring_sign_step(c, n, mem, keys, nkeys, wire, kidx, kp, verdict, r, r_mode, o, o_st, ret);
-    });
+    }, !res);
   if (out_counts) {      // status[] is complete behind the tail, whatever it returned
     std::vector<uint8_t> hs;
     const uint8_t *s = status, *r = repl;
@@ -191,6 +198,7 @@ static int replay_tail(act_ctx* c, act_nullifier_set* set, act_nullifier_set* re
     if (ok) replay_counts_of(out_counts, n, s, r);
   }
   if (rc_tail) return rc_tail;
+  if (rc_receipts && res) { c->err = "receipts set: " + receipts_err + " (every record was handed out; a fresh lane of this batch may not settle and its retry may be refused)"; return rc_receipts; }
   if (rc_receipts) { c->err = "receipts set: " + receipts_err + " (every refund was handed out; a retry of this batch's fresh lanes may be refused)"; return rc_receipts; }
   return ACT_OK;
 }
@@ -198,7 +206,8 @@ static int replay_tail(act_ctx* c, act_nullifier_set* set, act_nullifier_set* re
 // the verification and the tail over the caller's lanes; the caller has made the whole-call refusals and holds replay_mu
 static int redeem_replay_locked(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys, int nkeys,
                                 const uint32_t* key_epochs, int sign_key, const uint8_t* proof, const uint8_t* cbor, const uint64_t* offsets, const uint8_t* nonce_key,
-                                uint8_t* out, uint8_t* status, uint8_t* out_key, uint8_t* out_replayed, uint64_t* out_counts, const RedeemReturn* ret) {
+                                uint8_t* out, uint8_t* status, uint8_t* out_key, uint8_t* out_replayed, uint64_t* out_counts, const RedeemReturn* ret,
+                                const ReplayReserve* res) {
   const bool wire = cbor != nullptr, dev = mem == ACT_MEM_DEVICE;
   const size_t pb = act_spend_proof_bytes(c);
   // K', the verdicts and (wire form) the nullifiers
@@ -212,7 +221,7 @@ static int redeem_replay_locked(act_ctx* c, act_nullifier_set* set, act_nullifie
   else rc = act_verify_spend_keyring_batch(c, n, mem, keys, nkeys, proof, st, out_key, kp);
   if (rc) return rc;
   return replay_tail(c, set, receipts, n, mem, keys, nkeys, key_epochs, sign_key, wire, wire ? nul : proof, wire ? 32 : pb, kp, st, nonce_key, out, status, out_key,
-                     out_replayed, out_counts, nullptr, ret);
+                     out_replayed, out_counts, nullptr, ret, res);
 }
 
 static int redeem_replay_impl(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys, int nkeys,
@@ -228,7 +237,7 @@ static int redeem_replay_impl(act_ctx* c, act_nullifier_set* set, act_nullifier_
   // one replay call at a time per context: the staged secrets and the derived nonces live in the context's own buffer (d_replay)
   std::lock_guard<std::mutex> replay(c->replay_mu);
   return redeem_replay_locked(c, set, receipts, n, mem, keys, nkeys, key_epochs, sign_key, proof, cbor, offsets, nonce_key, out, status, out_key, out_replayed, out_counts,
-                              nullptr);
+                              nullptr, nullptr);
 }
 
 extern "C" int act_redeem_replay_batch(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys, int nkeys,

@@ -1022,6 +1022,8 @@ int act_ubench_table_read(act_ctx *ctx, int base, int waves_per_simd, int in_fli
  * hands out h1 (e + x)^-1 -- and with it anyone raises the balance of a token signed under that e.  The calls here use drawn nonces.
  * The replay form WITH amounts is a pair of calls of its own, act_redeem_(cbor_)return_replay_batch below ("replayable partial
  * refunds"), where t is bound into BOTH the receipt tag and the nonce derivation.  Also not offered here: the node-handle forms.
+ * A service that learns t only from the work takes act_redeem_(cbor_)reserve_batch and act_redeem_(cbor_)settle_batch ("reserve and
+ * settle", at the end of this file): the spend is recorded first and t is named when the refund is signed.
  *
  * act_refund_to_credit_token_return_keyring_batch is act_refund_to_credit_token_keyring_batch over n * 160 RefundReturn records: a
  * RefundReturn names no key either.  The same chunk schedule, staging and wiping of `pre`, ring checks (an entry that is not a canonical
@@ -1115,7 +1117,8 @@ int act_redeem_cbor_return_unique_batch(act_ctx *ctx, act_nullifier_set *set, si
  * call's: after ACT_STATUS_RECORDED_UNSIGNED a later retry with the same t is served.
  * The unique forms are act_redeem_(cbor_)return_replay_unique_batch below ("replayable partial refunds, unique forms"): a copy that
  * names another t than its leader is not served the leader's row, it is refused.  Still not offered: node-handle forms; tiny or fused
- * roads; a `returned` argument on the screenless act_redeem_(cbor_)replay_batch -- the bound t <= s lives in the screen.
+ * roads; a `returned` argument on the screenless act_redeem_(cbor_)replay_batch -- the bound t <= s lives in the screen.  A service
+ * that cannot know t when the spend is recorded: act_redeem_(cbor_)reserve_batch / act_redeem_(cbor_)settle_batch ("reserve and settle").
  *
  * act_replay_derive_return_batch is act_replay_derive_batch plus `returned` (nullable: that call): the tags and nonces above for
  * callers that compose the feature over the node-level calls with act_refund_sign_return_keyring_batch -- which is how it reaches
@@ -1189,6 +1192,107 @@ int act_redeem_cbor_return_replay_unique_batch(act_ctx *ctx, act_nullifier_set *
                                                const uint8_t *charge /* nullable */, const uint8_t *amounts /* t; nullable: all zero */, const uint8_t nonce_key[32],
                                                uint8_t *out_refund_return_cbor, uint8_t *status, uint8_t *out_key, uint8_t *out_replayed /* nullable */,
                                                uint64_t *out_counts /* nullable, host */);
+
+/* ======== reserve and settle: record a spend now, sign its partial refund later ========
+ * "A metered service reserves s, does the work, and the work costs s - t" in that order.  Every call above that records a nullifier
+ * also signs in the same call, so t must be known before the spend is recorded.  act_redeem_reserve_batch / act_redeem_cbor_reserve_
+ * batch are act_redeem_(cbor_)admit_replay_batch WITHOUT the signature: they screen, verify, record k and hand back a reservation
+ * record.  act_redeem_settle_batch / act_redeem_cbor_settle_batch take reservation records and amounts t <= s, check that the
+ * reservation is in the receipts, PIN the amount and sign a RefundReturn with the derived nonces of the replayable partial refunds.
+ * Settling one reservation with the same amount again gives the same bytes.
+ *
+ * Definitions.  Write k^ = k mod l, s^ = s mod l, t^ = t mod l; enc(K') is the encoding the verification computes.
+ *   reservation record   96 bytes, public: k^ | enc(K') | s^.  A rejected lane's record is all zero.  The matched ring index is
+ *                        out_key[i], as in every ring call; it is not part of the record (a service stores 97 bytes and, later, t).
+ *   reservation tag      tag_res = BLAKE3("act-mi355x/reservation/v1" padded to 32 | k^ | enc(K') | s^)[0:32], top nibble cleared
+ *                        (128 bytes, two blocks).  s^ is in the tag so that settle's bound t <= s rests on what was reserved, not on
+ *                        what the caller kept.
+ *   settlement marker    BLAKE3("act-mi355x/settled/v1" padded to 32 | k^ | enc(K'))[0:32], top nibble cleared (96 bytes).
+ *   amount tag, nonces   exactly act_replay_derive_return_batch's tag and nonces for (nonce_key, key_j, k^, enc(K'), t^), key_j the
+ *                        key the lane is signed with: the v1 hashes at t^ = 0, the "-t" hashes otherwise.
+ *
+ * RESERVE, per lane and in this order (no sign_key, no nonce_key, no rng: nothing secret beyond the ring is staged):
+ *   1. the wire reader's code (wire form) and the charge (ACT_STATUS_WRONG_CHARGE): as act_redeem_(cbor_)admit_replay_batch.
+ *   2. k is already in `set`: enc(K') from the lane's Com_j, tag_res with the lane's s^, looked up in `receipts` (read only).  A lane
+ *      with an undecodable Com_j or an absent tag is ACT_STATUS_DOUBLE_SPEND: not verified, ACT_KEY_NONE, a zero record.  A lane whose
+ *      tag is there is a retry candidate.
+ *   3. every remaining lane is verified against the ring.
+ *   4. k is checked and inserted under the matched key's epoch; tag_res is recorded in `receipts` under the same epoch ONLY where k was
+ *      fresh; where k was spent tag_res is looked up -- found: status 0 and out_replayed = 1, absent: ACT_STATUS_DOUBLE_SPEND.
+ *   5. accepted lanes, fresh or replayed, get their record.  A retry gets the bytes of the first time: the record is a function of the proof.
+ * What out_replayed = 1 obliges the service to do: the spend was reserved before -- look the job up by k^, never start a second one.
+ * Failure contract: the replay calls' without its signature half.  ACT_STATUS_NULLIFIER_UNDETERMINED exists (also behind a device
+ * failure of the last step: the same call again is then served as a retry); ACT_STATUS_RECORDED_UNSIGNED cannot occur.  A receipts
+ * failure behind a recorded k returns the receipts set's error with status[] complete.  Whole-call refusals and locks are those of
+ * act_redeem_(cbor_)admit_replay_batch (receipts == set, a receipts set without room for n more keys, epoch tables, a bad ring); one
+ * call runs at a time per context.  out_counts: nullable, host, ACT_RESERVE_COUNTS values -- the eleven of ACT_ADMIT_REPLAY_COUNTS
+ * in their order.
+ *
+ * SETTLE, per lane and in this order (key_index[i] is what reserve wrote to out_key[i]):
+ *   1. key_index[i] >= nkeys -> ACT_STATUS_NOT_RESERVED; nothing is touched.
+ *   2. t^ > s^ as integers, s^ from the record -> ACT_STATUS_RETURN_TOO_BIG: in front of every look-up, no trace.
+ *   3. tag_res(k^, enc(K'), s^) is not in `receipts` (read only) -> ACT_STATUS_NOT_RESERVED: a record the caller altered, a spend
+ *      recorded by any one-phase call, an epoch that was retired.
+ *   4. THE PIN: the marker is checked and inserted into `receipts` under key_epochs[key_index[i]].  Fresh: the amount tag is recorded
+ *      under the same epoch, out_settled_before = 0.  Spent before the call or by an earlier lane of the batch: the amount tag is
+ *      looked up -- found: status 0, out_settled_before = 1 and the same bytes as before; absent: ACT_STATUS_SETTLED_OTHER_AMOUNT and a
+ *      zero record.  So [R t1, R t1, R t2] ends 0 / 0 (settled before) / 247.
+ *   5. the nonces of (nonce_key, key_j, k^, enc(K'), t^) and the signature over X_A = g + K' + t h1, by the ring signing step with
+ *      amounts; key_j = sign_key, or key_index[i] for ACT_SIGN_MATCHED.  160-byte RefundReturn records (wire form: ACT_CBOR_REFUND_RETURN
+ *      messages), all zero where not signed.
+ * Why the pin: a SpendProof is not bound to a request.  A client can resend an expensive spend beside a cheap request; reserve answers
+ * out_replayed = 1, and a service that nevertheless starts a second job and settles it with a larger t is stopped at the second
+ * settlement.  t is in the nonces, so two amounts never share an e whatever the sets' history.
+ * Failure contract: marker and amount tag are written before signing.  A failed signature step leaves ACT_STATUS_RECORDED_UNSIGNED;
+ * the repair is the same call again with the same amounts.  A lane the receipts could not answer for is
+ * ACT_STATUS_NULLIFIER_UNDETERMINED (nothing recorded for it: resubmit).
+ * Refused as a whole (nothing written, nothing recorded): a NULL receipts handle or nonce_key, receipts with len + 2 n > slots / 2,
+ * an epoch table that does not fit the receipts, a bad ring.
+ * Races: two settlements of ONE reservation that race may see ACT_STATUS_SETTLED_OTHER_AMOUNT once -- the marker is recorded and the
+ * amount tag not yet -- as two racing retries of one spend may see one ACT_STATUS_DOUBLE_SPEND in the replay calls; the same call
+ * again is served.
+ * out_counts: nullable, host, ACT_SETTLE_COUNTS values: lanes, not_reserved, return_too_big, settled, settled_again, other_amount,
+ * unanswered (ACT_STATUS_NULLIFIER_UNDETERMINED and ACT_STATUS_RECORDED_UNSIGNED).
+ * Hygiene: nonce_key, the ring and the derived nonces live in the context's replay buffer and are wiped on every exit;
+ * act_debug_secret_residue stays 0.
+ *
+ * What follows from the definitions:
+ *   - Settle equals the one-phase call.  After reserve and settle with t every output byte, status, out_key and the contents of `set`
+ *     with their epochs are those of act_redeem_(cbor_)return_replay_batch on the same batch and amounts (identical empty sets;
+ *     ACT_SIGN_MATCHED or the same sign_key).  Only the receipts differ: tag_res, the marker and the amount tag instead of the
+ *     amount tag alone.  Two kinds of lane are answered under another name or leave more behind: a lane reserve shed (wrong charge, wire
+ *     code) has no reservation, so settling its zero record with ACT_KEY_NONE is ACT_STATUS_NOT_RESERVED; and a lane with t^ > s^ is
+ *     ACT_STATUS_RETURN_TOO_BIG on both roads, but reserve, which never sees t, HAS recorded its k -- the reservation stays open until it
+ *     is settled with an amount that fits, and then the sets agree again.
+ *   - A later client retry is served by the one-phase call: after settlement `receipts` holds the amount tag (k, K', t^), so
+ *     act_redeem_(cbor_)return_replay_batch with that t serves the same RefundReturn (out_replayed = 1); with another t it is a
+ *     double spend.
+ *   - Unsettled reservations are closed to the one-phase calls: for every other redeem call such a spend is a foreign spend,
+ *     ACT_STATUS_DOUBLE_SPEND, shed by the screen where there is one.
+ *   - t = s cancels a reservation: the client gets its whole balance back.
+ *   - Retire an epoch on both sets, as before: all three new keys carry the matched key's epoch.
+ * Not offered: unique forms, node-handle forms, tiny or fused roads, a listing of unsettled reservations, a wire type for the
+ * reservation record (it never goes to a client). */
+#define ACT_STATUS_NOT_RESERVED 248           /* settle: no such reservation in the receipts (or key_index >= nkeys); nothing recorded, nothing signed */
+#define ACT_STATUS_SETTLED_OTHER_AMOUNT 247   /* settle: the reservation was settled with another amount; nothing recorded, nothing signed */
+#define ACT_RESERVE_COUNTS 11
+#define ACT_SETTLE_COUNTS 7
+int act_redeem_reserve_batch(act_ctx *ctx, act_nullifier_set *set, act_nullifier_set *receipts, size_t n, int mem, const uint8_t *keys, int nkeys,
+                             const uint32_t *key_epochs /* nullable */, const uint8_t *proof, const uint8_t *charge /* nullable */,
+                             uint8_t *out_reservation, uint8_t *status, uint8_t *out_key, uint8_t *out_replayed /* nullable */,
+                             uint64_t *out_counts /* nullable, host */);
+int act_redeem_cbor_reserve_batch(act_ctx *ctx, act_nullifier_set *set, act_nullifier_set *receipts, size_t n, int mem, const uint8_t *keys, int nkeys,
+                                  const uint32_t *key_epochs /* nullable */, const uint8_t *cbor, const uint64_t *offsets,
+                                  const uint8_t *charge /* nullable */, uint8_t *out_reservation, uint8_t *status, uint8_t *out_key,
+                                  uint8_t *out_replayed /* nullable */, uint64_t *out_counts /* nullable, host */);
+int act_redeem_settle_batch(act_ctx *ctx, act_nullifier_set *receipts, size_t n, int mem, const uint8_t *keys, int nkeys,
+                            const uint32_t *key_epochs /* nullable */, int sign_key, const uint8_t *reservation, const uint8_t *key_index,
+                            const uint8_t *amounts /* t; nullable: all zero */, const uint8_t nonce_key[32], uint8_t *out_refund_return,
+                            uint8_t *status, uint8_t *out_settled_before /* nullable */, uint64_t *out_counts /* nullable, host */);
+int act_redeem_cbor_settle_batch(act_ctx *ctx, act_nullifier_set *receipts, size_t n, int mem, const uint8_t *keys, int nkeys,
+                                 const uint32_t *key_epochs /* nullable */, int sign_key, const uint8_t *reservation, const uint8_t *key_index,
+                                 const uint8_t *amounts /* t; nullable: all zero */, const uint8_t nonce_key[32], uint8_t *out_refund_return_cbor,
+                                 uint8_t *status, uint8_t *out_settled_before /* nullable */, uint64_t *out_counts /* nullable, host */);
 
 #ifdef __cplusplus
 }

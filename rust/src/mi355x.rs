@@ -200,6 +200,19 @@ extern "C" {
                                                   nkeys: c_int, key_epochs: *const u32, sign_key: c_int, cbor: *const u8, offsets: *const u64, charge: *const u8,
                                                   amounts: *const u8, nonce_key: *const u8, out_refund_return_cbor: *mut u8, status: *mut u8, out_key: *mut u8,
                                                   out_replayed: *mut u8, out_counts: *mut u64) -> c_int;
+    // reserve and settle: record a spend now, sign its partial refund later
+    fn act_redeem_reserve_batch(ctx: *mut ActCtx, set: *mut ActNullifierSet, receipts: *mut ActNullifierSet, n: usize, mem: c_int, keys: *const u8, nkeys: c_int,
+                                key_epochs: *const u32, proof: *const u8, charge: *const u8, out_reservation: *mut u8, status: *mut u8, out_key: *mut u8,
+                                out_replayed: *mut u8, out_counts: *mut u64) -> c_int;
+    fn act_redeem_cbor_reserve_batch(ctx: *mut ActCtx, set: *mut ActNullifierSet, receipts: *mut ActNullifierSet, n: usize, mem: c_int, keys: *const u8, nkeys: c_int,
+                                     key_epochs: *const u32, cbor: *const u8, offsets: *const u64, charge: *const u8, out_reservation: *mut u8, status: *mut u8,
+                                     out_key: *mut u8, out_replayed: *mut u8, out_counts: *mut u64) -> c_int;
+    fn act_redeem_settle_batch(ctx: *mut ActCtx, receipts: *mut ActNullifierSet, n: usize, mem: c_int, keys: *const u8, nkeys: c_int, key_epochs: *const u32,
+                               sign_key: c_int, reservation: *const u8, key_index: *const u8, amounts: *const u8, nonce_key: *const u8, out_refund_return: *mut u8,
+                               status: *mut u8, out_settled_before: *mut u8, out_counts: *mut u64) -> c_int;
+    fn act_redeem_cbor_settle_batch(ctx: *mut ActCtx, receipts: *mut ActNullifierSet, n: usize, mem: c_int, keys: *const u8, nkeys: c_int, key_epochs: *const u32,
+                                    sign_key: c_int, reservation: *const u8, key_index: *const u8, amounts: *const u8, nonce_key: *const u8,
+                                    out_refund_return_cbor: *mut u8, status: *mut u8, out_settled_before: *mut u8, out_counts: *mut u64) -> c_int;
 }
 
 /// ACT_MI355X_DEVICES = "0,1,2,3,4,5,6,7" (default: device 0)
@@ -1576,6 +1589,103 @@ impl GpuReplay {
         } };
         tags.truncate(32 * n); nonces.truncate(128 * n);
         (rc, tags, nonces)
+    }
+}
+
+/// the eleven of `ACT_ADMIT_REPLAY_COUNTS` in their order (`GpuReserve::reserve_batch`)
+pub const ACT_RESERVE_COUNTS: usize = 11;
+/// lanes / not_reserved / return_too_big / settled / settled_again / other_amount / unanswered (`GpuReserve::settle_batch`)
+pub const ACT_SETTLE_COUNTS: usize = 7;
+pub const ACT_STATUS_NOT_RESERVED: u8 = 248;
+pub const ACT_STATUS_SETTLED_OTHER_AMOUNT: u8 = 247;
+/// k^ | enc(K') | s^: what a service keeps per job, with the matched ring index (97 bytes) and, once known, t
+pub const RESERVATION_BYTES: usize = 96;
+/// statuses, 96-byte reservation records (all zero where rejected), matched ring keys, the replay marks and the counts
+pub struct Reserved {
+    pub rc: c_int,
+    pub status: Vec<u8>,
+    pub reservation: Vec<u8>,
+    pub out_key: Vec<u8>,
+    pub replayed: Vec<u8>,
+    pub counts: [u64; ACT_RESERVE_COUNTS],
+}
+/// statuses, outputs (160-byte RefundReturn records or `REFUND_RETURN_CBOR_BYTES` messages, all zero where not signed), the
+/// settled-before marks and the counts
+pub struct Settled {
+    pub rc: c_int,
+    pub status: Vec<u8>,
+    pub out: Vec<u8>,
+    pub settled_before: Vec<u8>,
+    pub counts: [u64; ACT_SETTLE_COUNTS],
+}
+/// Reserve and settle on ONE GPU (include/act_mi355x.h "reserve and settle"): a metered service records a spend of s with
+/// `reserve_batch`, does the work, and signs the partial refund t <= s with `settle_batch`.  `Reserved::replayed[i] == 1` obliges the
+/// service to find the job it already started for that nullifier, never to start a second one; settling one reservation again with the
+/// same amount gives the same bytes, with another amount `ACT_STATUS_SETTLED_OTHER_AMOUNT`.  Thin: bytes in, bytes out.
+pub struct GpuReserve {
+    ctx: *mut ActCtx,
+    set: *mut ActNullifierSet,
+    receipts: *mut ActNullifierSet,
+    nonce_key: [u8; 32],
+}
+impl GpuReserve {
+    /// # Safety
+    /// `ctx`, `set` and `receipts` are live handles on one device, `set != receipts`, and all three outlive `self`.
+    pub unsafe fn from_raw(ctx: *mut ActCtx, set: *mut ActNullifierSet, receipts: *mut ActNullifierSet, nonce_key: [u8; 32]) -> Self {
+        GpuReserve { ctx, set, receipts, nonce_key }
+    }
+    fn reserved(n: usize) -> Reserved {
+        Reserved { rc: 0, status: vec![0u8; n + 1], reservation: vec![0u8; RESERVATION_BYTES * n + 1], out_key: vec![ACT_KEY_NONE; n + 1], replayed: vec![0u8; n + 1],
+                   counts: [0; ACT_RESERVE_COUNTS] }
+    }
+    /// `keys`: nkeys records of 64 bytes; `proofs`: n records of `PROOF_BYTES`; `charges`: n scalars of 32 bytes or `None`.
+    pub fn reserve_batch(&self, keys: &[u8], key_epochs: Option<&[u32]>, proofs: &[u8], charges: Option<&[u8]>) -> Reserved {
+        let (n, nkeys) = (proofs.len() / PROOF_BYTES, keys.len() / 64);
+        assert!(proofs.len() == n * PROOF_BYTES && key_epochs.map_or(true, |e| e.len() == nkeys) && charges.map_or(true, |c| c.len() == 32 * n));
+        let mut r = Self::reserved(n);
+        r.rc = unsafe {
+            act_redeem_reserve_batch(self.ctx, self.set, self.receipts, n, 0, keys.as_ptr(), nkeys as c_int, key_epochs.map_or(std::ptr::null(), |e| e.as_ptr()),
+                                     proofs.as_ptr(), charges.map_or(std::ptr::null(), |c| c.as_ptr()), r.reservation.as_mut_ptr(), r.status.as_mut_ptr(),
+                                     r.out_key.as_mut_ptr(), r.replayed.as_mut_ptr(), r.counts.as_mut_ptr())
+        };
+        r.status.truncate(n); r.reservation.truncate(RESERVATION_BYTES * n); r.out_key.truncate(n); r.replayed.truncate(n);
+        r
+    }
+    /// The same on wire bytes: CBOR SpendProof messages in (a retry may be another spelling of the same proof).
+    pub fn reserve_cbor_batch(&self, keys: &[u8], key_epochs: Option<&[u32]>, msgs: &[&[u8]], charges: Option<&[u8]>) -> Reserved {
+        let (blob, offsets) = gather(msgs);
+        let (n, nkeys) = (msgs.len(), keys.len() / 64);
+        assert!(key_epochs.map_or(true, |e| e.len() == nkeys) && charges.map_or(true, |c| c.len() == 32 * n));
+        let mut r = Self::reserved(n);
+        r.rc = unsafe {
+            act_redeem_cbor_reserve_batch(self.ctx, self.set, self.receipts, n, 0, keys.as_ptr(), nkeys as c_int, key_epochs.map_or(std::ptr::null(), |e| e.as_ptr()),
+                                          blob.as_ptr(), offsets.as_ptr(), charges.map_or(std::ptr::null(), |c| c.as_ptr()), r.reservation.as_mut_ptr(),
+                                          r.status.as_mut_ptr(), r.out_key.as_mut_ptr(), r.replayed.as_mut_ptr(), r.counts.as_mut_ptr())
+        };
+        r.status.truncate(n); r.reservation.truncate(RESERVATION_BYTES * n); r.out_key.truncate(n); r.replayed.truncate(n);
+        r
+    }
+    /// `reservations`: n records of `RESERVATION_BYTES`; `key_index`: what reserve left in `out_key`; `amounts`: n scalars of 32 bytes
+    /// (`None`: every t = 0); `cbor`: CBOR RefundReturn messages out instead of 160-byte records.
+    pub fn settle_batch(&self, keys: &[u8], key_epochs: Option<&[u32]>, sign_with: Option<usize>, reservations: &[u8], key_index: &[u8], amounts: Option<&[u8]>,
+                        cbor: bool) -> Settled {
+        let (n, nkeys) = (key_index.len(), keys.len() / 64);
+        assert!(reservations.len() == RESERVATION_BYTES * n && key_epochs.map_or(true, |e| e.len() == nkeys) && amounts.map_or(true, |t| t.len() == 32 * n));
+        let rec = if cbor { REFUND_RETURN_CBOR_BYTES } else { 160 };
+        let mut r = Settled { rc: 0, status: vec![0u8; n + 1], out: vec![0u8; rec * n + 1], settled_before: vec![0u8; n + 1], counts: [0; ACT_SETTLE_COUNTS] };
+        r.rc = if cbor { unsafe {
+            act_redeem_cbor_settle_batch(self.ctx, self.receipts, n, 0, keys.as_ptr(), nkeys as c_int, key_epochs.map_or(std::ptr::null(), |e| e.as_ptr()),
+                                         sign_with.map_or(ACT_SIGN_MATCHED, |i| i as c_int), reservations.as_ptr(), key_index.as_ptr(),
+                                         amounts.map_or(std::ptr::null(), |t| t.as_ptr()), self.nonce_key.as_ptr(), r.out.as_mut_ptr(), r.status.as_mut_ptr(),
+                                         r.settled_before.as_mut_ptr(), r.counts.as_mut_ptr())
+        } } else { unsafe {
+            act_redeem_settle_batch(self.ctx, self.receipts, n, 0, keys.as_ptr(), nkeys as c_int, key_epochs.map_or(std::ptr::null(), |e| e.as_ptr()),
+                                    sign_with.map_or(ACT_SIGN_MATCHED, |i| i as c_int), reservations.as_ptr(), key_index.as_ptr(),
+                                    amounts.map_or(std::ptr::null(), |t| t.as_ptr()), self.nonce_key.as_ptr(), r.out.as_mut_ptr(), r.status.as_mut_ptr(),
+                                    r.settled_before.as_mut_ptr(), r.counts.as_mut_ptr())
+        } };
+        r.status.truncate(n); r.out.truncate(rec * n); r.settled_before.truncate(n);
+        r
     }
 }
 
