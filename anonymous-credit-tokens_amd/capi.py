@@ -42,7 +42,7 @@ EXPORTS = [
     "act_ctx_set_host_threads", "act_host_usable_cpus", "act_host_hash_many", "act_host_parallel_for", "act_host_pool_stats", "act_ctx_streams_overlap", "act_ctx_set_pipeline_depth", "act_ctx_set_small_batch_max", "act_ctx_set_fixed_base_bits", "act_node_set_fixed_base_bits", "act_tuning_set", "act_build_has_ct_secret_tables", "act_ctx_fixed_base_bits", "act_last_error", "act_spend_proof_bytes", "act_prove_rng_bytes",
     "act_spend_transcript_bytes", "act_private_key_random", "act_pre_issuance_random_batch", "act_request_batch",
     "act_issue_batch", "act_issuance_to_credit_token_batch", "act_prove_spend_batch", "act_prove_spend_seeded_batch", "act_node_prove_spend_seeded_batch", "act_verify_spend_batch",
-    "act_refund_batch", "act_refund_to_credit_token_batch", "act_debug_last_spend_transcripts", "act_debug_scalarmult_batch", "act_debug_fixed_base_batch", "act_debug_secret_residue", "act_prof_enable",
+    "act_refund_batch", "act_refund_to_credit_token_batch", "act_debug_last_spend_transcripts", "act_debug_scalarmult_batch", "act_debug_fixed_base_batch", "act_debug_fe_batch", "act_debug_secret_residue", "act_prof_enable",
     "act_prof_reset", "act_prof_kernel_count", "act_prof_kernel_name", "act_prof_get", "act_prof_get_busy", "act_ubench_mad_u64_u32", "act_ubench_random_read", "act_ubench_table_read",
     "act_cbor_size", "act_cbor_record_bytes", "act_cbor_encode_batch", "act_cbor_decode_batch", "act_cbor_read_batch", "act_ctx_set_wire_reader", "act_ctx_wire_stats", "act_node_set_wire_reader", "act_verify_spend_cbor_batch",
     "act_node_verify_spend_cbor_batch", "act_redeem_batch", "act_node_redeem_batch",
@@ -155,6 +155,7 @@ def load() -> C.CDLL:
     lib.act_debug_last_spend_transcripts.argtypes = [vp, sz, u8p, C.POINTER(sz)]
     lib.act_debug_scalarmult_batch.argtypes = [vp, sz, i32, u8p, u8p, u8p, u8p]
     lib.act_debug_fixed_base_batch.argtypes = [vp, i32, sz, i32, u8p, u8p]
+    lib.act_debug_fe_batch.argtypes = [vp, i32, i32, sz, u8p, u8p, u8p, u8p, u8p, u8p]
     lib.act_debug_secret_residue.argtypes = [vp, C.POINTER(sz)]
     for f in ("act_cbor_size", "act_cbor_record_bytes"):
         getattr(lib, f).argtypes = [vp, i32]
@@ -628,6 +629,21 @@ class Engine:
         p0, k0 = _in(scalars, 32 * n)
         self._ck(self.lib.act_debug_fixed_base_batch(self.ctx, base, n, MEM_HOST, p0, out.ctypes.data))
         return out.tobytes()
+
+    FE_OPS = ("mul", "sq", "mul2", "sq2", "sqda_sq", "carry", "sub", "sub3", "sub4", "neg")
+
+    def debug_fe(self, pair_build: bool, op: str, n: int, f, g=None, fb=None, gb_or_a=None, fill: int = 0):
+        """One field operation per lane on raw limbs (act_debug_fe_batch).  f, g, fb, gb_or_a: uint32 arrays of 9 n limbs (those the
+        operation names).  Returns (h, hb) as uint32 arrays of 9 * (n rounded up to 256) limbs pre-filled with `fill`; hb is None for
+        the operations with one result."""
+        lanes = (n + 255) // 256 * 256
+        two = op in ("mul2", "sq2", "sqda_sq")
+        ins = [None if a is None else np.ascontiguousarray(a, np.uint32) for a in (f, g, fb, gb_or_a)]
+        assert all(a is None or a.size == 9 * n for a in ins)
+        h = np.full(9 * lanes, fill, np.uint32); hb = np.full(9 * lanes, fill, np.uint32) if two else None
+        self._ck(self.lib.act_debug_fe_batch(self.ctx, int(bool(pair_build)), self.FE_OPS.index(op), n, *[None if a is None else a.ctypes.data for a in ins],
+                                             h.ctypes.data, None if hb is None else hb.ctypes.data))
+        return h, hb
 
     # ---- CBOR wire codec (src/cbor.rs) -----------------------------------------------------------------
     def cbor_size(self, type_name: str) -> int:

@@ -127,6 +127,39 @@ int act_debug_fixed_base_batch(act_ctx* c, int base, size_t n, int mem, const ui
   return call.finish();
 }
 
+// One field operation per lane on raw limbs (k_debug_fe.hip), in the per-column build of fe25519.h or in the range kernel's
+// (pair_build).  h / hb go IN as well, rounded up to whole blocks of 256 lanes, and come back whole: a lane from n on that the kernel
+// wrote would show in what the caller pre-filled.
+int act_debug_fe_batch(act_ctx* c, int pair_build, int op, size_t n, const uint32_t* f, const uint32_t* g, const uint32_t* fb, const uint32_t* gb_or_a, uint32_t* h, uint32_t* hb) {
+  if (!c || op < 0 || op >= DFE_COUNT) return ACT_ERR_ARG;
+  const bool two = op == DFE_MUL2 || op == DFE_SQ2 || op == DFE_SQDA_SQ;
+  const bool need_g = op == DFE_MUL || op == DFE_MUL2 || op == DFE_SUB || op == DFE_SUB3 || op == DFE_SUB4, need_ga = op == DFE_MUL2 || op == DFE_SQDA_SQ;
+  if (n && (!f || !h || (need_g && !g) || (two && (!fb || !hb)) || (need_ga && !gb_or_a))) return ACT_ERR_ARG;
+  Call call(c, n);
+  HIPCK(c, hipSetDevice(c->device));
+  Slot& sl = c->slots[0];
+  const size_t LB = FE_LIMBS * 4;                                   // bytes of a lane
+  const size_t chunk = std::max<size_t>(256, c->max_batch / 256 * 256);      // whole blocks
+  for (size_t off = 0; off < n; off += chunk) {
+    const uint32_t m = (uint32_t)std::min(chunk, n - off);
+    const size_t in_b = (size_t)m * LB, out_b = ((size_t)m + 255) / 256 * 256 * LB;
+    const uint8_t *d_f, *d_g = nullptr, *d_fb = nullptr, *d_ga = nullptr, *d_hin, *d_hbin = nullptr; uint8_t *d_h, *d_hb = nullptr; int rc;
+    if ((rc = dev_in(c, sl, 0, ACT_MEM_HOST, (const uint8_t*)f + off * LB, in_b, &d_f))) return rc;
+    if (need_g && (rc = dev_in(c, sl, 1, ACT_MEM_HOST, (const uint8_t*)g + off * LB, in_b, &d_g))) return rc;
+    if (two && (rc = dev_in(c, sl, 2, ACT_MEM_HOST, (const uint8_t*)fb + off * LB, in_b, &d_fb))) return rc;
+    if (need_ga && (rc = dev_in(c, sl, 3, ACT_MEM_HOST, (const uint8_t*)gb_or_a + off * LB, in_b, &d_ga))) return rc;
+    if ((rc = dev_in(c, sl, 4, ACT_MEM_HOST, (const uint8_t*)h + off * LB, out_b, &d_hin))) return rc;
+    if (two && (rc = dev_in(c, sl, 5, ACT_MEM_HOST, (const uint8_t*)hb + off * LB, out_b, &d_hbin))) return rc;
+    d_h = const_cast<uint8_t*>(d_hin); d_hb = const_cast<uint8_t*>(d_hbin);
+    (pair_build ? launch_debug_fe_pair : launch_debug_fe)(op, m, (const uint32_t*)d_f, (const uint32_t*)d_g, (const uint32_t*)d_fb, (const uint32_t*)d_ga, (uint32_t*)d_h, (uint32_t*)d_hb, sl.stream);
+    HIPCK(c, hipGetLastError());
+    if ((rc = dev_out_end(c, sl, ACT_MEM_HOST, (uint8_t*)h + off * LB, d_h, out_b))) return rc;
+    if (two && (rc = dev_out_end(c, sl, ACT_MEM_HOST, (uint8_t*)hb + off * LB, d_hb, out_b))) return rc;
+    HIPCK(c, hipStreamSynchronize(sl.stream));
+  }
+  return call.finish();
+}
+
 // Test hook: bytes that are not zero in the context's secret-bearing buffers (what finish_call wipes), read back to the host.
 int act_debug_secret_residue(act_ctx* c, size_t* nonzero_bytes) {
   if (!c || !nonzero_bytes) return ACT_ERR_ARG;

@@ -278,6 +278,11 @@ constexpr int UBENCH_MADS_PER_ITER = 80;    // 8 chains x 10 dependent multiply-
 void launch_ubench_mad(uint32_t* out, uint32_t blocks, uint32_t iters, hipStream_t s);
 void launch_debug_scalarmult(const uint8_t* pts, const uint8_t* scs, uint32_t n, uint32_t* pbk, uint8_t* out, uint8_t* status, hipStream_t s);
 void launch_debug_fixed_base(FbTab tab, const uint8_t* scs, uint32_t n, uint8_t* out, hipStream_t s);
+// k_debug_fe.hip, built twice: with the flags of every unit (per-column field products) and, as k_debug_fe_pair.hip, with the range
+// kernel's (the one-statement products).  One field operation per lane on raw limbs; DebugFeOp selects it.
+enum DebugFeOp : int { DFE_MUL = 0, DFE_SQ, DFE_MUL2, DFE_SQ2, DFE_SQDA_SQ, DFE_CARRY, DFE_SUB, DFE_SUB3, DFE_SUB4, DFE_NEG, DFE_COUNT };
+void launch_debug_fe(int op, uint32_t n, const uint32_t* f, const uint32_t* g, const uint32_t* fb, const uint32_t* ga, uint32_t* h, uint32_t* hb, hipStream_t s);
+void launch_debug_fe_pair(int op, uint32_t n, const uint32_t* f, const uint32_t* g, const uint32_t* fb, const uint32_t* ga, uint32_t* h, uint32_t* hb, hipStream_t s);
 void launch_spend_prep(const SpendArgs& a, hipStream_t s);
 void launch_spend_prep_role(const SpendArgs& a, int role /* 0 A, 1 B, 2 C, 3 join, 4 C1 (what k_spend_bits waits for), 5 C2 */, hipStream_t s);
 void launch_spend_enc_small(const SpendArgs& a, hipStream_t s);

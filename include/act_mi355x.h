@@ -955,6 +955,17 @@ int act_debug_scalarmult_batch(act_ctx *ctx, size_t n, int mem, const uint8_t *p
  * reduced mod l on load.  Exists so that every window and entry of a table of any width can be aimed at with a chosen scalar.
  * ACT_ERR_ARG for a base outside 0..3. */
 int act_debug_fixed_base_batch(act_ctx *ctx, int base, size_t n, int mem, const uint8_t *scalars, uint8_t *out);
+/* Debug / test hook: ONE operation of the device's field arithmetic (csrc/fe25519.h) per lane, on raw limbs.  An element is nine
+ * uint32_t limbs (limb i at bit ceil(85 i / 3)), lane i's at [9 i, 9 i + 9); nothing is reduced or checked on the way in or out, so
+ * operands may sit anywhere in their limb-size class.  op: 0 h = f * g, 1 h = f^2, 2 h = f * g and hb = fb * gb_or_a, 3 h = f^2 and
+ * hb = fb^2, 4 fe_sqda_sq: h = 2 f^2 + gb_or_a carried once and hb = fb^2, 5 h = fe_carry(f), 6 / 7 / 8 h = f - g + 2p / 3p / 4p
+ * (fe_sub, fe_sub3, fe_sub4: g at most the offset limb-wise), 9 h = 2p - f (fe_neg).  pair_build 0 runs the per-column form of the
+ * products that every kernel but one is built with, 1 the one-statement form of the range kernel's translation unit.  An array an
+ * operation does not name may be NULL.  HOST memory only.  h (and hb, where written) must hold n rounded up to a multiple of 256
+ * lanes: the lanes from n on make the round trip through device memory and come back as the caller filled them.  ACT_ERR_ARG for an
+ * op outside 0..9 or a missing array. */
+int act_debug_fe_batch(act_ctx *ctx, int pair_build, int op, size_t n, const uint32_t *f, const uint32_t *g, const uint32_t *fb,
+                       const uint32_t *gb_or_a, uint32_t *h, uint32_t *hb);
 
 /* Measurement hook: A/B switches and size overrides of tools/ and tests/ (csrc/kernels.h TuneKey: "no_mapped_reads", "no_fused_tiny",
  * "no_taper", "no_wide_sign", "no_wide_prove", "no_wide_client", "no_lds_isolation", "no_stream_probe", "small_sub", "small_in_flight",

@@ -213,6 +213,9 @@ extern "C" {
     fn act_redeem_cbor_settle_batch(ctx: *mut ActCtx, receipts: *mut ActNullifierSet, n: usize, mem: c_int, keys: *const u8, nkeys: c_int, key_epochs: *const u32,
                                     sign_key: c_int, reservation: *const u8, key_index: *const u8, amounts: *const u8, nonce_key: *const u8,
                                     out_refund_return_cbor: *mut u8, status: *mut u8, out_settled_before: *mut u8, out_counts: *mut u64) -> c_int;
+    // test hook: one field operation per lane on raw 9-limb operands, in the per-column or the range kernel's build of the field code
+    fn act_debug_fe_batch(ctx: *mut ActCtx, pair_build: c_int, op: c_int, n: usize, f: *const u32, g: *const u32, fb: *const u32, gb_or_a: *const u32,
+                          h: *mut u32, hb: *mut u32) -> c_int;
 }
 
 /// ACT_MI355X_DEVICES = "0,1,2,3,4,5,6,7" (default: device 0)

@@ -46,6 +46,18 @@ void hc_fe_mul_limbs(const uint32_t* a, const uint32_t* b, uint8_t* o) { fe x, y
 void hc_fe_sq_limbs(const uint32_t* a, uint8_t* o) { fe x; for (int i = 0; i < FE_LIMBS; i++) x.v[i] = a[i]; fe_out(o, fe_sq(x)); }
 void hc_fe_carry_limbs(const uint32_t* a, uint32_t* limbs_out, uint8_t* o) { fe x; for (int i = 0; i < FE_LIMBS; i++) x.v[i] = a[i]; fe c = fe_carry(x); for (int i = 0; i < FE_LIMBS; i++) limbs_out[i] = c.v[i]; fe_out(o, c); }
 void hc_fe_mul_out_limbs(const uint32_t* a, const uint32_t* b, uint32_t* limbs_out) { fe x, y; for (int i = 0; i < FE_LIMBS; i++) { x.v[i] = a[i]; y.v[i] = b[i]; } fe c = fe_mul(x, y); for (int i = 0; i < FE_LIMBS; i++) limbs_out[i] = c.v[i]; }
+// ... its siblings: the raw limbs the host branch returns, for the device test to hold the per-column device build to (tests/test_gpu_fe_forms.py)
+static fe fe_raw(const uint32_t* a) { fe x; for (int i = 0; i < FE_LIMBS; i++) x.v[i] = a[i]; return x; }
+static void fe_raw_out(uint32_t* o, const fe& x) { for (int i = 0; i < FE_LIMBS; i++) o[i] = x.v[i]; }
+void hc_fe_sq_out_limbs(const uint32_t* a, uint32_t* limbs_out) { fe_raw_out(limbs_out, fe_sq(fe_raw(a))); }
+void hc_fe_sqda_sq_out_limbs(const uint32_t* f, const uint32_t* a, const uint32_t* fb, uint32_t* h_out, uint32_t* hb_out) { fe h, hb; fe_sqda_sq(h, hb, fe_raw(f), fe_raw(a), fe_raw(fb)); fe_raw_out(h_out, h); fe_raw_out(hb_out, hb); }
+// k = 2, 3, 4: fe_sub, fe_sub3, fe_sub4 (f - g + k p)
+int hc_fe_sub_out_limbs(int k, const uint32_t* f, const uint32_t* g, uint32_t* limbs_out) {
+  if (k < 2 || k > 4) return 0;
+  fe_raw_out(limbs_out, k == 2 ? fe_sub(fe_raw(f), fe_raw(g)) : k == 3 ? fe_sub3(fe_raw(f), fe_raw(g)) : fe_sub4(fe_raw(f), fe_raw(g)));
+  return 1;
+}
+void hc_fe_neg_out_limbs(const uint32_t* f, uint32_t* limbs_out) { fe_raw_out(limbs_out, fe_neg(fe_raw(f))); }
 
 void hc_sc_reduce_wide(const uint8_t* a, uint8_t* o) { uint32_t w[16]; memcpy(w, a, 64); sc_out(o, sc_from_wide_words(w)); }
 void hc_sc_from_bytes(const uint8_t* a, uint8_t* o) { sc_out(o, sc_in(a)); }

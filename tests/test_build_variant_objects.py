@@ -17,3 +17,22 @@ def test_variants_link_every_host_object_of_the_product():
     for o in objs:
         assert o in make_line, (o, "not made by build_variant.sh")
         assert f'"$src/{o}"' in link_line, (o, "not linked by build_variant.sh")
+
+
+def test_variants_compile_every_hip_unit_of_the_product():
+    """... and every HIP unit of the Makefile's SRCS must be compiled by the script's loop (its objects are linked as build/<name>/*.o):
+    a variant without k_admit, k_copies, k_replay, ... lacks their launchers and does not load.  The units built with the range
+    kernel's flags in the product (Makefile: TUFLAGS := $(BITSFLAGS)) must take the script's BITS flags as well."""
+    mk = open(os.path.join(ROOT, "anonymous-credit-tokens_amd", "csrc", "Makefile")).read()
+    srcs = re.search(r"^SRCS := (.*)$", mk, re.M).group(1).split()
+    assert len(srcs) >= 16 and all(s.endswith(".hip") for s in srcs), srcs
+    for s in srcs:
+        assert os.path.exists(os.path.join(ROOT, "anonymous-credit-tokens_amd", "csrc", s)), s
+    sh = open(os.path.join(ROOT, "tools", "build_variant.sh")).read()
+    units = re.search(r"^for f in (.*?); do$", sh, re.M).group(1).split()
+    assert sorted(units) == sorted(s[:-4] for s in srcs), set(units) ^ set(s[:-4] for s in srcs)
+    assert '-c "$src/$f.hip" -o "$out/$f.o"' in sh and '"$out"/*.o' in sh
+    bits_units = sorted(o[:-2] for l in re.findall(r"^(.*): TUFLAGS := \$\(BITSFLAGS\)$", mk, re.M) for o in l.split() if not o.startswith("fast_"))
+    assert "k_spend_bits" in bits_units
+    bits_line = next(l for l in sh.splitlines() if "${BITS--DACT_FE_PAIR_ASM}" in l)
+    assert sorted(re.findall(r'"\$f" = (\w+)', bits_line)) == bits_units, (bits_line, bits_units)
