@@ -42,7 +42,7 @@ EXPORTS = [
     "act_ctx_set_host_threads", "act_host_usable_cpus", "act_host_hash_many", "act_host_parallel_for", "act_host_pool_stats", "act_ctx_streams_overlap", "act_ctx_set_pipeline_depth", "act_ctx_set_small_batch_max", "act_ctx_set_fixed_base_bits", "act_node_set_fixed_base_bits", "act_tuning_set", "act_build_has_ct_secret_tables", "act_ctx_fixed_base_bits", "act_last_error", "act_spend_proof_bytes", "act_prove_rng_bytes",
     "act_spend_transcript_bytes", "act_private_key_random", "act_pre_issuance_random_batch", "act_request_batch",
     "act_issue_batch", "act_issuance_to_credit_token_batch", "act_prove_spend_batch", "act_prove_spend_seeded_batch", "act_node_prove_spend_seeded_batch", "act_verify_spend_batch",
-    "act_refund_batch", "act_refund_to_credit_token_batch", "act_debug_last_spend_transcripts", "act_debug_scalarmult_batch", "act_debug_fixed_base_batch", "act_debug_fe_batch", "act_debug_secret_residue", "act_prof_enable",
+    "act_refund_batch", "act_refund_to_credit_token_batch", "act_debug_last_spend_transcripts", "act_debug_scalarmult_batch", "act_debug_fixed_base_batch", "act_debug_fe_batch", "act_debug_fixed_base_mf_batch", "act_debug_chain_ct_batch", "act_debug_secret_residue", "act_prof_enable",
     "act_prof_reset", "act_prof_kernel_count", "act_prof_kernel_name", "act_prof_get", "act_prof_get_busy", "act_ubench_mad_u64_u32", "act_ubench_random_read", "act_ubench_table_read",
     "act_cbor_size", "act_cbor_record_bytes", "act_cbor_encode_batch", "act_cbor_decode_batch", "act_cbor_read_batch", "act_ctx_set_wire_reader", "act_ctx_wire_stats", "act_node_set_wire_reader", "act_verify_spend_cbor_batch",
     "act_node_verify_spend_cbor_batch", "act_redeem_batch", "act_node_redeem_batch",
@@ -156,6 +156,8 @@ def load() -> C.CDLL:
     lib.act_debug_scalarmult_batch.argtypes = [vp, sz, i32, u8p, u8p, u8p, u8p]
     lib.act_debug_fixed_base_batch.argtypes = [vp, i32, sz, i32, u8p, u8p]
     lib.act_debug_fe_batch.argtypes = [vp, i32, i32, sz, u8p, u8p, u8p, u8p, u8p, u8p]
+    lib.act_debug_fixed_base_mf_batch.argtypes = [vp, i32, i32, sz, i32, u8p, u8p]
+    lib.act_debug_chain_ct_batch.argtypes = [vp, i32, sz, i32, u8p, u8p, u8p, u8p, u8p, u8p]
     lib.act_debug_secret_residue.argtypes = [vp, C.POINTER(sz)]
     for f in ("act_cbor_size", "act_cbor_record_bytes"):
         getattr(lib, f).argtypes = [vp, i32]
@@ -629,6 +631,24 @@ class Engine:
         p0, k0 = _in(scalars, 32 * n)
         self._ck(self.lib.act_debug_fixed_base_batch(self.ctx, base, n, MEM_HOST, p0, out.ctypes.data))
         return out.tobytes()
+
+    def debug_fixed_base_mf(self, base: int, scalars: bytes, block_threads: int = 64, out_lanes: int = 0, fill: int = 0) -> bytes:
+        """enc(s_i * B) for the fixed base 0..3 through the product of secret scalars (act_debug_fixed_base_mf_batch: the matrix-core
+        look-up over this context's table image), in blocks of 64 or 256 threads.  The result holds max(n, out_lanes) records, pre-filled
+        with `fill`: what lies past record n must come back as it went in."""
+        n = len(scalars) // 32; out = np.full(32 * max(n, out_lanes), fill, np.uint8)
+        p0, k0 = _in(scalars, 32 * n)
+        self._ck(self.lib.act_debug_fixed_base_mf_batch(self.ctx, base, block_threads, n, MEM_HOST, p0, out.ctypes.data))
+        return out.tobytes()
+
+    def debug_chain_ct(self, mode: int, points: bytes, scalars: bytes, scalars2: bytes = None):
+        """The address-free chains, one per lane (act_debug_chain_ct_batch): mode 0 chain_ct<1>, 1 the four chain_ct_quarter pieces
+        added, 2 chain_ct<2> with (scalars, scalars2).  Returns (status, out), in mode 2 (status, out, out2)."""
+        n = len(points) // 32; out = np.zeros(32 * n, np.uint8); st = np.zeros(n, np.uint8)
+        out2 = np.zeros(32 * n, np.uint8) if scalars2 is not None else None
+        p0, k0 = _in(points, 32 * n); p1, k1 = _in(scalars, 32 * n); p2, k2 = _in(scalars2, 32 * n)
+        self._ck(self.lib.act_debug_chain_ct_batch(self.ctx, mode, n, MEM_HOST, p0, p1, p2, out.ctypes.data, None if out2 is None else out2.ctypes.data, st.ctypes.data))
+        return (st.tobytes(), out.tobytes()) if out2 is None else (st.tobytes(), out.tobytes(), out2.tobytes())
 
     FE_OPS = ("mul", "sq", "mul2", "sq2", "sqda_sq", "carry", "sub", "sub3", "sub4", "neg")
 

@@ -160,6 +160,54 @@ int act_debug_fe_batch(act_ctx* c, int pair_build, int op, size_t n, const uint3
   return call.finish();
 }
 
+// out[i] = enc(scalars[i] * B), B = base 0..3, through the product of SECRET scalars: fixed_base_acc_mf over the context's own
+// matrix-core table image of B (k_debug_secret.hip), in blocks of 64 or 256 threads.  Chunked by max_batch as the hook above is; lane
+// i of a chunk is thread i of the launch, so with max_batch a multiple of 64 scalar i sits in lane i mod 64 of its wavefront.
+int act_debug_fixed_base_mf_batch(act_ctx* c, int base, int block_threads, size_t n, int mem, const uint8_t* scalars, uint8_t* out) {
+  if (!c || base < 0 || base > 3 || (block_threads != 64 && block_threads != 256) || (n && (!scalars || !out))) return ACT_ERR_ARG;
+  Call call(c, n);
+  HIPCK(c, hipSetDevice(c->device));
+  Slot& sl = c->slots[0];
+  for (size_t off = 0; off < n; off += c->max_batch) {
+    uint32_t m = (uint32_t)std::min(c->max_batch, n - off);
+    const uint8_t* d_s; uint8_t* d_o; int rc;
+    if ((rc = dev_in(c, sl, 0, mem, scalars + off * 32, (size_t)m * 32, &d_s))) return rc;
+    if ((rc = dev_out_begin(c, sl, 1, mem, out + off * 32, (size_t)m * 32, &d_o))) return rc;
+    launch_debug_fixed_base_mf(c->P.tab_mf[base], block_threads, d_s, m, d_o, sl.stream);
+    HIPCK(c, hipGetLastError());
+    if ((rc = dev_out_end(c, sl, mem, out + off * 32, d_o, (size_t)m * 32))) return rc;
+    HIPCK(c, hipStreamSynchronize(sl.stream));
+  }
+  return call.finish();
+}
+
+// The address-free variable-base chains, one per lane (k_debug_secret.hip): mode 0 out = enc(s P) by chain_ct<1>, 1 the same from the
+// four chain_ct_quarter pieces, 2 out = enc(s P) and out2 = enc(s2 P) by chain_ct<2>.  status 255 and zero records for a point that
+// does not decode.  scalars2 / out2 are read and written in mode 2 only.
+int act_debug_chain_ct_batch(act_ctx* c, int mode, size_t n, int mem, const uint8_t* points, const uint8_t* scalars, const uint8_t* scalars2, uint8_t* out, uint8_t* out2, uint8_t* status) {
+  if (!c || mode < 0 || mode > 2 || (n && (!points || !scalars || !out || !status || (mode == 2 && (!scalars2 || !out2))))) return ACT_ERR_ARG;
+  Call call(c, n);
+  HIPCK(c, hipSetDevice(c->device));
+  Slot& sl = c->slots[0];
+  for (size_t off = 0; off < n; off += c->max_batch) {
+    uint32_t m = (uint32_t)std::min(c->max_batch, n - off);
+    const size_t b = (size_t)m * 32;
+    const uint8_t *d_p, *d_s, *d_s2 = nullptr; uint8_t *d_o, *d_o2 = nullptr; int rc;
+    if ((rc = dev_in(c, sl, 0, mem, points + off * 32, b, &d_p))) return rc;
+    if ((rc = dev_in(c, sl, 1, mem, scalars + off * 32, b, &d_s))) return rc;
+    if (mode == 2 && (rc = dev_in(c, sl, 2, mem, scalars2 + off * 32, b, &d_s2))) return rc;
+    if ((rc = dev_out_begin(c, sl, 3, mem, out + off * 32, b, &d_o))) return rc;
+    if (mode == 2 && (rc = dev_out_begin(c, sl, 4, mem, out2 + off * 32, b, &d_o2))) return rc;
+    launch_debug_chain_ct(mode, d_p, d_s, d_s2, m, d_o, d_o2, sl.d_status, sl.stream);
+    HIPCK(c, hipGetLastError());
+    if ((rc = dev_out_end(c, sl, mem, out + off * 32, d_o, b))) return rc;
+    if (mode == 2 && (rc = dev_out_end(c, sl, mem, out2 + off * 32, d_o2, b))) return rc;
+    if ((rc = copy_status_out(c, sl, mem, status + off, m))) return rc;
+    HIPCK(c, hipStreamSynchronize(sl.stream));
+  }
+  return call.finish();
+}
+
 // Test hook: bytes that are not zero in the context's secret-bearing buffers (what finish_call wipes), read back to the host.
 int act_debug_secret_residue(act_ctx* c, size_t* nonzero_bytes) {
   if (!c || !nonzero_bytes) return ACT_ERR_ARG;

@@ -283,6 +283,10 @@ void launch_debug_fixed_base(FbTab tab, const uint8_t* scs, uint32_t n, uint8_t*
 enum DebugFeOp : int { DFE_MUL = 0, DFE_SQ, DFE_MUL2, DFE_SQ2, DFE_SQDA_SQ, DFE_CARRY, DFE_SUB, DFE_SUB3, DFE_SUB4, DFE_NEG, DFE_COUNT };
 void launch_debug_fe(int op, uint32_t n, const uint32_t* f, const uint32_t* g, const uint32_t* fb, const uint32_t* ga, uint32_t* h, uint32_t* hb, hipStream_t s);
 void launch_debug_fe_pair(int op, uint32_t n, const uint32_t* f, const uint32_t* g, const uint32_t* fb, const uint32_t* ga, uint32_t* h, uint32_t* hb, hipStream_t s);
+// k_debug_secret.hip: one product of a secret scalar per lane -- the matrix-core look-up over a table image in blocks of 64 or 256
+// threads, and the address-free chains (mode 0 chain_ct<1>, 1 the four chain_ct_quarter pieces added, 2 chain_ct<2>)
+void launch_debug_fixed_base_mf(const uint8_t* tab_mf, int block_threads, const uint8_t* scs, uint32_t n, uint8_t* out, hipStream_t s);
+void launch_debug_chain_ct(int mode, const uint8_t* pts, const uint8_t* scs, const uint8_t* scs2, uint32_t n, uint8_t* out, uint8_t* out2, uint8_t* status, hipStream_t s);
 void launch_spend_prep(const SpendArgs& a, hipStream_t s);
 void launch_spend_prep_role(const SpendArgs& a, int role /* 0 A, 1 B, 2 C, 3 join, 4 C1 (what k_spend_bits waits for), 5 C2 */, hipStream_t s);
 void launch_spend_enc_small(const SpendArgs& a, hipStream_t s);

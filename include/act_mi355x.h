@@ -966,6 +966,18 @@ int act_debug_fixed_base_batch(act_ctx *ctx, int base, size_t n, int mem, const 
  * op outside 0..9 or a missing array. */
 int act_debug_fe_batch(act_ctx *ctx, int pair_build, int op, size_t n, const uint32_t *f, const uint32_t *g, const uint32_t *fb,
                        const uint32_t *gb_or_a, uint32_t *h, uint32_t *hb);
+/* Debug / test hook: out[i] = enc(scalars[i] * B) for the fixed base B = 0..3 (g, h1, h2, h3) through the product every SECRET scalar
+ * takes in the default build: 37 signed 7-bit digits, entry |digit| of a 64-entry window picked on the matrix cores from this context's
+ * table image of B.  One product per lane, in blocks of block_threads = 64 or 256 threads (both shapes exist in the library), chunked
+ * by the context's max_batch: with max_batch a multiple of 64, scalar i runs in lane i mod 64 of its wavefront.  32-byte scalars,
+ * reduced mod l on load.  ACT_ERR_ARG for a base outside 0..3 or any other block_threads. */
+int act_debug_fixed_base_mf_batch(act_ctx *ctx, int base, int block_threads, size_t n, int mem, const uint8_t *scalars, uint8_t *out);
+/* Debug / test hook: the address-free variable-base chains of secret scalars, one per lane.  mode 0: out[i] = enc(scalars[i] *
+ * points[i]) by the one-scalar chain; mode 1: the same product as the sum of its four 64-bit quarters (the single-item calls' form);
+ * mode 2: out[i] as in mode 0 and out2[i] = enc(scalars2[i] * points[i]), both on one doubling chain.  scalars2 and out2 may be NULL
+ * in modes 0 and 1.  status[i] = 0, or 255 with zero records where points[i] does not decode.  ACT_ERR_ARG for any other mode. */
+int act_debug_chain_ct_batch(act_ctx *ctx, int mode, size_t n, int mem, const uint8_t *points, const uint8_t *scalars,
+                             const uint8_t *scalars2, uint8_t *out, uint8_t *out2, uint8_t *status);
 
 /* Measurement hook: A/B switches and size overrides of tools/ and tests/ (csrc/kernels.h TuneKey: "no_mapped_reads", "no_fused_tiny",
  * "no_taper", "no_wide_sign", "no_wide_prove", "no_wide_client", "no_lds_isolation", "no_stream_probe", "small_sub", "small_in_flight",

@@ -216,6 +216,10 @@ extern "C" {
     // test hook: one field operation per lane on raw 9-limb operands, in the per-column or the range kernel's build of the field code
     fn act_debug_fe_batch(ctx: *mut ActCtx, pair_build: c_int, op: c_int, n: usize, f: *const u32, g: *const u32, fb: *const u32, gb_or_a: *const u32,
                           h: *mut u32, hb: *mut u32) -> c_int;
+    // test hooks: one product of a secret scalar per lane -- the matrix-core look-up over the context's table image, the address-free chains
+    fn act_debug_fixed_base_mf_batch(ctx: *mut ActCtx, base: c_int, block_threads: c_int, n: usize, mem: c_int, scalars: *const u8, out: *mut u8) -> c_int;
+    fn act_debug_chain_ct_batch(ctx: *mut ActCtx, mode: c_int, n: usize, mem: c_int, points: *const u8, scalars: *const u8, scalars2: *const u8,
+                                out: *mut u8, out2: *mut u8, status: *mut u8) -> c_int;
 }
 
 /// ACT_MI355X_DEVICES = "0,1,2,3,4,5,6,7" (default: device 0)

@@ -208,6 +208,15 @@ extern "C" int hc_chain_ct2(const uint8_t* pt, const uint8_t* s0, const uint8_t*
   ristretto_encode(r, acc[0]); st(o0, r); ristretto_encode(r, acc[1]); st(o1, r);
   return 1;
 }
+// the single-item calls' form of the same product (msm.h chain_ct_quarter): the four 33-step pieces, added up and encoded
+extern "C" int hc_chain_ct_quarters(const uint8_t* pt, const uint8_t* s0, uint8_t* o0) {
+  uint32_t w[8], r[8]; ld(w, pt); ge p; if (!ristretto_decode(p, w)) return 0;
+  const sc s = sc_in(s0);
+  ge sum = chain_ct_quarter(p, s, 0);
+  for (int q = 1; q < 4; q++) sum = ge_add(sum, chain_ct_quarter(p, s, q));
+  ristretto_encode(r, sum); st(o0, r);
+  return 1;
+}
 // fixed_base_acc_ct over a CT table of `pt` built here (T[pos][e-1] = e * 16^pos * pt, the recurrence of k_build_table_ct)
 extern "C" int hc_fixed_base_ct(const uint8_t* pt, const uint8_t* s0, uint8_t* o0) {
   uint32_t w[8], r[8]; ld(w, pt); ge b; if (!ristretto_decode(b, w)) return 0;

@@ -133,6 +133,9 @@ def test_group_and_msm_shapes(hostcheck):
         for fn in ("hc_chain2", "hc_chain2u", "hc_chain_bu", "hc_chain_bu_pre", "hc_chain_b2", "hc_chain_ct2"):      # radix-4 / radix-4, radix-4 / NAF, buckets / NAF (twice), buckets / buckets, the ct build's address-free form
             ok, o0, o1 = call(hc, fn, e, m.sc_bytes(s), m.sc_bytes(m.ELL - 1 - s), nout=2)
             assert o0 == m.ristretto_encode(m.pt_mul(m.BASEPOINT, s)) and o1 == m.ristretto_encode(m.pt_mul(m.BASEPOINT, m.ELL - 1 - s)), (fn, s)
+        for v in (s, m.ELL - 1 - s):                                   # ... and the four-quarter form of the address-free chain
+            ok, q = call(hc, "hc_chain_ct_quarters", e, m.sc_bytes(v))
+            assert ok and q == m.ristretto_encode(m.pt_mul(m.BASEPOINT, v)), ("hc_chain_ct_quarters", v)
     # width-3 NAF recoding of the wave-uniform scalar (msm.h naf3_next): runs of 1s, alternating digits, carries
     # rippling to the top, and values in [l, 2^253) that only the raw recoder (not the reduced scalar type) can see
     pats = [int(c * 63, 16) for c in "1357bdf"] + [(1 << 253) - 1, (1 << 253) - 3, (1 << 252) + (1 << 251) + 3,
@@ -145,6 +148,30 @@ def test_group_and_msm_shapes(hostcheck):
     for fn in ("hc_chain2", "hc_chain2u", "hc_chain_bu", "hc_chain_bu_pre", "hc_chain_b2", "hc_chain_ct2"):   # identity base
         ok, o0, o1 = call(hc, fn, bytes(32), m.sc_bytes(5), m.sc_bytes(m.ELL - 7), nout=2)
         assert o0 == bytes(32) and o1 == bytes(32), fn
+
+
+def test_chain_ct_quarters(hostcheck, oracle):
+    """msm.h chain_ct_quarter, which nothing ran on the host: the four 33-step pieces of s P, added, against the plain radix-4 chain
+    (chain<1>), the address-free one (chain_ct<2>) and the C oracle, on the chain scalars of tests/secret_fb_cases.py -- each quarter all
+    ones, so that a piece's 33rd step is the carry; 2^(64 q) +- 1 at the pieces' boundaries; the ends of the scalar range -- over
+    three points, and over the identity."""
+    import secret_fb_cases as sf
+    hc = hostcheck
+    g = load_golden("primitives.json")
+    pts = [bytes.fromhex(g["generator_multiples"][1]), bytes.fromhex(g["from_uniform_bytes"][0]["encoding"]), bytes.fromhex(g["from_uniform_bytes"][1]["encoding"])]
+    scs = sf.chain_scalars()
+    assert len(scs) > 500 and all(sf.value(s) in [sf.value(x) for x in scs] for s in (v.to_bytes(32, "little") for v in sf.quarter_scalars()))
+    for e in pts:
+        for i, s in enumerate(scs):
+            want = oracle.mul(e, m.sc_bytes(int.from_bytes(s, "little")))
+            ok, q = call(hc, "hc_chain_ct_quarters", e, s)
+            ok1, o1 = call(hc, "hc_chain1", e, s)
+            ok2, c0, c1 = call(hc, "hc_chain_ct2", e, s, scs[(i + 7) % len(scs)], nout=2)
+            assert ok and ok1 and ok2 and q == o1 == c0 == want, (e.hex(), s.hex())
+            assert c1 == oracle.mul(e, m.sc_bytes(int.from_bytes(scs[(i + 7) % len(scs)], "little"))), (e.hex(), s.hex())
+    for s in scs[:16] + [v.to_bytes(32, "little") for v in sf.quarter_scalars()]:
+        ok, q = call(hc, "hc_chain_ct_quarters", bytes(32), s)
+        assert ok and q == bytes(32), s.hex()
 
 
 def test_batched_double_and_compress(hostcheck):
