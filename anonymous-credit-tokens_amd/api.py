@@ -307,17 +307,18 @@ class PrivateKey(_Cbor):
 
     # ---- replayable redemption: a retried SpendProof gets its Refund again ----------------------------------
     def redeem_replay_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", proofs: Sequence["SpendProof"], nonce_key: bytes,
-                            admit: bool = False, charges: Sequence = None, unique: bool = False, returned: Sequence = None) -> Tuple[list, list]:
+                            admit: bool = False, charges: Sequence = None, unique: bool = False, returned: Sequence = None, binds: Sequence = None) -> Tuple[list, list]:
         """redeem_batch without a generator: the nonces are derived from `nonce_key` (32 secret bytes the issuer keeps), this key, the
         nullifier and K', and `receipts` (a second NullifierDb) remembers which K' a nullifier was spent for -- a proof that is sent
-        again gets the same Refund, byte for byte, instead of DoubleSpendError.  admit / charges / unique / returned: Keyring.redeem_replay_batch.  -> (results, replayed flags)"""
-        res, _, replayed = Keyring([self]).redeem_replay_batch(params, db, receipts, proofs, nonce_key, admit=admit, charges=charges, unique=unique, returned=returned)
+        again gets the same Refund, byte for byte, instead of DoubleSpendError.  admit / charges / unique / returned / binds: Keyring.redeem_replay_batch.  -> (results, replayed flags)"""
+        res, _, replayed = Keyring([self]).redeem_replay_batch(params, db, receipts, proofs, nonce_key, admit=admit, charges=charges, unique=unique, returned=returned,
+                                                               binds=binds)
         return res, replayed
 
     def redeem_replay_cbor_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", msgs: Sequence[bytes], nonce_key: bytes, nbits: int = L,
-                                 admit: bool = False, charges: Sequence = None, unique: bool = False, returned: Sequence = None) -> Tuple[list, list]:
+                                 admit: bool = False, charges: Sequence = None, unique: bool = False, returned: Sequence = None, binds: Sequence = None) -> Tuple[list, list]:
         res, _, replayed = Keyring([self]).redeem_replay_cbor_batch(params, db, receipts, msgs, nonce_key, nbits, admit=admit, charges=charges, unique=unique,
-                                                                    returned=returned)
+                                                                    returned=returned, binds=binds)
         return res, replayed
 
     def redeem_return_replay_unique_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", proofs: Sequence["SpendProof"], nonce_key: bytes,
@@ -332,20 +333,26 @@ class PrivateKey(_Cbor):
         return res, replayed
 
     # ---- reserve and settle: record a spend now, sign its partial refund later -----------------------------------
-    def reserve_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", proofs: Sequence["SpendProof"], charges: Sequence = None) -> Tuple[list, list]:
+    def reserve_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", proofs: Sequence["SpendProof"], charges: Sequence = None,
+                      binds: Sequence = None) -> Tuple[list, list]:
         """Keyring.reserve_batch with this key alone.  -> (results: a Reservation or an Error per proof, replayed flags)"""
-        return Keyring([self]).reserve_batch(params, db, receipts, proofs, charges=charges)
+        return Keyring([self]).reserve_batch(params, db, receipts, proofs, charges=charges, binds=binds)
 
-    def reserve_cbor_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", msgs: Sequence[bytes], nbits: int = L, charges: Sequence = None) -> Tuple[list, list]:
-        return Keyring([self]).reserve_cbor_batch(params, db, receipts, msgs, nbits, charges=charges)
+    def reserve_cbor_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", msgs: Sequence[bytes], nbits: int = L, charges: Sequence = None,
+                           binds: Sequence = None) -> Tuple[list, list]:
+        return Keyring([self]).reserve_cbor_batch(params, db, receipts, msgs, nbits, charges=charges, binds=binds)
 
     def settle_batch(self, params: Params, receipts: "NullifierDb", reservations: Sequence["Reservation"], returned: Sequence, nonce_key: bytes, nbits: int = L,
                      cbor: bool = False) -> Tuple[list, list]:
         """Keyring.settle_batch with this key alone.  -> (results, settled-before flags)"""
         return Keyring([self]).settle_batch(params, receipts, reservations, returned, nonce_key, nbits=nbits, cbor=cbor)
 
-    def verify_spend_batch(self, params: Params, proofs: Sequence["SpendProof"]) -> bytes:
+    def verify_spend_batch(self, params: Params, proofs: Sequence["SpendProof"], binds: Sequence = None) -> bytes:
+        """binds (one 32-byte request binding per proof): Keyring.verify_spend_batch with this key alone -- a ring of one key is the
+        bound one-key call"""
         nbits = proofs[0].nbits if proofs else L
+        if binds is not None:
+            return Keyring([self]).verify_spend_batch(params, proofs, binds=binds)[0]
         return params.engine(nbits).verify_spend(self.record, b"".join(p.record for p in proofs))
 
 
@@ -384,9 +391,21 @@ class Keyring:
     def _indices(st, ok):
         return [ok[i] if ok[i] != capi.KEY_NONE else None for i in range(len(st))]
 
-    def verify_spend_batch(self, params: Params, proofs: Sequence["SpendProof"]) -> Tuple[bytes, list]:
+    @staticmethod
+    def _binds(binds, n):
+        """request bindings (INTEGRATION.md "request binding"): one 32-byte value per lane -> n * 32 bytes"""
+        if len(binds) != n or any(len(b) != 32 for b in binds):
+            raise ValueError("binds: one 32-byte request binding per proof")
+        return b"".join(bytes(b) for b in binds)
+
+    def verify_spend_batch(self, params: Params, proofs: Sequence["SpendProof"], binds: Sequence = None) -> Tuple[bytes, list]:
+        """binds (one 32-byte request binding per proof; act_verify_spend_keyring_bound_batch): proof i verifies only if it was made
+        with binds[i] (CreditToken.prove_spend(..., bind=)); a proof made without a binding does not verify under any"""
         nbits = proofs[0].nbits if proofs else L
-        st, ok = params.engine(nbits).verify_spend_keyring(self._records(), b"".join(p.record for p in proofs))
+        if binds is not None:
+            st, ok = params.engine(nbits).verify_spend_keyring(self._records(), b"".join(p.record for p in proofs), bind=self._binds(binds, len(proofs)))
+        else:
+            st, ok = params.engine(nbits).verify_spend_keyring(self._records(), b"".join(p.record for p in proofs))
         return st, self._indices(st, ok)
 
     def refund_batch(self, params: Params, proofs: Sequence["SpendProof"], rng, sign_with=None) -> Tuple[list, list]:
@@ -469,7 +488,7 @@ class Keyring:
         return [out[i] if st[i] == 0 else _wire_error(st[i]) for i in range(len(msgs))], self._indices(st, ok)
 
     def redeem_replay_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", proofs: Sequence["SpendProof"], nonce_key: bytes, sign_with=None,
-                            admit: bool = False, charges: Sequence = None, unique: bool = False, returned: Sequence = None) -> Tuple[list, list, list]:
+                            admit: bool = False, charges: Sequence = None, unique: bool = False, returned: Sequence = None, binds: Sequence = None) -> Tuple[list, list, list]:
         """redeem_batch made retry-safe (act_redeem_replay_batch): no generator -- the nonces are derived from `nonce_key`, the key a
         lane is signed with, the nullifier and K' -- and `receipts`, a second NullifierDb, records for which K' every nullifier was
         spent.  A proof that is sent again (same ring key to sign with, same nonce_key) gets the same Refund, byte for byte; another
@@ -485,10 +504,25 @@ class Keyring:
         sent again with the same amount gets the same RefundReturn, with another amount DoubleSpendError -- derive the amount from the
         request, or remember it.  The counts are capi.RETURN_REPLAY_COUNTS.  Not with unique=True (ValueError): that form is a method
         of its own, redeem_return_replay_unique_batch.
+        binds (one 32-byte request binding per proof; with admit=True; act_redeem_return_replay_bound_batch): proof i is verified under
+        binds[i] -- a proof made with another binding, or with none, is Error 7 and nothing is recorded or signed for it; the binding
+        enters neither the receipt nor the nonces, so a retry under the same binding gets the same bytes.  Entry i is a RefundReturn
+        (over 0 where `returned` is None).  Not with unique=True (ValueError): the bound calls have no unique form.
         -> (results, matched ring indices, replayed flags); `self.last_replay_counts`: the call's counts."""
         nbits = proofs[0].nbits if proofs else L
         if returned is not None and unique:
             raise ValueError("a copy may name another amount than its leader: the unique form with returned amounts is redeem_return_replay_unique_batch")
+        if binds is not None:
+            if unique:
+                raise ValueError("request binding: the bound calls have no unique form")
+            if not admit and returned is None:
+                raise ValueError("request binding: the bound redeem call is an admission call: admit=True")
+            cc = b"".join(scalar(c) for c in charges) if charges is not None else None
+            tt = b"".join(scalar(t) for t in returned) if returned is not None else None
+            st, out, ok, rep, self.last_replay_counts = params.engine(nbits).redeem_return_replay(
+                db.set, receipts.set, self._records(), b"".join(p.record for p in proofs), nonce_key, self._sign_key(sign_with), key_epochs=self.epochs, charges=cc,
+                returned=tt, bind=self._binds(binds, len(proofs)))
+            return [RefundReturn(out[160 * i:160 * i + 160]) if st[i] == 0 else Error(st[i]) for i in range(len(proofs))], self._indices(st, ok), [bool(r) for r in rep]
         admit = admit or returned is not None
         if charges is not None and not admit:
             raise ValueError("charges are compared by the admission screen: admit=True")
@@ -510,13 +544,26 @@ class Keyring:
         return [Refund(out[128 * i:128 * i + 128]) if st[i] == 0 else Error(st[i]) for i in range(len(proofs))], self._indices(st, ok), [bool(r) for r in rep]
 
     def redeem_replay_cbor_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", msgs: Sequence[bytes], nonce_key: bytes, nbits: int = L,
-                                 sign_with=None, admit: bool = False, charges: Sequence = None, unique: bool = False, returned: Sequence = None) -> Tuple[list, list, list]:
+                                 sign_with=None, admit: bool = False, charges: Sequence = None, unique: bool = False, returned: Sequence = None,
+                                 binds: Sequence = None) -> Tuple[list, list, list]:
         """the same on wire bytes (act_redeem_cbor_replay_batch; admit=True: act_redeem_cbor_admit_replay_batch): a retry may be another
         CBOR spelling of the same proof.  unique=True (with admit=True): act_redeem_cbor_admit_replay_unique_batch -- a copy is a message
         of the same length and the same bytes; another spelling is verified on its own.  returned: act_redeem_cbor_return_replay_batch --
-        entry i is a CBOR RefundReturn message (implies admit=True; not with unique=True: redeem_return_replay_unique_cbor_batch)"""
+        entry i is a CBOR RefundReturn message (implies admit=True; not with unique=True: redeem_return_replay_unique_cbor_batch).
+        binds: as in redeem_replay_batch (act_redeem_cbor_return_replay_bound_batch); entry i is a CBOR RefundReturn message"""
         if returned is not None and unique:
             raise ValueError("a copy may name another amount than its leader: the unique form with returned amounts is redeem_return_replay_unique_cbor_batch")
+        if binds is not None:
+            if unique:
+                raise ValueError("request binding: the bound calls have no unique form")
+            if not admit and returned is None:
+                raise ValueError("request binding: the bound redeem call is an admission call: admit=True")
+            cc = b"".join(scalar(c) for c in charges) if charges is not None else None
+            tt = b"".join(scalar(t) for t in returned) if returned is not None else None
+            st, out, ok, rep, self.last_replay_counts = params.engine(nbits).redeem_cbor_return_replay(
+                db.set, receipts.set, self._records(), list(msgs), nonce_key, self._sign_key(sign_with), key_epochs=self.epochs, charges=cc, returned=tt,
+                bind=self._binds(binds, len(msgs)))
+            return [out[i] if st[i] == 0 else _wire_error(st[i]) for i in range(len(msgs))], self._indices(st, ok), [bool(r) for r in rep]
         admit = admit or returned is not None
         if charges is not None and not admit:
             raise ValueError("charges are compared by the admission screen: admit=True")
@@ -571,24 +618,32 @@ class Keyring:
         res = [Reservation(out[96 * i:96 * i + 96], ok[i]) if st[i] == 0 else Error(st[i]) for i in range(len(st))]
         return res, [bool(r) for r in rep]
 
-    def reserve_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", proofs: Sequence["SpendProof"], charges: Sequence = None) -> Tuple[list, list]:
+    def reserve_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", proofs: Sequence["SpendProof"], charges: Sequence = None,
+                      binds: Sequence = None) -> Tuple[list, list]:
         """The first half of the metered-service step (act_redeem_reserve_batch): redeem_replay_batch(..., admit=True) WITHOUT the
         signature.  Every proof is screened (`charges`, optional: Error 250 where s differs; a spent nullifier that is not this proof's
         own reservation: DoubleSpendError, unverified), verified and RECORDED as spent, and entry i is a Reservation -- what the service
         keeps beside the job until it knows what the work cost.  No nonce_key, no generator: nothing is signed.  A proof that is sent
         again gets the same Reservation and replayed[i] = True: the job for it exists already -- never start a second one.
+        binds (one 32-byte request binding per proof; act_redeem_reserve_bound_batch): proof i is verified under binds[i]; a recorded
+        reservation's proof sent again beside ANOTHER request is Error 7, not a replay.
         -> (results, replayed flags); `self.last_reserve_counts`: the call's counts (capi.RESERVE_COUNTS)."""
         nbits = proofs[0].nbits if proofs else L
         cc = b"".join(scalar(c) for c in charges) if charges is not None else None
+        kw = dict(bind=self._binds(binds, len(proofs))) if binds is not None else {}
         st, out, ok, rep, self.last_reserve_counts = params.engine(nbits).redeem_reserve(db.set, receipts.set, self._records(), b"".join(p.record for p in proofs),
-                                                                                        key_epochs=self.epochs, charges=cc)
+                                                                                        key_epochs=self.epochs, charges=cc, **kw)
         return self._reservations(st, out, ok, rep)
 
-    def reserve_cbor_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", msgs: Sequence[bytes], nbits: int = L, charges: Sequence = None) -> Tuple[list, list]:
+    def reserve_cbor_batch(self, params: Params, db: "NullifierDb", receipts: "NullifierDb", msgs: Sequence[bytes], nbits: int = L, charges: Sequence = None,
+                           binds: Sequence = None) -> Tuple[list, list]:
         """the same on CBOR SpendProof messages (act_redeem_cbor_reserve_batch): a retry may be another spelling of the same proof.  Entry i
-        is a Reservation, a CborError or an Error -- the reservation has no wire type, it never goes to a client"""
+        is a Reservation, a CborError or an Error -- the reservation has no wire type, it never goes to a client.  binds: as in
+        reserve_batch (act_redeem_cbor_reserve_bound_batch)"""
         cc = b"".join(scalar(c) for c in charges) if charges is not None else None
-        st, out, ok, rep, self.last_reserve_counts = params.engine(nbits).redeem_cbor_reserve(db.set, receipts.set, self._records(), list(msgs), key_epochs=self.epochs, charges=cc)
+        kw = dict(bind=self._binds(binds, len(msgs))) if binds is not None else {}
+        st, out, ok, rep, self.last_reserve_counts = params.engine(nbits).redeem_cbor_reserve(db.set, receipts.set, self._records(), list(msgs), key_epochs=self.epochs, charges=cc,
+                                                                                             **kw)
         res, replayed = self._reservations(st, out, ok, rep)
         return [r if st[i] == 0 else _wire_error(st[i]) for i, r in enumerate(res)], replayed
 
@@ -669,9 +724,15 @@ class CreditToken(_Cbor):
     def credits(self) -> bytes:
         return self.record[128:160]
 
-    def prove_spend(self, params: Params, s, rng, nbits: int = L) -> Tuple["SpendProof", "PreRefund"]:
+    def prove_spend(self, params: Params, s, rng, nbits: int = L, bind: bytes = None) -> Tuple["SpendProof", "PreRefund"]:
+        """bind (32 bytes, typically a hash of the request this spend pays for; act_prove_spend_bound_batch): the bytes enter the
+        proof's challenge, and the issuer verifies it under the same bytes (binds= of the Keyring / PrivateKey calls).  A bound proof
+        is not a crate SpendProof: the crate's refund and every call here without its binding reject it."""
         e = params.engine(nbits)
-        st, proof, pre = e.prove_spend(self.record, scalar(s), rng.fill_bytes(e.prove_rng_bytes))
+        if bind is not None and len(bind) != 32:
+            raise ValueError("bind: 32 bytes")
+        kw = dict(bind=bytes(bind)) if bind is not None else {}
+        st, proof, pre = e.prove_spend(self.record, scalar(s), rng.fill_bytes(e.prove_rng_bytes), **kw)
         if st[0]:
             raise Error(st[0])
         return SpendProof(proof, nbits), PreRefund(pre)

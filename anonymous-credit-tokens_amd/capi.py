@@ -75,6 +75,8 @@ EXPORTS = [
     "act_redeem_return_replay_batch", "act_redeem_cbor_return_replay_batch", "act_replay_derive_return_batch",
     "act_redeem_return_replay_unique_batch", "act_redeem_cbor_return_replay_unique_batch",
     "act_redeem_reserve_batch", "act_redeem_cbor_reserve_batch", "act_redeem_settle_batch", "act_redeem_cbor_settle_batch",
+    "act_prove_spend_bound_batch", "act_verify_spend_keyring_bound_batch", "act_redeem_return_replay_bound_batch", "act_redeem_cbor_return_replay_bound_batch",
+    "act_redeem_reserve_bound_batch", "act_redeem_cbor_reserve_bound_batch",
     "act_ctx_host_hash_stats", "act_ctx_set_tiny_calls", "act_node_set_balance", "act_node_device_stats", "act_node_balance_state", "act_debug_set_slowdown", "act_debug_fail_next_signs",
 ]
 CBOR_TYPES = {"IssuanceRequest": 1, "IssuanceResponse": 2, "SpendProof": 3, "Refund": 4, "PrivateKey": 5, "PublicKey": 6,
@@ -83,6 +85,9 @@ CBOR_TYPES = {"IssuanceRequest": 1, "IssuanceResponse": 2, "SpendProof": 3, "Ref
 
 class ActError(RuntimeError):
     pass
+
+
+_UNBOUND = object()      # request binding: "no bind argument" (the unbound call); bind=None is the bound call with a NULL pointer
 
 
 def build(jobs: int = 8) -> str:
@@ -296,6 +301,13 @@ def load() -> C.CDLL:
     # reservation records, key indices and amounts in, RefundReturn records or messages out (ACT_SETTLE_COUNTS values)
     lib.act_redeem_reserve_batch.argtypes = [vp, vp, vp, sz, i32, u8p, i32, u32p, u8p, u8p, u8p, u8p, u8p, u8p, u64p]
     lib.act_redeem_cbor_reserve_batch.argtypes = [vp, vp, vp, sz, i32, u8p, i32, u32p, u8p, vp, u8p, u8p, u8p, u8p, u8p, u64p]
+    # request binding: the signature of the call each extends, with bind directly behind the proof or message arguments
+    lib.act_prove_spend_bound_batch.argtypes = [vp, sz, i32, u8p, u8p, u8p, u8p, u8p, u8p, u8p]
+    lib.act_verify_spend_keyring_bound_batch.argtypes = [vp, sz, i32, u8p, i32, u8p, u8p, u8p, u8p, u8p]
+    lib.act_redeem_return_replay_bound_batch.argtypes = [vp, vp, vp, sz, i32, u8p, i32, u32p, i32, u8p, u8p, u8p, u8p, u8p, u8p, u8p, u8p, u8p, u64p]
+    lib.act_redeem_cbor_return_replay_bound_batch.argtypes = [vp, vp, vp, sz, i32, u8p, i32, u32p, i32, u8p, vp, u8p, u8p, u8p, u8p, u8p, u8p, u8p, u8p, u64p]
+    lib.act_redeem_reserve_bound_batch.argtypes = [vp, vp, vp, sz, i32, u8p, i32, u32p, u8p, u8p, u8p, u8p, u8p, u8p, u8p, u64p]
+    lib.act_redeem_cbor_reserve_bound_batch.argtypes = [vp, vp, vp, sz, i32, u8p, i32, u32p, u8p, vp, u8p, u8p, u8p, u8p, u8p, u8p, u64p]
     lib.act_redeem_settle_batch.argtypes = [vp, vp, sz, i32, u8p, i32, u32p, i32, u8p, u8p, u8p, u8p, u8p, u8p, u8p, u64p]
     lib.act_redeem_cbor_settle_batch.argtypes = lib.act_redeem_settle_batch.argtypes
     lib.act_replay_derive_return_batch.argtypes = [vp, sz, i32, u8p, i32, u8p, u8p, u8p, sz, u8p, u8p, u8p, u8p, u8p]
@@ -577,10 +589,15 @@ class Engine:
         self._ck(self.lib.act_issuance_to_credit_token_batch(self.ctx, n, MEM_HOST, p0, pw, p1, p2, out.ctypes.data, st.ctypes.data))
         return st.tobytes(), out.tobytes()
 
-    def prove_spend(self, tok: bytes, s: bytes, rng: bytes):
+    def prove_spend(self, tok: bytes, s: bytes, rng: bytes, bind=_UNBOUND):
+        """bind given (32 bytes a lane, or None: NULL): act_prove_spend_bound_batch -- the bytes enter each proof's challenge hash"""
         n = len(tok) // 160; out = np.zeros(self.proof_bytes * n, np.uint8); pr = np.zeros(96 * n, np.uint8); st = np.zeros(n, np.uint8)
         p0, k0 = _in(tok, 160 * n); p1, k1 = _in(s, 32 * n); p2, k2 = _in(rng, self.prove_rng_bytes * n)
-        self._ck(self.lib.act_prove_spend_batch(self.ctx, n, MEM_HOST, p0, p1, p2, out.ctypes.data, pr.ctypes.data, st.ctypes.data))
+        if bind is _UNBOUND:
+            self._ck(self.lib.act_prove_spend_batch(self.ctx, n, MEM_HOST, p0, p1, p2, out.ctypes.data, pr.ctypes.data, st.ctypes.data))
+        else:
+            pb, kb = _in(bind, 32 * n) if bind is not None else (None, None)
+            self._ck(self.lib.act_prove_spend_bound_batch(self.ctx, n, MEM_HOST, p0, p1, p2, pb, out.ctypes.data, pr.ctypes.data, st.ctypes.data))
         return st.tobytes(), out.tobytes(), pr.tobytes()
 
     def prove_spend_seeded(self, tok: bytes, s: bytes, seed: bytes, first_lane: int = 0):
@@ -789,12 +806,18 @@ class Engine:
             self._ck(self.lib.act_redeem_cbor_batch(self.ctx, nullifier_set.h, n, mem, ps, p_cbor, p_offsets or None, p_rng, rng_mode, p_out, p_status))
 
     # ---- key rotation: one batch against an ordered ring of issuer keys (act_*_keyring_batch; keys = list of 64-byte sk) ----------
-    def verify_spend_keyring(self, keys, proofs: bytes, want_kprime: bool = False):
-        """-> (statuses, out_key bytes: the ring index every accepted lane verified under, KEY_NONE elsewhere[, enc(K')])"""
+    def verify_spend_keyring(self, keys, proofs: bytes, want_kprime: bool = False, bind=_UNBOUND):
+        """-> (statuses, out_key bytes: the ring index every accepted lane verified under, KEY_NONE elsewhere[, enc(K')]).  bind given
+        (32 bytes a lane, or None: NULL): act_verify_spend_keyring_bound_batch"""
         n = len(proofs) // self.proof_bytes; st = np.zeros(n, np.uint8); ok = np.zeros(n, np.uint8)
         kp = np.zeros(32 * n, np.uint8) if want_kprime else None
         pk, kk = _in(b"".join(keys)); p0, k0 = _in(proofs, self.proof_bytes * n)
-        self._ck(self.lib.act_verify_spend_keyring_batch(self.ctx, n, MEM_HOST, pk, len(keys), p0, st.ctypes.data, ok.ctypes.data, kp.ctypes.data if want_kprime else None))
+        if bind is _UNBOUND:
+            self._ck(self.lib.act_verify_spend_keyring_batch(self.ctx, n, MEM_HOST, pk, len(keys), p0, st.ctypes.data, ok.ctypes.data, kp.ctypes.data if want_kprime else None))
+        else:
+            pb, kb = _in(bind, 32 * n) if bind is not None else (None, None)
+            self._ck(self.lib.act_verify_spend_keyring_bound_batch(self.ctx, n, MEM_HOST, pk, len(keys), p0, pb, st.ctypes.data, ok.ctypes.data,
+                                                                   kp.ctypes.data if want_kprime else None))
         return (st.tobytes(), ok.tobytes(), kp.tobytes()) if want_kprime else (st.tobytes(), ok.tobytes())
 
     def refund_sign_keyring(self, keys, key_index: bytes, kprime: bytes, status_in: bytes, rng: bytes, rng_mode: int = RNG_SEQUENTIAL):
@@ -870,7 +893,9 @@ class Engine:
     def keyring_ptr(self, fn: str, keys, n: int, mem: int, **p):
         """the ring calls on raw pointers of either kind (device-memory callers): fn = verify / sign / redeem / redeem_cbor"""
         pk, kk = _in(b"".join(keys)); nk = len(keys)
-        if fn == "verify":
+        if fn == "verify" and "bind" in p:      # request binding (0 / None: NULL)
+            self._ck(self.lib.act_verify_spend_keyring_bound_batch(self.ctx, n, mem, pk, nk, p["proofs"], p["bind"] or None, p["status"], p["out_key"], p.get("kprime") or None))
+        elif fn == "verify":
             self._ck(self.lib.act_verify_spend_keyring_batch(self.ctx, n, mem, pk, nk, p["proofs"], p["status"], p["out_key"], p.get("kprime") or None))
         elif fn == "sign":
             self._ck(self.lib.act_refund_sign_keyring_batch(self.ctx, n, mem, pk, nk, p["key_index"], p["kprime"], p["status_in"], p["rng"], p["rng_mode"], p["out"], p["status"]))
@@ -903,27 +928,32 @@ class Engine:
         with raw; raw=None: what p asks for, where the kind's _ptr method honours it"""
         stem, names, unique_names, _, _, has_charges, has_returned, replay, honours_raw = self._FAMILY[kind]
         raw = (honours_raw and bool(p.get("raw"))) if raw is None else raw; unique = kind != "replay" and bool(p.get("unique")); wire = fn != "redeem"
+        bound = "bind" in p      # request binding: p["bind"] = n * 32 bytes behind the proofs or messages (0 / None: NULL)
+        if bound and (kind != "return_replay" or unique):
+            raise ActError("request binding: only the return-replay and reserve calls have a bound form, and it has no unique form")
         pk, kk = _in(b"".join(keys)); nk = len(keys)
         ke = _epoch_table(p["key_epochs"], nk) if p.get("key_epochs") is not None else None
         names = unique_names if unique else names
         cnt = (C.c_uint64 * len(names))()
         args = [self.ctx, p["set"].h] + ([p["receipts"].h] if replay else []) + [n, mem, pk, nk, ke.ctypes.data if ke is not None else None, p.get("sign_key", SIGN_MATCHED)]
         args += [p["cbor"], p.get("offsets") or None] if wire else [p["proofs"]]
+        args += [p["bind"] or None] if bound else []
         args += ([p.get("charges") or None] if has_charges else []) + ([p.get("returned") or None] if has_returned else [])
         if replay:
             pn, kn = _in(p["nonce_key"], 32)
             args += [pn, p["out"], p["status"], p["out_key"], p.get("replayed") or None, cnt]
         else:
             args += [p["rng"], p["rng_mode"], p["out"], p["status"], p["out_key"], cnt]
-        rc = getattr(self.lib, "act_redeem_%s%s%s_batch" % ("cbor_" if wire else "", stem, "_unique" if unique else ""))(*args)
+        rc = getattr(self.lib, "act_redeem_%s%s%s_batch" % ("cbor_" if wire else "", stem, "_unique" if unique else "_bound" if bound else ""))(*args)
         if not raw:
             self._ck(rc)
         counts = dict(zip(names, (int(v) for v in cnt)))
         return (rc, counts) if raw else counts
 
-    def _family_host(self, kind: str, nullifier_set, keys, rows, tail: dict, sign_key, key_epochs, charges, returned, raw: bool, unique: bool):
+    def _family_host(self, kind: str, nullifier_set, keys, rows, tail: dict, sign_key, key_epochs, charges, returned, raw: bool, unique: bool, bind=_UNBOUND):
         """one call of the family from host memory; rows: records (bytes) or messages (a list).  -> (statuses, records | list of messages
-        (b"" where not signed), out_key, [replayed,] counts dict); raw=True: (rc, ...), no exception"""
+        (b"" where not signed), out_key, [replayed,] counts dict); raw=True: (rc, ...), no exception.  bind given (32 bytes a lane, or
+        None: NULL): the kind's bound call"""
         _, _, _, row, cbor_type, _, _, replay, _ = self._FAMILY[kind]
         wire = isinstance(rows, (list, tuple))
         if wire:
@@ -943,6 +973,9 @@ class Engine:
             p.update(rng=pr, rng_mode=tail["rng_mode"])
         p.update(set=nullifier_set, sign_key=sign_key, key_epochs=key_epochs, charges=pc, returned=pt, out=out.ctypes.data, status=st.ctypes.data, out_key=ok.ctypes.data,
                  unique=unique)
+        if bind is not _UNBOUND:
+            pb, kb = _in(bind, 32 * n) if bind is not None else (None, None)
+            p.update(bind=pb)
         rc, counts = self._family_ptr(kind, "redeem_cbor" if wire else "redeem", keys, n, MEM_HOST, p, raw=True)
         b = out.tobytes()
         res = (st.tobytes(), [b[i * ob:(i + 1) * ob] if st[i] == 0 else b"" for i in range(n)] if wire else b, ok.tobytes()) + ((rp.tobytes(),) if replay else ()) + (counts,)
@@ -1058,19 +1091,21 @@ class Engine:
 
     # ---- replayable partial refunds (act_redeem_return_replay_batch / act_redeem_cbor_return_replay_batch / act_replay_derive_return_batch)
     def redeem_return_replay(self, nullifier_set, receipts, keys, proofs: bytes, nonce_key: bytes, sign_key: int = SIGN_MATCHED, key_epochs=None, charges: bytes = None,
-                             returned: bytes = None, raw: bool = False, unique: bool = False):
+                             returned: bytes = None, raw: bool = False, unique: bool = False, bind=_UNBOUND):
         """redeem_admit_replay with the amounts the issuer returns: t > s is STATUS_RETURN_TOO_BIG in the screen; the receipt pins t, so
         a retry with the same t is served byte for byte and one with another t is STATUS_DOUBLE_SPEND.
         -> (statuses, 160-byte RefundReturn records, out_key, replayed, counts dict); raw=True: (rc, ...), no exception
         unique=True: act_redeem_return_replay_unique_batch -- a lane with the bytes of an earlier lane is not verified; it takes that
         lane's answer if it names that lane's amount and is STATUS_DOUBLE_SPEND behind an accepted leader if it names another"""
-        return self._family_host("return_replay", nullifier_set, keys, proofs, dict(receipts=receipts, nonce_key=nonce_key), sign_key, key_epochs, charges, returned, raw, unique)
+        return self._family_host("return_replay", nullifier_set, keys, proofs, dict(receipts=receipts, nonce_key=nonce_key), sign_key, key_epochs, charges, returned, raw, unique,
+                                 bind)
 
     def redeem_cbor_return_replay(self, nullifier_set, receipts, keys, messages: list, nonce_key: bytes, sign_key: int = SIGN_MATCHED, key_epochs=None,
-                                  charges: bytes = None, returned: bytes = None, raw: bool = False, unique: bool = False):
+                                  charges: bytes = None, returned: bytes = None, raw: bool = False, unique: bool = False, bind=_UNBOUND):
         """wire bytes in, wire bytes out -> (statuses, list of CBOR RefundReturn messages (b"" where not signed), out_key, replayed, counts dict)
         unique=True: act_redeem_cbor_return_replay_unique_batch (a copy has the same length and the same bytes as an earlier message)"""
-        return self._family_host("return_replay", nullifier_set, keys, list(messages), dict(receipts=receipts, nonce_key=nonce_key), sign_key, key_epochs, charges, returned, raw, unique)
+        return self._family_host("return_replay", nullifier_set, keys, list(messages), dict(receipts=receipts, nonce_key=nonce_key), sign_key, key_epochs, charges, returned, raw, unique,
+                                 bind)
 
     def return_replay_ptr(self, fn: str, keys, n: int, mem: int, **p):
         """the two calls on raw pointers of either kind: fn = redeem / redeem_cbor; p as admit_replay_ptr's plus returned (unique: the
@@ -1108,20 +1143,25 @@ class Engine:
         cnt = (C.c_uint64 * len(RESERVE_COUNTS))()
         args = [self.ctx, p["set"].h, p["receipts"].h if p["receipts"] is not None else None, n, mem, pk, nk, ke.ctypes.data if ke is not None else None]
         args += [p["cbor"], p.get("offsets") or None] if wire else [p["proofs"]]
+        bound = "bind" in p      # request binding (0 / None: NULL): the bound calls
+        args += [p["bind"] or None] if bound else []
         args += [p.get("charges") or None, p["out"], p["status"], p["out_key"], p.get("replayed") or None, cnt]
-        rc = (self.lib.act_redeem_cbor_reserve_batch if wire else self.lib.act_redeem_reserve_batch)(*args)
+        rc = getattr(self.lib, "act_redeem_%sreserve%s_batch" % ("cbor_" if wire else "", "_bound" if bound else ""))(*args)
         counts = dict(zip(RESERVE_COUNTS, (int(v) for v in cnt)))
         if p.get("raw"):
             return rc, counts
         self._ck(rc)
         return counts
 
-    def _reserve_host(self, nullifier_set, receipts, keys, rows, key_epochs, charges, raw: bool):
+    def _reserve_host(self, nullifier_set, receipts, keys, rows, key_epochs, charges, raw: bool, bind=_UNBOUND):
         wire = isinstance(rows, (list, tuple))
         if wire:
             n = len(rows); p0, k0, offs = _msgs(rows); p = dict(cbor=p0, offsets=offs.ctypes.data)
         else:
             n = len(rows) // self.proof_bytes; p0, k0 = _in(rows, self.proof_bytes * n); p = dict(proofs=p0)
+        if bind is not _UNBOUND:
+            pb, kb = _in(bind, 32 * n) if bind is not None else (None, None)
+            p.update(bind=pb)
         out = np.full(RESERVATION_BYTES * n, 7 if raw else 0, np.uint8); st = np.full(n, 99 if raw else 0, np.uint8); ok = np.zeros(n, np.uint8); rp = np.zeros(n, np.uint8)
         pc, kc = _in(charges, 32 * n) if charges is not None else (None, None)
         rc, counts = self.reserve_ptr("redeem_cbor" if wire else "redeem", keys, n, MEM_HOST, set=nullifier_set, receipts=receipts, key_epochs=key_epochs, charges=pc,
@@ -1132,14 +1172,14 @@ class Engine:
         self._ck(rc)
         return res
 
-    def redeem_reserve(self, nullifier_set, receipts, keys, proofs: bytes, key_epochs=None, charges: bytes = None, raw: bool = False):
+    def redeem_reserve(self, nullifier_set, receipts, keys, proofs: bytes, key_epochs=None, charges: bytes = None, raw: bool = False, bind=_UNBOUND):
         """redeem_admit_replay WITHOUT the signature: screen, verify, record k and a reservation tag.  -> (statuses, 96-byte reservation
         records k^ | enc(K') | s^ (zero where rejected), out_key, replayed, counts dict); raw=True: (rc, ...), no exception"""
-        return self._reserve_host(nullifier_set, receipts, keys, proofs, key_epochs, charges, raw)
+        return self._reserve_host(nullifier_set, receipts, keys, proofs, key_epochs, charges, raw, bind)
 
-    def redeem_cbor_reserve(self, nullifier_set, receipts, keys, messages: list, key_epochs=None, charges: bytes = None, raw: bool = False):
+    def redeem_cbor_reserve(self, nullifier_set, receipts, keys, messages: list, key_epochs=None, charges: bytes = None, raw: bool = False, bind=_UNBOUND):
         """SpendProof messages in -> what redeem_reserve returns (the reservation record has no wire type)"""
-        return self._reserve_host(nullifier_set, receipts, keys, list(messages), key_epochs, charges, raw)
+        return self._reserve_host(nullifier_set, receipts, keys, list(messages), key_epochs, charges, raw, bind)
 
     def settle_ptr(self, keys, n: int, mem: int, **p):
         """the settle calls on raw pointers of either kind; p: receipts, reservations (96 bytes a lane), key_index, amounts (0: all zero),

@@ -189,6 +189,10 @@ struct AdmitCall {
     reserve = true; return replays(rs, unsigned_key, marks);
   }
   AdmitCall& uniquely() { form.unique = true; return *this; }
+  // request binding (DESIGN 4.12): n * 32 bytes in `mem` memory that enter every verified lane's challenge hash.  Only the verification
+  // step sees them: the screen, the candidate stage, the tags, the nonces and both sets do not.  Null: the unbound call
+  const uint8_t* bind = nullptr;
+  AdmitCall& bound(const uint8_t* b) { bind = b; return *this; }
   AdmitCall& answers(uint8_t* o, uint8_t* st, uint8_t* key, uint64_t* counts) { out = o; status = st; out_key = key; out_counts = counts; return *this; }
 
   bool wire() const { return cbor != nullptr; }
@@ -225,7 +229,7 @@ static int replay_tail(act_ctx* c, act_nullifier_set* set, act_nullifier_set* re
 static int redeem_replay_locked(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys, int nkeys,
                                 const uint32_t* key_epochs, int sign_key, const uint8_t* proof, const uint8_t* cbor, const uint64_t* offsets, const uint8_t* nonce_key,
                                 uint8_t* out, uint8_t* status, uint8_t* out_key, uint8_t* out_replayed, uint64_t* out_counts, const RedeemReturn* ret = nullptr,
-                                const ReplayReserve* res = nullptr);
+                                const ReplayReserve* res = nullptr, const uint8_t* bind = nullptr);
 
 namespace {
 
@@ -249,6 +253,7 @@ struct AdmitState {
   uint8_t *kp = nullptr, *knul = nullptr, *st = nullptr, *sp = nullptr, *kidx = nullptr, *okey = nullptr, *cst = nullptr, *crepl = nullptr;
   AdmitRngDev rng_dev; std::vector<uint8_t> rng_host; AdmitHostWipe rng_wipe{rng_host};      // the verified lanes' rng slices (secret): wiped on every exit
   const uint8_t* c_rng; RedeemReturn cret{nullptr};
+  const uint8_t* c_bind = nullptr;      // a bound call: the verified lanes' request bindings, behind the other compact arrays
   uint8_t* d_sred = nullptr; std::vector<uint8_t> h_sred; ReplayReserve cres{nullptr};      // the reserve form: every lane's s^ (device; host copy), the verified lanes'
   uint64_t tc[ACT_REPLAY_COUNTS] = {0, 0, 0, 0, 0, 0};      // replay: the tail's counts
   std::vector<uint8_t> h_cst, h_fin, h_t;  // device-memory callers, for the counts: compact statuses; the replay unique forms' final statuses and amounts
@@ -445,7 +450,7 @@ struct AdmitState {
         if (!dev) { h_sred.resize(n * 32); ADCK(c, hipMemcpy(h_sred.data(), d_sred, n * 32, hipMemcpyDeviceToHost)); cres.s = h_sred.data(); }
       }
       const int rc = redeem_replay_locked(c, a.set, a.receipts, n, a.mem, a.keys, a.nkeys, a.key_epochs, a.sign_key, a.proof, a.cbor, a.offsets, a.nonce_key, a.out, a.status,
-                                          a.out_key, a.out_replayed, a.out_counts ? tc : nullptr, ret, a.reserve ? &cres : nullptr);      // (the caller's `returned`, lane for lane)
+                                          a.out_key, a.out_replayed, a.out_counts ? tc : nullptr, ret, a.reserve ? &cres : nullptr, a.bind);      // (the caller's `returned` and bindings, lane for lane)
       counts(nullptr, tc);      // (tc[0] == 0: the call ended before its tail, and the counts stay zero)
       return rc;
     }
@@ -492,7 +497,8 @@ struct AdmitState {
     ADCK(c, hipMemcpy(h_vidx.data(), cp.v.idx, mv * 4, hipMemcpyDeviceToHost));
     if (!dev) { h_pos.resize(n); ADCK(c, hipMemcpy(h_pos.data(), cp.v.pos, n * 4, hipMemcpyDeviceToHost)); }
     const size_t arr_lane = rp ? 70 : 69;
-    if ((rc = arr.alloc(a.mem, mv * arr_lane + ((a.returned || a.reserve) ? mv * 32 + 32 : 0)))) { c->err = "admission: compact arrays"; return rc; }
+    const size_t o_bind = ((mv * arr_lane + 31) & ~(size_t)31) + ((a.returned || a.reserve) ? mv * 32 : 0);      // (a 32-byte boundary: the amounts or charges in front are whole rows)
+    if ((rc = arr.alloc(a.mem, mv * arr_lane + ((a.returned || a.reserve) ? mv * 32 + 32 : 0) + (a.bind ? mv * 32 + 32 : 0)))) { c->err = "admission: compact arrays"; return rc; }
     if ((rc = cout.alloc(a.mem, mv * out_b))) { c->err = "admission: compact output"; return rc; }
     kp = arr.p; knul = kp + mv * 32; st = knul + mv * 32; sp = st + mv; kidx = sp + mv; okey = kidx + mv; cst = okey + mv;
     crepl = cst + mv;      // (the replay form: the verified lanes' replay marks)
@@ -518,6 +524,12 @@ struct AdmitState {
       if ((rc = gather_verified(cs, d_sred, true, 32))) return rc;
       cres.s = cs;
     }
+    // the request bindings follow their lanes too, by the same row gather: survivor j is verified under the binding of lane v_idx[j]
+    if (a.bind) {
+      uint8_t* cb = arr.p + o_bind;
+      if ((rc = gather_verified(cb, a.bind, dev, 32))) return rc;
+      c_bind = cb;
+    }
     return ACT_OK;
   }
 
@@ -530,8 +542,9 @@ struct AdmitState {
       int rc = gather.run(cp.v.idx + w0, h_vidx.data() + w0, w);
       if (rc) return rc;
       const uint8_t* g = gather.data();
-      if (wire) { RingSel sel{a.keys, a.nkeys, okey + w0}; rc = verify_spend_cbor_impl(c, w, a.mem, nullptr, g, gather.offsets(), st + w0, kp + w0 * 32, nullptr, &sel); }
-      else rc = act_verify_spend_keyring_batch(c, w, a.mem, a.keys, a.nkeys, g, st + w0, okey + w0, kp + w0 * 32);
+      const uint8_t* wb = c_bind ? c_bind + w0 * 32 : nullptr;
+      if (wire) { RingSel sel{a.keys, a.nkeys, okey + w0, wb}; rc = verify_spend_cbor_impl(c, w, a.mem, nullptr, g, gather.offsets(), st + w0, kp + w0 * 32, nullptr, &sel); }
+      else rc = act_verify_spend_keyring_bound_batch(c, w, a.mem, a.keys, a.nkeys, g, wb, st + w0, okey + w0, kp + w0 * 32);
       if (rc) return rc;            // as in the redeem calls: nothing recorded, status untouched
     }
     return ACT_OK;
@@ -607,6 +620,7 @@ int admit_refused(const AdmitCall& a) {
   if (!a.c || (a.mem != ACT_MEM_HOST && a.mem != ACT_MEM_DEVICE) || a.n > ((size_t)1 << 30)) return ACT_ERR_ARG;
   if (a.n && ((!a.proof && !a.cbor) || !a.out || !a.status || !a.out_key)) return ACT_ERR_ARG;
   if (a.wire() && a.offsets) for (size_t i = 0; i < a.n; i++) if (a.offsets[i + 1] < a.offsets[i]) return ACT_ERR_ARG;
+  if (a.bind && a.form.unique) { a.c->err = "admission: a bound call has no unique form"; return ACT_ERR_ARG; }      // (equality of proof bytes says nothing about two lanes' bindings)
   // what the redeem call refuses (null handles, ring size, sign_key, rng convention, device, epochs), in the same words
   if (int rc = redeem_keyring_refused(a.c, a.set, 0, a.keys, a.nkeys, a.key_epochs, a.sign_key, nullptr, nullptr, a.rng, a.rng_mode, nullptr, nullptr, nullptr)) return rc;
   return a.replay() ? replay_refused(a.c, a.set, a.receipts, a.nonce_key, a.n, a.key_epochs, a.nkeys) : ACT_OK;

@@ -204,6 +204,23 @@ extern "C" int act_redeem_cbor_return_replay_batch(act_ctx* c, act_nullifier_set
                           .replays(receipts, nonce_key, out_replayed).answers(out_refund_return_cbor, status, out_key, out_counts));
 }
 
+// request binding (DESIGN 4.12): the two calls above with n * 32 bytes of associated data, which enter the challenge hash of every lane
+// that is verified and nothing else -- tags, nonces and both sets are those of the unbound call.  bind == NULL is the call above
+extern "C" int act_redeem_return_replay_bound_batch(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys, int nkeys,
+                                                    const uint32_t* key_epochs, int sign_key, const uint8_t* proof, const uint8_t* bind, const uint8_t* charge,
+                                                    const uint8_t* returned, const uint8_t nonce_key[32], uint8_t* out_refund_return, uint8_t* status, uint8_t* out_key,
+                                                    uint8_t* out_replayed, uint64_t* out_counts) {
+  return redeem_admit(AdmitCall(c, set, n, mem).ring(keys, nkeys, key_epochs, sign_key).records(proof).bound(bind).charged(charge).returns(returned)
+                          .replays(receipts, nonce_key, out_replayed).answers(out_refund_return, status, out_key, out_counts));
+}
+extern "C" int act_redeem_cbor_return_replay_bound_batch(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys,
+                                                         int nkeys, const uint32_t* key_epochs, int sign_key, const uint8_t* cbor, const uint64_t* offsets,
+                                                         const uint8_t* bind, const uint8_t* charge, const uint8_t* returned, const uint8_t nonce_key[32],
+                                                         uint8_t* out_refund_return_cbor, uint8_t* status, uint8_t* out_key, uint8_t* out_replayed, uint64_t* out_counts) {
+  return redeem_admit(AdmitCall(c, set, n, mem).ring(keys, nkeys, key_epochs, sign_key).messages(cbor, offsets).bound(bind).charged(charge).returns(returned)
+                          .replays(receipts, nonce_key, out_replayed).answers(out_refund_return_cbor, status, out_key, out_counts));
+}
+
 // The unique forms of the two calls above: the copy stage of the admit-replay unique forms behind this screen, equality decided on the
 // proof bytes ALONE (t takes no part, as in act_redeem_(cbor_)return_unique_batch), the amounts of the verified lanes gathered by v_idx --
 // a copy's t never reaches a tag, a nonce or a signature -- and behind the tail a copy answered from its leader's final status and from

@@ -572,7 +572,7 @@ static int verify_spend_cbor_impl(act_ctx* c, size_t n, int mem, const uint8_t s
   const DevKey* d_ring = nullptr;
   if (ring && (rc = ring_set(c, ring->keys, ring->nkeys, &d_ring))) { c->wire_layout = nullptr; return rc; }
   if (dev_reader) { c->wire_read_code = c->d_wire_codes; c->wire_read_info = c->d_wire_codes + c->d_wire_codes_cap; }
-  rc = ring ? ring_verify_locked(c, n, mem, d_ring, ring->nkeys, nullptr, status, ring->out_key, out_kprime, &w)
+  rc = ring ? ring_verify_locked(c, n, mem, d_ring, ring->nkeys, nullptr, status, ring->out_key, out_kprime, &w, ring->bind)
             : spend_batch_locked(c, n, mem, sk, nullptr, false, nullptr, ACT_RNG_PER_LANE, nullptr, status, out_kprime, &w);
   c->wire_layout = nullptr; c->wire_read_code = c->wire_read_info = nullptr;
   if (rc) return rc;
@@ -608,7 +608,7 @@ static int verify_spend_cbor_impl(act_ctx* c, size_t n, int mem, const uint8_t s
   c->wire_stats[0] += n; c->wire_stats[1] += n - which.size(); c->wire_stats[3] += which.size();
   const WireExtent x{cbor, offsets, ml};
   WireWindow win;
-  std::vector<uint8_t> st2, kp2, ok2, verdict, kprime, nul, key;
+  std::vector<uint8_t> st2, kp2, ok2, verdict, kprime, nul, key, bind2;      // bind2: a bound ring call's bindings of the window's records (DESIGN 4.12)
   std::vector<size_t> good;
   for (size_t w0 = 0; w0 < which.size(); w0 += WIRE_SETTLE_WINDOW) {
     const size_t cnt = std::min(which.size(), w0 + WIRE_SETTLE_WINDOW) - w0;
@@ -626,7 +626,15 @@ static int verify_spend_cbor_impl(act_ctx* c, size_t n, int mem, const uint8_t s
     if (!good.empty()) {
       st2.assign(good.size(), 0); ok2.assign(good.size(), (uint8_t)ACT_KEY_NONE);
       if (out_kprime) kp2.assign(good.size() * 32, 0);
-      rc = ring ? ring_verify_locked(c, good.size(), ACT_MEM_HOST, d_ring, ring->nkeys, win.recs.data(), st2.data(), ok2.data(), out_kprime ? kp2.data() : nullptr)
+      if (ring && ring->bind) {      // the bindings follow their records into the small call
+        bind2.resize(good.size() * 32);
+        for (size_t g = 0; g < good.size(); g++) {
+          const uint8_t* from = ring->bind + lanes[good[g]] * 32;
+          if (mem == ACT_MEM_DEVICE) HIPCK(c, hipMemcpy(bind2.data() + g * 32, from, 32, hipMemcpyDeviceToHost)); else memcpy(bind2.data() + g * 32, from, 32);
+        }
+      }
+      rc = ring ? ring_verify_locked(c, good.size(), ACT_MEM_HOST, d_ring, ring->nkeys, win.recs.data(), st2.data(), ok2.data(), out_kprime ? kp2.data() : nullptr, nullptr,
+                                     ring->bind ? bind2.data() : nullptr)
                 : spend_batch_locked(c, good.size(), ACT_MEM_HOST, sk, win.recs.data(), false, nullptr, ACT_RNG_PER_LANE, nullptr, st2.data(), out_kprime ? kp2.data() : nullptr);
       if (rc) return rc;
       for (size_t g = 0; g < good.size(); g++) {

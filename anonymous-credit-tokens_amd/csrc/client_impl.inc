@@ -6,11 +6,13 @@
 // rng: the caller's bytes, or (seed != nullptr) expanded on the device from a 32-byte seed: lane i draws from the BLAKE3 XOF of
 // seed | u64_le(first_lane + i) (k_misc.hip k_xof_expand) -- 33 536 bytes per proof that then never cross PCIe
 static int prove_spend_impl(act_ctx* c, size_t n, int mem, const uint8_t* token, const uint8_t* s, const uint8_t* rng, const uint8_t* seed,
-                            uint64_t first_lane, uint8_t* out_proof, uint8_t* out_prerefund, uint8_t* status) {
+                            uint64_t first_lane, uint8_t* out_proof, uint8_t* out_prerefund, uint8_t* status, const uint8_t* bind = nullptr) {
   Call call(c, n);
   HIPCK(c, hipSetDevice(c->device));
   const size_t pb = ProofLayout{c->L}.bytes(), rb = act_prove_rng_bytes(c);
-  const SpendTranscript st{c->L};
+  // bind (DESIGN 4.12, request binding): n * 32 bytes in `mem` memory or null; the head kernel writes a lane's bytes as its transcript's
+  // last element and the hash takes the bound length
+  const SpendTranscript st{c->L, bind != nullptr};
   // Chunk schedule: full-size chunks; a host-memory caller's LAST chunk is cut in two (11/16 + 5/16) -- its 16.8 KB per proof leave
   // after everything is computed (19 ms of a 76 ms call over 65 536 proofs), and the first part's copy out fits under the second
   // part's kernels (a proof takes ~0.3 us to leave, ~0.9 us to make)
@@ -34,6 +36,7 @@ static int prove_spend_impl(act_ctx* c, size_t n, int mem, const uint8_t* token,
     int rc;
     if ((rc = dev_in(c, sl, 0, mem, token + off * 160, (size_t)m * 160, &a.tok))) return rc;
     if ((rc = dev_in(c, sl, 1, mem, s + off * 32, (size_t)m * 32, &a.s))) return rc;
+    if (bind && (rc = dev_in(c, sl, 5, mem, bind + off * 32, (size_t)m * 32, &a.bind))) return rc;
     if (!seed) { if ((rc = dev_in(c, sl, 3, mem, rng + off * rb, (size_t)m * rb, &a.rng))) return rc; }
     else {
       // 48 bytes past the lanes' bytes hold the seed (read by the expansion kernel on this stream)
@@ -85,6 +88,12 @@ int act_prove_spend_batch(act_ctx* c, size_t n, int mem, const uint8_t* token, c
                           uint8_t* out_proof, uint8_t* out_prerefund, uint8_t* status) {
   if (!c || (n && (!token || !s || !rng || !out_proof || !out_prerefund || !status))) return ACT_ERR_ARG;
   return prove_spend_impl(c, n, mem, token, s, rng, nullptr, 0, out_proof, out_prerefund, status);
+}
+// request binding (DESIGN 4.12): prove_spend with n * 32 bytes of associated data in the challenge hash; bind == NULL is act_prove_spend_batch
+int act_prove_spend_bound_batch(act_ctx* c, size_t n, int mem, const uint8_t* token, const uint8_t* s, const uint8_t* rng, const uint8_t* bind,
+                                uint8_t* out_proof, uint8_t* out_prerefund, uint8_t* status) {
+  if (!c || (n && (!token || !s || !rng || !out_proof || !out_prerefund || !status))) return ACT_ERR_ARG;
+  return prove_spend_impl(c, n, mem, token, s, rng, nullptr, 0, out_proof, out_prerefund, status, bind);
 }
 int act_prove_spend_seeded_batch(act_ctx* c, size_t n, int mem, const uint8_t* token, const uint8_t* s, const uint8_t seed[32], uint64_t first_lane,
                                  uint8_t* out_proof, uint8_t* out_prerefund, uint8_t* status) {

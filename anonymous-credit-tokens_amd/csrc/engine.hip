@@ -623,15 +623,16 @@ int sign_phase(act_ctx* c, Slot& sl, uint32_t m, int label, const uint8_t* d_rng
 }
 
 // ---- spend verification, pipelined over two slots ----------------------------------------------------------
-struct SpendChunk { uint32_t m = 0; size_t off = 0; const uint8_t* d_proofs = nullptr; uint8_t* d_kprime = nullptr; uint8_t* d_out = nullptr; SpendArgs a{}; bool stagger = false; };
+struct SpendChunk { uint32_t m = 0; size_t off = 0; const uint8_t* d_proofs = nullptr; uint8_t* d_kprime = nullptr; uint8_t* d_out = nullptr; SpendArgs a{}; bool stagger = false;
+                    const uint8_t* d_bind = nullptr; };      // d_bind: the chunk's request bindings in device memory (a bound ring call, keyring_impl.inc), else null
 
 // stage 1: everything up to (and including the start of) the transcript hash.  spend_stage1_kernels = the kernels in front of the hash,
 // under `key` (the context's cached key; a ring call's key 0, keyring_impl.inc)
 int spend_stage1_kernels(act_ctx* c, Slot& sl, SpendChunk& ch, const DevKey& key) {
   ACT_RANGE("spend.phaseA off=%zu m=%zu (prep, bits, enc, tail enqueued; transcripts on their way)", ch.off, (size_t)ch.m);
-  const SpendTranscript st{c->L};
+  const SpendTranscript st{c->L, ch.d_bind != nullptr};
   SpendArgs& a = ch.a;
-  a = SpendArgs{}; a.P = c->P; a.K = key; a.proofs = ch.d_proofs; a.n = ch.m; a.tr = sl.d_tr; a.tr_stride = (uint32_t)st.stride();
+  a = SpendArgs{}; a.P = c->P; a.K = key; a.proofs = ch.d_proofs; a.n = ch.m; a.tr = sl.d_tr; a.tr_stride = (uint32_t)st.stride(); a.bind = ch.d_bind;
   a.coords = sl.d_coords; a.d01 = sl.d_d01; a.buckets = sl.d_buckets; a.xa = sl.d_xa; a.flags = sl.d_flags; a.xof = sl.d_xof; a.status = sl.d_status;
   a.kprime_enc = ch.d_kprime; a.naf = sl.d_naf; a.dig = sl.d_dig; a.pbk = sl.d_buckets;
   int rc;

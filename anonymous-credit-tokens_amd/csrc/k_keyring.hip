@@ -11,7 +11,7 @@ __global__ void __launch_bounds__(64, 2) k_ring_cand(RingArgs r) { ring_cand_lan
 __global__ void __launch_bounds__(64) k_ring_hash_full(RingArgs r) {
   const uint32_t p = blockIdx.x * 64 + threadIdx.x;
   if (p >= r.s.n) return;
-  const SpendTranscript st{r.s.P.L};
+  const SpendTranscript st{r.s.P.L, r.s.bind != nullptr};      // a bound call hashes the bound length
   const uint32_t* msg = reinterpret_cast<const uint32_t*>(r.s.tr + (size_t)p * r.s.tr_stride);
   const uint32_t len = (uint32_t)st.bytes();
   uint32_t* sib = r.sib + (size_t)p * B3_MAX_SIBLINGS * 8;

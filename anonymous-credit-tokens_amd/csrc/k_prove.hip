@@ -52,6 +52,7 @@ __global__ void __launch_bounds__(64) k_prove_head_wide(ProveArgs a) {
       ge_store(park_q + (size_t)(first ? 0 : BUCKET_WORDS) + (size_t)q * GE_WORDS, chain_ct_quarter(A, first ? r1r2 : sc_mul(rv.e_prime(), r1r2), q));
       if (role == R_AP0) {
         tr_put_prefix(a.tr + (size_t)p * a.tr_stride, a.P, LABEL_SPEND);
+        if (a.bind) tr_put_bind(a.tr + (size_t)p * a.tr_stride, L, a.bind + (size_t)p * 32);      // request binding
         tr_put_aligned(el + 40 * st.el_k(), k.v);
         store_sc(rec + 32 * pl.k(), k); store_sc(rec + 32 * pl.s(), s);
         const sc r3 = sc_invert(r1);                                                // :992

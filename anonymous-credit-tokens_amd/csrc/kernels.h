@@ -78,8 +78,11 @@ struct ProofLayout {
   ACT_HDC size_t bytes() const { return 32u * (14u + 4u * (size_t)L); }
 };
 // "spend" transcript element slots (40 bytes each after the prefix; src/lib.rs:831-840)
+// The bound form (request binding): one more element behind C that carries 32 caller bytes instead of a point encoding.
+// Nothing in front of it moves; an unbound call (bound == 0) has the crate's transcript, byte for byte.
 struct SpendTranscript {
   int L;
+  int bound = 0;
   ACT_HDC int el_k() const { return 0; }
   ACT_HDC int el_a_prime() const { return 1; }
   ACT_HDC int el_b_bar() const { return 2; }
@@ -88,7 +91,8 @@ struct SpendTranscript {
   ACT_HDC int el_com(int j) const { return 5 + j; }
   ACT_HDC int el_cprime(int j, int b) const { return 5 + L + 2 * j + b; }
   ACT_HDC int el_c() const { return 5 + 3 * L; }
-  ACT_HDC size_t bytes() const { return 184u + 40u * (6u + 3u * (size_t)L); }
+  ACT_HDC int el_bind() const { return 6 + 3 * L; }
+  ACT_HDC size_t bytes() const { return 184u + 40u * (6u + 3u * (size_t)L + (bound ? 1u : 0u)); }
   ACT_HDC size_t stride() const { return (bytes() + 15u) & ~(size_t)15u; }
 };
 
@@ -119,6 +123,7 @@ struct SpendArgs {
   uint32_t* part;            // small-batch schedule only: n * 4 * GE_WORDS partial sums of A1 / A2 (spend_lanes.h PART_POINTS)
   uint32_t* progress;        // nullable: k_spend_bits counts its finished workgroups here (engine.hip spend_stage1: the next chunk's range kernel
                              // is released when this one's LAST ROUND of workgroups is running, not when it has drained)
+  const uint8_t* bind;       // n * 32 request bindings or null (unbound): the transcript's last element (SpendTranscript el_bind)
 };
 
 struct SignArgs {
@@ -232,6 +237,7 @@ struct ProveArgs {
   uint8_t* prerefund;        // n * 96
   uint8_t* status;
   uint32_t* group_counter;   // k_prove_head_wide: one word per group of 64 proofs, zero between launches (which role block arrives last)
+  const uint8_t* bind;       // n * 32 request bindings or null (unbound), as in SpendArgs
 };
 // PreIssuance::to_credit_token (src/lib.rs:528-562) / PreRefund::to_credit_token (:1217-1253)
 struct ClientArgs {
@@ -482,6 +488,13 @@ ACT_HD void tr_put_bytes(uint8_t* slot, const uint32_t w[8]) {
 ACT_HD void tr_put_prefix(uint8_t* tr, const DevParams& P, int label) {
   uint32_t* q = reinterpret_cast<uint32_t*>(tr);
   for (int i = 0; i < PREFIX_WORDS; i++) if (4u * i < P.prefix_len[label]) q[i] = P.prefix[label][i];
+}
+// the bound form's last element (SpendTranscript el_bind): the lane's 32 request-binding bytes, at any byte alignment in the caller's
+// array, where the other elements carry a point encoding.  `tr` = the start of the lane's transcript
+ACT_HD void tr_put_bind(uint8_t* tr, int L, const uint8_t* bind32) {
+  uint32_t w[8];
+  load32_bytes(w, bind32);
+  tr_put_aligned(tr + 184 + 40 * SpendTranscript{L}.el_bind(), w);
 }
 // per-proof flag words are OR-ed by several lanes of one launch
 #if defined(__HIP_DEVICE_COMPILE__)

@@ -19,7 +19,7 @@ struct RingWs {
   uint8_t keys_cached[KEYRING_MAX * 64] = {}; uint32_t nkeys_cached = 0; DevKey ring[KEYRING_MAX] = {};
 };
 
-struct RingSel { const uint8_t* keys; int nkeys; uint8_t* out_key; };      // a ring in place of `sk` (cbor_impl.inc verify_spend_cbor_impl)
+struct RingSel { const uint8_t* keys; int nkeys; uint8_t* out_key; const uint8_t* bind = nullptr; };      // a ring in place of `sk` (cbor_impl.inc verify_spend_cbor_impl); bind: the lanes' request bindings in the call's kind of memory, or null
 
 extern "C" void act_host_hash_ring_many(const uint8_t* msgs, size_t stride, uint32_t len, size_t n, int max_threads, uint32_t nkeys, uint32_t rep_off,
                                         const uint8_t* cand, uint32_t* xofs);      // host_pool.cpp
@@ -79,14 +79,17 @@ static int ring_set(act_ctx* c, const uint8_t* keys, int nkeys, const DevKey** d
 }
 
 // spend_batch_locked's pipeline with the ring steps in it.  The caller holds the context (Call) and has staged the ring (ring_set).
+// bind (DESIGN 4.12, request binding): n * 32 bytes in `mem` memory or null.  Each chunk brings its 32 m bytes in the way it brings its
+// proofs in, the prep kernel writes them as the transcript's last element, and every hash of the call takes the bound length.
 static int ring_verify_locked(act_ctx* c, size_t n, int mem, const DevKey* d_ring, int nkeys, const uint8_t* proof, uint8_t* status, uint8_t* out_key,
-                              uint8_t* out_kprime, const WireSrc* wire = nullptr) {
+                              uint8_t* out_kprime, const WireSrc* wire = nullptr, const uint8_t* bind = nullptr) {
   RingWs* w = c->ring_ws;
-  const SpendTranscript st{c->L};
+  const SpendTranscript st{c->L, bind != nullptr};
   const size_t pb = ProofLayout{c->L}.bytes();
   const uint32_t extra = (uint32_t)nkeys - 1u, stride = (uint32_t)st.stride(), len = (uint32_t)st.bytes();
   const uint8_t* proof_view = (mem == ACT_MEM_HOST && !wire) ? mapped_view(c, proof, n * pb) : nullptr;
   const bool in_host = mem == ACT_MEM_HOST && !proof_view;
+  const uint8_t* bind_view = (bind && mem == ACT_MEM_HOST) ? mapped_view(c, bind, n * 32) : nullptr;
   bool stagger = false;
   const std::vector<std::pair<size_t, size_t>> sched = spend_schedule(c, n, in_host, &stagger);
   const size_t nchunks = sched.size(), depth = (size_t)c->depth;
@@ -101,6 +104,8 @@ static int ring_verify_locked(act_ctx* c, size_t n, int mem, const DevKey* d_rin
     if (wire) { if ((rc = wire_unframe_chunk(c, sl, *wire, mem, ch.off, ch.m, &ch.d_proofs))) return rc; }
     else if (proof_view) ch.d_proofs = proof_view + ch.off * pb;
     else if ((rc = dev_in(c, sl, 0, mem, proof + ch.off * pb, (size_t)ch.m * pb, &ch.d_proofs))) return rc;
+    if (bind_view) ch.d_bind = bind_view + ch.off * 32;
+    else if (bind && (rc = dev_in(c, sl, 5, mem, bind + ch.off * 32, (size_t)ch.m * 32, &ch.d_bind))) return rc;
     if (out_kprime && (rc = dev_out_begin(c, sl, 2, mem, out_kprime + ch.off * 32, (size_t)ch.m * 32, &ch.d_kprime))) return rc;
     if ((rc = spend_stage1_kernels(c, sl, ch, w->ring[0]))) return rc;
     r = RingArgs{}; r.s = ch.a; r.ring = d_ring; r.nkeys = (uint32_t)nkeys;
@@ -152,16 +157,21 @@ static int ring_verify_locked(act_ctx* c, size_t n, int mem, const DevKey* d_rin
   return sync_all(c);
 }
 
-int act_verify_spend_keyring_batch(act_ctx* c, size_t n, int mem, const uint8_t* keys, int nkeys, const uint8_t* proof, uint8_t* status,
-                                   uint8_t* out_key, uint8_t* out_kprime) {
+// request binding (DESIGN 4.12): the ring call with n * 32 bytes of associated data in the challenge hash; bind == NULL is the ring call
+int act_verify_spend_keyring_bound_batch(act_ctx* c, size_t n, int mem, const uint8_t* keys, int nkeys, const uint8_t* proof, const uint8_t* bind,
+                                         uint8_t* status, uint8_t* out_key, uint8_t* out_kprime) {
   if (!c || !keys || nkeys < 1 || nkeys > ACT_KEYRING_MAX || (n && (!proof || !status || !out_key))) return ACT_ERR_ARG;
   if (n >= ((size_t)1 << 32)) return ACT_ERR_ARG;
   Call call(c, n);
   HIPCK(c, hipSetDevice(c->device));
   const DevKey* d_ring = nullptr;
   int rc = ring_set(c, keys, nkeys, &d_ring); if (rc) return rc;
-  if ((rc = ring_verify_locked(c, n, mem, d_ring, nkeys, proof, status, out_key, out_kprime))) return rc;
+  if ((rc = ring_verify_locked(c, n, mem, d_ring, nkeys, proof, status, out_key, out_kprime, nullptr, bind))) return rc;
   return call.finish();
+}
+int act_verify_spend_keyring_batch(act_ctx* c, size_t n, int mem, const uint8_t* keys, int nkeys, const uint8_t* proof, uint8_t* status,
+                                   uint8_t* out_key, uint8_t* out_kprime) {
+  return act_verify_spend_keyring_bound_batch(c, n, mem, keys, nkeys, proof, nullptr, status, out_key, out_kprime);
 }
 
 // act_refund_sign_batch with the key chosen per lane: a lane whose status_in is 0 and whose key_index is not below nkeys is not signed

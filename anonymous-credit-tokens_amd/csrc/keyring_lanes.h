@@ -46,7 +46,7 @@ ACT_HD void ring_hash_lane(const RingArgs& r, uint32_t gid) {
   const uint32_t extra = r.nkeys - 1u;
   const uint32_t p = gid / extra, k = gid % extra + 1u;
   if (p >= r.s.n) return;
-  const SpendTranscript st{r.s.P.L};
+  const SpendTranscript st{r.s.P.L, r.s.bind != nullptr};      // a bound call hashes the bound length
   uint32_t rep[8], o[16];
   load8(rep, r.cand + ((size_t)p * extra + (k - 1u)) * 32);
   b3_xof64_patched(o, reinterpret_cast<const uint32_t*>(r.s.tr + (size_t)p * r.s.tr_stride), (uint32_t)st.bytes(),

@@ -103,6 +103,7 @@ ACT_HD void prove_head_lane(const ProveArgs& a, uint32_t p, Fb& fb) {
   uint8_t* rec = a.proof + (size_t)p * pl.bytes();
   uint8_t* el = a.tr + (size_t)p * a.tr_stride + 184;
   tr_put_prefix(a.tr + (size_t)p * a.tr_stride, a.P, LABEL_SPEND);
+  if (a.bind) tr_put_bind(a.tr + (size_t)p * a.tr_stride, L, a.bind + (size_t)p * 32);      // request binding
   uint32_t enc[8];
   tr_put_aligned(el + 40 * st.el_k(), k.v);
   store_sc(rec + 32 * pl.k(), k); store_sc(rec + 32 * pl.s(), s);

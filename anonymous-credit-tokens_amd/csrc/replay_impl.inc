@@ -207,7 +207,7 @@ static int replay_tail(act_ctx* c, act_nullifier_set* set, act_nullifier_set* re
 static int redeem_replay_locked(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys, int nkeys,
                                 const uint32_t* key_epochs, int sign_key, const uint8_t* proof, const uint8_t* cbor, const uint64_t* offsets, const uint8_t* nonce_key,
                                 uint8_t* out, uint8_t* status, uint8_t* out_key, uint8_t* out_replayed, uint64_t* out_counts, const RedeemReturn* ret,
-                                const ReplayReserve* res) {
+                                const ReplayReserve* res, const uint8_t* bind) {
   const bool wire = cbor != nullptr, dev = mem == ACT_MEM_DEVICE;
   const size_t pb = act_spend_proof_bytes(c);
   // K', the verdicts and (wire form) the nullifiers
@@ -217,8 +217,9 @@ static int redeem_replay_locked(act_ctx* c, act_nullifier_set* set, act_nullifie
   if (dev) { if ((rc = d.alloc(n * per_lane))) return rc; base = d.p; }
   else { h.resize(n * per_lane); base = h.data(); }
   uint8_t *kp = base, *nul = base + n * 32, *st = base + n * (per_lane - 1);
-  if (wire) { RingSel sel{keys, nkeys, out_key}; rc = verify_spend_cbor_impl(c, n, mem, nullptr, cbor, offsets, st, kp, nul, &sel); }
-  else rc = act_verify_spend_keyring_batch(c, n, mem, keys, nkeys, proof, st, out_key, kp);
+  // bind (DESIGN 4.12): the lanes' request bindings or null; they gate the verification and nothing behind it
+  if (wire) { RingSel sel{keys, nkeys, out_key, bind}; rc = verify_spend_cbor_impl(c, n, mem, nullptr, cbor, offsets, st, kp, nul, &sel); }
+  else rc = act_verify_spend_keyring_bound_batch(c, n, mem, keys, nkeys, proof, bind, st, out_key, kp);
   if (rc) return rc;
   return replay_tail(c, set, receipts, n, mem, keys, nkeys, key_epochs, sign_key, wire, wire ? nul : proof, wire ? 32 : pb, kp, st, nonce_key, out, status, out_key,
                      out_replayed, out_counts, nullptr, ret, res);

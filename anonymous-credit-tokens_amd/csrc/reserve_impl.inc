@@ -74,6 +74,23 @@ extern "C" int act_redeem_cbor_reserve_batch(act_ctx* c, act_nullifier_set* set,
                           .answers(out_reservation, status, out_key, out_counts));
 }
 
+// request binding (DESIGN 4.12): reserve with n * 32 bytes of associated data in every verified lane's challenge hash; bind == NULL is the
+// call above.  A recorded reservation's proof resent under another binding is an invalid proof, not a replay.  Settle takes no binding
+extern "C" int act_redeem_reserve_bound_batch(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys, int nkeys,
+                                              const uint32_t* key_epochs, const uint8_t* proof, const uint8_t* bind, const uint8_t* charge, uint8_t* out_reservation,
+                                              uint8_t* status, uint8_t* out_key, uint8_t* out_replayed, uint64_t* out_counts) {
+  if (n && !proof) return ACT_ERR_ARG;
+  return redeem_admit(AdmitCall(c, set, n, mem).ring(keys, nkeys, key_epochs, ACT_SIGN_MATCHED).records(proof).bound(bind).charged(charge).reserves(receipts, out_replayed)
+                          .answers(out_reservation, status, out_key, out_counts));
+}
+extern "C" int act_redeem_cbor_reserve_bound_batch(act_ctx* c, act_nullifier_set* set, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys, int nkeys,
+                                                   const uint32_t* key_epochs, const uint8_t* cbor, const uint64_t* offsets, const uint8_t* bind, const uint8_t* charge,
+                                                   uint8_t* out_reservation, uint8_t* status, uint8_t* out_key, uint8_t* out_replayed, uint64_t* out_counts) {
+  if (n && !cbor) return ACT_ERR_ARG;
+  return redeem_admit(AdmitCall(c, set, n, mem).ring(keys, nkeys, key_epochs, ACT_SIGN_MATCHED).messages(cbor, offsets).bound(bind).charged(charge).reserves(receipts, out_replayed)
+                          .answers(out_reservation, status, out_key, out_counts));
+}
+
 // ---- settle -----------------------------------------------------------------------------------------------------------------------------
 // Everything settle refuses as a whole: replay_refused's rules against ONE set, under one hold of its lock, with room for 2 n keys
 static int settle_refused(act_ctx* c, act_nullifier_set* receipts, size_t n, int mem, const uint8_t* keys, int nkeys, const uint32_t* key_epochs, int sign_key,

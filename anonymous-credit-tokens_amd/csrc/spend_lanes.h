@@ -80,6 +80,7 @@ ACT_PIECE ge spend_prep_role_c_a2(const SpendArgs& a, uint32_t p) {
   const ProofLayout pl{a.P.L};
   const uint8_t* rec = a.proofs + (size_t)p * pl.bytes();
   tr_put_prefix(a.tr + (size_t)p * a.tr_stride, a.P, LABEL_SPEND);
+  if (a.bind) tr_put_bind(a.tr + (size_t)p * a.tr_stride, a.P.L, a.bind + (size_t)p * 32);      // request binding
   sc k = load_sc(rec + 32 * pl.k()), gamma = load_sc(rec + 32 * pl.gamma());
   sc c_bar = load_sc(rec + 32 * pl.c_bar()), r_bar = load_sc(rec + 32 * pl.r_bar());
   sc ngamma = sc_neg(gamma);

@@ -44,7 +44,7 @@ bool table_cached(int device, const uint8_t enc[32], int bits) {
 }
 
 int workspace_alloc(act_ctx* c) {
-  const SpendTranscript st{c->L};
+  const SpendTranscript st{c->L, 1};      // the slot holds a bound call's stride (DESIGN 4.12); an unbound call keeps its own stride and length inside it
   size_t B = c->max_batch;
   HIPCK(c, hipMalloc(&c->d_group_ctr, GROUP_CTR_WORDS * 4));
   HIPCK(c, hipMemset(c->d_group_ctr, 0, GROUP_CTR_WORDS * 4));

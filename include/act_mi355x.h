@@ -1317,6 +1317,50 @@ int act_redeem_cbor_settle_batch(act_ctx *ctx, act_nullifier_set *receipts, size
                                  const uint8_t *amounts /* t; nullable: all zero */, const uint8_t nonce_key[32], uint8_t *out_refund_return_cbor,
                                  uint8_t *status, uint8_t *out_settled_before /* nullable */, uint64_t *out_counts /* nullable, host */);
 
+/* ======== request binding: 32 caller bytes enter the spend challenge ========
+ * A SpendProof is a bearer instrument: nothing in it says which request it pays for, so whoever sees it before the issuer does can
+ * present it beside a request of their own.  The calls below take associated data for the proof's Fiat-Shamir challenge: `bind`, n * 32
+ * bytes in `mem` memory beside the proofs, typically a hash of the request.  The library hashes nothing for the caller, and the binding
+ * is never sent inside the proof: both sides derive it from the request.
+ * The construction: the "spend" transcript followed by one more Transcript::update(bind_i) -- the 8-byte big-endian length 00..20 and
+ * the 32 bytes, appended behind the last existing element C -- hashed and reduced as before.  The unbound pre-image is a strict prefix
+ * of the bound one and no element moves; an unbound L-bit transcript has 6 + 3 L items and a bound one 7 + 3 L, so the two never
+ * coincide.  An all-zero binding is a binding: such a proof is not an unbound proof.
+ * A BOUND PROOF IS NOT A CRATE SpendProof: the crate's PrivateKey::refund rejects it, as every unbound call here does.  It has the
+ * record layout, size and CBOR type of a SpendProof.
+ * bind == NULL makes each call below the call it extends, byte for byte.  Each has the signature of that call with `bind` directly
+ * behind the proof or message arguments.  A lane whose binding is not the one its proof was made with gets the status a tampered
+ * proof gets (7, or the ring call's ACT_KEY_NONE): nothing is recorded, signed or reserved for it.
+ * What the binding does not enter: the screen, the retry-candidate stage, the receipt tags, the derived nonces and both sets.  The
+ * same proof served again under the same binding gives the same refund bytes with out_replayed = 1; under another binding it is an
+ * invalid proof and both sets stay as they are.  For reserve this closes what "Why the pin" describes above: a recorded reservation's
+ * proof resent beside another request no longer answers out_replayed = 1.  Settle takes no binding: it never sees a proof.
+ * Not offered: node-handle forms, unique forms (ACT_ERR_ARG; equal proof bytes say nothing about two lanes' bindings), the one-key
+ * calls with their small-batch and tiny roads (a ring of one key is the bound one-key call), act_prove_spend_seeded_batch, a wire
+ * field.  act_debug_last_spend_transcripts reports unbound pre-images and is meaningful after an unbound call only. */
+int act_prove_spend_bound_batch(act_ctx *ctx, size_t n, int mem, const uint8_t *token, const uint8_t *s, const uint8_t *rng,
+                                const uint8_t *bind /* n*32; nullable */, uint8_t *out_proof, uint8_t *out_prerefund, uint8_t *status);
+int act_verify_spend_keyring_bound_batch(act_ctx *ctx, size_t n, int mem, const uint8_t *keys, int nkeys, const uint8_t *proof,
+                                         const uint8_t *bind /* n*32; nullable */, uint8_t *status, uint8_t *out_key, uint8_t *out_kprime /* nullable */);
+int act_redeem_return_replay_bound_batch(act_ctx *ctx, act_nullifier_set *set, act_nullifier_set *receipts, size_t n, int mem, const uint8_t *keys, int nkeys,
+                                         const uint32_t *key_epochs /* nullable */, int sign_key, const uint8_t *proof, const uint8_t *bind /* n*32; nullable */,
+                                         const uint8_t *charge /* nullable */, const uint8_t *amounts /* t; nullable: all zero */, const uint8_t nonce_key[32],
+                                         uint8_t *out_refund_return, uint8_t *status, uint8_t *out_key, uint8_t *out_replayed /* nullable */,
+                                         uint64_t *out_counts /* nullable, host */);
+int act_redeem_cbor_return_replay_bound_batch(act_ctx *ctx, act_nullifier_set *set, act_nullifier_set *receipts, size_t n, int mem, const uint8_t *keys, int nkeys,
+                                              const uint32_t *key_epochs /* nullable */, int sign_key, const uint8_t *cbor, const uint64_t *offsets,
+                                              const uint8_t *bind /* n*32; nullable */, const uint8_t *charge /* nullable */,
+                                              const uint8_t *amounts /* t; nullable: all zero */, const uint8_t nonce_key[32], uint8_t *out_refund_return_cbor,
+                                              uint8_t *status, uint8_t *out_key, uint8_t *out_replayed /* nullable */, uint64_t *out_counts /* nullable, host */);
+int act_redeem_reserve_bound_batch(act_ctx *ctx, act_nullifier_set *set, act_nullifier_set *receipts, size_t n, int mem, const uint8_t *keys, int nkeys,
+                                   const uint32_t *key_epochs /* nullable */, const uint8_t *proof, const uint8_t *bind /* n*32; nullable */,
+                                   const uint8_t *charge /* nullable */, uint8_t *out_reservation, uint8_t *status, uint8_t *out_key,
+                                   uint8_t *out_replayed /* nullable */, uint64_t *out_counts /* nullable, host */);
+int act_redeem_cbor_reserve_bound_batch(act_ctx *ctx, act_nullifier_set *set, act_nullifier_set *receipts, size_t n, int mem, const uint8_t *keys, int nkeys,
+                                        const uint32_t *key_epochs /* nullable */, const uint8_t *cbor, const uint64_t *offsets,
+                                        const uint8_t *bind /* n*32; nullable */, const uint8_t *charge /* nullable */, uint8_t *out_reservation,
+                                        uint8_t *status, uint8_t *out_key, uint8_t *out_replayed /* nullable */, uint64_t *out_counts /* nullable, host */);
+
 #ifdef __cplusplus
 }
 #endif

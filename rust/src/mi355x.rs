@@ -213,6 +213,25 @@ extern "C" {
     fn act_redeem_cbor_settle_batch(ctx: *mut ActCtx, receipts: *mut ActNullifierSet, n: usize, mem: c_int, keys: *const u8, nkeys: c_int, key_epochs: *const u32,
                                     sign_key: c_int, reservation: *const u8, key_index: *const u8, amounts: *const u8, nonce_key: *const u8,
                                     out_refund_return_cbor: *mut u8, status: *mut u8, out_settled_before: *mut u8, out_counts: *mut u64) -> c_int;
+    // request binding: 32 caller bytes per lane enter the spend challenge (bind null: the call each extends)
+    fn act_prove_spend_bound_batch(ctx: *mut ActCtx, n: usize, mem: c_int, token: *const u8, s: *const u8, rng: *const u8, bind: *const u8,
+                                   out_proof: *mut u8, out_prerefund: *mut u8, status: *mut u8) -> c_int;
+    fn act_verify_spend_keyring_bound_batch(ctx: *mut ActCtx, n: usize, mem: c_int, keys: *const u8, nkeys: c_int, proof: *const u8, bind: *const u8,
+                                            status: *mut u8, out_key: *mut u8, out_kprime: *mut u8) -> c_int;
+    fn act_redeem_return_replay_bound_batch(ctx: *mut ActCtx, set: *mut ActNullifierSet, receipts: *mut ActNullifierSet, n: usize, mem: c_int, keys: *const u8,
+                                            nkeys: c_int, key_epochs: *const u32, sign_key: c_int, proof: *const u8, bind: *const u8, charge: *const u8,
+                                            amounts: *const u8, nonce_key: *const u8, out_refund_return: *mut u8, status: *mut u8, out_key: *mut u8,
+                                            out_replayed: *mut u8, out_counts: *mut u64) -> c_int;
+    fn act_redeem_cbor_return_replay_bound_batch(ctx: *mut ActCtx, set: *mut ActNullifierSet, receipts: *mut ActNullifierSet, n: usize, mem: c_int, keys: *const u8,
+                                                 nkeys: c_int, key_epochs: *const u32, sign_key: c_int, cbor: *const u8, offsets: *const u64, bind: *const u8,
+                                                 charge: *const u8, amounts: *const u8, nonce_key: *const u8, out_refund_return_cbor: *mut u8, status: *mut u8,
+                                                 out_key: *mut u8, out_replayed: *mut u8, out_counts: *mut u64) -> c_int;
+    fn act_redeem_reserve_bound_batch(ctx: *mut ActCtx, set: *mut ActNullifierSet, receipts: *mut ActNullifierSet, n: usize, mem: c_int, keys: *const u8, nkeys: c_int,
+                                      key_epochs: *const u32, proof: *const u8, bind: *const u8, charge: *const u8, out_reservation: *mut u8, status: *mut u8,
+                                      out_key: *mut u8, out_replayed: *mut u8, out_counts: *mut u64) -> c_int;
+    fn act_redeem_cbor_reserve_bound_batch(ctx: *mut ActCtx, set: *mut ActNullifierSet, receipts: *mut ActNullifierSet, n: usize, mem: c_int, keys: *const u8,
+                                           nkeys: c_int, key_epochs: *const u32, cbor: *const u8, offsets: *const u64, bind: *const u8, charge: *const u8,
+                                           out_reservation: *mut u8, status: *mut u8, out_key: *mut u8, out_replayed: *mut u8, out_counts: *mut u64) -> c_int;
     // test hook: one field operation per lane on raw 9-limb operands, in the per-column or the range kernel's build of the field code
     fn act_debug_fe_batch(ctx: *mut ActCtx, pair_build: c_int, op: c_int, n: usize, f: *const u32, g: *const u32, fb: *const u32, gb_or_a: *const u32,
                           h: *mut u32, hb: *mut u32) -> c_int;
@@ -594,6 +613,42 @@ impl CreditToken {
         });
         proofs_out(&proofs, &prer)
     }
+}
+
+/// `prove_spend_batch` under request bindings on ONE GPU (include/act_mi355x.h "request binding"): `binds[i]`, 32 bytes that both sides
+/// derive from the request spend i pays for, enter proof i's challenge.  The issuer verifies under the same bytes
+/// (`verify_spend_keyring_bound`, `GpuReplay::bound`, `GpuReserve::reserve_bound_batch`).  A bound proof has the layout of a
+/// `SpendProof` and is NOT one: the crate's `refund` and every unbound call reject it.  Draw order and bytes are those of
+/// `prove_spend_batch`; only the challenge differs.
+/// # Safety
+/// `ctx` is a live handle (`act_ctx_create` / `act_node_ctx`) made with `params` and L = 128.
+pub unsafe fn prove_spend_bound(ctx: *mut ActCtx, tokens: &[CreditToken], charges: &[Scalar], binds: &[[u8; 32]], mut rng: impl CryptoRngCore)
+    -> Result<Vec<(SpendProof, PreRefund)>, c_int> {
+    let n = tokens.len();
+    assert!(charges.len() == n && binds.len() == n);
+    let tok = marshal(tokens, 160, |t, out| t.write_record(out));
+    let mut s = Vec::with_capacity(32 * n);
+    charges.iter().for_each(|c| put_s(&mut s, c));
+    let bind: Vec<u8> = binds.iter().flat_map(|b| b.iter().copied()).collect();
+    let rng_bytes = draw(&mut rng, (4 * L + 12) * n);
+    let (mut proofs, mut prer, mut status) = (vec![0u8; PROOF_BYTES * n], vec![0u8; 96 * n], vec![0u8; n]);
+    let rc = act_prove_spend_bound_batch(ctx, n, 0, tok.as_ptr(), s.as_ptr(), rng_bytes.as_ptr(), bind.as_ptr(), proofs.as_mut_ptr(), prer.as_mut_ptr(),
+                                         status.as_mut_ptr());
+    if rc != 0 { return Err(rc); }
+    Ok(proofs_out(&proofs, &prer))
+}
+/// The ring verification under request bindings on ONE GPU: `proofs` = n records of `PROOF_BYTES`, `binds` = n values of 32 bytes.
+/// -> (rc, statuses, matched ring indices, enc(K') per lane).
+/// # Safety
+/// `ctx` is a live handle and outlives the call.
+pub unsafe fn verify_spend_keyring_bound(ctx: *mut ActCtx, keys: &[u8], proofs: &[u8], binds: &[u8]) -> (c_int, Vec<u8>, Vec<u8>, Vec<u8>) {
+    let (n, nkeys) = (proofs.len() / PROOF_BYTES, keys.len() / 64);
+    assert!(proofs.len() == n * PROOF_BYTES && binds.len() == 32 * n);
+    let (mut status, mut out_key, mut kprime) = (vec![0u8; n + 1], vec![ACT_KEY_NONE; n + 1], vec![0u8; 32 * n + 1]);
+    let rc = act_verify_spend_keyring_bound_batch(ctx, n, 0, keys.as_ptr(), nkeys as c_int, proofs.as_ptr(), binds.as_ptr(), status.as_mut_ptr(), out_key.as_mut_ptr(),
+                                                  kprime.as_mut_ptr());
+    status.truncate(n); out_key.truncate(n); kprime.truncate(32 * n);
+    (rc, status, out_key, kprime)
 }
 
 /// (proof records, PreRefund records) -> structs; 130 `decompress()` per proof, on scoped worker threads
@@ -1468,12 +1523,13 @@ pub struct GpuReplay {
     unique: bool,
     charges: Option<Vec<u8>>,
     returned: Option<Vec<u8>>,
+    binds: Option<Vec<u8>>,
 }
 impl GpuReplay {
     /// # Safety
     /// `ctx`, `set` and `receipts` are live handles on one device, `set != receipts`, and all three outlive `self`.
     pub unsafe fn from_raw(ctx: *mut ActCtx, set: *mut ActNullifierSet, receipts: *mut ActNullifierSet, nonce_key: [u8; 32]) -> Self {
-        GpuReplay { ctx, set, receipts, nonce_key, admit: false, unique: false, charges: None, returned: None }
+        GpuReplay { ctx, set, receipts, nonce_key, admit: false, unique: false, charges: None, returned: None, binds: None }
     }
     /// `true`: the calls go through the admission screen (include/act_mi355x.h "admission for the replayable redemption") -- a spent
     /// nullifier whose receipt is not this proof's is `DoubleSpendError` without being verified; a retry is verified and served.
@@ -1493,6 +1549,15 @@ impl GpuReplay {
     /// lane with the bytes of an earlier lane is not verified whatever amount it names, and gets that lane's RefundReturn only if it
     /// names that lane's amount (`Replayed::copies_other_amount` counts the others).  `None`: the calls without amounts.
     pub fn returned(mut self, returned: Option<Vec<u8>>) -> Self { self.returned = returned; self }
+    /// Request bindings for the next calls (include/act_mi355x.h "request binding"): n values of 32 bytes, typically a hash of the
+    /// request each spend pays for.  `Some`: the calls go to `act_redeem_(cbor_)return_replay_bound_batch` -- the admission screen is
+    /// implied, the outputs are RefundReturns (over 0 without `returned`), and lane i verifies only if its proof was made with the same
+    /// 32 bytes (`prove_spend_bound`).  The binding enters neither the receipt nor the nonces.  There is no unique form: with
+    /// `unique(true)` the calls panic.  `None`: the unbound calls.
+    pub fn bound(mut self, binds: Option<Vec<u8>>) -> Self { self.binds = binds; self }
+    fn bind_ptr(&self, n: usize) -> *const u8 {
+        self.binds.as_ref().map_or(std::ptr::null(), |b| { assert!(b.len() == 32 * n); b.as_ptr() })
+    }
     fn returned_ptr(&self, n: usize) -> *const u8 {
         self.returned.as_ref().map_or(std::ptr::null(), |t| { assert!(t.len() == 32 * n); t.as_ptr() })
     }
@@ -1503,13 +1568,20 @@ impl GpuReplay {
     pub fn redeem_replay_batch(&self, keys: &[u8], key_epochs: Option<&[u32]>, sign_with: Option<usize>, proofs: &[u8]) -> Replayed {
         let (n, nkeys) = (proofs.len() / PROOF_BYTES, keys.len() / 64);
         assert!(proofs.len() == n * PROOF_BYTES && key_epochs.map_or(true, |e| e.len() == nkeys));
-        let rec = if self.returned.is_some() { 160 } else { 128 };
+        assert!(!(self.binds.is_some() && self.unique), "request binding: the bound calls have no unique form");
+        let with_t = self.returned.is_some() || self.binds.is_some();
+        let rec = if with_t { 160 } else { 128 };
         let mut r = Replayed { rc: 0, status: vec![0u8; n + 1], out: vec![0u8; rec * n + 1], out_key: vec![ACT_KEY_NONE; n + 1], replayed: vec![0u8; n + 1], counts: [0; ACT_REPLAY_COUNTS],
                                admit_counts: [0; ACT_ADMIT_REPLAY_COUNTS], copy_counts: [0; 2], return_too_big: 0, copies_other_amount: 0 };
         let mut u = [0u64; ACT_ADMIT_REPLAY_UNIQUE_COUNTS];
         let mut t = [0u64; ACT_RETURN_REPLAY_COUNTS];
         let mut v = [0u64; ACT_RETURN_REPLAY_UNIQUE_COUNTS];
-        r.rc = if self.returned.is_some() && self.unique { unsafe {
+        r.rc = if self.binds.is_some() { unsafe {
+            act_redeem_return_replay_bound_batch(self.ctx, self.set, self.receipts, n, 0, keys.as_ptr(), nkeys as c_int, key_epochs.map_or(std::ptr::null(), |e| e.as_ptr()),
+                                                 sign_with.map_or(ACT_SIGN_MATCHED, |i| i as c_int), proofs.as_ptr(), self.bind_ptr(n), self.charge_ptr(n), self.returned_ptr(n),
+                                                 self.nonce_key.as_ptr(), r.out.as_mut_ptr(), r.status.as_mut_ptr(), r.out_key.as_mut_ptr(), r.replayed.as_mut_ptr(),
+                                                 t.as_mut_ptr())
+        } } else if self.returned.is_some() && self.unique { unsafe {
             act_redeem_return_replay_unique_batch(self.ctx, self.set, self.receipts, n, 0, keys.as_ptr(), nkeys as c_int, key_epochs.map_or(std::ptr::null(), |e| e.as_ptr()),
                                                   sign_with.map_or(ACT_SIGN_MATCHED, |i| i as c_int), proofs.as_ptr(), self.charge_ptr(n), self.returned_ptr(n),
                                                   self.nonce_key.as_ptr(), r.out.as_mut_ptr(), r.status.as_mut_ptr(), r.out_key.as_mut_ptr(), r.replayed.as_mut_ptr(),
@@ -1532,9 +1604,9 @@ impl GpuReplay {
                                     r.status.as_mut_ptr(), r.out_key.as_mut_ptr(), r.replayed.as_mut_ptr(), r.counts.as_mut_ptr())
         } };
         if self.returned.is_some() && self.unique { r.take_return_unique_counts(&v); }
-        else if self.returned.is_some() { r.take_return_counts(&t); }
+        else if with_t { r.take_return_counts(&t); }
         else if self.admit && self.unique { r.take_unique_counts(&u); }
-        if self.admit || self.returned.is_some() { r.take_admit_counts(); }
+        if self.admit || with_t { r.take_admit_counts(); }
         r.status.truncate(n); r.out.truncate(rec * n); r.out_key.truncate(n); r.replayed.truncate(n);
         r
     }
@@ -1543,13 +1615,20 @@ impl GpuReplay {
         let (blob, offsets) = gather(msgs);
         let (n, nkeys) = (msgs.len(), keys.len() / 64);
         assert!(key_epochs.map_or(true, |e| e.len() == nkeys));
-        let rec = if self.returned.is_some() { REFUND_RETURN_CBOR_BYTES } else { REFUND_CBOR_BYTES };
+        assert!(!(self.binds.is_some() && self.unique), "request binding: the bound calls have no unique form");
+        let with_t = self.returned.is_some() || self.binds.is_some();
+        let rec = if with_t { REFUND_RETURN_CBOR_BYTES } else { REFUND_CBOR_BYTES };
         let mut r = Replayed { rc: 0, status: vec![0u8; n + 1], out: vec![0u8; rec * n + 1], out_key: vec![ACT_KEY_NONE; n + 1], replayed: vec![0u8; n + 1],
                                counts: [0; ACT_REPLAY_COUNTS], admit_counts: [0; ACT_ADMIT_REPLAY_COUNTS], copy_counts: [0; 2], return_too_big: 0, copies_other_amount: 0 };
         let mut u = [0u64; ACT_ADMIT_REPLAY_UNIQUE_COUNTS];
         let mut t = [0u64; ACT_RETURN_REPLAY_COUNTS];
         let mut v = [0u64; ACT_RETURN_REPLAY_UNIQUE_COUNTS];
-        r.rc = if self.returned.is_some() && self.unique { unsafe {
+        r.rc = if self.binds.is_some() { unsafe {
+            act_redeem_cbor_return_replay_bound_batch(self.ctx, self.set, self.receipts, n, 0, keys.as_ptr(), nkeys as c_int, key_epochs.map_or(std::ptr::null(), |e| e.as_ptr()),
+                                                      sign_with.map_or(ACT_SIGN_MATCHED, |i| i as c_int), blob.as_ptr(), offsets.as_ptr(), self.bind_ptr(n), self.charge_ptr(n),
+                                                      self.returned_ptr(n), self.nonce_key.as_ptr(), r.out.as_mut_ptr(), r.status.as_mut_ptr(), r.out_key.as_mut_ptr(),
+                                                      r.replayed.as_mut_ptr(), t.as_mut_ptr())
+        } } else if self.returned.is_some() && self.unique { unsafe {
             act_redeem_cbor_return_replay_unique_batch(self.ctx, self.set, self.receipts, n, 0, keys.as_ptr(), nkeys as c_int, key_epochs.map_or(std::ptr::null(), |e| e.as_ptr()),
                                                        sign_with.map_or(ACT_SIGN_MATCHED, |i| i as c_int), blob.as_ptr(), offsets.as_ptr(), self.charge_ptr(n),
                                                        self.returned_ptr(n), self.nonce_key.as_ptr(), r.out.as_mut_ptr(), r.status.as_mut_ptr(), r.out_key.as_mut_ptr(),
@@ -1575,9 +1654,9 @@ impl GpuReplay {
                                          r.out.as_mut_ptr(), r.status.as_mut_ptr(), r.out_key.as_mut_ptr(), r.replayed.as_mut_ptr(), r.counts.as_mut_ptr())
         } };
         if self.returned.is_some() && self.unique { r.take_return_unique_counts(&v); }
-        else if self.returned.is_some() { r.take_return_counts(&t); }
+        else if with_t { r.take_return_counts(&t); }
         else if self.admit && self.unique { r.take_unique_counts(&u); }
-        if self.admit || self.returned.is_some() { r.take_admit_counts(); }
+        if self.admit || with_t { r.take_admit_counts(); }
         r.status.truncate(n); r.out.truncate(rec * n); r.out_key.truncate(n); r.replayed.truncate(n);
         r
     }
@@ -1654,6 +1733,35 @@ impl GpuReserve {
             act_redeem_reserve_batch(self.ctx, self.set, self.receipts, n, 0, keys.as_ptr(), nkeys as c_int, key_epochs.map_or(std::ptr::null(), |e| e.as_ptr()),
                                      proofs.as_ptr(), charges.map_or(std::ptr::null(), |c| c.as_ptr()), r.reservation.as_mut_ptr(), r.status.as_mut_ptr(),
                                      r.out_key.as_mut_ptr(), r.replayed.as_mut_ptr(), r.counts.as_mut_ptr())
+        };
+        r.status.truncate(n); r.reservation.truncate(RESERVATION_BYTES * n); r.out_key.truncate(n); r.replayed.truncate(n);
+        r
+    }
+    /// `reserve_batch` under request bindings (include/act_mi355x.h "request binding"): `binds` = n values of 32 bytes; lane i verifies
+    /// only if its proof was made with binds[i], so a recorded reservation's proof resent beside another request is an invalid proof,
+    /// not `replayed[i] == 1`.  Settle takes no binding.
+    pub fn reserve_bound_batch(&self, keys: &[u8], key_epochs: Option<&[u32]>, proofs: &[u8], binds: &[u8], charges: Option<&[u8]>) -> Reserved {
+        let (n, nkeys) = (proofs.len() / PROOF_BYTES, keys.len() / 64);
+        assert!(proofs.len() == n * PROOF_BYTES && binds.len() == 32 * n && key_epochs.map_or(true, |e| e.len() == nkeys) && charges.map_or(true, |c| c.len() == 32 * n));
+        let mut r = Self::reserved(n);
+        r.rc = unsafe {
+            act_redeem_reserve_bound_batch(self.ctx, self.set, self.receipts, n, 0, keys.as_ptr(), nkeys as c_int, key_epochs.map_or(std::ptr::null(), |e| e.as_ptr()),
+                                           proofs.as_ptr(), binds.as_ptr(), charges.map_or(std::ptr::null(), |c| c.as_ptr()), r.reservation.as_mut_ptr(),
+                                           r.status.as_mut_ptr(), r.out_key.as_mut_ptr(), r.replayed.as_mut_ptr(), r.counts.as_mut_ptr())
+        };
+        r.status.truncate(n); r.reservation.truncate(RESERVATION_BYTES * n); r.out_key.truncate(n); r.replayed.truncate(n);
+        r
+    }
+    /// The same on wire bytes.
+    pub fn reserve_cbor_bound_batch(&self, keys: &[u8], key_epochs: Option<&[u32]>, msgs: &[&[u8]], binds: &[u8], charges: Option<&[u8]>) -> Reserved {
+        let (blob, offsets) = gather(msgs);
+        let (n, nkeys) = (msgs.len(), keys.len() / 64);
+        assert!(binds.len() == 32 * n && key_epochs.map_or(true, |e| e.len() == nkeys) && charges.map_or(true, |c| c.len() == 32 * n));
+        let mut r = Self::reserved(n);
+        r.rc = unsafe {
+            act_redeem_cbor_reserve_bound_batch(self.ctx, self.set, self.receipts, n, 0, keys.as_ptr(), nkeys as c_int, key_epochs.map_or(std::ptr::null(), |e| e.as_ptr()),
+                                                blob.as_ptr(), offsets.as_ptr(), binds.as_ptr(), charges.map_or(std::ptr::null(), |c| c.as_ptr()),
+                                                r.reservation.as_mut_ptr(), r.status.as_mut_ptr(), r.out_key.as_mut_ptr(), r.replayed.as_mut_ptr(), r.counts.as_mut_ptr())
         };
         r.status.truncate(n); r.reservation.truncate(RESERVATION_BYTES * n); r.out_key.truncate(n); r.replayed.truncate(n);
         r
