@@ -42,7 +42,7 @@ EXPORTS = [
     "act_ctx_set_host_threads", "act_host_usable_cpus", "act_host_hash_many", "act_host_parallel_for", "act_host_pool_stats", "act_ctx_streams_overlap", "act_ctx_set_pipeline_depth", "act_ctx_set_small_batch_max", "act_ctx_set_fixed_base_bits", "act_node_set_fixed_base_bits", "act_tuning_set", "act_build_has_ct_secret_tables", "act_ctx_fixed_base_bits", "act_last_error", "act_spend_proof_bytes", "act_prove_rng_bytes",
     "act_spend_transcript_bytes", "act_private_key_random", "act_pre_issuance_random_batch", "act_request_batch",
     "act_issue_batch", "act_issuance_to_credit_token_batch", "act_prove_spend_batch", "act_prove_spend_seeded_batch", "act_node_prove_spend_seeded_batch", "act_verify_spend_batch",
-    "act_refund_batch", "act_refund_to_credit_token_batch", "act_debug_last_spend_transcripts", "act_debug_scalarmult_batch", "act_debug_fixed_base_batch", "act_debug_fe_batch", "act_debug_fixed_base_mf_batch", "act_debug_chain_ct_batch", "act_debug_secret_residue", "act_prof_enable",
+    "act_refund_batch", "act_refund_to_credit_token_batch", "act_debug_last_spend_transcripts", "act_debug_scalarmult_batch", "act_debug_fixed_base_batch", "act_debug_fe_batch", "act_debug_sc_batch", "act_debug_fixed_base_mf_batch", "act_debug_chain_ct_batch", "act_debug_secret_residue", "act_prof_enable",
     "act_prof_reset", "act_prof_kernel_count", "act_prof_kernel_name", "act_prof_get", "act_prof_get_busy", "act_ubench_mad_u64_u32", "act_ubench_random_read", "act_ubench_table_read",
     "act_cbor_size", "act_cbor_record_bytes", "act_cbor_encode_batch", "act_cbor_decode_batch", "act_cbor_read_batch", "act_ctx_set_wire_reader", "act_ctx_wire_stats", "act_node_set_wire_reader", "act_verify_spend_cbor_batch",
     "act_node_verify_spend_cbor_batch", "act_redeem_batch", "act_node_redeem_batch",
@@ -161,6 +161,7 @@ def load() -> C.CDLL:
     lib.act_debug_scalarmult_batch.argtypes = [vp, sz, i32, u8p, u8p, u8p, u8p]
     lib.act_debug_fixed_base_batch.argtypes = [vp, i32, sz, i32, u8p, u8p]
     lib.act_debug_fe_batch.argtypes = [vp, i32, i32, sz, u8p, u8p, u8p, u8p, u8p, u8p]
+    lib.act_debug_sc_batch.argtypes = [vp, i32, sz, u8p, u8p, u8p, u8p]
     lib.act_debug_fixed_base_mf_batch.argtypes = [vp, i32, i32, sz, i32, u8p, u8p]
     lib.act_debug_chain_ct_batch.argtypes = [vp, i32, sz, i32, u8p, u8p, u8p, u8p, u8p, u8p]
     lib.act_debug_secret_residue.argtypes = [vp, C.POINTER(sz)]
@@ -681,6 +682,20 @@ class Engine:
         self._ck(self.lib.act_debug_fe_batch(self.ctx, int(bool(pair_build)), self.FE_OPS.index(op), n, *[None if a is None else a.ctypes.data for a in ins],
                                              h.ctypes.data, None if hb is None else hb.ctypes.data))
         return h, hb
+
+    SC_OPS = ("load_sc", "load_wide", "add", "sub", "neg", "half", "mul", "muladd", "invert", "scm_mul", "equal", "is_zero")
+    SC_WORDS = 16
+
+    def debug_sc(self, op: str, n: int, a, b=None, c=None, fill: int = 0):
+        """One operation of the scalar arithmetic mod l per lane (act_debug_sc_batch).  a, b, c: uint32 arrays of 16 n words, a record of
+        16 words per lane (those the operation names; "load_sc" / "load_wide" read 32 / 64 bytes at the start of a's record).  Returns r
+        as a uint32 array of 16 * (n rounded up to 256) words pre-filled with `fill`."""
+        lanes = (n + 255) // 256 * 256
+        ins = [None if x is None else np.ascontiguousarray(x, np.uint32) for x in (a, b, c)]
+        assert all(x is None or x.size == self.SC_WORDS * n for x in ins)
+        r = np.full(self.SC_WORDS * lanes, fill, np.uint32)
+        self._ck(self.lib.act_debug_sc_batch(self.ctx, self.SC_OPS.index(op), n, *[None if x is None else x.ctypes.data for x in ins], r.ctypes.data))
+        return r
 
     # ---- CBOR wire codec (src/cbor.rs) -----------------------------------------------------------------
     def cbor_size(self, type_name: str) -> int:

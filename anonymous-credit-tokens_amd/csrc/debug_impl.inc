@@ -160,6 +160,35 @@ int act_debug_fe_batch(act_ctx* c, int pair_build, int op, size_t n, const uint3
   return call.finish();
 }
 
+// One operation of the scalar arithmetic mod l per lane (k_debug_sc.hip) on records of DSC_WORDS words.  r goes IN as well, rounded up
+// to whole blocks of 256 lanes, and comes back whole, as h does above: a word the kernel wrote past its result, or past lane n, shows
+// in what the caller pre-filled.
+int act_debug_sc_batch(act_ctx* c, int op, size_t n, const uint32_t* a, const uint32_t* b, const uint32_t* c3, uint32_t* r) {
+  if (!c || op < 0 || op >= DSC_COUNT) return ACT_ERR_ARG;
+  const bool need_b = op == DSC_ADD || op == DSC_SUB || op == DSC_MUL || op == DSC_MULADD || op == DSC_SCM_MUL || op == DSC_EQUAL, need_c = op == DSC_MULADD;
+  if (n && (!a || !r || (need_b && !b) || (need_c && !c3))) return ACT_ERR_ARG;
+  Call call(c, n);
+  HIPCK(c, hipSetDevice(c->device));
+  Slot& sl = c->slots[0];
+  const size_t LB = DSC_WORDS * 4;                                  // bytes of a lane's record
+  const size_t chunk = std::max<size_t>(256, c->max_batch / 256 * 256);      // whole blocks
+  for (size_t off = 0; off < n; off += chunk) {
+    const uint32_t m = (uint32_t)std::min(chunk, n - off);
+    const size_t in_b = (size_t)m * LB, out_b = ((size_t)m + 255) / 256 * 256 * LB;
+    const uint8_t *d_a, *d_b = nullptr, *d_c = nullptr, *d_rin; int rc;
+    if ((rc = dev_in(c, sl, 0, ACT_MEM_HOST, (const uint8_t*)a + off * LB, in_b, &d_a))) return rc;
+    if (need_b && (rc = dev_in(c, sl, 1, ACT_MEM_HOST, (const uint8_t*)b + off * LB, in_b, &d_b))) return rc;
+    if (need_c && (rc = dev_in(c, sl, 2, ACT_MEM_HOST, (const uint8_t*)c3 + off * LB, in_b, &d_c))) return rc;
+    if ((rc = dev_in(c, sl, 3, ACT_MEM_HOST, (const uint8_t*)r + off * LB, out_b, &d_rin))) return rc;
+    uint8_t* d_r = const_cast<uint8_t*>(d_rin);
+    launch_debug_sc(op, m, (const uint32_t*)d_a, (const uint32_t*)d_b, (const uint32_t*)d_c, (uint32_t*)d_r, sl.stream);
+    HIPCK(c, hipGetLastError());
+    if ((rc = dev_out_end(c, sl, ACT_MEM_HOST, (uint8_t*)r + off * LB, d_r, out_b))) return rc;
+    HIPCK(c, hipStreamSynchronize(sl.stream));
+  }
+  return call.finish();
+}
+
 // out[i] = enc(scalars[i] * B), B = base 0..3, through the product of SECRET scalars: fixed_base_acc_mf over the context's own
 // matrix-core table image of B (k_debug_secret.hip), in blocks of 64 or 256 threads.  Chunked by max_batch as the hook above is; lane
 // i of a chunk is thread i of the launch, so with max_batch a multiple of 64 scalar i sits in lane i mod 64 of its wavefront.

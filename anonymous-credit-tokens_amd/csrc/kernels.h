@@ -289,6 +289,10 @@ void launch_debug_fixed_base(FbTab tab, const uint8_t* scs, uint32_t n, uint8_t*
 enum DebugFeOp : int { DFE_MUL = 0, DFE_SQ, DFE_MUL2, DFE_SQ2, DFE_SQDA_SQ, DFE_CARRY, DFE_SUB, DFE_SUB3, DFE_SUB4, DFE_NEG, DFE_COUNT };
 void launch_debug_fe(int op, uint32_t n, const uint32_t* f, const uint32_t* g, const uint32_t* fb, const uint32_t* ga, uint32_t* h, uint32_t* hb, hipStream_t s);
 void launch_debug_fe_pair(int op, uint32_t n, const uint32_t* f, const uint32_t* g, const uint32_t* fb, const uint32_t* ga, uint32_t* h, uint32_t* hb, hipStream_t s);
+// k_debug_sc.hip: one operation of the scalar arithmetic mod l (sc25519.h) per lane, on records of DSC_WORDS words; DebugScOp selects it
+enum DebugScOp : int { DSC_LOAD_SC = 0, DSC_LOAD_WIDE, DSC_ADD, DSC_SUB, DSC_NEG, DSC_HALF, DSC_MUL, DSC_MULADD, DSC_INVERT, DSC_SCM_MUL, DSC_EQUAL, DSC_IS_ZERO, DSC_COUNT };
+constexpr int DSC_WORDS = 16;
+void launch_debug_sc(int op, uint32_t n, const uint32_t* a, const uint32_t* b, const uint32_t* c, uint32_t* r, hipStream_t s);
 // k_debug_secret.hip: one product of a secret scalar per lane -- the matrix-core look-up over a table image in blocks of 64 or 256
 // threads, and the address-free chains (mode 0 chain_ct<1>, 1 the four chain_ct_quarter pieces added, 2 chain_ct<2>)
 void launch_debug_fixed_base_mf(const uint8_t* tab_mf, int block_threads, const uint8_t* scs, uint32_t n, uint8_t* out, hipStream_t s);

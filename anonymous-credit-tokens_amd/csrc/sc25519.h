@@ -79,7 +79,7 @@ ACT_HD sc sc_reduce512(const uint32_t x[16]) {
   bn_mul<9, 4>(y1, h0, c);                // < 2^385
   bn_split252<13>(lo1, h1, y1);           // h1 < 2^133 (5 limbs used of 6)
   bn_mul<6, 4>(y2, h1, c);                // < 2^258
-  bn_split252<10>(lo2, h2, y2);           // h2 < 2^6
+  bn_split252<10>(lo2, h2, y2);           // h2 < 2^6 (at most 27, at x = 2^512 - 1: tests/sc_model.py)
   bn_mul<3, 4>(y3, h2, c);                // < 2^131 (7 limbs written)
   y3[7] = 0u;
   // x = lo0 - lo1 + lo2 - y3 (mod l); add 2l to stay positive
@@ -91,6 +91,8 @@ ACT_HD sc sc_reduce512(const uint32_t x[16]) {
   bn_add<8>(A, A, l2);
   bn_add<8>(B, lo1, y3);
   bn_sub<8>(A, A, B);
+  // A - B >= 2l - 2^252 - 2^131 > l and A < 4l: 1, 2 or 3 of the four are taken, the third by one product of random scalars in
+  // 1 400 (tests/sc_edge_cases.py aims at each count)
   sc_cond_sub_l(A, 4);
   sc r;
 #pragma unroll
@@ -210,6 +212,8 @@ ACT_HD sc sc_invert(const sc& a) {
     if (sh > 20 && i + 2 < SCM_LIMBS) v |= o[i + 2] << (52 - sh);
     r.v[w] = v;
   }
+  // o = (acc + m l) / R <= l for acc < 2l, and = l only for acc = l, a multiple of l that the power of a canonical a never is: for
+  // a < l this subtraction is never taken (0 of 442 aimed and random inputs, tests/test_sc_edges_host.py).  It stays for raw operands.
   sc_cond_sub_l(r.v, 1);
   return r;
 }

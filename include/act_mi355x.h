@@ -966,6 +966,15 @@ int act_debug_fixed_base_batch(act_ctx *ctx, int base, size_t n, int mem, const 
  * op outside 0..9 or a missing array. */
 int act_debug_fe_batch(act_ctx *ctx, int pair_build, int op, size_t n, const uint32_t *f, const uint32_t *g, const uint32_t *fb,
                        const uint32_t *gb_or_a, uint32_t *h, uint32_t *hb);
+/* Debug / test hook: ONE operation of the device's scalar arithmetic mod l (csrc/sc25519.h) per lane.  Lane i owns a record of 16
+ * uint32_t words, [16 i, 16 i + 16), in every array the operation names.  op: 0 r = from_bytes_mod_order of the 32 BYTES at the start
+ * of a's record and 1 r = from_bytes_mod_order_wide of its 64 bytes, both through the production loads and store; on raw 8-word
+ * operands, which nothing reduces on the way in: 2 r = a + b, 3 r = a - b, 4 r = -a, 5 r = a / 2, 6 r = a b, 7 r = a b + c,
+ * 8 r = 1 / a (0 for 0); 9 the Montgomery product inside the inversion on raw operands of ten 26-bit limbs, ten limbs out; 10 / 11
+ * word 0 of r = 1 if a = b / a = 0 as words, else 0.  An array an operation does not name may be NULL.  HOST memory only.  r must
+ * hold n rounded up to a multiple of 256 records: every word the operation does not write, in the records from n on too, makes the
+ * round trip through device memory and comes back as the caller filled it.  ACT_ERR_ARG for an op outside 0..11 or a missing array. */
+int act_debug_sc_batch(act_ctx *ctx, int op, size_t n, const uint32_t *a, const uint32_t *b, const uint32_t *c, uint32_t *r);
 /* Debug / test hook: out[i] = enc(scalars[i] * B) for the fixed base B = 0..3 (g, h1, h2, h3) through the product every SECRET scalar
  * takes in the default build: 37 signed 7-bit digits, entry |digit| of a 64-entry window picked on the matrix cores from this context's
  * table image of B.  One product per lane, in blocks of block_threads = 64 or 256 threads (both shapes exist in the library), chunked

@@ -235,6 +235,8 @@ extern "C" {
     // test hook: one field operation per lane on raw 9-limb operands, in the per-column or the range kernel's build of the field code
     fn act_debug_fe_batch(ctx: *mut ActCtx, pair_build: c_int, op: c_int, n: usize, f: *const u32, g: *const u32, fb: *const u32, gb_or_a: *const u32,
                           h: *mut u32, hb: *mut u32) -> c_int;
+    // test hook: one operation of the scalar arithmetic mod l per lane, on records of 16 words
+    fn act_debug_sc_batch(ctx: *mut ActCtx, op: c_int, n: usize, a: *const u32, b: *const u32, c: *const u32, r: *mut u32) -> c_int;
     // test hooks: one product of a secret scalar per lane -- the matrix-core look-up over the context's table image, the address-free chains
     fn act_debug_fixed_base_mf_batch(ctx: *mut ActCtx, base: c_int, block_threads: c_int, n: usize, mem: c_int, scalars: *const u8, out: *mut u8) -> c_int;
     fn act_debug_chain_ct_batch(ctx: *mut ActCtx, mode: c_int, n: usize, mem: c_int, points: *const u8, scalars: *const u8, scalars2: *const u8,

@@ -66,6 +66,19 @@ void hc_sc_sub(const uint8_t* a, const uint8_t* b, uint8_t* o) { sc_out(o, sc_su
 void hc_sc_neg(const uint8_t* a, uint8_t* o) { sc_out(o, sc_neg(sc_in(a))); }
 void hc_sc_half(const uint8_t* a, uint8_t* o) { sc_out(o, sc_half(sc_in(a))); }
 void hc_sc_invert(const uint8_t* a, uint8_t* o) { sc_out(o, sc_invert(sc_in(a))); }
+// ... on RAW operands: the eight words go in as they are (sc_in above reduces through sc_from_words, so a wrong sc_from_words would
+// hide behind every other operation), and scm_mul on its ten 26-bit limbs (tests/test_sc_edges_host.py, tests/sc_edge_cases.py)
+static sc sc_raw(const uint8_t* b) { sc s; memcpy(s.v, b, 32); return s; }
+void hc_sc_add(const uint8_t* a, const uint8_t* b, uint8_t* o) { sc_out(o, sc_add(sc_raw(a), sc_raw(b))); }
+void hc_sc_mul(const uint8_t* a, const uint8_t* b, uint8_t* o) { sc_out(o, sc_mul(sc_raw(a), sc_raw(b))); }
+void hc_sc_muladd_raw(const uint8_t* a, const uint8_t* b, const uint8_t* c, uint8_t* o) { sc_out(o, sc_muladd(sc_raw(a), sc_raw(b), sc_raw(c))); }
+void hc_sc_sub_raw(const uint8_t* a, const uint8_t* b, uint8_t* o) { sc_out(o, sc_sub(sc_raw(a), sc_raw(b))); }
+void hc_sc_neg_raw(const uint8_t* a, uint8_t* o) { sc_out(o, sc_neg(sc_raw(a))); }
+void hc_sc_half_raw(const uint8_t* a, uint8_t* o) { sc_out(o, sc_half(sc_raw(a))); }
+void hc_sc_invert_raw(const uint8_t* a, uint8_t* o) { sc_out(o, sc_invert(sc_raw(a))); }
+void hc_scm_mul(const uint32_t* a, const uint32_t* b, uint32_t* limbs_out) { uint32_t o[SCM_LIMBS]; scm_mul(o, a, b); memcpy(limbs_out, o, sizeof(o)); }
+int hc_sc_equal(const uint8_t* a, const uint8_t* b) { return sc_equal(sc_raw(a), sc_raw(b)); }
+int hc_sc_is_zero(const uint8_t* a) { return sc_is_zero(sc_raw(a)); }
 
 int hc_decode_encode(const uint8_t* a, uint8_t* o) {
   uint32_t w[8], r[8]; ld(w, a); ge p; bool ok = ristretto_decode(p, w);

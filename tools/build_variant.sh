@@ -10,7 +10,7 @@ mkdir -p "$out"
 make -C "$src" host_hash.o host_pool.o node.o node_nullifier.o node_issue_wire.o node_keyring.o node_epochs.o >/dev/null
 pids=()
 # FILES="k_spend_verify ..." restricts the extra flags to those translation units (default: all)
-for f in engine k_misc k_spend_verify k_spend_bits k_sign k_prove k_client k_client_ring k_keyring k_admit k_copies k_cbor_read k_replay k_admit_replay k_return_replay k_reserve k_debug_fe k_debug_fe_pair k_debug_secret; do
+for f in engine k_misc k_spend_verify k_spend_bits k_sign k_prove k_client k_client_ring k_keyring k_admit k_copies k_cbor_read k_replay k_admit_replay k_return_replay k_reserve k_debug_fe k_debug_fe_pair k_debug_sc k_debug_secret; do
   extra=("$@")
   if [ -n "$FILES" ] && ! [[ " $FILES " == *" $f "* ]]; then extra=(); fi
   # the range kernel's unit is built pair-interleaved in the product (csrc/Makefile BITSFLAGS); BITS= overrides that for A/B ("BITS=" = per-column form)
